@@ -7,6 +7,8 @@ of the fused kernel (stamp -> collide -> reward -> closest-tx -> gossip merge ->
 move -> observe), actions pre-generated in HBM, outputs written to HBM.
 
   python bench.py --gpus 1 --steps 200 --warmup 50
+  python bench.py --gpus 1 --steps 200 --warmup 50 --dump-outputs DIR   (+ the last timed step's outputs as DIR/*.npy)
+  python bench.py --full ...            (+ the CPU baseline, PRR parity and the other workloads / step forms)
   python bench.py --gpus N ...          (N > 1 without a launcher: re-executes itself as N ranks under
                                          torch.distributed.run on 127.0.0.1 with a free port, diral_amd/spawn.py)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -16,12 +18,19 @@ One process per GPU; envs are independent so ranks share nothing on the step
 path (weak scaling: B per GPU fixed); RCCL is used once, to all-reduce the
 episode metrics.  Rank 0 prints ONE JSON line.
 
-Timed region: after the reset every run first plays untimed pre-roll slots (at least
-PREROLL = 60, SURVEY 8d: >= 50, past the ghost-entry / table-filling phase of the first
-19 slots, Q4; and at least PREROLL_SECONDS, so that a GPU coming out of idle has reached
-its clocks), then the W warm-up slots it was asked for, then exactly K timed slots between
-barrier + synchronize pairs.  The kernel's own duration is measured with HIP events
-on the launch stream over the same K launches.
+A plain run measures the headline only: set-up, warm-up, the K timed steps, the result line (with the
+roofline object, computed from this run's kernel time and the committed counters).  `--full` adds what
+takes runs of its own: the other BASELINE.json configurations and step forms (`also_measured`), the CPU
+baseline (`cpu_baseline`) and the PRR parity check against the CPU oracle (`prr_parity`).
+
+Timed region: after the reset every run first plays a fixed number of untimed pre-roll slots
+(PREROLL_SLOTS of the workload: at least PREROLL = 60, SURVEY 8d: >= 50, past the ghost-entry /
+table-filling phase of the first 19 slots, Q4; and about 0.3 s of launches on an MI355X, so that
+a GPU coming out of idle has reached its clocks and the tables their steady state), then the W
+warm-up slots it was asked for, then exactly K timed slots between barrier + synchronize pairs.
+The slot count does not depend on time, so the same arguments give the same outputs from run to
+run (`--dump-outputs`).  The kernel's own duration is measured with HIP events on the launch
+stream over the same K launches.
 """
 from __future__ import annotations
 
@@ -58,8 +67,11 @@ WORKLOADS = {
     "n1024": (1024, 64, 16000.0, 256, False),
 }
 PREROLL = 60      # untimed slots after every reset, before the requested warm-up (>= 50)
-PREROLL_SECONDS = 0.3   # ... and at least this long: a GPU coming out of idle needs tens of ms to reach its clocks
+# untimed slots per workload: what >= 60 slots and >= 0.3 s of them came to on an MI355X (c2 6320-6360, c3 260, c5 360),
+# fixed so that the timed slots and their outputs are the same from run to run
+PREROLL_SLOTS = {"c2": 6340, "c3": 260, "c5": 360, "c4shard": 920, "n1024": PREROLL}
 GLOBAL_SEED = 1234
+DUMP_BYTES = 56 << 20   # --dump-outputs: at most this many bytes of arrays (a seeded sample of the envs beyond it)
 
 
 def usable_cores() -> int:
@@ -369,8 +381,7 @@ def run_workload(name, device, rank, world, steps, warmup, batch=0, out_dtype="f
             env.update_velocity(seed=t)      # main_test.py:226-233 (no-op unless mobility_vary)
 
     t = 0
-    t_pre = time.perf_counter()
-    while t < PREROLL or time.perf_counter() - t_pre < PREROLL_SECONDS:
+    while t < PREROLL_SLOTS[name]:
         for _ in range(20):
             one_step(t)
             t += 1
@@ -428,6 +439,33 @@ def run_workload(name, device, rank, world, steps, warmup, batch=0, out_dtype="f
         "preroll_slots": preroll, "wall_this_rank": wall_local,
     }
     return env, res
+
+
+def dump_outputs(env, out_dir, emit_chobs) -> dict:
+    """--dump-outputs: what the caller of the timed step received from its last call - state [B, N, S], reward [B, N],
+    done [B] and, with --emit-chobs 1, the channel observation [B, N, A] - as <out_dir>/<name>.npy in the output dtype
+    (done as float32).  Beyond DUMP_BYTES a fixed seeded sample of the envs is written, the same for every run with the
+    same arguments; env_index.npy (float64) names the envs written, in order."""
+    import numpy as np
+    outs = {"state": env._obs, "reward": env._rew, "done": env._done.to(torch.float32)}
+    if emit_chobs:
+        outs["channel_observation"] = env._chobs
+    per_env = sum(x[0].numel() * x.element_size() for x in outs.values()) + 8
+    B = env.B
+    if B * per_env <= DUMP_BYTES:
+        idx = np.arange(B)
+    else:
+        idx = np.sort(np.random.default_rng(GLOBAL_SEED).choice(B, DUMP_BYTES // per_env, replace=False))
+    sel = torch.from_numpy(idx).to(env.device)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, x in outs.items():
+        a = x.index_select(0, sel).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = list(a.shape)
+    np.save(os.path.join(out_dir, "env_index.npy"), idx.astype(np.float64))
+    written["env_index"] = [len(idx)]
+    return written
 
 
 def rollout_sps(device, envs=4096, slots=400, warm=80):
@@ -781,9 +819,18 @@ def main() -> int:
     ap.add_argument("--emit-chobs", type=int, default=1, choices=[0, 1],
                     help="1 (default): the timed step also writes the channel observation `obs` of the reference "
                          "step (4*N*A bytes per env-slot, part of SURVEY 8d's byte model); 0: state + reward only")
-    ap.add_argument("--no-cpu-baseline", "--lean", dest="lean", action="store_true",
-                    help="only the timed run (profiling passes): no CPU baseline, PRR parity or secondary workloads")
+    scope = ap.add_mutually_exclusive_group()
+    scope.add_argument("--full", action="store_true",
+                       help="also the CPU baseline, the PRR parity check and the other workloads / step forms "
+                            "(`cpu_baseline`, `prr_parity`, `also_measured`)")
+    scope.add_argument("--no-cpu-baseline", "--lean", dest="lean", action="store_true",
+                       help="only the timed run: what a run without --full does (kept for older command lines)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed step's outputs as DIR/<name>.npy (e.g. bench_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        print("bench.py: --steps must be >= 1 and --warmup >= 0", file=sys.stderr)
+        return 2
 
     if not under_launcher():
         if args.gpus > 1:
@@ -819,6 +866,8 @@ def main() -> int:
     emit = bool(args.emit_chobs)
     env, res = run_workload(args.workload, device, rank, world, args.steps, args.warmup, args.batch, args.out_dtype,
                             args.step_mode, emit, args.sticky, use_dist)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs, emit)       # rank 0's envs
     totals = gather_metrics(env)                         # RCCL all-reduce (metrics only)
     per_rank = None
     if use_dist:
@@ -874,9 +923,9 @@ def main() -> int:
     }
     if per_rank:
         line["per_rank"] = per_rank
-    if world == 1 and not args.lean:
+    if world == 1 and args.full:
         # short same-run measurements of the other BASELINE.json configurations and of the
-        # opposite --emit-chobs setting (each: PREROLL untimed slots + a few timed ones)
+        # opposite --emit-chobs setting (each: its PREROLL_SLOTS untimed slots + a few timed ones)
         also = {}
         specs = [("c2_emit_chobs_%d" % (0 if emit else 1), "c2", dict(emit_chobs=not emit, steps=300)),
                  ("c4shard", "c4shard", dict(emit_chobs=emit, steps=100)),
@@ -927,7 +976,7 @@ def main() -> int:
             except Exception as exc:
                 also["rollout_sps"] = {"error": repr(exc)[:200]}
         line["also_measured"] = also
-    if not args.lean:
+    if args.full:
         # host-side legs, on rank 0 at every N (the other ranks have left the job by now)
         line["cpu_baseline"] = cpu_baseline(cfg)
         line["prr_parity"] = prr_parity(cfg, device)
