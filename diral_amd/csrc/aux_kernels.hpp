@@ -42,11 +42,7 @@ __global__ void sample_kernel(int total, int A, uint64_t seed, uint64_t idx0, in
 __global__ void velocity_kernel(int total, const uint8_t* draws, uint64_t seed, uint64_t idx0, double* vel) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
-  const int r = draws ? (int)draws[i] : 1 + (int)(rng_u64(seed, 4, idx0 + (uint64_t)i) % 3ull);
-  double v = vel[i];
-  if (r == 1) { v += 0.55; if (v > 2.77) v = 2.77; }
-  else if (r == 2) { v -= 0.55; if (v < 1.1) v = 1.1; }
-  vel[i] = v;
+  vel[i] = draws ? velocity_step(vel[i], (int)draws[i]) : velocity_draw(vel[i], seed, idx0 + (uint64_t)i);
 }
 
 // subject-major packed table -> reference-shaped [env][viewer][subject] planes
@@ -387,32 +383,7 @@ __global__ void sps_step_wave_kernel(int agents, int A, const T* src, const int3
   }
 }
 
-// np.sum over one row in NumPy's order (numpy/_core/src/umath/loops_utils.h pairwise_sum): fewer
-// than 8 elements sequentially; up to 128: eight running accumulators combined as
-// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) plus a sequential tail; above: split at n/2 rounded down to a
-// multiple of 8, recursively.  Float addition is not associative: the driver's shaped rewards
-// (main_test.py:171, 205-206) are bit-identical only in this order.
-template <typename T>
-__device__ T np_pairwise_sum(const T* a, int n) {
-  if (n < 8) {
-    T res = (T)0;
-    for (int i = 0; i < n; ++i) res = res + a[i];
-    return res;
-  }
-  if (n <= 128) {
-    T r[8];
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8)
-      for (int j = 0; j < 8; ++j) r[j] = r[j] + a[i + j];
-    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res = res + a[i];
-    return res;
-  }
-  int n2 = n / 2;
-  n2 -= n2 % 8;
-  return np_pairwise_sum(a, n2) + np_pairwise_sum(a + n2, n - n2);
-}
+// (np_pairwise_sum, np.sum over one row in NumPy's order: policy_device.hpp)
 
 // The driver's per-slot reward post-processing (main_test.py:150-206), for `envs` envs in one
 // launch; 64 envs per 256-thread block: one thread per env sums and decides, then all threads

@@ -374,6 +374,7 @@ struct StepDispatch {
   bool pol_ok;          // the POL instantiation of step_fast64 (policy epilogue inside the launch) takes this call
   bool prefill_ok;      // ... and the K-slot form of it runs this configuration's random prefill (diral_env_prefill: my_step_design's
                         // reward is computed in P2 there, so the design switch does not count against it)
+  bool wide_kslots_ok;  // step_wide_slots_kernel (k_wide_slots.hip) takes K > 1 slots of diral_env_step_policy at 64 < N <= 256
 };
 StepDispatch step_dispatch(const DiralEnv* e, const StepParams& p) {
   StepDispatch d;
@@ -393,6 +394,7 @@ StepDispatch step_dispatch(const DiralEnv* e, const StepParams& p) {
   d.extra = d.design || d.la != nullptr || d.trace != nullptr || d.prr || d.notab || d.nomove;
   d.pol_ok = d.use_fast64 && e->flat_y && !d.ch && !d.extra && p.N >= 8;
   d.prefill_ok = d.use_fast64 && e->flat_y && d.design && d.la == nullptr && d.trace == nullptr && !d.prr && !d.notab && !d.nomove && p.N >= 8;
+  d.wide_kslots_ok = d.use_wide && !d.ch && !d.extra;
   return d;
 }
 
@@ -465,6 +467,7 @@ hipError_t launch_step_any(DiralEnv* e, const StepParams& p, hipStream_t s, cons
     // K slots per launch (diral_env_step_policy, DiralSlotPolicy::slots > 1): blocks = envs in order - over K slots a
     // straggler averages out; the slow-env sets stay as the last one-slot launch left them (complete or empty), unread
     const bool kslots = pol && ((d.pol_ok && pol->K > 1) || (pol->prefill && d.prefill_ok));
+    const bool wide_kslots = pol && !pol->prefill && pol->K > 1 && d.wide_kslots_ok;
     // (step_wide: the packed form at N <= 128 only - its slow envs are 4 x the others; the plane form's are 1.6 x and measured
     // 4 % SLOWER dispatched first, N > 128 packed runs on dense topologies without any: - 0.7 % for the bookkeeping)
     // Round 6: with the far-entry guard (step_wide.hpp `wide_far_guard`) the flagged passes of a highway that broke apart run
@@ -472,7 +475,7 @@ hipError_t launch_step_any(DiralEnv* e, const StepParams& p, hipStream_t s, cons
     // block) now costs more than it orders: C5 0.930 ms with it, 0.875 in batch order (one box, interleaved, profiles/r06).
     // DIRAL_WIDE_SLOW_FIRST=1 at create brings it back (A/B).
     const bool wide_slow = use_wide && vpl == 2 && e->tcode != nullptr && e->wide_slow_first;
-    if ((use_fast64 || wide_slow) && e->slow && e->slow_first && !kslots) {
+    if ((use_fast64 || wide_slow) && e->slow && e->slow_first && !kslots && !wide_kslots) {
       const size_t w = slow_set_words(e);
       uint32_t* const set_r = e->slow + (e->slow_launches % 3) * w;
       uint32_t* const set_w = e->slow + ((e->slow_launches + 1) % 3) * w;
@@ -503,6 +506,13 @@ hipError_t launch_step_any(DiralEnv* e, const StepParams& p, hipStream_t s, cons
     e->last_kernel = (use_wide ? DIRAL_KERNEL_WIDE : DIRAL_KERNEL_FAST64) | (k.rich ? DIRAL_KERNEL_RICH : 0) |
                      ((k.packed || use_fast64) ? DIRAL_KERNEL_PACKED : 0) |
                      (k.extra ? DIRAL_KERNEL_EXTRA : 0) | (k.ch ? DIRAL_KERNEL_CH : 0) | (use_ring ? DIRAL_KERNEL_RING : 0);
+    if (wide_kslots) {
+      // K slots per launch with the policy epilogue at 64 < N <= 256: step_wide_slots_kernel, blocks = envs in batch order
+      if (!k.rich) { r.plain_state = 1; }
+      e->last_kernel |= DIRAL_KERNEL_RICH | DIRAL_KERNEL_POLICY;
+      if (fused) *fused = true;
+      return launch_wide_slots(f, r, *pol, k, vpl, p.B, s);
+    }
     if (use_wide) {
       const int grid = p.B + (slow_first ? fast_slow_max(p.B) : 0);
       return vpl == 2 ? launch_wide2(f, r, k, grid, s) : launch_wide4(f, r, k, grid, s);
@@ -825,6 +835,7 @@ int diral_env_create(const DiralCfg* cfg, int batch, int device, DiralEnv** out)
     CREATE_TRY(set_attr_general(e->vpl, l.total));
     if (e->vpl == 2 && e->A <= kWideMaxA) CREATE_TRY(set_attr_wide2(e->A, e->K));
     if (e->vpl == 4 && e->A <= kWideMaxA) CREATE_TRY(set_attr_wide4(e->A, e->K));
+    if (e->vpl > 1 && e->A <= kWideMaxA) CREATE_TRY(set_attr_wide_slots(e->vpl, e->A, e->K));
     CREATE_TRY(set_attr_observe(e->N, e->K));
   }
 #undef CREATE_TRY
@@ -1019,7 +1030,9 @@ int diral_env_step_policy(DiralEnv* e, int mode, const int32_t* actions, int64_t
   q.prefill = 0; q.actions_all = nullptr; q.rew_in = nullptr;
   if (slots > 1 && (pol->draw_counter || pol->draw_keep || pol->draw_choice)) return DIRAL_ERR_BAD_ARG;
   // (decided before anything is launched: a caller without a channel-observation buffer can retry with one)
-  const bool will_fuse = step_dispatch(e, p).pol_ok;
+  // (K > 1 at 64 < N <= 256: step_wide_slots_kernel; a one-slot call there keeps its three launches)
+  const StepDispatch d = step_dispatch(e, p);
+  const bool will_fuse = d.pol_ok || (slots > 1 && d.wide_kslots_ok);
   if (!will_fuse && (!chobs_out || slots > 1)) return DIRAL_ERR_UNSUPPORTED;
   bool fused = false;
   HIP_TRY(e, launch_step_any(e, p, (hipStream_t)stream, will_fuse ? &q : nullptr, &fused));

@@ -1,5 +1,5 @@
 // launch.hpp - host-side launchers of the step kernels.  Each kernel family lives in its own
-// translation unit (k_fast64.hip, k_wide2.hip, k_wide4.hip, k_general.hip) so that hipcc builds
+// translation unit (k_fast64.hip, k_wide2.hip, k_wide4.hip, k_wide_slots.hip, k_general.hip) so that hipcc builds
 // them in parallel; diral_env.hip only sees these declarations.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -31,8 +31,12 @@ hipError_t launch_fast64_policy(const FastParams& f, const RichParams& r, const 
 hipError_t launch_fast64_slots(const FastParams& f, const RichParams& r, const PolParams& q, bool out64, int B, hipStream_t s);
 hipError_t launch_wide2(const FastParams& f, const RichParams& r, const KernelSel& k, int B, hipStream_t s);
 hipError_t launch_wide4(const FastParams& f, const RichParams& r, const KernelSel& k, int B, hipStream_t s);
+// K slots per launch of the wide step with the policy epilogue (k_wide_slots.hip): my_step, RICH, no run-time extras
+hipError_t launch_wide_slots(const FastParams& f, const RichParams& r, const PolParams& q, const KernelSel& k, int vpl, int B,
+                             hipStream_t s);
 hipError_t set_attr_wide2(int A, int K);
 hipError_t set_attr_wide4(int A, int K);
+hipError_t set_attr_wide_slots(int vpl, int A, int K);
 hipError_t launch_observe(const ObserveParams& p, const RichParams& r, bool flat, bool out64, int B, hipStream_t s);
 hipError_t set_attr_observe(int N, int K);
 hipError_t launch_general(int vpl, bool fast, const StepParams& p, uint32_t lds, hipStream_t s);

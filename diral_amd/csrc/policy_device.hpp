@@ -237,4 +237,49 @@ __device__ inline T np_row_sum_wave(T a, int N, int lane) {
   return sr;
 }
 
+// np.sum over one row in NumPy's order (numpy/_core/src/umath/loops_utils.h pairwise_sum): fewer
+// than 8 elements sequentially; up to 128: eight running accumulators combined as
+// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) plus a sequential tail; above: split at n/2 rounded down to a
+// multiple of 8, recursively.  Float addition is not associative: the driver's shaped rewards
+// (main_test.py:171, 205-206) are bit-identical only in this order.  DEPTH bounds the splits at compile time - a
+// recursive call would give the kernel a dynamic stack -: 24 cover any int n; n <= 256 needs 2 (n = 249 ... 255 split into
+// 120 + 129 ... 135, whose second half splits again).
+template <typename T, int DEPTH = 24>
+__device__ T np_pairwise_sum(const T* a, int n) {
+  if (n < 8) {
+    T res = (T)0;
+    for (int i = 0; i < n; ++i) res = res + a[i];
+    return res;
+  }
+  if (n <= 128) {
+    T r[8];
+    for (int j = 0; j < 8; ++j) r[j] = a[j];
+    int i = 8;
+    for (; i < n - (n % 8); i += 8)
+      for (int j = 0; j < 8; ++j) r[j] = r[j] + a[i + j];
+    T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+    for (; i < n; ++i) res = res + a[i];
+    return res;
+  }
+  if constexpr (DEPTH > 0) {
+    int n2 = n / 2;
+    n2 -= n2 % 8;
+    return np_pairwise_sum<T, DEPTH - 1>(a, n2) + np_pairwise_sum<T, DEPTH - 1>(a + n2, n - n2);
+  } else {
+    __builtin_trap();                                              // (n beyond what DEPTH splits reach: never called so)
+    return (T)0;
+  }
+}
+
+// Network.update_velocity (network.py:208-223) of one vehicle: draw r in {1, 2, 3} - +0.55 up to 2.77, -0.55 down to 1.1,
+// unchanged.  velocity_kernel and the K-slot step kernels (an episode end inside the launch) draw alike.
+__device__ inline double velocity_step(double v, int r) {
+  if (r == 1) { v += 0.55; if (v > 2.77) v = 2.77; }
+  else if (r == 2) { v -= 0.55; if (v < 1.1) v = 1.1; }
+  return v;
+}
+__device__ inline double velocity_draw(double v, uint64_t seed, uint64_t idx) {
+  return velocity_step(v, 1 + (int)(rng_u64(seed, 4, idx) % 3ull));
+}
+
 }  // namespace diral

@@ -1307,11 +1307,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
         if ((unsigned int)tt % (unsigned int)p.episode_interval == (unsigned int)p.episode_interval - 1u) {
           // (network.py:208-223, as velocity_kernel draws it: diral_env_update_velocity(env, NULL, vel_seed + episode))
           const uint64_t vseed = q.vel_seed + (uint64_t)((unsigned int)tt / (unsigned int)p.episode_interval);
-          const int r3 = 1 + (int)(rng_u64(vseed, 4, q.idx0 + (uint64_t)bN + (uint64_t)lane) % 3ull);
-          double v = myvel;
-          if (r3 == 1) { v += 0.55; if (v > 2.77) v = 2.77; }
-          else if (r3 == 2) { v -= 0.55; if (v < 1.1) v = 1.1; }
-          myvel = live ? v : 0.0;
+          myvel = live ? velocity_draw(myvel, vseed, q.idx0 + (uint64_t)bN + (uint64_t)lane) : 0.0;
         }
         if (last && wave == 0 && live) q.vel_w[bN + lane] = myvel;
       }

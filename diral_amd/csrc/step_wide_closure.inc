@@ -227,7 +227,13 @@
             // within 2^-45 of exact) - else (an edge hit, |v| at Rb) the lane takes the exact NumPy statement, behind a
             // uniform branch.  Three of four entries of a 4 km highway lie beyond the bin range: the histogram increment
             // stays predicated.
+#ifndef DIRAL_WIDE_KSLOTS
             const unsigned int agt = (uval ? (agq | ob) : 0xffffffffu) | kmask;
+#else /* DIRAL_WIDE_KSLOTS */
+            // (K slots without the histogram: every byte "past the age limit" - nothing counts, no plane xpos is fetched for
+            // counting; the hand-overs to the planes still happen)
+            const unsigned int agt = tally_on ? ((uval ? (agq | ob) : 0xffffffffu) | kmask) : 0xffffffffu;
+#endif /* DIRAL_WIDE_KSLOTS */
             // Network.dist_piggy + get_positional_dist_2_piggy (network.py:538-558, 473-513) of the entry at xpos xg; all
             // y == 0: v = x1 - x2 IS d * sign exactly, d = |v| (see step_fast64.hpp)
             auto exact_bin = [&](double xg, bool& cnt) -> int {               // (rare: an exact edge hit, |v| at Rb)

@@ -383,8 +383,10 @@ class VecV2VEnv:
         unsuccessful action more than `threshold` times (main_test.py:194-203; `counter`, `prev_actions` [B, N] int32,
         updated in place - diral_driver_shape's flag bit 2); needs `shaped_out`.
 
-        `slots` = K > 1: K slots in ONE launch, the env kept on the chip from slot to slot (include/diral_env.h,
-        DiralSlotPolicy::slots): `actions` are slot t's, the policy decides the later ones; obs / reward / done / the channel
+        `slots` = K > 1: K slots in ONE launch (include/diral_env.h, DiralSlotPolicy::slots; N <= 64: the env kept on
+        the chip from slot to slot, 64 < N <= 256: step_wide_slots_kernel, the tables in HBM between slots, no channel
+        observation written unless `want_chobs`; measured per slot against slots = 1 - profiles/kslots_wide/ -: 3 %
+        faster at 256 vehicles (C3), about a third SLOWER at 128 vehicles (C5)): `actions` are slot t's, the policy decides the later ones; obs / reward / done / the channel
         observation are the LAST slot's (without `want_obs` no slot computes a state vector), `shaped_out` [K, B, N] and
         `sum_r_out` / `collision_out` [K, B] hold every slot's; configs with mobility_vary update the velocities at the
         episode ends inside the launch (`update_velocity(seed=vel_seed + slot // episode_interval)`).  Equal, bit for bit,
@@ -416,7 +418,9 @@ class VecV2VEnv:
         # (whether the slot runs fused is the library's decision - kernel family, step mode, run-time extras; a call
         # without a channel-observation buffer that cannot run fused comes back DIRAL_ERR_UNSUPPORTED before anything
         # is launched, and is repeated with the buffer from then on)
-        fusable = (self.N <= 64 and self.N >= 8 and self.A <= 64) and not getattr(self, "_policy_needs_chobs", False)
+        # K > 1 runs fused or not at all (DIRAL_ERR_UNSUPPORTED): no channel-observation buffer unless asked for - at
+        # 64 < N <= 256 the K-slot kernel would otherwise write [B, N, A] for nothing on every launch
+        fusable = K > 1 or ((self.N <= 64 and self.N >= 8 and self.A <= 64) and not getattr(self, "_policy_needs_chobs", False))
         if (want_chobs or not fusable) and slot["chobs"] is None:
             slot["chobs"] = torch.zeros((self.B, self.N, self.CW), dtype=self.out_dtype, device=self.device)
         self._obs, self._rew, self._done, self._chobs = slot["obs"], slot["rew"], slot["done"], slot["chobs"]

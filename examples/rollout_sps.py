@@ -4,6 +4,7 @@ B parallel envs, with the SPS baseline (algorithms/v2x_sps.py) as the policy.
 Everything stays on the GPU; the only host traffic is the final metric read-out.
 
   python examples/rollout_sps.py --envs 1024 --slots 500
+  python examples/rollout_sps.py --config c3 --envs 8192 --slots 100 --one-launch --slots-per-launch 25   # 256 UE / 64 res
   python -m torch.distributed.run --nproc-per-node 8 examples/rollout_sps.py --envs 262144   # sharded
 """
 import argparse
@@ -16,6 +17,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from diral_amd import c2_config  # noqa: E402
+from diral_amd.config import bench_config  # noqa: E402
 from diral_amd.driver import DriverLoop  # noqa: E402
 from diral_amd.metrics import gather_metrics  # noqa: E402
 from diral_amd.shard import make_sharded_env, rank_world  # noqa: E402
@@ -34,12 +36,16 @@ def main():
     ap.add_argument("--slots-per-launch", type=int, default=1,
                     help="with --one-launch: K slots in ONE launch (DiralSlotPolicy::slots): the env stays on the chip from "
                          "slot to slot, only the per-slot shaped rewards and the metrics leave it")
+    ap.add_argument("--config", choices=["c2", "c5", "c3"], default="c2",
+                    help="c2: 64 UE / 32 res (the default); c5: 128 UE / 64 res with mobility_vary; c3: 256 UE / 64 res "
+                         "(BASELINE configs[1], [4], [2])")
     args = ap.parse_args()
     rank, local_rank, world = rank_world()
     torch.cuda.set_device(local_rank)
     if world > 1:
         torch.distributed.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-    cfg = c2_config()
+    cfg = {"c2": lambda: c2_config(), "c5": lambda: bench_config(128, 64, 4000.0, mobility_vary=True),
+           "c3": lambda: bench_config(256, 64, 4000.0)}[args.config]()
     # io_ring=2: state and next_state of consecutive slots live in two alternating output sets (no copies)
     env, start = make_sharded_env(cfg, args.envs, out_dtype=torch.float32, io_ring=2)
     env.reset_topology(seed=1234)                     # one global seed: the shard offset selects the envs

@@ -440,9 +440,12 @@ typedef struct DiralSlotPolicy {
   uint64_t seed;
   const int64_t* seed_clock;      /* NULL, or a device counter added to the seed */
   int32_t* actions_out;           /* [B][N] */
-  /* K slots in ONE launch (ABI 6).  slots <= 1: one slot, as above.  slots = K > 1 (configurations the fused kernel takes -
-   * N <= 64, my_step, the flat highway; otherwise DIRAL_ERR_UNSUPPORTED with nothing launched): the workgroup of an env
-   * keeps it on the chip for K slots of [env step -> shaping -> SPS decision], `actions` being slot 0's and the policy's
+  /* K slots in ONE launch (ABI 6).  slots <= 1: one slot, as above.  slots = K > 1 (configurations the fused kernels take -
+   * N <= 256 vehicles, my_step, the flat highway, A <= 64, none of the run-time extras (arrival stamps, trace replay, PRR
+   * tracking, static topologies, handles without piggybacked tables), no State.piggybacking; otherwise
+   * DIRAL_ERR_UNSUPPORTED with nothing launched): the workgroup of an env runs K slots of [env step -> shaping -> SPS
+   * decision] back to back (N <= 64 keeps the env on the chip; 64 < N <= 256 leaves its tables in HBM / L2 between
+   * slots, as a one-slot launch does), `actions` being slot 0's and the policy's
    * decisions the later ones'.  Equal, bit for bit, to K one-slot calls with t, t + 1, ... and seed, seed + 1, ... (plus
    * diral_env_update_velocity(env, NULL, vel_seed + slot / episode_interval) behind every slot that ends an episode, when
    * the config has mobility_vary) - tables, positions, velocities, metrics, policy state, actions_out (the actions of

@@ -1,0 +1,113 @@
+"""The closed SPS loop at 64 < N <= 256 (BASELINE configs[4] = C5: 128 UE / 64 res, mobility_vary, 16384 envs; configs[2]
+= C3: 256 UE / 64 res, 8192 envs), timed interleaved in one process, one env per form:
+  three-launch  step_policy(slots=1): the step with the channel observation, diral_driver_shape, diral_sps_step_chobs;
+  K=25          step_policy(slots=25) with per-slot outputs (shaped rewards, sums, collisions), no state vector;
+  K=25 + state  the same plus the last slot's state vector.
+Prints us per slot per form and checks that the forms leave equal tables, positions, velocities, metrics and policy state.
+
+  python profiles/kslots_wide_bench.py [--configs c5,c3] [--rounds 6] [--warm 2]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from diral_amd.config import KERNEL_POLICY, bench_config  # noqa: E402
+from diral_amd.sps import SpsPolicy  # noqa: E402
+from diral_amd.vec_env import VecV2VEnv  # noqa: E402
+
+SHAPES = {"c5": (128, 64, 4000.0, 16384, True), "c3": (256, 64, 4000.0, 8192, False)}
+K = 25
+VEL_SEED = 77
+
+
+def run(name, rounds, warm):
+    N, A, L, B, vary = SHAPES[name]
+    cfg = bench_config(N, A, L, mobility_vary=vary)
+    dev = torch.device("cuda:0")
+    forms = []
+    for form in ("three-launch", "K=25", "K=25 + state"):
+        env = VecV2VEnv(cfg, batch=B, device=dev, out_dtype=torch.float32)
+        env.reset_topology(seed=1234)
+        pol = SpsPolicy(B, N, A, device=dev, seed=5)
+        acts = [pol.prev_action.clone(), torch.empty_like(pol.prev_action)]
+        sh = torch.empty((K, B, N), dtype=torch.float32, device=dev)
+        sr = torch.empty((K, B), dtype=torch.float32, device=dev)
+        co = torch.empty((K, B), dtype=torch.float32, device=dev)
+        forms.append(dict(form=form, env=env, pol=pol, acts=acts, sh=sh, sr=sr, co=co, t=0, i=0, ms=[]))
+
+    def slots25(f):
+        env, pol = f["env"], f["pol"]
+        if f["form"] == "three-launch":
+            for k in range(K):
+                i = f["i"]
+                env.step_policy(f["acts"][i], f["t"], pol, f["acts"][i ^ 1], shaped_out=f["sh"][k], sum_r_out=f["sr"][k],
+                                collision_out=f["co"][k], global_reward_avg=True, want_obs=False)
+                if vary and f["t"] % cfg.episode_interval == cfg.episode_interval - 1:
+                    env.update_velocity(seed=VEL_SEED + f["t"] // cfg.episode_interval)
+                f["i"] ^= 1
+                f["t"] += 1
+        else:
+            i = f["i"]
+            env.step_policy(f["acts"][i], f["t"], pol, f["acts"][i ^ 1], shaped_out=f["sh"], sum_r_out=f["sr"],
+                            collision_out=f["co"], global_reward_avg=True, slots=K, vel_seed=VEL_SEED,
+                            want_obs=f["form"] == "K=25 + state")
+            assert env.last_kernel() & KERNEL_POLICY
+            f["i"] ^= 1
+            f["t"] += K
+
+    for r in range(warm + rounds):
+        for f in forms:                                         # interleaved: one round of 25 slots per form
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            slots25(f)
+            e1.record()
+            torch.cuda.synchronize()
+            if r >= warm:
+                f["ms"].append(e0.elapsed_time(e1))
+    ref = forms[0]
+    sa = ref["env"].export_state()
+    equal = {}
+    for f in forms[1:]:
+        sb = f["env"].export_state()
+        ok = all(torch.equal(sa[k], sb[k]) for k in sa)
+        ok = ok and torch.equal(ref["env"].metrics(), f["env"].metrics())
+        ok = ok and torch.equal(ref["pol"].prev_action, f["pol"].prev_action) and torch.equal(ref["pol"].counter, f["pol"].counter)
+        ok = ok and torch.equal(ref["acts"][ref["i"]], f["acts"][f["i"]])
+        ok = ok and torch.equal(ref["sh"], f["sh"]) and torch.equal(ref["sr"], f["sr"]) and torch.equal(ref["co"], f["co"])
+        equal[f["form"]] = bool(ok)
+    out = {"config": name, "N": N, "A": A, "B": B, "mobility_vary": vary, "slots_per_round": K, "rounds": rounds,
+           "us_per_slot": {}, "us_per_slot_rounds": {}, "equal_to_three_launch": equal}
+    for f in forms:
+        ms = sorted(f["ms"])
+        out["us_per_slot"][f["form"]] = round(ms[len(ms) // 2] * 1e3 / K, 2)
+        out["us_per_slot_rounds"][f["form"]] = [round(m * 1e3 / K, 2) for m in f["ms"]]
+    base = out["us_per_slot"]["three-launch"]
+    out["saving_vs_three_launch"] = {k: round(1.0 - v / base, 4) for k, v in out["us_per_slot"].items() if k != "three-launch"}
+    for f in forms:
+        f["env"].check()
+    del forms
+    torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="c5,c3")
+    ap.add_argument("--rounds", type=int, default=6)
+    ap.add_argument("--warm", type=int, default=2)
+    args = ap.parse_args()
+    for name in args.configs.split(","):
+        r = run(name, args.rounds, args.warm)
+        print("%s: %s  equal: %s" % (name, "  ".join("%s %.1f us/slot" % kv for kv in r["us_per_slot"].items()),
+                                     r["equal_to_three_launch"]))
+        print(json.dumps(r))
+
+
+if __name__ == "__main__":
+    main()
