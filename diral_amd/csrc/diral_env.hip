@@ -54,7 +54,6 @@ struct DiralEnv {
   bool slow_first = true;       // DIRAL_NO_SLOW_FIRST=1 at create: blocks = envs in order (A/B timing, tests)
   bool capture_rotates = false; // diral_env_set_capture_rotation: captured launches rotate the sets too (graphs of 3 k launches)
   bool wide_slow_first = false;  // DIRAL_WIDE_SLOW_FIRST=1 at create: step_wide's packed form at N <= 128 dispatches its slow envs first (round 5's default)
-  bool type1_wide_lanes = false; // DIRAL_TYPE1_LANES=wide at create: rounds 3-4's 64 values per lane in posdist_type1_lanes_kernel (A/B)
   int f32_margin = -1;          // DIRAL_F32_MARGIN=<n> at create: 0 = no float32 screening of the bin, n > 0 = a band of at
                                 //   least n / 65536 bin widths (tests: a wide band sends many entries to float64); -1 = the bound
   int32_t* la = nullptr;
@@ -448,8 +447,8 @@ hipError_t launch_step_any(DiralEnv* e, const StepParams& p, hipStream_t s, cons
     f.B = p.B;
     {
       // float32 screening of the histogram bin (step_fast64.hpp, fast quads): everything float32 can lose, in bin widths,
-      // for positions in [0, L] - two conversions of a position, the subtraction of an in-range difference, the
-      // constant and the fma at t <= K - with a factor of two on top; as 1 / 65536ths, rounded up, + 1
+      // for positions in [0, L] - the three conversions and the fma at t <= K below - with a factor of two on top; as
+      // 1 / 65536ths, rounded up, + 1
       const double w = (p.Rb - (-p.Rb)) / (double)p.K;
       const double xmax = p.L;
       // (the kernel computes t = fma(float(xpos), float(inv_w 2^16), float((Rb - npx) inv_w 2^16)): the conversion of the
@@ -557,7 +556,7 @@ hipError_t launch_posdist_if_needed(DiralEnv* e, const StepParams& p, hipStream_
   q.flat_y = e->flat_y ? 1 : 0;
   const bool full_flat = full && e->flat_y;                     // one ranking of the env's x serves every viewer
   const bool type1_n64 = type1 && p.NV == 64 && p.K <= DIRAL_SMALL_MAX_BINS;   // lane = viewer, sort in registers
-  const bool type1_lanes = type1 && !type1_n64 && p.N <= DIRAL_SMALL_MAX_USERS && p.K <= DIRAL_SMALL_MAX_BINS;   // 2 / 4 lanes per viewer (N <= 128 / 256)
+  const bool type1_lanes = type1 && !type1_n64 && p.N <= DIRAL_SMALL_MAX_USERS && p.K <= DIRAL_SMALL_MAX_BINS;   // 4 / 8 lanes per viewer (N <= 128 / 256)
   const bool type1_generic = type1 && !type1_n64 && !type1_lanes;   // beyond: posdist_kernel's literal statement
   if (full_flat) {
     q.do_full = 1;
@@ -572,17 +571,14 @@ hipError_t launch_posdist_if_needed(DiralEnv* e, const StepParams& p, hipStream_
     q.do_type1 = 0; q.ring = nullptr; q.tcode = nullptr; q.tage = nullptr; q.tseq = nullptr;
   }
   if (type1_lanes) {
-    const bool wide_lanes = e->type1_wide_lanes;               // (read once at create: never an env lookup on the step path)
     const int npad = p.N <= 128 ? 128 : 256;
-    const int lpv = npad / (wide_lanes ? 64 : 32), vw = 64 / lpv, nvb = (p.N + vw - 1) / vw;
+    const int lpv = npad / 32, vw = 64 / lpv, nvb = (p.N + vw - 1) / vw;
     q.do_type1 = 1;
     q.ring = (e->ring && !e->plane_valid) ? e->ring : nullptr;
     if (q.ring && e->tcode) { q.tcode = e->tcode; q.tage = e->tage; q.tseq = e->tseq; }
     const uint32_t lds = posdist_type1_lanes_lds_bytes(p.K, npad, lpv);
     const dim3 grid((unsigned)p.B * nvb);
-    if (wide_lanes && lpv == 2) hipLaunchKernelGGL((posdist_type1_lanes_kernel<2, 64>), grid, dim3(64), lds, s, q);
-    else if (wide_lanes) hipLaunchKernelGGL((posdist_type1_lanes_kernel<4, 64>), grid, dim3(64), lds, s, q);
-    else if (lpv == 4) hipLaunchKernelGGL((posdist_type1_lanes_kernel<4, 32>), grid, dim3(64), lds, s, q);
+    if (lpv == 4) hipLaunchKernelGGL((posdist_type1_lanes_kernel<4, 32>), grid, dim3(64), lds, s, q);
     else hipLaunchKernelGGL((posdist_type1_lanes_kernel<8, 32>), grid, dim3(64), lds, s, q);
     q.do_type1 = 0; q.ring = nullptr; q.tcode = nullptr; q.tage = nullptr; q.tseq = nullptr;
   }
@@ -874,7 +870,6 @@ int diral_env_create(const DiralCfg* cfg, int batch, int device, DiralEnv** out)
   r.H = cfg->highway_height; r.vel = e->vel; r.pos_y = e->pos_y;
   // test hooks, read ONCE here (never on the step path): force the general kernel
   if (const char* ws = std::getenv("DIRAL_WIDE_SLOW_FIRST")) e->wide_slow_first = ws[0] == '1';
-  if (const char* tl = std::getenv("DIRAL_TYPE1_LANES")) e->type1_wide_lanes = std::strcmp(tl, "wide") == 0;
   if (std::getenv("DIRAL_NO_FAST64") && e->vpl == 1) e->kernel_path = DIRAL_PATH_GENERAL;
   if (std::getenv("DIRAL_NO_WIDE") && e->vpl > 1 && !e->large) e->kernel_path = DIRAL_PATH_GENERAL;
   *out = e;

@@ -418,9 +418,6 @@ __device__ inline double pd_quad_perm(double x) {
 }
 constexpr int kQuadXor1 = 0xB1, kQuadXor2 = 0x4E, kQuadXor3 = 0x1B, kQuadShr1 = 0x90;   // quad_perm [1,0,3,2] [2,3,0,1] [3,2,1,0] [0,0,1,2]
 constexpr int kRowHalfMirror = 0x141, kRowShr1 = 0x111;                                 // lane s <-> 7 - s within a row half; lane s <- s - 1 within a row of 16
-#ifndef DIRAL_TYPE1_CUMSUM_INPLACE
-#define DIRAL_TYPE1_CUMSUM_INPLACE 1     // posdist_type1_lanes_kernel: the sequential sum by the lane whose turn it is only, one store per slot boundary
-#endif
 #ifndef DIRAL_TYPE1_MINWAVES
 #define DIRAL_TYPE1_MINWAVES 4           // posdist_type1_lanes_kernel<LPV, 32>: waves per SIMD the register allocation is held to
 #endif
@@ -431,11 +428,11 @@ __device__ inline double pd_pick(bool upper, double a, double b) {        // the
 }
 
 template <int LPV, int VL>
-__global__ __launch_bounds__(64, VL == 64 ? 2 : DIRAL_TYPE1_MINWAVES) void posdist_type1_lanes_kernel(const PosdistParams p) {
-  // VL subjects per lane, LPV lanes per viewer: <2, 64> / <4, 64> (rounds 3-4: 128 VGPRs of values, two waves per SIMD - the
-  // kernel waited for its own round trips) or <4, 32> / <8, 32> (N <= 128 / 256: half the values per lane, one more level of
-  // cross-lane merging, twice the waves)
-  static_assert((LPV == 2 || LPV == 4 || LPV == 8) && (VL == 32 || VL == 64), "a viewer's lanes share a row of 8");
+__global__ __launch_bounds__(64, DIRAL_TYPE1_MINWAVES) void posdist_type1_lanes_kernel(const PosdistParams p) {
+  // VL subjects per lane, LPV lanes per viewer: <4, 32> / <8, 32> (N <= 128 / 256).  (Rounds 3-4 ran <2, 64> / <4, 64>:
+  // 128 VGPRs of values, two waves per SIMD - the kernel waited for its own round trips: removed; last at d94e7da.)
+  static_assert(LPV == 2 || LPV == 4 || LPV == 8, "a viewer's lanes share a row of 8");
+  static_assert(VL == 32, "32 subjects per lane");
   constexpr int VW = 64 / LPV;                                           // viewers per wave
   constexpr int ST = VW | 1;                                             // doubles per row of edge sums (one column per viewer of the wave)
   extern __shared__ __align__(16) unsigned char smem[];
@@ -560,7 +557,7 @@ __global__ __launch_bounds__(64, VL == 64 ? 2 : DIRAL_TYPE1_MINWAVES) void posdi
       }
     }
   }
-  // a lane's 64 values are a bitonic sequence: ascending by the last six steps of the network
+  // a lane's VL values are a bitonic sequence: ascending by the last log2(VL) steps of the network
   auto merge_in_lane = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int j = VL / 2; j > 0; j >>= 1) {
@@ -649,7 +646,6 @@ __global__ __launch_bounds__(64, VL == 64 ? 2 : DIRAL_TYPE1_MINWAVES) void posdi
     const int c = est + 1 - (s < e0 ? 1 : 0) + ((est + 1 < K && !(s < e1)) ? 1 : 0);
     cpk[i >> 2] |= (uint32_t)(real ? c : K + 1) << (8 * (i & 3));
   }
-#if DIRAL_TYPE1_CUMSUM_INPLACE
   // NumPy's cumsum in its own order (cw[j + 1] = cw[j] + sa[j], numpy/lib/_histograms_impl.py): a viewer's LPV lanes take
   // turns, lowest ranks first, each continuing from the total the lane below ended with.  The histogram needs the running
   // sum behind the LAST value of every slot only (searchsorted + diff): that value - and no other, and only in its lane's
@@ -682,21 +678,6 @@ __global__ __launch_bounds__(64, VL == 64 ? 2 : DIRAL_TYPE1_MINWAVES) void posdi
       }
     }
   }
-#else
-  double acc = 0.0;
-#pragma unroll 1
-  for (int ph = 0; ph < LPV; ++ph) {
-    const double before = pd_quad_perm<kRowShr1>(acc);                     // the running sum of the lane below, complete by now
-    const bool active = sub == ph;
-    if (active) acc = ph > 0 ? before : 0.0;                               // (what a lane adds outside its own pass goes to the spare slot)
-#pragma unroll
-    for (int i = 0; i < VL; ++i) {
-      acc = acc + v[i];
-      const int c = (int)((cpk[i >> 2] >> (8 * (i & 3))) & 255u);
-      col[(active ? c : K + 1) * ST] = acc;
-    }
-  }
-#endif
   if (sub == 0) {
     double cur = 0.0;
     for (int j = 0; j <= K; ++j) {

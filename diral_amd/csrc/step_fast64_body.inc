@@ -725,19 +725,17 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   // inv_w * 2^20 (exact: the exponent field + 20) and K * 2^20: the fixed-point bin of the fast quads
   const double inv_w20 = __hiloint2double(__double2hiint(inv_w) + (20 << 20), __double2loint(inv_w));
   const unsigned int k20 = (unsigned int)K << 20;
-  // float32 screening (FastParams::f32_m16): float32 copies of the lag-ordered ring rows and of the own position; off for
+  // float32 screening (FastParams::f32_m16): float32 copies of the lag-ordered ring rows (the own position: cfix16f); off for
   // this wave when a stamp or a position lies outside the range the host's error bound was made for
   const int m16 = p.f32_m16;
-  const float ringf0 = (float)ringv0, ringf1 = (float)ringv1, npxf = (float)mynpx;
+  const float ringf0 = (float)ringv0, ringf1 = (float)ringv1;
   const bool f32_ok = FLAT && m16 > 0 &&
                       __ballot(!(__builtin_fabs(ringv0) <= (double)p.f32_xmax && __builtin_fabs(ringv1) <= (double)p.f32_xmax &&
                                  __builtin_fabs(mynpx) <= (double)p.f32_xmax)) == 0ull;
-  const float invw16f = (float)(inv_w * 65536.0), halfk16f = (float)(p.Rb * inv_w * 65536.0);
-#if DIRAL_FAST_F32_FMA
+  const float invw16f = (float)(inv_w * 65536.0);
   // (the own position folded into the addend: t16 = xpos * (inv_w 2^16) + (Rb - npx) * inv_w 2^16 - one v_fma_f32 per entry
   // instead of a subtraction and the fma; the host's bound FastParams::f32_m16 covers this form: csrc/diral_env.hip)
   const float cfix16f = (float)((p.Rb - mynpx) * inv_w * 65536.0);
-#endif
   const unsigned int k16m = ((unsigned int)K << 16) + 2u * (unsigned int)m16;   // -m16 <= t16 < K * 2^16 + m16
   unsigned int* const hrow = s_hist + lane * KP;
   // Network.dist_piggy + get_positional_dist_2_piggy (network.py:538-558, 473-513) of one entry:
@@ -838,11 +836,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
             if (!f32_ok) return true;
             const int src = ((int)((__builtin_ctz((cnq >> (8 * cc)) | 0x100u)) & 7) << 2) + (((4 * q + cc) & 7) << 5);
             const float xf = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(q >= 2 ? ringf1 : ringf0)));
-#if DIRAL_FAST_F32_FMA
             const int t16 = cvt_i32_f32_sat(__builtin_fmaf(xf, invw16f, cfix16f));
-#else
-            const int t16 = cvt_i32_f32_sat(__builtin_fmaf(xf - npxf, invw16f, halfk16f));
-#endif
             return (unsigned int)(t16 + m16) < k16m && (((unsigned int)(t16 - m16)) & 0xffffu) >= 65536u - 2u * (unsigned int)m16;
           };
           auto column = [&](auto cc_tag) {
@@ -891,11 +885,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
             const int c = 4 * q + cc;
             const int src = (ffbl_byte<cc>(cnq) << 2) + ((c & 7) << 5);
             const float xf = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(q >= 2 ? ringf1 : ringf0)));
-#if DIRAL_FAST_F32_FMA
             const int t16 = cvt_i32_f32_sat(__builtin_fmaf(xf, invw16f, cfix16f));
-#else
-            const int t16 = cvt_i32_f32_sat(__builtin_fmaf(xf - npxf, invw16f, halfk16f));
-#endif
             const bool agev = ((agt >> (8 * cc)) & 255u) < (unsigned int)p.age_limit;
             const bool mm = agev && (unsigned int)(t16 + m16) < k16m;
             const bool band = (((unsigned int)(t16 - m16)) & 0xffffu) >= 65536u - 2u * (unsigned int)m16;

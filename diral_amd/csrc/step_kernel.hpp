@@ -43,12 +43,6 @@ namespace diral {
 #ifndef DIRAL_MINWAVES
 #define DIRAL_MINWAVES 1
 #endif
-#ifndef DIRAL_PREFETCH
-#define DIRAL_PREFETCH 1
-#endif
-#ifndef DIRAL_PACKED_WIDE
-#define DIRAL_PACKED_WIDE 1            // N > 64: 16-bit packed gossip merge (exact; falls back per pass)
-#endif
 
 template <int VPL>
 struct Geo {
@@ -249,7 +243,7 @@ __global__ __launch_bounds__(Geo<VPL>::THREADS, (VPL == 1 ? DIRAL_MINWAVES : 4))
   // ---- prefetch (N <= 64): this wave's 16 table columns, before any compute --
   unsigned int pre_w[VPL == 1 ? 16 : 1];
   double pre_x[VPL == 1 ? 16 : 1];
-  if constexpr (VPL == 1 && DIRAL_PREFETCH) {
+  if constexpr (VPL == 1) {
     if (piggy) {
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
@@ -509,7 +503,7 @@ __global__ __launch_bounds__(Geo<VPL>::THREADS, (VPL == 1 ? DIRAL_MINWAVES : 4))
     auto load_stamp = [&](int k, int j, unsigned int pre) -> unsigned int {
       const int u = lane + 64 * j;
       unsigned int w = pre;
-      if (VPL > 1 || !DIRAL_PREFETCH) w = (k < N && u < N) ? p.tkey[(bR + k) * NV + u] : 0u;
+      if (VPL > 1) w = (k < N && u < N) ? p.tkey[(bR + k) * NV + u] : 0u;
       if (do_step) {
         const bool own = (u == k) && (u < N);
         const unsigned int seq = (w >> 8) + (own ? 1u : 0u);
@@ -672,7 +666,7 @@ __global__ __launch_bounds__(Geo<VPL>::THREADS, (VPL == 1 ? DIRAL_MINWAVES : 4))
         unsigned int w1[16], key[16];
 #pragma unroll
         for (int c = 0; c < 16; ++c) {
-          w1[c] = load_stamp(kbase + c, 0, DIRAL_PREFETCH ? pre_w[c] : 0u);
+          w1[c] = load_stamp(kbase + c, 0, pre_w[c]);
           key[c] = (w1[c] & ~255u) | (unsigned int)lane;
         }
         if (do_step) {
@@ -687,15 +681,9 @@ __global__ __launch_bounds__(Geo<VPL>::THREADS, (VPL == 1 ? DIRAL_MINWAVES : 4))
           }
         }
         DIRAL_STAMP(5);
-        double xo1[16];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-          if (DIRAL_PREFETCH) xo1[c] = pre_x[c];
-          else xo1[c] = (kbase + c < N && lane < N) ? p.tx[(bR + kbase + c) * NV + lane] : 0.0;
-        }
 #pragma unroll
         for (int c = 0; c < 16; ++c)
-          if (kbase + c < N) finalize(kbase + c, &key[c], &w1[c], &xo1[c]);
+          if (kbase + c < N) finalize(kbase + c, &key[c], &w1[c], &pre_x[c]);
       }
     } else {
       // N > 64.  CC columns per pass (16 key registers); packed as CC/2 column PAIRS of 16-bit keys
@@ -748,7 +736,7 @@ __global__ __launch_bounds__(Geo<VPL>::THREADS, (VPL == 1 ? DIRAL_MINWAVES : 4))
               else kp[(c >> 1) * VPL + j] |= k16 << 16;
             }
           }
-          const bool packed_ok = (DIRAL_PACKED_WIDE != 0) && (__ballot(bad) == 0ull);
+          const bool packed_ok = __ballot(bad) == 0ull;
           if (packed_ok) {
 #pragma unroll
             for (int c2 = 0; c2 < HP; ++c2)

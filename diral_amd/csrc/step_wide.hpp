@@ -50,13 +50,8 @@ __host__ __device__ constexpr int wide_waves(int vpl) { return vpl == 2 ? 8 : DI
 #define DIRAL_WIDE_PC4 8                 // subject columns per merge pass, N <= 256 (4 until the xpos ring freed the registers: C3 -3.5 %)
 #endif
 // The B operand's table: 256 entries of 8 x bf16 - one 16-byte read per K step; the rows a quarter wave reads are random, half
-// the LDS cycles of the product are bank conflicts.  DIRAL_WIDE_NIBBLE_LUT=1: 16 entries of 4 x bf16 instead - 128 bytes, every
-// entry in banks of its own, two conflict-free 8-byte reads per K step: bit-exact, and measured SLOWER (C3 1.33 -> 1.36 ms, C5
-// +- 0: twice the LDS instructions and two more VALU instructions per K step cost more than the conflicts).
-#ifndef DIRAL_WIDE_NIBBLE_LUT
-#define DIRAL_WIDE_NIBBLE_LUT 0
-#endif
-constexpr uint32_t kWideLutBytes = DIRAL_WIDE_NIBBLE_LUT ? 128u : 4096u;
+// the LDS cycles of the product are bank conflicts.  A 16-entry form of 4 x bf16 (128 bytes, conflict-free) was bit-exact and
+// measured slower (C3 1.33 -> 1.36 ms, C5 +- 0): removed; last at d94e7da.
 // merge scratch per wave: a pass's rank words (one byte per column and viewer), then the
 // rank -> xpos table (256 doubles)
 // (N <= 256: + 64 bytes in front of the lag -> xpos table of the packed form's finalize phase, whose lookup of a
@@ -86,7 +81,7 @@ __host__ __device__ inline WideLds wide_lds_layout(int vpl, int A, int K, bool p
   // 256-entry bits -> 8 x bf16 table of the product's B operand
   l.pbytes = l.lut = o;
   // (+ the closure's own rows of P - npad / 16 bytes x 2 waves per viewer - and one row-ready flag per resource: it runs beside P1)
-  if (packed) { l.pbytes = o; o += 8u * vpl * npad; l.lut = o; o += kWideLutBytes; o += 8u * vpl * npad; o += 4u * (uint32_t)kWideMaxA; }
+  if (packed) { l.pbytes = o; o += 8u * vpl * npad; l.lut = o; o += 4096u; o += 8u * vpl * npad; o += 4u * (uint32_t)kWideMaxA; }
   l.px = o;    o += 8u * npad;
   l.npx = o;   o += 8u * npad;
   l.rv = o;    o += 8u * A;
@@ -210,16 +205,16 @@ __device__ inline void unpack_src(unsigned int mw, unsigned int (&a)[VPL]) {
   }
 }
 
-// byte BYTE of a word of table indices, times 2^SH: the LDS byte offset of that row of the bits -> bf16 table
+// byte BYTE of a word of table indices, times 16: the LDS byte offset of that row of the bits -> bf16 table
 // (step_wide_closure.inc), shift and byte extraction in one SDWA instruction
-template <int BYTE, unsigned int SH = 4u>
+template <int BYTE>
 __device__ inline unsigned int lut_row(unsigned int w) {
   unsigned int r;
   static_assert(BYTE >= 0 && BYTE < 4, "byte select");
-  if constexpr (BYTE == 0) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(r) : "s"(SH), "v"(w));
-  if constexpr (BYTE == 1) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(r) : "s"(SH), "v"(w));
-  if constexpr (BYTE == 2) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(r) : "s"(SH), "v"(w));
-  if constexpr (BYTE == 3) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(r) : "s"(SH), "v"(w));
+  if constexpr (BYTE == 0) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0" : "=v"(r) : "s"(4u), "v"(w));
+  if constexpr (BYTE == 1) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_1" : "=v"(r) : "s"(4u), "v"(w));
+  if constexpr (BYTE == 2) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_2" : "=v"(r) : "s"(4u), "v"(w));
+  if constexpr (BYTE == 3) asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_3" : "=v"(r) : "s"(4u), "v"(w));
   return r;
 }
 
@@ -380,33 +375,8 @@ __device__ __attribute__((noinline)) unsigned int wide_far_guard(const unsigned 
 #ifndef DIRAL_WIDE_MINWAVES4P
 #define DIRAL_WIDE_MINWAVES4P 4          // ... the packed form: 128 VGPRs (the product's A operand alone takes 64), two workgroups per CU
 #endif
-#ifndef DIRAL_WIDE_INV_LDS
-#define DIRAL_WIDE_INV_LDS 1             // the float32 state vector's 1 / n per viewer through LDS (fetched in the count pass) instead of a global load in P4
-#endif
-#ifndef DIRAL_WIDE_FUSED_FLAGGED
-#define DIRAL_WIDE_FUSED_FLAGGED 1       // packed form: a flagged pass reads and writes the code words itself (no round trip through `tkey`)
-#endif
 #ifndef DIRAL_WIDE_FLAG_UNROLL
 #define DIRAL_WIDE_FLAG_UNROLL 1         // column loops of a flagged pass's unpack / repack stages (4 - the four loads of a word in flight together - measured C5 + 4 %: registers)
-#endif
-#ifndef DIRAL_WIDE_FAR_GUARD
-#define DIRAL_WIDE_FAR_GUARD 1           // packed form at N <= 128: a flagged pass whose far entries provably stay put this slot runs on the coded path
-#endif
-#ifndef DIRAL_WIDE_EARLY_P3
-#define DIRAL_WIDE_EARLY_P3 0            // packed form, my_step: 1 = the P1 waves run P3's prologue + the A operand of pass 0 in front of the P1 barrier;
-                                         // 2 = the two walking waves too, before their walk.  Measured on C3 (one box, interleaved): 0: 1.247 ms,
-                                         // 1: 1.290, 2: 1.242 - the work costs in front of the barrier what it saves behind it (the kernel is paced
-                                         // by the instructions it issues, not by who waits where): off
-#endif
-#ifndef DIRAL_WIDE_P4V2
-#define DIRAL_WIDE_P4V2 1                // the output tail: channel observation written by each wave right behind its P3 (branch-free, the LDS reads of a
-                                         // piece in flight together), neighbour counts + 1 / n per WAVE for the rows it writes (one barrier less, no table load)
-#endif
-#ifndef DIRAL_WIDE_FIN_FMA
-#define DIRAL_WIDE_FIN_FMA 1             // packed form's finalize: the fixed-point bin as one v_fma_f64 per entry, the histogram word from its bits
-#endif
-#ifndef DIRAL_WIDE_FIN_UNROLL
-#define DIRAL_WIDE_FIN_UNROLL 0          // packed form's finalize: the quad loop of a viewer slot unrolled (static indices instead of rotating the words)
 #endif
 #ifndef DIRAL_WIDE_MINWAVES2P
 #define DIRAL_WIDE_MINWAVES2P 6          // N <= 128, packed form: 84 VGPRs, three workgroups per CU (43 KB of LDS each)

@@ -142,19 +142,17 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
   if (tid == THREADS - 1) s_slow[0] = 0u;
   // PACKED: the closure of the slot's gossip runs beside P1 (below): compile-time LDS addresses behind the merge scratch
   // (step_wide_closure.inc), the bits -> 8 x bf16 table of the product and the row-ready flags of the gather table
-  constexpr unsigned int kClPb = wide_scratch(VPL) * WAVES, kClLut = kClPb + 8u * VPL * NPAD, kClRows = kClLut + kWideLutBytes,
+  constexpr unsigned int kClPb = wide_scratch(VPL) * WAVES, kClLut = kClPb + 8u * VPL * NPAD, kClRows = kClLut + 4096u,
                          kClFlag = kClRows + 8u * VPL * NPAD;
   constexpr int P1W = PACKED ? WAVES - 2 : WAVES;         // waves that run P1 (PACKED: the last two walk the closure)
   if constexpr (PACKED) {
-    if (tid < (DIRAL_WIDE_NIBBLE_LUT ? 16 : 256)) {
+    if (tid < 256) {
       typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-      typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
       u32x4 t;                                              // entry e, element j = bit j of e, 0.0 / 1.0
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj)
         t[jj] = ((((unsigned int)tid >> (2 * jj)) & 1u) ? 0x3f80u : 0u) | ((((unsigned int)tid >> (2 * jj + 1)) & 1u) ? 0x3f800000u : 0u);
-      if constexpr (DIRAL_WIDE_NIBBLE_LUT) reinterpret_cast<u32x2*>(smem + kClLut)[tid] = u32x2{t[0], t[1]};
-      else reinterpret_cast<u32x4*>(smem + kClLut)[tid] = t;
+      reinterpret_cast<u32x4*>(smem + kClLut)[tid] = t;
     } else if (tid >= 256 && tid < 256 + kWideMaxA) {
       reinterpret_cast<unsigned int*>(smem + kClFlag)[tid - 256] = 0u;
     }
@@ -181,20 +179,16 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
   // ---- (PACKED) the prologue of P3 - step_wide_closure.inc - as two pieces that depend on nothing this slot computes
   // after P0: the wave's columns (which passes are clean, fresh sequence numbers stamped, the [column][lag] -> xpos
   // table from the ring rows, the ring stamped) and the product's A operand of a pass (the raw code words of the pass's
-  // 16 subjects over all sources, as bf16 powers of two with the stamp folded in).  DIRAL_WIDE_EARLY_P3: the P1 waves run
-  // both in front of the barrier that ends P1, where they otherwise wait for the closure walk; the two walking waves build
-  // theirs before the first rows of the gather table are ready.  (my_step without the run-time extras only: my_step_ch /
-  // the EXTRA switches park per-transmitter values in the merge scratch until P2.)
+  // 16 subjects over all sources, as bf16 powers of two with the stamp folded in).
   typedef __attribute__((ext_vector_type(4))) unsigned int cl_u32x4;
   constexpr int CL_KS = NPAD / 32;
   cl_u32x4 cl_a[CL_KS];
   unsigned int cl_passbits = 0u, cl_tkov = 0u;
-  bool cl_ovf = false, cl_done = false, cl_a_ready = false;
+  bool cl_ovf = false;
   unsigned int cl_stable = 0u;                             // bit pch: a flagged pass the guard below found stable this slot
   auto cl_prologue = [&]() {
     const int kbase = wave * CPW;
     const unsigned int ul = (unsigned int)lane;
-    cl_done = true;
     if (kbase >= NRows) return;                            // (uniform) waves past the last subject row only help with the closure
     const LateFastArgs la = (LateFastArgs)late_kernarg_base();
     const global_ptr<double> ringp = uniform_ptr(la->ring, 0);
@@ -247,7 +241,7 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
   // runs on the coded path, its quads stay flagged.  A viewer that ends the slot with a coded entry makes the test
   // conservative, never wrong; a failed guard costs the pass its old price plus the test.
   auto cl_far_guard = [&]() -> unsigned int {
-    if constexpr (PACKED && VPL == 2 && DIRAL_WIDE_FAR_GUARD) {
+    if constexpr (PACKED && VPL == 2) {
       const int kbase = wave * CPW;
       if (kbase >= NRows) return 0u;
       const LateFastArgs la = (LateFastArgs)late_kernarg_base();
@@ -336,12 +330,6 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
         default: fix_own(std::integral_constant<int, 3>{}); break;
       }
     }
-  };
-  constexpr bool CL_EARLY = PACKED && !CH && !EXTRA && DIRAL_WIDE_EARLY_P3 != 0;
-  auto cl_early = [&]() {
-    if (lds_addr(smem) != 0u) return;                       // (the scratch carve below assumes what the P3 code checks)
-    cl_prologue();
-    if (wave * CPW < NRows && (FULL || wave * CPW < NRows)) { cl_build_a(0); cl_a_ready = true; }
   };
 
   // ---- P1: per owned resource: transmitter set, closest in-range transmitter
@@ -498,9 +486,6 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
       }
     }
   }
-  if constexpr (CL_EARLY) {
-    if (wave < P1W) cl_early();                              // (the P1 waves: in front of the barrier, beside the closure walk)
-  }
   if constexpr (PACKED) {
     // ---- the reachability closure of the slot (step_wide_closure.inc: final = P . stamped, P = (I + E_A) ... (I + E_1)),
     //      walked ONCE per env, BESIDE P1: waves 6 and 7 - 128 source bits each, rows of P in LDS, gather the source's 16
@@ -528,9 +513,6 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
         reinterpret_cast<rowv_t*>(rows)[u] = id;
       }
       wave_lds_order();
-#if DIRAL_WIDE_EARLY_P3 >= 2
-      if constexpr (CL_EARLY) cl_early();                     // (the walking waves: before the first rows of the gather table are ready)
-#endif
       const volatile unsigned int* const flag = reinterpret_cast<const volatile unsigned int*>(smem + kClFlag);
       // (the flag and the row of step i + 1 are requested in front of step i's gathers - flag first: in-order LDS queue, a
       // set flag vouches for the row read behind it - so that a walk that lags the P1 waves pays no LDS round trip per
@@ -762,23 +744,18 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
     const global_ptr<unsigned int> tcrow = uniform_ptr(g_tcode, qrow * NV);
     const global_ptr<unsigned int> tarow = uniform_ptr(g_tage, qrow * NV);
     const global_ptr<unsigned int> tsrow = uniform_ptr(g_tseq, bR + kbase);
-    {
-      // (the flags as the previous slot left them: the coded loop above only ever SETS flags of clean quads it
-      // handed an entry over in - those passes ran there and must not run again)
-      if (((passbits >> pch) & 1u) == 0u) continue;
-#ifdef DIRAL_WIDE_NO_FLAGGED
-      continue;   // (compile-time probe: the coded loop's own register needs)
-#endif
-    }
+    // (the flags as the previous slot left them: the coded loop above only ever SETS flags of clean quads it
+    // handed an entry over in - those passes ran there and must not run again)
+    if (((passbits >> pch) & 1u) == 0u) continue;
     // ---- flagged pass: through the planes ------------------------------------------------------------------
     // (timing builds: unpack / plane pass / repack of the flagged passes go to the load / merge / finalize accumulators)
     unsigned long long tf0 = 0, tf1 = 0, tf2 = 0, tf3 = 0;
     DIRAL_WCLOCK(tf0);
-    // the pass's entries as (seq, age) words in `tkey` / the packed words again from `tkey`: the round trip of round 4's
-    // flagged pass (unpack 35 k + repack 20 k cycles per wave beside a plane pass of 75 k, profiles/r05/phase_timing_wide.txt).
-    // DIRAL_WIDE_FUSED_FLAGGED: the pass builds its lag bytes from the code words and writes code words back itself
-    // (step_wide_pass.inc, DIRAL_PASS_PACKED_IO) - `tkey` is read for code-0 entries and written for entries 7 or more
-    // behind only - and the two stages below serve the 32-bit path alone (it walks `tkey` column by column).
+    // The pass builds its lag bytes from the code words and writes code words back itself (step_wide_pass.inc,
+    // DIRAL_PASS_PACKED_IO) - `tkey` is read for code-0 entries and written for entries 7 or more behind only.  The two
+    // stages below - the pass's entries as (seq, age) words in `tkey`, the packed words again from `tkey` - serve the
+    // 32-bit path alone (it walks `tkey` column by column).  (As a round trip around every flagged pass they cost 35 k +
+    // 20 k cycles per wave beside a plane pass of 75 k: profiles/r05/phase_timing_wide.txt.)
     auto unpack_pass = [&]() {
       {
         // the pass's entries as (seq, age) words, unstamped: coded ones from the subject's own number and the lag,
@@ -855,19 +832,13 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
         }
       }
     };
-#if !DIRAL_WIDE_FUSED_FLAGGED
-    unpack_pass();
-#endif
     DIRAL_WCLOCK(tf1);
 #define DIRAL_PASS_THERMO_FIRST false             // (a flagged pass: the codes do not reach - byte ranks, then 32-bit keys)
-#define DIRAL_PASS_PACKED_IO DIRAL_WIDE_FUSED_FLAGGED
+#define DIRAL_PASS_PACKED_IO 1
 #include "step_wide_pass.inc"
 #undef DIRAL_PASS_PACKED_IO
 #undef DIRAL_PASS_THERMO_FIRST
     DIRAL_WCLOCK(tf2);
-#if !DIRAL_WIDE_FUSED_FLAGGED
-    repack_pass(tkov);
-#endif
 #ifdef DIRAL_TIMING
     DIRAL_WCLOCK(tf3);
     acc_load += tf1 - tf0; acc_merge += tf2 - tf1; acc_fin += tf3 - tf2;
@@ -913,7 +884,7 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
   // paid two dependent LDS round trips per VALUE); the distance is |dx| outright when the env's positions allow it
   // (p1_fast: decided once per env, as in P1).
   bool chobs_done = false;
-  if constexpr (RICH && DIRAL_WIDE_P4V2) {
+  if constexpr (RICH) {
     const LateRichArgs lr0 = (LateRichArgs)(late_kernarg_base() + kRichArgOffset);
 #ifndef DIRAL_WIDE_KSLOTS
     void* const chobs_out0 = lr0->chobs_out;
@@ -970,12 +941,12 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
   }
   __syncthreads();
   // neighbours counted per viewer (network.py:497-501 `count`) = the row sum of its histogram
-  // P4V2: where the plain state writer runs, every wave counts the NPAD / WAVES viewers whose rows it writes itself and
+  // Where the plain state writer runs, every wave counts the NPAD / WAVES viewers whose rows it writes itself and
   // leaves count and 1 / n (one IEEE division: the value the host's table holds) in LDS for its own lanes - no second
   // barrier, no table load whose s_waitcnt vmcnt would wait for the streaming stores in front of it
   constexpr int RPW = NPAD / WAVES;              // state rows a wave writes
   bool rows_by_wave = false;
-  if constexpr (!REGCNT && DIRAL_WIDE_P4V2) {
+  if constexpr (!REGCNT) {
     bool plain_writer = true;
     if constexpr (RICH) plain_writer = ((LateRichArgs)(late_kernarg_base() + kRichArgOffset))->plain_state != 0;
 #ifndef DIRAL_WIDE_KSLOTS
@@ -1006,7 +977,7 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
       // 1 / n for the float32 state vector, fetched HERE and parked in the merge scratch (dead since the barrier above): in
       // P4 the table load sat between streaming stores, and a wave's s_waitcnt vmcnt for it also waits for every store
       // issued before it (step_wide_closure.inc found the same for its table words)
-      if constexpr (!OUT64 && DIRAL_WIDE_INV_LDS) {
+      if constexpr (!OUT64) {
         const double* const it = ((LateFastArgs)late_kernarg_base())->inv_tab;
         reinterpret_cast<double*>(smem + lay.scratch)[tid] = it[n < 256u ? n : 0u];
       }
@@ -1209,7 +1180,7 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
           const unsigned int* hw = s_hist + u * KP + ((s0 - A) >> 1);        // s0 - A is a multiple of 4: two words
           const unsigned int h01 = hw[0], h23 = hw[1];
           // one table load instead of four IEEE divisions: exact, see step_fast64.hpp
-          const double inv = (!REGCNT && DIRAL_WIDE_INV_LDS) ? reinterpret_cast<const double*>(smem + lay.scratch)[u] : inv_tab[n];
+          const double inv = !REGCNT ? reinterpret_cast<const double*>(smem + lay.scratch)[u] : inv_tab[n];
           v = make_float4((float)((double)(h01 & 0xffffu) * inv), (float)((double)(h01 >> 16) * inv),
                           (float)((double)(h23 & 0xffffu) * inv), (float)((double)(h23 >> 16) * inv));
         }

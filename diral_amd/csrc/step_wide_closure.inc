@@ -53,8 +53,9 @@
       const int c16 = lane & 15, g4 = lane >> 4;         // product: lane = (subject or viewer of the tile, K group)
       unsigned char* const xt2 = reinterpret_cast<unsigned char*>(sw) + 64;   // [column][lag] -> xpos, 8 doubles per column
       // (the wave's columns - which passes are clean, fresh sequence numbers, the [column][lag] -> xpos table - and the A
-      // operand of pass 0: `cl_prologue` / `cl_build_a`, step_wide.hpp; run in front of the P1 barrier where that pays)
-      if (!cl_done) { cl_stable = cl_far_guard(); cl_prologue(); }
+      // operand of a pass: `cl_prologue` / `cl_build_a`, step_wide_body.inc)
+      cl_stable = cl_far_guard();
+      cl_prologue();
       passbits = cl_passbits;
       tkov = cl_tkov;
       ovf = ovf || cl_ovf;
@@ -71,9 +72,9 @@
 #pragma unroll 1
       for (int pass = 0; pass < CPW / 16; ++pass) {
         DIRAL_WCLOCK(tc0);
-        // A operand: [K step of 32 sources] 8 x bf16 of this lane's subject (cl_a; pass 0's may have been built already)
+        // A operand: [K step of 32 sources] 8 x bf16 of this lane's subject (cl_a)
         const bool pass_cols = has_cols && (FULL || kbase + 16 * pass < NRows);
-        if (pass_cols && !(pass == 0 && cl_a_ready)) cl_build_a(pass);
+        if (pass_cols) cl_build_a(pass);
         DIRAL_WCLOCK(tc1);
 #ifdef DIRAL_TIMING
         acc_load += tc1 - tc0;
@@ -112,33 +113,24 @@
                 idx0 = *lds_at<unsigned int>(pba);
               }
               // the B operand of K step n: the table row(s) of byte n of the index word
-              auto brow = [&](auto ntag, unsigned int w, unsigned int wlo, unsigned int whi) -> u32x4 {
-                constexpr int NB = decltype(ntag)::value;
-                if constexpr (DIRAL_WIDE_NIBBLE_LUT) {
-                  const u32x2 lo = *lds_at<u32x2>(kLut + lut_row<NB, 3u>(wlo));
-                  const u32x2 hi = *lds_at<u32x2>(kLut + lut_row<NB, 3u>(whi));
-                  return u32x4{lo.x, lo.y, hi.x, hi.y};
-                } else {
-                  return *lds_at<u32x4>(kLut + lut_row<NB>(w));
-                }
+              auto brow = [&](auto ntag, unsigned int w) -> u32x4 {
+                return *lds_at<u32x4>(kLut + lut_row<decltype(ntag)::value>(w));
               };
               {
-                const unsigned int l0 = idx0 & 0x0f0f0f0fu, h0 = (idx0 >> 4) & 0x0f0f0f0fu;
-                const u32x4 b0 = brow(std::integral_constant<int, 0>{}, idx0, l0, h0);
-                const u32x4 b1 = brow(std::integral_constant<int, 1>{}, idx0, l0, h0);
-                const u32x4 b2 = brow(std::integral_constant<int, 2>{}, idx0, l0, h0);
-                const u32x4 b3 = brow(std::integral_constant<int, 3>{}, idx0, l0, h0);
+                const u32x4 b0 = brow(std::integral_constant<int, 0>{}, idx0);
+                const u32x4 b1 = brow(std::integral_constant<int, 1>{}, idx0);
+                const u32x4 b2 = brow(std::integral_constant<int, 2>{}, idx0);
+                const u32x4 b3 = brow(std::integral_constant<int, 3>{}, idx0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cl_a[0]), __builtin_bit_cast(bf16x8, b0), acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cl_a[1]), __builtin_bit_cast(bf16x8, b1), acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cl_a[2]), __builtin_bit_cast(bf16x8, b2), acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cl_a[3]), __builtin_bit_cast(bf16x8, b3), acc, 0, 0, 0);
               }
               if constexpr (KS == 8) {
-                const unsigned int l1 = idx1 & 0x0f0f0f0fu, h1 = (idx1 >> 4) & 0x0f0f0f0fu;
-                const u32x4 b4 = brow(std::integral_constant<int, 0>{}, idx1, l1, h1);
-                const u32x4 b5 = brow(std::integral_constant<int, 1>{}, idx1, l1, h1);
-                const u32x4 b6 = brow(std::integral_constant<int, 2>{}, idx1, l1, h1);
-                const u32x4 b7 = brow(std::integral_constant<int, 3>{}, idx1, l1, h1);
+                const u32x4 b4 = brow(std::integral_constant<int, 0>{}, idx1);
+                const u32x4 b5 = brow(std::integral_constant<int, 1>{}, idx1);
+                const u32x4 b6 = brow(std::integral_constant<int, 2>{}, idx1);
+                const u32x4 b7 = brow(std::integral_constant<int, 3>{}, idx1);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cl_a[KS - 4]), __builtin_bit_cast(bf16x8, b4), acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cl_a[KS - 3]), __builtin_bit_cast(bf16x8, b5), acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, cl_a[KS - 2]), __builtin_bit_cast(bf16x8, b6), acc, 0, 0, 0);
@@ -164,28 +156,17 @@
           // ---- 3. ages, stores, xpos, histogram of this viewer slot
           const bool uval = FULL || (lane + 64 * j < N);
           const unsigned int uo = ul + 64u * (unsigned int)j;
-          const unsigned int uo4 = uo * 4u;
           const double npx_j = s_npx[uo];                                      // this viewer's post-move position
-#if DIRAL_WIDE_FIN_FMA
           const double cfix_j = (pRb - npx_j) * inv_w20;
-#endif
           unsigned int* const hrow_j = s_hist + uo * (unsigned int)KP;         // ... and its histogram row (two 16-bit bins per word)
           // (rolled over the pass's four quads, the merged words rotating through element 0: a dynamically indexed register
           // array would live in scratch memory)
-#if DIRAL_WIDE_FIN_UNROLL
-          // (unrolled over the pass's four quads: static register indices, no rotation of the merged words - nine moves a quad)
-#pragma unroll
-          for (int qq = 0; qq < 4; ++qq) {
-            const int q = 4 * pass + qq;                                     // quad of the wave's eight
-            const unsigned int kq = kpn[qq], raw = rawv[qq], ag = agv[qq];
-#else
 #pragma unroll 1
           for (int qq = 0; qq < 4; ++qq) {
             const int q = 4 * pass + qq;                                     // quad of the wave's eight
             const unsigned int kq = kpn[0], raw = rawv[0], ag = agv[0];
 #pragma unroll
             for (int i = 0; i < 3; ++i) { kpn[i] = kpn[i + 1]; rawv[i] = rawv[i + 1]; agv[i] = agv[i + 1]; }
-#endif
             if ((passbits >> (q >> 1)) & 1u) continue;                       // (uniform) a flagged pass: the loop below
             if (!FULL && kbase + 4 * q >= NRows) continue;                   // (uniform) no such subject rows
             // Vehicle.periodic_update (vehicle.py:56-70): every lag + 1 (a shift), every age + 1 (saturating, packed), the
@@ -209,15 +190,8 @@
               agq &= ~(nz | (nz - (nz >> 7)));
             }
             if (uval) {
-#if DIRAL_WIDE_FIN_UNROLL
-              // (uniform row base + one 32-bit byte offset per viewer slot: the scalar-base form of the store, no 64-bit
-              // address arithmetic per quad)
-              __builtin_nontemporal_store(kn, (global_ptr<unsigned int>)((global_ptr<unsigned char>)(tcrow + (unsigned int)(q * NV)) + uo4));
-              __builtin_nontemporal_store(agq, (global_ptr<unsigned int>)((global_ptr<unsigned char>)(tarow + (unsigned int)(q * NV)) + uo4));
-#else
               __builtin_nontemporal_store(kn, &tcrow[(unsigned int)(q * NV) + uo]);
               __builtin_nontemporal_store(agq, &tarow[(unsigned int)(q * NV) + uo]);
-#endif
             }
             // One entry per lane and column (the body of step_fast64's fast quad, csrc/step_fast64.hpp P3b): whether the
             // entry counts - vehicle and subject exist, not the own entry, age < limit (network.py:547) - is ONE byte compare
@@ -307,7 +281,6 @@
               xs[3] = *reinterpret_cast<const double*>(xt2 + q * 256 + 3 * 64 + ffbl_byte<3>(kn) * 8);
             }
             // the four bins side by side, ONE test for the rare exact-edge statement
-#if DIRAL_WIDE_FIN_FMA
             // ti = trunc(((xpos - npx) + Rb) * inv_w * 2^20) as ONE fused multiply-add, xpos * (inv_w 2^20) + cfix_j with
             // cfix_j = (Rb - npx) * inv_w 2^20 once per viewer slot: ti only has to be within 2^-20 bin widths of the exact
             // quotient (an estimate nearer an edge than that takes the exact NumPy statement below, as before), and either
@@ -339,30 +312,6 @@
                           ((t >> 20) & 1u) * 0xffffu + 1u);
               }
             }
-#else
-            int binv[4];
-            bool cntv[4], needv[4];
-            bool anyneed = false;
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc) {
-              const double v = xs[cc] - npx_j;
-              const int ti = cvt_i32_f64_sat((v + pRb) * inv_w20);
-              const bool agev = ((agt >> (8 * cc)) & 255u) < (unsigned int)age_limit;
-              const bool m = agev && (unsigned int)ti <= k20;
-              needv[cc] = m && ((unsigned int)(ti + 1) & 0xfffffu) <= 1u;
-              cntv[cc] = m && !needv[cc];
-              anyneed = anyneed || needv[cc];
-              binv[cc] = ti >> 20;
-            }
-            if (__ballot(anyneed) != 0ull) {
-#pragma unroll
-              for (int cc = 0; cc < 4; ++cc)
-                if (needv[cc]) binv[cc] = exact_bin(xs[cc], cntv[cc]);
-            }
-#pragma unroll
-            for (int cc = 0; cc < 4; ++cc)
-              if (cntv[cc]) atomicAdd(&hrow_j[binv[cc] >> 1], 1u << (16 * (binv[cc] & 1)));
-#endif
           }
 #ifdef DIRAL_TIMING
           DIRAL_WCLOCK(tc2);

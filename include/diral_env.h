@@ -180,8 +180,12 @@ int diral_env_abi_version(void);
  * network.py:15-67) for B independent envs on HIP device `device`.
  * Allocates all persistent state in HBM; tables zeroed (vehicle.py:24-33).
  * Test hooks, read from the process environment ONCE here: DIRAL_NO_FAST64 /
- * DIRAL_NO_WIDE (the general kernel also for N <= 64 / N > 64), DIRAL_NO_RING
- * (N <= 64: no xpos ring, every xpos in the per-entry plane). */
+ * DIRAL_NO_WIDE (the general kernel also for N <= 64 / N > 64),
+ * DIRAL_TABLE_FORM=packed|plane (the table form for N > 64),
+ * DIRAL_NO_SLOW_FIRST=1 (blocks = envs in order, no slow envs first),
+ * DIRAL_WIDE_SLOW_FIRST=1 (step_wide's packed form at N <= 128 dispatches its
+ * slow envs first), DIRAL_F32_MARGIN=<n> (N <= 64: 0 = no float32 screening of
+ * the histogram bin, n > 0 = a band of at least n / 65536 bin widths). */
 int diral_env_create(const DiralCfg* cfg, int batch, int device, DiralEnv** out);
 int diral_env_destroy(DiralEnv* env);
 
