@@ -22,8 +22,33 @@
 
 using namespace diral;
 
+// One device allocation of a handle (`own`, below): what diral_env_destroy frees, diral_env_hbm_bytes sums and
+// diral_env_reset fills again.
+struct DevBuf {
+  void* p;
+  size_t bytes;         // allocated and filled at create, slack included
+  size_t reset_bytes;   // what diral_env_reset fills again (never the slack); 0 = reset leaves the buffer alone
+  int fill;             // the fill byte; kNoFill = left as allocated (written before its first read)
+};
+constexpr int kNoFill = -1;
+constexpr bool kOnReset = true;
+
+// The test hooks of diral_env_create (include/diral_env.h lists them): read from the process environment ONCE per
+// handle (read_hooks), never on the step path.
+struct Hooks {
+  int table_form = 0;            // DIRAL_TABLE_FORM=packed (+1) | plane (-1): the table form for N > 64 (use_packed_table)
+  bool no_fast64 = false;        // DIRAL_NO_FAST64: the general kernel also for N <= 64
+  bool no_wide = false;          // DIRAL_NO_WIDE: ... and for N > 64
+  bool slow_first = true;        // DIRAL_NO_SLOW_FIRST=1 clears it: blocks = envs in order (A/B timing, tests)
+  bool wide_slow_first = false;  // DIRAL_WIDE_SLOW_FIRST=1: step_wide's packed form at N <= 128 dispatches its slow envs first (round 5's default)
+  int f32_margin = -1;           // DIRAL_F32_MARGIN=<n> (N <= 64): 0 = no float32 screening of the bin, n > 0 = a band of at
+                                 //   least n / 65536 bin widths (tests: a wide band sends many entries to float64); -1 = the bound
+};
+
 struct DiralEnv {
   DiralCfg cfg;
+  Hooks hooks;
+  std::vector<DevBuf> bufs;   // every device buffer of the handle but `trace` and `dbg`
   int B = 0, N = 0, A = 0, K = 0, S = 0, NV = 0, NR = 0, vpl = 1;
   int device = 0;
   StepParams base;       // everything that does not change per call
@@ -51,21 +76,16 @@ struct DiralEnv {
   // slow envs first (step_fast64.hpp FastParams::slow_*): three rotating sets of [count (16 words) | list | flag per env]
   uint32_t* slow = nullptr;
   uint64_t slow_launches = 0;   // launches that rotated the sets
-  bool slow_first = true;       // DIRAL_NO_SLOW_FIRST=1 at create: blocks = envs in order (A/B timing, tests)
   bool capture_rotates = false; // diral_env_set_capture_rotation: captured launches rotate the sets too (graphs of 3 k launches)
-  bool wide_slow_first = false;  // DIRAL_WIDE_SLOW_FIRST=1 at create: step_wide's packed form at N <= 128 dispatches its slow envs first (round 5's default)
-  int f32_margin = -1;          // DIRAL_F32_MARGIN=<n> at create: 0 = no float32 screening of the bin, n > 0 = a band of at
-                                //   least n / 65536 bin widths (tests: a wide band sends many entries to float64); -1 = the bound
   int32_t* la = nullptr;
   int32_t* pf = nullptr;
   double* metrics = nullptr;
   uint32_t* err = nullptr;
   double* edges = nullptr;
-  double* edges1 = nullptr;
+  double* edges1 = nullptr;    // np.linspace(-1, 1, K+1) for the type-1 histogram
   double* inv_tab = nullptr;   // [256] 1.0 / n (n = 0: 0): f32 histogram output, csrc/step_fast64.hpp
   double* trace = nullptr;    // handle-owned copy of the replay trace
-  int trace_len = 0, trace_per_env = 0;   // np.linspace(-1, 1, K+1) for the type-1 histogram
-  int64_t hbm_bytes = 0;
+  int trace_len = 0, trace_per_env = 0;
   bool flat_y = true;      // every pos_y == 0 (random topologies, network.py:104): |dx| distance path
   uint32_t* yflag = nullptr;
   // State.piggybacking (piggyback_kernel.hpp): TestEnv.prev_obs, and this slot's plain observation / closest transmitters
@@ -95,6 +115,7 @@ int note_hip(DiralEnv* e, hipError_t st, const char* what) {
   if (e) e->last_hip_error = std::string(what) + ": " + hipGetErrorString(st);
   return DIRAL_ERR_HIP;
 }
+int hip_status(hipError_t st) { return st == hipSuccess ? DIRAL_OK : DIRAL_ERR_HIP; }   // the handle-less entry points
 
 #define HIP_TRY(env, call)                                   \
   do {                                                       \
@@ -157,6 +178,22 @@ bool is_large_cfg(const DiralCfg* c) {
 }
 bool runs_large(const DiralEnv* e) { return e->large || e->kernel_path == DIRAL_PATH_LARGE; }
 
+// The sizes the specialised kernels take, step_fast64 and step_wide: such a handle keeps an xpos ring (diral_env_create),
+// and only such a handle is ever planned onto them (plan_step).
+bool fits_fast64(const DiralEnv* e) { return !e->large && e->vpl == 1 && e->NV == 64 && e->A <= kFastMaxA; }
+bool fits_wide(const DiralEnv* e) { return !e->large && e->vpl > 1 && e->A <= kWideMaxA; }
+
+Hooks read_hooks() {
+  Hooks h;
+  if (const char* f = std::getenv("DIRAL_TABLE_FORM")) h.table_form = std::strcmp(f, "packed") == 0 ? 1 : (std::strcmp(f, "plane") == 0 ? -1 : 0);
+  h.no_fast64 = std::getenv("DIRAL_NO_FAST64") != nullptr;
+  h.no_wide = std::getenv("DIRAL_NO_WIDE") != nullptr;
+  if (const char* off = std::getenv("DIRAL_NO_SLOW_FIRST")) h.slow_first = off[0] != '1';
+  if (const char* ws = std::getenv("DIRAL_WIDE_SLOW_FIRST")) h.wide_slow_first = ws[0] == '1';
+  if (const char* fm = std::getenv("DIRAL_F32_MARGIN")) h.f32_margin = std::max(0, std::atoi(fm));
+  return h;
+}
+
 // The table form of a handle (fixed at create): packed thermometer codes + ages + own sequence numbers, or the (seq, age)
 // plane `tkey` of round 2.  N <= 64: always packed (step_fast64 has no other form).  64 < N <= 256 (step_wide): packed
 // where the vehicles are dense enough for tables to stay fresh - on average at least kPackedMinNeighbours vehicles within
@@ -171,25 +208,52 @@ constexpr double kPackedMinNeighbours = 20.0;
 constexpr double kPackedMinNeighbours2 = 15.0;           // 64 < N <= 128
 bool use_packed_table(const DiralEnv* e) {
   if (e->vpl == 1) return true;
-  if (const char* f = std::getenv("DIRAL_TABLE_FORM")) {
-    if (std::strcmp(f, "packed") == 0) return true;
-    if (std::strcmp(f, "plane") == 0) return false;
-  }
+  if (e->hooks.table_form != 0) return e->hooks.table_form > 0;
   const double neigh = e->N * 2.0 * e->cfg.communication_range / e->cfg.highway_length;
   return neigh >= (e->vpl == 2 ? kPackedMinNeighbours2 : kPackedMinNeighbours);
 }
 
-// Every entry point that touches the device runs with the handle's device current and
-// restores the caller's (torch's) current device afterwards.
+// The handle-less entry points (diral_sps_*, diral_driver_shape) take device pointers only: they run on the
+// device that owns `p` (their first mandatory buffer), whatever device is current in the calling thread.
+int device_of_ptr(const void* p) {
+  hipPointerAttribute_t a;
+  if (p && hipPointerGetAttributes(&a, p) == hipSuccess) return a.device;
+  (void)hipGetLastError();
+  return -1;
+}
+
+// Every entry point that touches the device runs with the handle's device current - or the device that owns a buffer -
+// and restores the caller's (torch's) current device afterwards.
 struct DeviceGuard {
   int prev = -1, dev;
   bool ok = true;
   explicit DeviceGuard(int d) : dev(d) {
+    if (dev < 0) return;                                        // not a device allocation HIP knows: current device
     if (hipGetDevice(&prev) != hipSuccess) prev = -1;
     if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
   }
-  ~DeviceGuard() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
+  explicit DeviceGuard(const void* p) : DeviceGuard(device_of_ptr(p)) {}
+  ~DeviceGuard() { if (dev >= 0 && prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
 };
+#define DEVICE_ENTER(owner) \
+  DeviceGuard guard(owner); \
+  if (!guard.ok) return DIRAL_ERR_NO_DEVICE
+
+int blocks(size_t total, int threads) { return (int)((total + threads - 1) / threads); }
+
+// a launch and its status; launch_1d: one thread per item, in blocks of 256
+template <auto Kernel, typename... Args>
+hipError_t launch_k(dim3 grid, dim3 block, uint32_t lds, hipStream_t s, Args... args) {
+  hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
+  return hipGetLastError();
+}
+template <auto Kernel, typename... Args>
+hipError_t launch_1d(size_t total, hipStream_t s, Args... args) {
+  return launch_k<Kernel>(dim3(blocks(total, 256)), dim3(256), 0, s, args...);
+}
+// run-time DIRAL_F32 / DIRAL_F64 -> the element type, handed to `f` as a value of it
+template <typename F>
+hipError_t by_dtype(int dtype, F&& f) { return dtype == DIRAL_F64 ? f(double{}) : f(float{}); }
 
 // State flags that only add OUTPUT columns to the state vector (test_env.py:527-583): served
 // by the RICH instantiations of the specialised kernels (rich_out.hpp)
@@ -213,33 +277,15 @@ bool is_specialised_cfg(const StepParams& p) {
 }
 // the state vector carries the type-2 piggybacked histogram
 bool has_hist2(const StepParams& p) { return (p.flags & DIRAL_F_ADD_POSDIST_PIGGY) && p.posdist_type == 2; }
-// ... of which the PLAIN instantiations serve the toy YAML's State flags with the state vector
-// as the only observation output (the metric's configuration)
+// the toy YAML's State flags: a state row is [action one-hot | type-2 histogram] (RichParams::plain_state)
+bool is_plain_state(const StepParams& p) {
+  return (p.flags & (kRichFlags | DIRAL_F_ADD_POSDIST)) == 0 && has_hist2(p) && (p.flags & DIRAL_F_ADD_ACTION);
+}
+// ... of which the PLAIN instantiations serve that state vector as the only observation output, without
+// proportional fairness (the metric's configuration)
 bool is_plain_cfg(const StepParams& p) {
-  return (p.flags & (kRichFlags | DIRAL_F_PROPORTIONAL_FAIR | DIRAL_F_ADD_POSDIST)) == 0 && has_hist2(p) &&
-         (p.flags & DIRAL_F_ADD_ACTION) && p.state_out != nullptr && p.chobs_out == nullptr;
+  return is_plain_state(p) && !(p.flags & DIRAL_F_PROPORTIONAL_FAIR) && p.state_out != nullptr && p.chobs_out == nullptr;
 }
-
-int blocks(size_t total, int threads) { return (int)((total + threads - 1) / threads); }
-
-// The handle-less entry points (diral_sps_*, diral_driver_shape) take device pointers only: they run on the
-// device that owns `p` (their first mandatory buffer), whatever device is current in the calling thread.
-int device_of_ptr(const void* p) {
-  hipPointerAttribute_t a;
-  if (p && hipPointerGetAttributes(&a, p) == hipSuccess) return a.device;
-  (void)hipGetLastError();
-  return -1;
-}
-struct PtrDeviceGuard {
-  int prev = -1, dev = -1;
-  bool ok = true;
-  explicit PtrDeviceGuard(const void* p) : dev(device_of_ptr(p)) {
-    if (dev < 0) return;                                        // not a device allocation HIP knows: current device
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
-  }
-  ~PtrDeviceGuard() { if (dev >= 0 && prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
 
 // A switch between the xpos ring and the per-entry plane (ring_rebuild / ring_materialize) is a launch that
 // depends on HOST-side validity flags: recorded into a hipGraph it would replay against tables it no longer
@@ -251,37 +297,43 @@ bool stream_is_capturing(hipStream_t s) {
   return st != hipStreamCaptureStatusNone;
 }
 
+// Every hipMalloc of a handle: `bytes` + `slack` are allocated, recorded (DevBuf) and filled with `fill`; with `on_reset`
+// diral_env_reset fills the `bytes` again, on the caller's stream.  The slack is what a kernel reads past the end
+// UNMASKED: it is filled here once and nobody writes it, so each size is stated at its one call of `own` and nowhere else.
+template <typename T>
+hipError_t own(DiralEnv* e, T*& p, size_t bytes, size_t slack = 0, bool on_reset = false, int fill = 0) {
+  const hipError_t st = hipMalloc((void**)&p, bytes + slack);
+  if (st != hipSuccess) return st;
+  e->bufs.push_back({p, bytes + slack, on_reset ? bytes : 0, fill});
+  return fill == kNoFill ? hipSuccess : hipMemset(p, fill, bytes + slack);
+}
+const DevBuf& buf_of(const DiralEnv* e, const void* p) {
+  for (const DevBuf& b : e->bufs) if (b.p == p) return b;
+  std::abort();   // (not a buffer of `own`: a bug in this file)
+}
+
 // every consumer of the per-entry xpos plane other than step_fast64 goes through here first
 hipError_t ensure_plane(DiralEnv* e, hipStream_t s) {
   if (e->plane_valid || !e->ring) { e->plane_valid = true; return hipSuccess; }
   if (stream_is_capturing(s)) { e->capture_violation = true; return hipErrorStreamCaptureUnsupported; }
-  if (e->tcode) {
-    const size_t total = (size_t)e->B * (e->NR / 4) * e->NV;
-    hipLaunchKernelGGL(unpack_codes_kernel, dim3(blocks(total, 256)), dim3(256), 0, s, e->B, e->N, e->NV, e->NR, e->tcode,
-                       e->tage, e->tseq, e->ring, e->tkey, e->tx);
-  } else {
-    const size_t total = (size_t)e->B * e->N * e->N;
-    hipLaunchKernelGGL(ring_materialize_kernel, dim3(blocks(total, 256)), dim3(256), 0, s, e->B, e->N, e->NV, e->NR, e->tkey,
-                       e->ring, e->tx);
-  }
   e->plane_valid = true;
-  return hipGetLastError();
+  if (e->tcode)
+    return launch_1d<unpack_codes_kernel>((size_t)e->B * (e->NR / 4) * e->NV, s, e->B, e->N, e->NV, e->NR, e->tcode, e->tage,
+                                          e->tseq, e->ring, e->tkey, e->tx);
+  return launch_1d<ring_materialize_kernel>((size_t)e->B * e->N * e->N, s, e->B, e->N, e->NV, e->NR, e->tkey, e->ring, e->tx);
 }
 hipError_t ensure_ring(DiralEnv* e, hipStream_t s) {
   if (e->ring_valid) return hipSuccess;
   if (stream_is_capturing(s)) { e->capture_violation = true; return hipErrorStreamCaptureUnsupported; }
-  const size_t total = (size_t)e->B * e->N * e->N;
-  hipLaunchKernelGGL(ring_rebuild_kernel, dim3(blocks(total, 256)), dim3(256), 0, s, e->B, e->N, e->NV, e->NR, e->tkey,
-                     e->tx, e->ring);
-  if (e->tcode) {
-    const size_t nq = (size_t)e->B * (e->NR / 4);
-    hipError_t st = hipMemsetAsync(e->told, 0, nq * 4, s);
-    if (st != hipSuccess) return st;
-    hipLaunchKernelGGL(pack_codes_kernel, dim3(blocks(nq * e->NV, 256)), dim3(256), 0, s, e->B, e->N, e->NV, e->NR, e->tkey,
-                       e->tcode, e->tage, e->tseq, e->told);
+  hipError_t st = launch_1d<ring_rebuild_kernel>((size_t)e->B * e->N * e->N, s, e->B, e->N, e->NV, e->NR, e->tkey, e->tx, e->ring);
+  if (st == hipSuccess && e->tcode) {
+    st = hipMemsetAsync(e->told, 0, buf_of(e, e->told).reset_bytes, s);
+    if (st == hipSuccess)
+      st = launch_1d<pack_codes_kernel>((size_t)e->B * (e->NR / 4) * e->NV, s, e->B, e->N, e->NV, e->NR, e->tkey, e->tcode, e->tage,
+                                        e->tseq, e->told);
   }
-  e->ring_valid = true;
-  return hipGetLastError();
+  e->ring_valid = st == hipSuccess;
+  return st;
 }
 
 // The RICH output-tail description of one call: section layout of the state vector, and which of its columns
@@ -289,7 +341,8 @@ hipError_t ensure_ring(DiralEnv* e, hipStream_t s) {
 RichParams rich_for(const DiralEnv* e, const StepParams& p) {
   RichParams r = e->rich;
   r.chobs_out = nullptr; r.episode = p.episode; r.eps = p.eps;
-  r.plain_state = ((p.flags & (kRichFlags | DIRAL_F_ADD_POSDIST)) == 0 && has_hist2(p) && (p.flags & DIRAL_F_ADD_ACTION)) ? 1 : 0;
+  // (the row's layout, whatever else the call writes: is_plain_cfg without its conditions on outputs and fairness)
+  r.plain_state = is_plain_state(p) ? 1 : 0;
   if (!has_hist2(p)) r.off_hist = -1;                         // (type 1: posdist_kernel writes those columns)
   // the sorted-distance columns and the type-1 histogram are posdist_kernel.hpp's, every one of them (and
   // neighbours in the state vector, state_offsets): not written here at all
@@ -329,10 +382,7 @@ hipError_t launch_observe_any(DiralEnv* e, const StepParams& p, hipStream_t s) {
 
 // after an import: the ring must answer every young entry with that entry's own xpos (aux_kernels.hpp)
 hipError_t verify_ring(DiralEnv* e, hipStream_t s) {
-  const size_t total = (size_t)e->B * e->N * e->N;
-  hipLaunchKernelGGL(ring_verify_kernel, dim3(blocks(total, 256)), dim3(256), 0, s, e->B, e->N, e->NV, e->NR, e->tkey, e->tx,
-                     e->ring, e->err);
-  return hipGetLastError();
+  return launch_1d<ring_verify_kernel>((size_t)e->B * e->N * e->N, s, e->B, e->N, e->NV, e->NR, e->tkey, e->tx, e->ring, e->err);
 }
 
 // scratch of the three-launch form (step_large.hpp), and its kernels' LDS attributes: at create for a large handle,
@@ -340,206 +390,197 @@ hipError_t verify_ring(DiralEnv* e, hipStream_t s) {
 hipError_t alloc_large_scratch(DiralEnv* e) {
   if (e->lg.src) return hipSuccess;
   const size_t bn = (size_t)e->B * e->N, ba = (size_t)e->B * e->A;
-  struct { void** p; size_t bytes; } bufs[] = {
-    {(void**)&e->lg.src, ba * e->N * 2}, {(void**)&e->lg.cnt, ba * 4}, {(void**)&e->lg.alist, ba * 2},
-    {(void**)&e->lg.nact, (size_t)e->B * 4}, {(void**)&e->lg.qflag, (size_t)e->B * ((e->N + 1) / 2) + 16}, {(void**)&e->lg.px0, bn * 8},
-    {(void**)&e->lg.rew, bn * 8}, {(void**)&e->lg.rtx, bn * 8}};
-  for (auto& q : bufs) {
-    hipError_t r = hipMalloc(q.p, q.bytes);
-    if (r != hipSuccess) return r;
-    e->hbm_bytes += (int64_t)q.bytes;
-    r = hipMemset(*q.p, 0, q.bytes);
-    if (r != hipSuccess) return r;
-  }
-  return set_attr_large(e->N, e->A, e->K);
+  hipError_t st = own(e, e->lg.src, ba * e->N * 2);
+  if (st == hipSuccess) st = own(e, e->lg.cnt, ba * 4);
+  if (st == hipSuccess) st = own(e, e->lg.alist, ba * 2);
+  if (st == hipSuccess) st = own(e, e->lg.nact, (size_t)e->B * 4);
+  if (st == hipSuccess) st = own(e, e->lg.qflag, (size_t)e->B * ((e->N + 1) / 2) + 16);
+  if (st == hipSuccess) st = own(e, e->lg.px0, bn * 8);
+  if (st == hipSuccess) st = own(e, e->lg.rew, bn * 8);
+  if (st == hipSuccess) st = own(e, e->lg.rtx, bn * 8);
+  return st == hipSuccess ? set_attr_large(e->N, e->A, e->K) : st;
 }
 
 size_t slow_set_words(const DiralEnv* e) { return 16 + (size_t)fast_slow_max(e->B) + (size_t)e->B; }
-hipError_t clear_slow_sets(DiralEnv* e, hipStream_t s) {
-  if (!e->slow) return hipSuccess;
-  e->slow_launches = 0;
-  return hipMemsetAsync(e->slow, 0, 3 * slow_set_words(e) * 4, s);
-}
 
-// Which kernel family and instantiation a step call runs on: decided in ONE place, for the launch itself
-// (launch_step_any) and for everyone who must know the outcome before anything is launched (diral_env_step_policy).
-struct StepDispatch {
-  bool spec, plain, ch, use_fast64, use_wide;
+// What one step call launches: decided in ONE place and without side effects, from the handle, the call's parameters
+// and its policy request (`pol`: diral_env_step_policy / diral_env_prefill, else null) - for the launch itself
+// (launch_step_any) and for everyone who must know the outcome before anything is launched (`fused`).
+enum class StepLaunch { Large, General, Fast64, Wide, Fast64Policy, Fast64Slots, WideSlots };
+struct StepPlan {
+  StepLaunch launch;
+  bool use_fast64, use_wide;   // the kernel family of the five specialised launches
+  bool use_ring;               // xpos ring (step_fast64.hpp): the kernel keeps the plane only for entries older than the ring reaches
+  bool slow_sets;              // the launch reads the slow-env sets (and rotates them: rotate_slow_sets); its grid has their blocks
+  bool fused;                  // the policy request is part of the launch (Fast64Policy, Fast64Slots, WideSlots)
   // the run-time switches of the EXTRA instantiations, host-folded (FastParams::design ... nomove)
   bool design, prr, notab, nomove;
   int32_t* la;
   const double* trace;
-  bool extra;
-  bool pol_ok;          // the POL instantiation of step_fast64 (policy epilogue inside the launch) takes this call
-  bool prefill_ok;      // ... and the K-slot form of it runs this configuration's random prefill (diral_env_prefill: my_step_design's
-                        // reward is computed in P2 there, so the design switch does not count against it)
-  bool wide_kslots_ok;  // step_wide_slots_kernel (k_wide_slots.hip) takes K > 1 slots of diral_env_step_policy at 64 < N <= 256
+  bool general_fast;           // StepLaunch::General: the FAST instantiation of the general kernel
+  KernelSel k;
+  int last_kernel;             // DIRAL_KERNEL_*
 };
-StepDispatch step_dispatch(const DiralEnv* e, const StepParams& p) {
-  StepDispatch d;
-  d.spec = is_specialised_cfg(p) && e->kernel_path == DIRAL_PATH_AUTO && !e->large;
-  d.plain = d.spec && is_plain_cfg(p);
-  d.ch = p.mode == DIRAL_STEP_MY_STEP_CH;
+StepPlan plan_step(const DiralEnv* e, const StepParams& p, const PolParams* pol) {
+  StepPlan d = {};
+  if (runs_large(e)) {
+    // (and diral_env_observe: the search kernel's observe mode + the histogram launch)
+    d.launch = StepLaunch::Large; d.last_kernel = DIRAL_KERNEL_LARGE;
+    return d;
+  }
+  // (DIRAL_PATH_GENERAL keeps the general kernel's FAST instantiation: plain_cfg does not ask for the path)
+  const bool plain_cfg = is_specialised_cfg(p) && is_plain_cfg(p);
+  const bool spec = is_specialised_cfg(p) && e->kernel_path == DIRAL_PATH_AUTO;
+  const bool plain = spec && plain_cfg;
+  const bool ch = p.mode == DIRAL_STEP_MY_STEP_CH;
   // the wide kernels read the reward column of a RICH state back from rew_out
-  const bool wide_rich_ok = d.plain || !(p.flags & DIRAL_F_ADD_REWARD) || p.state_out == nullptr || p.rew_out != nullptr;
-  d.use_fast64 = d.spec && e->vpl == 1 && p.A <= kFastMaxA && p.NV == 64;
-  d.use_wide = d.spec && e->vpl > 1 && p.A <= kWideMaxA && e->flat_y && wide_rich_ok;
+  const bool wide_rich_ok = plain || !(p.flags & DIRAL_F_ADD_REWARD) || p.state_out == nullptr || p.rew_out != nullptr;
+  d.use_fast64 = spec && fits_fast64(e);
+  d.use_wide = spec && fits_wide(e) && e->flat_y && wide_rich_ok;
+  if (!d.use_fast64 && !d.use_wide) {
+    // the generic FAST instantiation of the general kernel: the plain configuration on sizes the
+    // specialised kernels do not take (A > 64, vehicles off the y = 0 lane at N > 64): my_step,
+    // f32 outputs, no arrival stamps, no trace replay
+    d.general_fast = plain_cfg && !p.out_f64 && p.mode == DIRAL_STEP_MY_STEP && !(p.flags & DIRAL_F_TRACK_ARRIVAL) && p.trace == nullptr;
+    d.launch = StepLaunch::General; d.last_kernel = DIRAL_KERNEL_GENERAL;
+    return d;
+  }
+  d.use_ring = e->ring != nullptr;
   d.design = p.mode == DIRAL_STEP_DESIGN;
   d.prr = (p.flags & DIRAL_F_TRACK_PRR) && p.mode == DIRAL_STEP_MY_STEP;
   d.notab = !(p.flags & DIRAL_F_ADD_POSDIST_PIGGY);          // no piggybacked tables: test_env.py:138-139, 231-238
   d.nomove = !(p.flags & DIRAL_F_MOBILITY);                  // static (design) topology: network.py:302-305
   d.la = (p.flags & DIRAL_F_TRACK_ARRIVAL) ? p.la : nullptr;
   d.trace = d.nomove ? nullptr : p.trace;
-  d.extra = d.design || d.la != nullptr || d.trace != nullptr || d.prr || d.notab || d.nomove;
-  d.pol_ok = d.use_fast64 && e->flat_y && !d.ch && !d.extra && p.N >= 8;
-  d.prefill_ok = d.use_fast64 && e->flat_y && d.design && d.la == nullptr && d.trace == nullptr && !d.prr && !d.notab && !d.nomove && p.N >= 8;
-  d.wide_kslots_ok = d.use_wide && !d.ch && !d.extra;
+  const bool switches = d.la != nullptr || d.trace != nullptr || d.prr || d.notab || d.nomove;
+  const bool extra = d.design || switches;
+  // the POL instantiation of step_fast64 (policy epilogue inside the launch) takes this call
+  const bool pol_ok = d.use_fast64 && e->flat_y && !ch && !extra && p.N >= 8;
+  // ... and the K-slot form of it runs this configuration's random prefill (diral_env_prefill: my_step_design's
+  // reward is computed in P2 there, so the design switch does not count against it)
+  const bool prefill_ok = d.use_fast64 && e->flat_y && d.design && !switches && p.N >= 8;
+  // step_wide_slots_kernel (k_wide_slots.hip) takes K > 1 slots of diral_env_step_policy at 64 < N <= 256; a one-slot
+  // call there keeps its three launches
+  const bool wide_kslots_ok = d.use_wide && !ch && !extra;
+  d.launch = d.use_wide ? StepLaunch::Wide : StepLaunch::Fast64;
+  if (pol && pol->prefill) { if (prefill_ok) d.launch = StepLaunch::Fast64Slots; }
+  else if (pol && pol->K > 1) { if (pol_ok) d.launch = StepLaunch::Fast64Slots; else if (wide_kslots_ok) d.launch = StepLaunch::WideSlots; }
+  else if (pol && pol_ok) d.launch = StepLaunch::Fast64Policy;
+  // K slots per launch (DiralSlotPolicy::slots > 1, prefill): blocks = envs in order - over K slots a straggler averages
+  // out; the slow-env sets stay as the last one-slot launch left them (complete or empty), unread
+  const bool kslots = d.launch == StepLaunch::Fast64Slots || d.launch == StepLaunch::WideSlots;
+  d.fused = kslots || d.launch == StepLaunch::Fast64Policy;
+  // (step_wide: the packed form at N <= 128 only - its slow envs are 4 x the others; the plane form's are 1.6 x and measured
+  // 4 % SLOWER dispatched first, N > 128 packed runs on dense topologies without any: - 0.7 % for the bookkeeping)
+  // Round 6: with the far-entry guard (step_wide.hpp `wide_far_guard`) the flagged passes of a highway that broke apart run
+  // on the coded path - those envs are no longer 3 x the others, and the slow-first grid (B / 4 more blocks, a flag load per
+  // block) now costs more than it orders: C5 0.930 ms with it, 0.875 in batch order (one box, interleaved, profiles/r06).
+  // DIRAL_WIDE_SLOW_FIRST=1 at create brings it back (A/B).
+  const bool wide_slow = d.use_wide && e->vpl == 2 && e->tcode != nullptr && e->hooks.wide_slow_first;
+  d.slow_sets = (d.use_fast64 || wide_slow) && e->slow && e->hooks.slow_first && !kslots;
+  KernelSel& k = d.k;
+  k.flat = e->flat_y; k.out64 = p.out_f64 != 0; k.full = p.N == 64 * e->vpl; k.ch = ch;
+  k.extra = extra;                                            // EXTRA instantiation: the run-time switches compiled in
+  k.rich = !plain;
+  k.packed = d.use_wide && e->tcode != nullptr;
+  // (a fused launch is a RICH instantiation: the channel observation is staged in LDS whether or not it is written out)
+  d.last_kernel = (d.use_wide ? DIRAL_KERNEL_WIDE : DIRAL_KERNEL_FAST64) | ((k.rich || d.fused) ? DIRAL_KERNEL_RICH : 0) |
+                  ((k.packed || d.use_fast64) ? DIRAL_KERNEL_PACKED : 0) | (k.extra ? DIRAL_KERNEL_EXTRA : 0) |
+                  (k.ch ? DIRAL_KERNEL_CH : 0) | (d.use_ring ? DIRAL_KERNEL_RING : 0) | (d.fused ? DIRAL_KERNEL_POLICY : 0);
   return d;
 }
 
-// `pol` / `fused`: diral_env_step_policy - when the configuration runs on the POL instantiation of step_fast64 the policy
-// epilogue is part of this launch and *fused is set; otherwise the plain step is launched and the caller adds the two
-// policy launches
-hipError_t launch_step_any(DiralEnv* e, const StepParams& p, hipStream_t s, const PolParams* pol = nullptr, bool* fused = nullptr) {
-  const int vpl = e->vpl;
-  const bool flat_y = e->flat_y;
-  if (runs_large(e)) {
-    // (and diral_env_observe: the search kernel's observe mode + the histogram launch)
-    const hipError_t st = ensure_plane(e, s);
-    if (st != hipSuccess) return st;
-    if (p.mode != kModeObserve) e->ring_valid = false;
-    e->last_kernel = DIRAL_KERNEL_LARGE;
-    return launch_large(p, e->lg, s);
+// float32 screening of the histogram bin (step_fast64.hpp, fast quads), FastParams::f32_m16: everything float32 can lose,
+// in bin widths, for positions in [0, L] - the three conversions and the fma at t <= K below - with a factor of two on
+// top; as 1 / 65536ths, rounded up, + 1.  0 = no screening: the band would be too wide, or `hook` (DIRAL_F32_MARGIN) is 0;
+// a hook > 0 widens the band to at least that.
+int f32_margin16(double L, double Rb, int K, int hook) {
+  const double w = (Rb - (-Rb)) / (double)K;
+  const double xmax = L;
+  // (the kernel computes t = fma(float(xpos), float(inv_w 2^16), float((Rb - npx) inv_w 2^16)): the conversion of the
+  // stamp and of the factor lose 2 |xpos| 2^-24 / w bin widths, the addend's |Rb - npx| 2^-24 / w <= (xmax + Rb) 2^-24 / w,
+  // the fma's own rounding K 2^-24)
+  const double lost = 2.0 * (((3.0 * xmax + Rb) * 0x1p-24) / w + 2.0 * (double)K * 0x1p-23);
+  const double m = std::ceil(lost * 65536.0) + 1.0;
+  const bool on = m <= 64.0 && xmax < 1e6 && hook != 0;
+  return on ? std::max((int)m, std::min(hook, 16384)) : 0;
+}
+
+// the arguments of a specialised launch, but for the slow-env sets (rotate_slow_sets)
+FastParams fast_params(const DiralEnv* e, const StepParams& p, const StepPlan& d) {
+  FastParams f;
+  f.N = p.N; f.A = p.A; f.K = p.K; f.NR = p.NR; f.NV = p.NV; f.flags = p.flags;
+  f.reward_design = p.reward_design; f.age_limit = p.age_limit; f.episode_interval = p.episode_interval;
+  f.design = d.design ? 1 : 0;
+  f.done_now = (!p.t_dev && (p.t % p.episode_interval) == p.episode_interval - 1) ? 1 : 0;   // main_test.py:226 (with a slot clock: on the device)
+  f.prr = d.prr ? 1 : 0;
+  f.notab = d.notab ? 1 : 0;
+  f.nomove = d.nomove ? 1 : 0;
+  f.trace = d.trace;
+  f.chobs_mode = (p.chobs_out ? 1 : 0) | ((p.mode == DIRAL_STEP_MY_STEP && p.state_type == 2) ? 2 : 0);
+  f.L = p.L; f.Rc = p.Rc; f.Rb = p.Rb; f.inv_w = p.hist_inv_width; f.t = p.t; f.t_dev = p.t_dev;
+  f.actions = p.actions; f.pos_x = p.pos_x; f.pos_y = p.pos_y; f.vel = p.vel; f.tkey = p.tkey; f.tx = p.tx;
+  f.metrics = p.metrics; f.err = p.err; f.edges = p.edges; f.inv_tab = e->inv_tab;
+  f.ring = d.use_ring ? e->ring : nullptr;
+  f.tcode = e->tcode; f.tage = e->tage; f.tseq = e->tseq; f.told = e->told;
+  f.la = d.la;
+  f.trace_len = p.trace_len; f.trace_per_env = p.trace_per_env;
+  f.state_out = p.state_out; f.rew_out = p.rew_out;
+  f.done_out = p.done_out; f.dbg = p.dbg;
+  f.B = p.B;
+  f.f32_m16 = d.use_fast64 ? f32_margin16(p.L, p.Rb, p.K, e->hooks.f32_margin) : 0;
+  f.f32_xmax = (float)p.L;
+  f.slow_cnt_r = nullptr; f.slow_list_r = nullptr; f.slow_flag_r = nullptr;
+  f.slow_cnt_w = nullptr; f.slow_list_w = nullptr; f.slow_flag_w = nullptr; f.slow_cnt_z = nullptr;
+  return f;
+}
+
+// Slow envs first: this launch reads set (launches % 3), builds the next one and clears the one after, and moves on.
+void rotate_slow_sets(DiralEnv* e, FastParams& f, hipStream_t s) {
+  const size_t w = slow_set_words(e);
+  uint32_t* const set_r = e->slow + (e->slow_launches % 3) * w;
+  uint32_t* const set_w = e->slow + ((e->slow_launches + 1) % 3) * w;
+  uint32_t* const set_z = e->slow + ((e->slow_launches + 2) % 3) * w;
+  f.slow_cnt_r = set_r; f.slow_list_r = set_r + 16; f.slow_flag_r = set_r + 16 + fast_slow_max(e->B);
+  if (e->capture_rotates || !stream_is_capturing(s)) {
+    f.slow_cnt_w = set_w; f.slow_list_w = set_w + 16; f.slow_flag_w = set_w + 16 + fast_slow_max(e->B);
+    f.slow_cnt_z = set_z;
+    ++e->slow_launches;
   }
-  const StepDispatch d = step_dispatch(e, p);
-  const bool plain = d.plain, ch = d.ch, use_fast64 = d.use_fast64, use_wide = d.use_wide;
-  // xpos ring (step_fast64.hpp): the N <= 64 kernel keeps the plane only for entries older than the ring reaches
-  const bool use_ring = (use_fast64 || use_wide) && e->ring != nullptr;
-  if (use_ring) {
-    const hipError_t st = ensure_ring(e, s);
-    if (st != hipSuccess) return st;
-  } else {
-    const hipError_t st = ensure_plane(e, s);
-    if (st != hipSuccess) return st;
-    if (p.mode != kModeObserve) e->ring_valid = false;         // this step moves the tables without the ring
+  // (a CAPTURED launch reads the set it was baked with and builds none: a replayed graph could not rotate the sets -
+  // unless the caller keeps every graph at a multiple of three launches and its phase aligned:
+  // diral_env_set_capture_rotation.  Eager launches between two replays keep rotating through that set: they leave it
+  // either rebuilt or EMPTY - count and flags, step_fast64.hpp - never half cleared, so the replay runs every env
+  // exactly once whatever happened in between; the list it reads ages - slow envs stay slow for hundreds of slots,
+  // profiles/launch_timeline.py - or is empty, which costs time, not correctness.)
+}
+
+// Executes a plan.  `pol`: the policy request the plan was made for; where the plan is `fused` the policy epilogue is
+// part of this launch, otherwise the plain step is launched and diral_env_step_policy adds the two policy launches.
+hipError_t launch_step_any(DiralEnv* e, const StepParams& p, const StepPlan& d, hipStream_t s, const PolParams* pol = nullptr) {
+  const hipError_t st = d.use_ring ? ensure_ring(e, s) : ensure_plane(e, s);
+  if (st != hipSuccess) return st;
+  if (d.use_ring) e->plane_valid = false;
+  else if (p.mode != kModeObserve) e->ring_valid = false;      // this step moves the tables without the ring
+  e->last_kernel = d.last_kernel;
+  if (d.launch == StepLaunch::Large) return launch_large(p, e->lg, s);
+  if (d.launch == StepLaunch::General) return launch_general(e->vpl, d.general_fast, p, e->lds_bytes, s);
+  FastParams f = fast_params(e, p, d);
+  if (d.slow_sets) rotate_slow_sets(e, f, s);
+  RichParams r = rich_for(e, p);
+  r.chobs_out = p.chobs_out;
+  r.pf = ((p.flags & DIRAL_F_PROPORTIONAL_FAIR) && p.mode == DIRAL_STEP_MY_STEP) ? p.pf : nullptr;
+  r.pf_threshold = p.pf_threshold; r.pf_penalty = p.pf_penalty;
+  const int grid = p.B + (d.slow_sets ? fast_slow_max(p.B) : 0);
+  switch (d.launch) {
+    // K slots per launch with the policy epilogue at 64 < N <= 256: step_wide_slots_kernel, blocks = envs in batch order
+    case StepLaunch::WideSlots: return launch_wide_slots(f, r, *pol, d.k, e->vpl, p.B, s);
+    case StepLaunch::Wide: return e->vpl == 2 ? launch_wide2(f, r, d.k, grid, s) : launch_wide4(f, r, d.k, grid, s);
+    // the env stays on the chip from slot to slot: step_fast64_slots_kernel
+    case StepLaunch::Fast64Slots: return launch_fast64_slots(f, r, *pol, d.k.out64, p.B, s);
+    case StepLaunch::Fast64Policy: return launch_fast64_policy(f, r, *pol, d.k.out64, grid, s);
+    default: return launch_fast64(f, r, d.k, grid, s);
   }
-  if (use_fast64 || use_wide) {
-    FastParams f;
-    f.N = p.N; f.A = p.A; f.K = p.K; f.NR = p.NR; f.NV = p.NV; f.flags = p.flags;
-    f.reward_design = p.reward_design; f.age_limit = p.age_limit; f.episode_interval = p.episode_interval;
-    f.design = d.design ? 1 : 0;
-    f.done_now = (!p.t_dev && (p.t % p.episode_interval) == p.episode_interval - 1) ? 1 : 0;   // main_test.py:226 (with a slot clock: on the device)
-    f.prr = d.prr ? 1 : 0;
-    f.notab = d.notab ? 1 : 0;
-    f.nomove = d.nomove ? 1 : 0;
-    f.trace = d.trace;
-    f.chobs_mode = (p.chobs_out ? 1 : 0) | ((p.mode == DIRAL_STEP_MY_STEP && p.state_type == 2) ? 2 : 0);
-    f.L = p.L; f.Rc = p.Rc; f.Rb = p.Rb; f.inv_w = p.hist_inv_width; f.t = p.t; f.t_dev = p.t_dev;
-    f.actions = p.actions; f.pos_x = p.pos_x; f.pos_y = p.pos_y; f.vel = p.vel; f.tkey = p.tkey; f.tx = p.tx;
-    f.metrics = p.metrics; f.err = p.err; f.edges = p.edges; f.inv_tab = e->inv_tab;
-    f.ring = use_ring ? e->ring : nullptr;
-    f.tcode = e->tcode; f.tage = e->tage; f.tseq = e->tseq; f.told = e->told;
-    if (use_ring) e->plane_valid = false;
-    f.la = d.la;
-    f.trace_len = p.trace_len; f.trace_per_env = p.trace_per_env;
-    f.state_out = p.state_out; f.rew_out = p.rew_out;
-    f.done_out = p.done_out; f.dbg = p.dbg;
-    f.B = p.B;
-    {
-      // float32 screening of the histogram bin (step_fast64.hpp, fast quads): everything float32 can lose, in bin widths,
-      // for positions in [0, L] - the three conversions and the fma at t <= K below - with a factor of two on top; as
-      // 1 / 65536ths, rounded up, + 1
-      const double w = (p.Rb - (-p.Rb)) / (double)p.K;
-      const double xmax = p.L;
-      // (the kernel computes t = fma(float(xpos), float(inv_w 2^16), float((Rb - npx) inv_w 2^16)): the conversion of the
-      // stamp and of the factor lose 2 |xpos| 2^-24 / w bin widths, the addend's |Rb - npx| 2^-24 / w <= (xmax + Rb) 2^-24 / w,
-      // the fma's own rounding K 2^-24)
-      const double lost = 2.0 * (((3.0 * xmax + p.Rb) * 0x1p-24) / w + 2.0 * (double)p.K * 0x1p-23);
-      const double m = std::ceil(lost * 65536.0) + 1.0;
-      const bool on = use_fast64 && m <= 64.0 && xmax < 1e6 && e->f32_margin != 0;
-      f.f32_m16 = on ? std::max((int)m, std::min(e->f32_margin, 16384)) : 0;
-      f.f32_xmax = (float)xmax;
-    }
-    f.slow_cnt_r = nullptr; f.slow_list_r = nullptr; f.slow_flag_r = nullptr;
-    f.slow_cnt_w = nullptr; f.slow_list_w = nullptr; f.slow_flag_w = nullptr; f.slow_cnt_z = nullptr;
-    bool slow_first = false;
-    // K slots per launch (diral_env_step_policy, DiralSlotPolicy::slots > 1): blocks = envs in order - over K slots a
-    // straggler averages out; the slow-env sets stay as the last one-slot launch left them (complete or empty), unread
-    const bool kslots = pol && ((d.pol_ok && pol->K > 1) || (pol->prefill && d.prefill_ok));
-    const bool wide_kslots = pol && !pol->prefill && pol->K > 1 && d.wide_kslots_ok;
-    // (step_wide: the packed form at N <= 128 only - its slow envs are 4 x the others; the plane form's are 1.6 x and measured
-    // 4 % SLOWER dispatched first, N > 128 packed runs on dense topologies without any: - 0.7 % for the bookkeeping)
-    // Round 6: with the far-entry guard (step_wide.hpp `wide_far_guard`) the flagged passes of a highway that broke apart run
-    // on the coded path - those envs are no longer 3 x the others, and the slow-first grid (B / 4 more blocks, a flag load per
-    // block) now costs more than it orders: C5 0.930 ms with it, 0.875 in batch order (one box, interleaved, profiles/r06).
-    // DIRAL_WIDE_SLOW_FIRST=1 at create brings it back (A/B).
-    const bool wide_slow = use_wide && vpl == 2 && e->tcode != nullptr && e->wide_slow_first;
-    if ((use_fast64 || wide_slow) && e->slow && e->slow_first && !kslots && !wide_kslots) {
-      const size_t w = slow_set_words(e);
-      uint32_t* const set_r = e->slow + (e->slow_launches % 3) * w;
-      uint32_t* const set_w = e->slow + ((e->slow_launches + 1) % 3) * w;
-      uint32_t* const set_z = e->slow + ((e->slow_launches + 2) % 3) * w;
-      f.slow_cnt_r = set_r; f.slow_list_r = set_r + 16; f.slow_flag_r = set_r + 16 + fast_slow_max(e->B);
-      if (e->capture_rotates || !stream_is_capturing(s)) {
-        f.slow_cnt_w = set_w; f.slow_list_w = set_w + 16; f.slow_flag_w = set_w + 16 + fast_slow_max(e->B);
-        f.slow_cnt_z = set_z;
-        ++e->slow_launches;
-      }
-      // (a CAPTURED launch reads the set it was baked with and builds none: a replayed graph could not rotate the sets -
-      // unless the caller keeps every graph at a multiple of three launches and its phase aligned:
-      // diral_env_set_capture_rotation.  Eager launches between two replays keep rotating through that set: they leave it
-      // either rebuilt or EMPTY - count and flags, step_fast64.hpp - never half cleared, so the replay runs every env
-      // exactly once whatever happened in between; the list it reads ages - slow envs stay slow for hundreds of slots,
-      // profiles/launch_timeline.py - or is empty, which costs time, not correctness.)
-      slow_first = true;
-    }
-    RichParams r = rich_for(e, p);
-    r.chobs_out = p.chobs_out;
-    r.pf = ((p.flags & DIRAL_F_PROPORTIONAL_FAIR) && p.mode == DIRAL_STEP_MY_STEP) ? p.pf : nullptr;
-    r.pf_threshold = p.pf_threshold; r.pf_penalty = p.pf_penalty;
-    KernelSel k;
-    k.flat = flat_y; k.out64 = p.out_f64 != 0; k.full = p.N == 64 * vpl; k.ch = ch;
-    k.extra = d.extra;                                          // EXTRA instantiation: the run-time switches compiled in
-    k.rich = !plain;
-    k.packed = use_wide && e->tcode != nullptr;
-    e->last_kernel = (use_wide ? DIRAL_KERNEL_WIDE : DIRAL_KERNEL_FAST64) | (k.rich ? DIRAL_KERNEL_RICH : 0) |
-                     ((k.packed || use_fast64) ? DIRAL_KERNEL_PACKED : 0) |
-                     (k.extra ? DIRAL_KERNEL_EXTRA : 0) | (k.ch ? DIRAL_KERNEL_CH : 0) | (use_ring ? DIRAL_KERNEL_RING : 0);
-    if (wide_kslots) {
-      // K slots per launch with the policy epilogue at 64 < N <= 256: step_wide_slots_kernel, blocks = envs in batch order
-      if (!k.rich) { r.plain_state = 1; }
-      e->last_kernel |= DIRAL_KERNEL_RICH | DIRAL_KERNEL_POLICY;
-      if (fused) *fused = true;
-      return launch_wide_slots(f, r, *pol, k, vpl, p.B, s);
-    }
-    if (use_wide) {
-      const int grid = p.B + (slow_first ? fast_slow_max(p.B) : 0);
-      return vpl == 2 ? launch_wide2(f, r, k, grid, s) : launch_wide4(f, r, k, grid, s);
-    }
-    if (kslots) {
-      // the env stays on the chip from slot to slot: step_fast64_slots_kernel
-      if (!k.rich) { r.plain_state = 1; }
-      e->last_kernel |= DIRAL_KERNEL_RICH | DIRAL_KERNEL_POLICY;
-      if (fused) *fused = true;
-      return launch_fast64_slots(f, r, *pol, k.out64, p.B, s);
-    }
-    const int grid = p.B + (slow_first ? fast_slow_max(p.B) : 0);
-    if (pol && d.pol_ok) {
-      // the policy epilogue: RICH instantiation (the channel observation is staged in LDS whether or not it is written out)
-      if (!k.rich) { r.plain_state = 1; }
-      e->last_kernel |= DIRAL_KERNEL_RICH | DIRAL_KERNEL_POLICY;
-      if (fused) *fused = true;
-      return launch_fast64_policy(f, r, *pol, k.out64, grid, s);
-    }
-    return launch_fast64(f, r, k, grid, s);
-  }
-  // the generic FAST instantiation of the general kernel: the plain configuration on sizes the
-  // specialised kernels do not take (A > 64, vehicles off the y = 0 lane at N > 64): my_step,
-  // f32 outputs, no arrival stamps, no trace replay
-  const bool fast = is_specialised_cfg(p) && is_plain_cfg(p) && !p.out_f64 && p.mode == DIRAL_STEP_MY_STEP &&
-                    !(p.flags & DIRAL_F_TRACK_ARRIVAL) && p.trace == nullptr;
-  e->last_kernel = DIRAL_KERNEL_GENERAL;
-  return launch_general(vpl, fast, p, e->lds_bytes, s);
 }
 
 // Secondary observation modes (a15/a16) run as their own launch after the step (posdist_kernel.hpp).
@@ -604,17 +645,38 @@ PiggyParams piggy_params(const DiralEnv* e, const StepParams& p) {
   return q;
 }
 
+// The parameters of one call: the handle's `base` plus what every step / observe entry point is handed.  The output
+// and input buffers other than the state vector stay null (as in `base`) for the caller to set.
+StepParams call_params(const DiralEnv* e, int mode, int64_t t, const int32_t* actions, void* state_out, int out_dtype,
+                       double episode, double epsilon) {
+  StepParams p = e->base;
+  p.mode = mode; p.t = t; p.episode = episode; p.eps = epsilon; p.out_f64 = (out_dtype == DIRAL_F64);
+  p.actions = actions;
+  p.state_out = e->S > 0 ? state_out : nullptr;
+  return p;
+}
+
 // Recompute DiralEnv::flat_y (all pos_y == 0) after pos_y was written by the
 // caller.  Synchronises the stream; only reset/import call it, never step.
 int refresh_flat_y(DiralEnv* e, hipStream_t s) {
   const size_t bn = (size_t)e->B * e->N;
   if (hipMemsetAsync(e->yflag, 0, 4, s) != hipSuccess) return DIRAL_ERR_HIP;
-  hipLaunchKernelGGL(any_nonzero_kernel, dim3(blocks(bn, 256)), dim3(256), 0, s, (int)bn, e->pos_y, e->yflag);
+  if (launch_1d<any_nonzero_kernel>(bn, s, (int)bn, e->pos_y, e->yflag) != hipSuccess) return DIRAL_ERR_HIP;
   uint32_t f = 1;
   if (hipMemcpyAsync(&f, e->yflag, 4, hipMemcpyDeviceToHost, s) != hipSuccess) return DIRAL_ERR_HIP;
   if (hipStreamSynchronize(s) != hipSuccess) return DIRAL_ERR_HIP;
   e->flat_y = (f == 0);
   return DIRAL_OK;
+}
+
+// sps_step_wave_kernel, one wave lane per 1 / 2 / 4 resources (num_channels <= kSpsWaveMaxA).  `src` holds T: the float64
+// selection window, or (CHOBS) the env's channel observation in its own dtype; `rest`: the kernel's other arguments
+template <typename T, bool CHOBS, typename... Rest>
+hipError_t launch_sps_wave(int agents, int num_channels, const void* src, hipStream_t s, Rest... rest) {
+  const T* in = static_cast<const T*>(src);
+  if (num_channels <= 64) return launch_1d<sps_step_wave_kernel<1, T, CHOBS>>((size_t)agents, s, agents, num_channels, in, rest...);
+  if (num_channels <= 128) return launch_1d<sps_step_wave_kernel<2, T, CHOBS>>((size_t)agents, s, agents, num_channels, in, rest...);
+  return launch_1d<sps_step_wave_kernel<4, T, CHOBS>>((size_t)agents, s, agents, num_channels, in, rest...);
 }
 
 }  // namespace
@@ -715,6 +777,7 @@ int diral_env_create(const DiralCfg* cfg, int batch, int device, DiralEnv** out)
 
   DiralEnv* e = new DiralEnv();
   e->cfg = *cfg;
+  e->hooks = read_hooks();
   e->B = batch; e->N = cfg->num_users; e->A = cfg->num_channels;
   e->K = cfg->num_bins > 0 ? cfg->num_bins : 1;
   e->NV = e->N <= 64 ? 64 : (int)align_up((uint32_t)e->N, 16);   // one wave lane per viewer, no lane predicate
@@ -731,65 +794,47 @@ int diral_env_create(const DiralCfg* cfg, int batch, int device, DiralEnv** out)
 
   const size_t bn = (size_t)e->B * e->N;
   const size_t tab = (size_t)e->B * e->NR * e->NV;
-  auto alloc = [&](void** p, size_t bytes) {
-    hipError_t r = hipMalloc(p, bytes);
-    if (r == hipSuccess) e->hbm_bytes += (int64_t)bytes;
-    return r;
-  };
 #define CREATE_TRY(call) do { hipError_t r__ = (call); if (r__ != hipSuccess) { note_hip(e, r__, #call); \
       std::fprintf(stderr, "diral_env_create: %s\n", e->last_hip_error.c_str()); return fail(DIRAL_ERR_HIP); } } while (0)
-  CREATE_TRY(alloc((void**)&e->pos_x, bn * 8));
-  CREATE_TRY(alloc((void**)&e->pos_y, bn * 8));
-  CREATE_TRY(alloc((void**)&e->vel, bn * 8));
-  // + 256 elements of slack: step_wide.hpp loads a padded viewer slot (lane + 64 j) past the
+  // (diral_env_reset fills the buffers marked kOnReset in THIS order; reset_kernel writes the first three)
+  CREATE_TRY(own(e, e->pos_x, bn * 8));
+  CREATE_TRY(own(e, e->pos_y, bn * 8));
+  CREATE_TRY(own(e, e->vel, bn * 8));
+  // + 512 elements of slack: step_wide.hpp loads a padded viewer slot (lane + 64 j) past the
   // end of a row without clamping (the values are masked, never stored)
   // + 64 rows: the type-1 kernels (posdist_kernel.hpp) read the rows up to the next multiple of 64 of their env
   // unmasked as well
-  CREATE_TRY(alloc((void**)&e->tkey, (tab + 512 + 64 * 256) * 4));
-  CREATE_TRY(alloc((void**)&e->tx, (tab + 512 + 64 * 256) * 8));
-  // the xpos ring of the specialised kernels
-  if (!e->large && ((e->vpl == 1 && e->NV == 64 && e->A <= kFastMaxA) || (e->vpl > 1 && e->A <= kWideMaxA))) {
-    CREATE_TRY(alloc((void**)&e->ring, (size_t)e->B * e->NR * 8 * 8));
-    CREATE_TRY(hipMemset(e->ring, 0, (size_t)e->B * e->NR * 8 * 8));
+  const size_t tab_slack = 512 + 64 * 256;
+  CREATE_TRY(own(e, e->tkey, tab * 4, tab_slack * 4, kOnReset));
+  CREATE_TRY(own(e, e->tx, tab * 8, tab_slack * 8, kOnReset));
+  if (fits_fast64(e) || fits_wide(e)) {                         // the xpos ring of the specialised kernels
+    CREATE_TRY(own(e, e->ring, (size_t)e->B * e->NR * 8 * 8, 0, kOnReset));
     if (use_packed_table(e)) {                                  // the packed table of step_fast64 and of step_wide at N > 128
       // (+ 512 words of slack: step_wide.hpp loads a padded viewer slot past the end of a row without clamping)
       const size_t nq = (size_t)e->B * (e->NR / 4);
-      CREATE_TRY(alloc((void**)&e->tcode, (nq * e->NV + 512) * 4));
-      CREATE_TRY(alloc((void**)&e->tage, (nq * e->NV + 512) * 4));
-      CREATE_TRY(alloc((void**)&e->tseq, ((size_t)e->B * e->NR + 64) * 4));
-      CREATE_TRY(alloc((void**)&e->told, (nq + 16) * 4));
-      CREATE_TRY(hipMemset(e->tcode, 0, (nq * e->NV + 512) * 4));
-      CREATE_TRY(hipMemset(e->tage, 0, (nq * e->NV + 512) * 4));
-      CREATE_TRY(hipMemset(e->tseq, 0, ((size_t)e->B * e->NR + 64) * 4));
-      CREATE_TRY(hipMemset(e->told, 0, (nq + 16) * 4));
+      CREATE_TRY(own(e, e->tcode, nq * e->NV * 4, 512 * 4, kOnReset));
+      CREATE_TRY(own(e, e->tage, nq * e->NV * 4, 512 * 4, kOnReset));
+      CREATE_TRY(own(e, e->tseq, (size_t)e->B * e->NR * 4, 64 * 4, kOnReset));
+      CREATE_TRY(own(e, e->told, nq * 4, 16 * 4, kOnReset));
     }
-    {
-      CREATE_TRY(alloc((void**)&e->slow, 3 * slow_set_words(e) * 4));
-      CREATE_TRY(hipMemset(e->slow, 0, 3 * slow_set_words(e) * 4));
-      const char* off = std::getenv("DIRAL_NO_SLOW_FIRST");
-      e->slow_first = !(off && off[0] == '1');
-    }
-    if (e->vpl == 1) {
-      if (const char* fm = std::getenv("DIRAL_F32_MARGIN")) e->f32_margin = std::max(0, std::atoi(fm));
-    }
+    CREATE_TRY(own(e, e->slow, 3 * slow_set_words(e) * 4, 0, kOnReset));
     e->ring_valid = true;                                       // all tables zero: never heard, age 0, xpos 0
   }
-  CREATE_TRY(alloc((void**)&e->metrics, (size_t)e->B * DIRAL_M_COLUMNS * 8));
-  CREATE_TRY(alloc((void**)&e->err, 4));
-  CREATE_TRY(alloc((void**)&e->yflag, 4));
-  CREATE_TRY(alloc((void**)&e->edges, (size_t)(e->K + 1) * 8));
-  CREATE_TRY(alloc((void**)&e->edges1, (size_t)(e->K + 1) * 8));
-  CREATE_TRY(alloc((void**)&e->inv_tab, 256 * 8));
-  if (has(cfg, DIRAL_F_TRACK_ARRIVAL)) CREATE_TRY(alloc((void**)&e->la, bn * e->N * 4));
-  if (has(cfg, DIRAL_F_PROPORTIONAL_FAIR)) CREATE_TRY(alloc((void**)&e->pf, bn * 4));
+  CREATE_TRY(own(e, e->metrics, (size_t)e->B * DIRAL_M_COLUMNS * 8, 0, kOnReset));
+  CREATE_TRY(own(e, e->err, 4));
+  CREATE_TRY(own(e, e->yflag, 4, 0, false, kNoFill));
+  CREATE_TRY(own(e, e->edges, (size_t)(e->K + 1) * 8, 0, false, kNoFill));
+  CREATE_TRY(own(e, e->edges1, (size_t)(e->K + 1) * 8, 0, false, kNoFill));
+  CREATE_TRY(own(e, e->inv_tab, 256 * 8, 0, false, kNoFill));
+  if (has(cfg, DIRAL_F_TRACK_ARRIVAL)) CREATE_TRY(own(e, e->la, bn * e->N * 4, 0, kOnReset, 0xFF));
+  if (has(cfg, DIRAL_F_PROPORTIONAL_FAIR)) CREATE_TRY(own(e, e->pf, bn * 4, 0, kOnReset));
   if (has(cfg, DIRAL_F_PIGGYBACKING)) {
     if (piggy_search_lds_bytes(e->N) > 48u * 1024u)
       CREATE_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(piggy_search_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)piggy_search_lds_bytes(e->N)));
-    CREATE_TRY(alloc((void**)&e->prev_obs, bn * e->A * 8));
-    CREATE_TRY(alloc((void**)&e->obs_new, bn * e->A * 8));
-    CREATE_TRY(alloc((void**)&e->txid, bn * e->A * 4));
-    CREATE_TRY(hipMemset(e->prev_obs, 0, bn * e->A * 8));       // test_env.py:76-79
+    CREATE_TRY(own(e, e->prev_obs, bn * e->A * 8, 0, kOnReset));   // test_env.py:76-79
+    CREATE_TRY(own(e, e->obs_new, bn * e->A * 8, 0, false, kNoFill));
+    CREATE_TRY(own(e, e->txid, bn * e->A * 4, 0, false, kNoFill));
   }
 
   std::vector<double> edges;
@@ -813,15 +858,6 @@ int diral_env_create(const DiralCfg* cfg, int batch, int device, DiralEnv** out)
   if (!e->large)
     CREATE_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(posdist_type1_n64_kernel),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)posdist_type1_lds_bytes(e->K)));
-  CREATE_TRY(hipMemset(e->pos_x, 0, bn * 8));
-  CREATE_TRY(hipMemset(e->pos_y, 0, bn * 8));
-  CREATE_TRY(hipMemset(e->vel, 0, bn * 8));
-  CREATE_TRY(hipMemset(e->tkey, 0, (tab + 512 + 64 * 256) * 4));
-  CREATE_TRY(hipMemset(e->tx, 0, (tab + 512 + 64 * 256) * 8));
-  CREATE_TRY(hipMemset(e->metrics, 0, (size_t)e->B * DIRAL_M_COLUMNS * 8));
-  CREATE_TRY(hipMemset(e->err, 0, 4));
-  if (e->la) CREATE_TRY(hipMemset(e->la, 0xFF, bn * e->N * 4));
-  if (e->pf) CREATE_TRY(hipMemset(e->pf, 0, bn * 4));
 
   if (e->large) {
     CREATE_TRY(alloc_large_scratch(e));
@@ -829,9 +865,10 @@ int diral_env_create(const DiralCfg* cfg, int batch, int device, DiralEnv** out)
     const LdsLayout l = lds_layout(64 * e->vpl, e->A, e->K, e->vpl, 4 * e->vpl);
     e->lds_bytes = l.total;
     CREATE_TRY(set_attr_general(e->vpl, l.total));
-    if (e->vpl == 2 && e->A <= kWideMaxA) CREATE_TRY(set_attr_wide2(e->A, e->K));
-    if (e->vpl == 4 && e->A <= kWideMaxA) CREATE_TRY(set_attr_wide4(e->A, e->K));
-    if (e->vpl > 1 && e->A <= kWideMaxA) CREATE_TRY(set_attr_wide_slots(e->vpl, e->A, e->K));
+    if (fits_wide(e)) {
+      CREATE_TRY(e->vpl == 2 ? set_attr_wide2(e->A, e->K) : set_attr_wide4(e->A, e->K));
+      CREATE_TRY(set_attr_wide_slots(e->vpl, e->A, e->K));
+    }
     CREATE_TRY(set_attr_observe(e->N, e->K));
   }
 #undef CREATE_TRY
@@ -868,10 +905,9 @@ int diral_env_create(const DiralCfg* cfg, int batch, int device, DiralEnv** out)
   r.off_skip = 0; r.len_skip = 0;
   r.off_pos = off.pos; r.off_vel = off.vel; r.off_fp = off.fp;
   r.H = cfg->highway_height; r.vel = e->vel; r.pos_y = e->pos_y;
-  // test hooks, read ONCE here (never on the step path): force the general kernel
-  if (const char* ws = std::getenv("DIRAL_WIDE_SLOW_FIRST")) e->wide_slow_first = ws[0] == '1';
-  if (std::getenv("DIRAL_NO_FAST64") && e->vpl == 1) e->kernel_path = DIRAL_PATH_GENERAL;
-  if (std::getenv("DIRAL_NO_WIDE") && e->vpl > 1 && !e->large) e->kernel_path = DIRAL_PATH_GENERAL;
+  // test hooks: force the general kernel
+  if (e->hooks.no_fast64 && e->vpl == 1) e->kernel_path = DIRAL_PATH_GENERAL;
+  if (e->hooks.no_wide && e->vpl > 1 && !e->large) e->kernel_path = DIRAL_PATH_GENERAL;
   *out = e;
   return DIRAL_OK;
 }
@@ -879,14 +915,18 @@ int diral_env_create(const DiralCfg* cfg, int batch, int device, DiralEnv** out)
 int diral_env_destroy(DiralEnv* e) {
   if (!e) return DIRAL_OK;
   DeviceGuard guard(e->device);
-  void* ptrs[] = {e->pos_x, e->pos_y, e->vel, e->tkey, e->tx, e->ring, e->tcode, e->tage, e->tseq, e->told, e->slow, e->la, e->pf, e->metrics, e->err, e->edges, e->edges1, e->inv_tab, e->trace, e->yflag,
-                  e->prev_obs, e->obs_new, e->txid, e->dbg, e->lg.src, e->lg.cnt, e->lg.alist, e->lg.nact, e->lg.qflag, e->lg.px0, e->lg.rew, e->lg.rtx};
-  for (void* q : ptrs) if (q) (void)hipFree(q);
+  for (const DevBuf& b : e->bufs) (void)hipFree(b.p);
+  if (e->trace) (void)hipFree(e->trace);
+  if (e->dbg) (void)hipFree(e->dbg);
   delete e;
   return DIRAL_OK;
 }
 
-int64_t diral_env_hbm_bytes(const DiralEnv* e) { return e ? e->hbm_bytes : 0; }
+int64_t diral_env_hbm_bytes(const DiralEnv* e) {
+  int64_t sum = 0;
+  if (e) for (const DevBuf& b : e->bufs) sum += (int64_t)b.bytes;
+  return sum;
+}
 
 int diral_env_set_option(DiralEnv* e, int option, int64_t value) {
   if (!e) return DIRAL_ERR_BAD_ARG;
@@ -900,8 +940,7 @@ int diral_env_set_option(DiralEnv* e, int option, int64_t value) {
       if (e->large) return value == DIRAL_PATH_GENERAL ? DIRAL_ERR_UNSUPPORTED : DIRAL_OK;   // (there is one path for such a handle)
       if (value == DIRAL_PATH_LARGE) {
         if (large_lds_bytes(e->N, e->A, e->K) > 160u * 1024u) return DIRAL_ERR_UNSUPPORTED;
-        DeviceGuard guard(e->device);
-        if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+        DEVICE_ENTER(e->device);
         HIP_TRY(e, alloc_large_scratch(e));
       }
       e->kernel_path = (int)value;
@@ -918,31 +957,16 @@ const char* diral_env_last_hip_error(const DiralEnv* e) { return e ? e->last_hip
 int diral_env_reset(DiralEnv* e, const double* x0, const double* y0, const double* v0, uint64_t seed,
                     void* stream) {
   if (!e) return DIRAL_ERR_BAD_ARG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   hipStream_t s = (hipStream_t)stream;
   const size_t bn = (size_t)e->B * e->N;
-  const size_t tab = (size_t)e->B * e->NR * e->NV;
-  HIP_TRY(e, hipMemsetAsync(e->tkey, 0, tab * 4, s));
-  HIP_TRY(e, hipMemsetAsync(e->tx, 0, tab * 8, s));
-  if (e->ring) HIP_TRY(e, hipMemsetAsync(e->ring, 0, (size_t)e->B * e->NR * 8 * 8, s));
-  if (e->tcode) {
-    const size_t nq = (size_t)e->B * (e->NR / 4);
-    HIP_TRY(e, hipMemsetAsync(e->tcode, 0, nq * e->NV * 4, s));
-    HIP_TRY(e, hipMemsetAsync(e->tage, 0, nq * e->NV * 4, s));
-    HIP_TRY(e, hipMemsetAsync(e->tseq, 0, (size_t)e->B * e->NR * 4, s));
-    HIP_TRY(e, hipMemsetAsync(e->told, 0, nq * 4, s));
-  }
-  HIP_TRY(e, clear_slow_sets(e, s));
+  // tables, ring, packed table, slow-env sets, metrics, la (0xFF), pf, prev_obs - as a fresh handle has them
+  for (const DevBuf& b : e->bufs)
+    if (b.reset_bytes) HIP_TRY(e, hipMemsetAsync(b.p, b.fill, b.reset_bytes, s));
+  e->slow_launches = 0;
   e->plane_valid = true; e->ring_valid = e->ring != nullptr;
-  HIP_TRY(e, hipMemsetAsync(e->metrics, 0, (size_t)e->B * DIRAL_M_COLUMNS * 8, s));
-  if (e->la) HIP_TRY(e, hipMemsetAsync(e->la, 0xFF, bn * e->N * 4, s));
-  if (e->pf) HIP_TRY(e, hipMemsetAsync(e->pf, 0, bn * 4, s));
-  if (e->prev_obs) HIP_TRY(e, hipMemsetAsync(e->prev_obs, 0, bn * e->A * 8, s));
-  hipLaunchKernelGGL(reset_kernel, dim3(blocks(bn, 256)), dim3(256), 0, s, (int)bn, e->cfg.highway_length,
-                     has(&e->cfg, DIRAL_F_MOBILITY_VARY) ? 1 : 0, seed, (uint64_t)e->env_offset * (uint64_t)e->N, x0, y0, v0,
-                     e->pos_x, e->pos_y, e->vel);
-  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, launch_1d<reset_kernel>(bn, s, (int)bn, e->cfg.highway_length, has(&e->cfg, DIRAL_F_MOBILITY_VARY) ? 1 : 0, seed,
+                                     (uint64_t)e->env_offset * (uint64_t)e->N, x0, y0, v0, e->pos_x, e->pos_y, e->vel));
   if (y0) { if (refresh_flat_y(e, s) != DIRAL_OK) return DIRAL_ERR_HIP; }
   else e->flat_y = true;
   return DIRAL_OK;
@@ -958,30 +982,24 @@ int diral_env_step(DiralEnv* e, int mode, const int32_t* actions, int64_t t, voi
   // my_step_ch defines rewards only for reward_design 2,3,4 (test_env.py:413-429)
   if (mode == DIRAL_STEP_MY_STEP_CH && (e->cfg.reward_design < 2 || e->cfg.reward_design > 4))
     return DIRAL_ERR_BAD_CONFIG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
-  StepParams p = e->base;
-  p.mode = mode; p.t = t; p.episode = episode; p.eps = epsilon; p.out_f64 = (out_dtype == DIRAL_F64);
-  p.actions = actions;
-  p.state_out = e->S > 0 ? state_out : nullptr;
+  DEVICE_ENTER(e->device);
+  hipStream_t s = (hipStream_t)stream;
+  StepParams p = call_params(e, mode, t, actions, state_out, out_dtype, episode, epsilon);
   p.rew_out = rew_out; p.done_out = done_out; p.chobs_out = chobs_out;
-  p.chobs_in = nullptr; p.rew_in = nullptr;
   if (e->prev_obs) {
     // State.piggybacking: my_step_ch / my_step_design hand obtain_state the plain A-wide observation (test_env.py:316,
     // 443) - a state vector shorter than get_state_space()
     if (mode != DIRAL_STEP_MY_STEP) return DIRAL_ERR_BAD_CONFIG;
-    PiggyParams q = piggy_params(e, p);
+    const PiggyParams q = piggy_params(e, p);
     p.chobs_out = nullptr;                                       // (the A * A observation is piggy_emit_kernel's)
-    hipLaunchKernelGGL(piggy_search_kernel, dim3(e->B), dim3(256), piggy_search_lds_bytes(e->N), (hipStream_t)stream, q);
-    HIP_TRY(e, hipGetLastError());
-    HIP_TRY(e, launch_step_any(e, p, (hipStream_t)stream));
-    HIP_TRY(e, launch_posdist_if_needed(e, p, (hipStream_t)stream));
-    hipLaunchKernelGGL(piggy_emit_kernel, dim3(e->B), dim3(256), 0, (hipStream_t)stream, q);
-    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, launch_k<piggy_search_kernel>(dim3(e->B), dim3(256), piggy_search_lds_bytes(e->N), s, q));
+    HIP_TRY(e, launch_step_any(e, p, plan_step(e, p, nullptr), s));
+    HIP_TRY(e, launch_posdist_if_needed(e, p, s));
+    HIP_TRY(e, launch_k<piggy_emit_kernel>(dim3(e->B), dim3(256), 0, s, q));
     return DIRAL_OK;
   }
-  HIP_TRY(e, launch_step_any(e, p, (hipStream_t)stream));
-  HIP_TRY(e, launch_posdist_if_needed(e, p, (hipStream_t)stream));
+  HIP_TRY(e, launch_step_any(e, p, plan_step(e, p, nullptr), s));
+  HIP_TRY(e, launch_posdist_if_needed(e, p, s));
   return DIRAL_OK;
 }
 
@@ -1003,14 +1021,9 @@ int diral_env_step_policy(DiralEnv* e, int mode, const int32_t* actions, int64_t
   if (pol->shaped_out && (pol->shape_flags & 4) && (!pol->pen_counter || !pol->pen_prev_actions)) return DIRAL_ERR_BAD_ARG;
   if (e->A > kSpsWaveMaxA) return DIRAL_ERR_UNSUPPORTED;
   if (e->prev_obs) return DIRAL_ERR_UNSUPPORTED;                // State.piggybacking: the SPS agents sense A values, not A * A
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
-  StepParams p = e->base;
-  p.mode = mode; p.t = t; p.episode = 0.0; p.eps = 1.0; p.out_f64 = (out_dtype == DIRAL_F64);
-  p.actions = actions;
-  p.state_out = e->S > 0 ? state_out : nullptr;
+  DEVICE_ENTER(e->device);
+  StepParams p = call_params(e, mode, t, actions, state_out, out_dtype, 0.0, 1.0);
   p.rew_out = rew_out; p.done_out = done_out; p.chobs_out = chobs_out;
-  p.chobs_in = nullptr; p.rew_in = nullptr;
   PolParams q;
   q.shape_flags = pol->shape_flags; q.pen_threshold = pol->pen_threshold; q.pen_value = pol->pen_value;
   q.shaped_out = pol->shaped_out; q.sum_r_out = pol->sum_r_out; q.coll_out = pol->collision_out;
@@ -1025,16 +1038,12 @@ int diral_env_step_policy(DiralEnv* e, int mode, const int32_t* actions, int64_t
   q.prefill = 0; q.actions_all = nullptr; q.rew_in = nullptr;
   if (slots > 1 && (pol->draw_counter || pol->draw_keep || pol->draw_choice)) return DIRAL_ERR_BAD_ARG;
   // (decided before anything is launched: a caller without a channel-observation buffer can retry with one)
-  // (K > 1 at 64 < N <= 256: step_wide_slots_kernel; a one-slot call there keeps its three launches)
-  const StepDispatch d = step_dispatch(e, p);
-  const bool will_fuse = d.pol_ok || (slots > 1 && d.wide_kslots_ok);
-  if (!will_fuse && (!chobs_out || slots > 1)) return DIRAL_ERR_UNSUPPORTED;
-  bool fused = false;
-  HIP_TRY(e, launch_step_any(e, p, (hipStream_t)stream, will_fuse ? &q : nullptr, &fused));
+  const StepPlan d = plan_step(e, p, &q);
+  if (!d.fused && (!chobs_out || slots > 1)) return DIRAL_ERR_UNSUPPORTED;
+  HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
   HIP_TRY(e, launch_posdist_if_needed(e, p, (hipStream_t)stream));
-  if (fused) return DIRAL_OK;
+  if (d.fused) return DIRAL_OK;
   // the same slot as three launches (configurations the POL instantiation does not take)
-  if (!chobs_out) return DIRAL_ERR_HIP;                                      // (cannot happen: one step_dispatch decides both)
   if (pol->shaped_out) {
     const int st = diral_driver_shape(e->B, e->N, e->A, rew_out, out_dtype, actions, nullptr, nullptr, pol->pen_counter,
                                       pol->pen_prev_actions, pol->shape_flags, pol->pen_threshold, pol->pen_value,
@@ -1055,21 +1064,16 @@ int diral_env_prefill(DiralEnv* e, const int32_t* actions, int32_t slots, uint64
   // the secondary observation modes are launches of their own behind ONE state vector (posdist_kernel.hpp)
   if (states_out && (has(&e->cfg, DIRAL_F_ADD_POSDIST) || (has(&e->cfg, DIRAL_F_ADD_POSDIST_PIGGY) && e->cfg.posdist_type == 1)))
     return DIRAL_ERR_UNSUPPORTED;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
-  StepParams p = e->base;
-  p.mode = DIRAL_STEP_DESIGN; p.t = 0; p.episode = episode; p.eps = epsilon; p.out_f64 = (out_dtype == DIRAL_F64);
-  p.actions = actions;
-  p.state_out = e->S > 0 ? states_out : nullptr;
-  p.rew_out = nullptr; p.done_out = nullptr; p.chobs_out = nullptr; p.chobs_in = nullptr; p.rew_in = nullptr;
-  if (!step_dispatch(e, p).prefill_ok) return DIRAL_ERR_UNSUPPORTED;   // (nothing launched: the caller loops sample + step + observe)
+  DEVICE_ENTER(e->device);
+  const StepParams p = call_params(e, DIRAL_STEP_DESIGN, 0, actions, states_out, out_dtype, episode, epsilon);
   PolParams q;
   std::memset(&q, 0, sizeof(q));
   q.K = slots; q.prefill = 1; q.seed = seed; q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N;
   q.actions_out = actions_next_out; q.actions_all = actions_all_out; q.rew_in = rew_in; q.vel_w = e->vel;
-  bool fused = false;
-  HIP_TRY(e, launch_step_any(e, p, (hipStream_t)stream, &q, &fused));
-  return fused ? DIRAL_OK : DIRAL_ERR_HIP;
+  const StepPlan d = plan_step(e, p, &q);
+  if (!d.fused) return DIRAL_ERR_UNSUPPORTED;                    // (nothing launched: the caller loops sample + step + observe)
+  HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
+  return DIRAL_OK;
 }
 
 int diral_env_observe(DiralEnv* e, const int32_t* actions, const double* chobs_in, const double* rew_in,
@@ -1077,21 +1081,16 @@ int diral_env_observe(DiralEnv* e, const int32_t* actions, const double* chobs_i
   if (!e || !actions || !state_out) return DIRAL_ERR_BAD_ARG;
   if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
   if (e->S == 0) return DIRAL_OK;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
-  StepParams p = e->base;
-  p.mode = kModeObserve; p.t = 0; p.episode = episode; p.eps = epsilon; p.out_f64 = (out_dtype == DIRAL_F64);
-  p.actions = actions; p.state_out = state_out;
-  p.rew_out = nullptr; p.done_out = nullptr; p.chobs_out = nullptr;
+  DEVICE_ENTER(e->device);
+  hipStream_t s = (hipStream_t)stream;
+  StepParams p = call_params(e, kModeObserve, 0, actions, state_out, out_dtype, episode, epsilon);
   p.chobs_in = chobs_in; p.rew_in = rew_in;
-  if (e->kernel_path == DIRAL_PATH_GENERAL || runs_large(e)) HIP_TRY(e, launch_step_any(e, p, (hipStream_t)stream));   // (tests: the general kernel's observe mode; step_large.hpp's)
-  else HIP_TRY(e, launch_observe_any(e, p, (hipStream_t)stream));
-  HIP_TRY(e, launch_posdist_if_needed(e, p, (hipStream_t)stream));
+  if (e->kernel_path == DIRAL_PATH_GENERAL || runs_large(e)) HIP_TRY(e, launch_step_any(e, p, plan_step(e, p, nullptr), s));   // (tests: the general kernel's observe mode; step_large.hpp's)
+  else HIP_TRY(e, launch_observe_any(e, p, s));
+  HIP_TRY(e, launch_posdist_if_needed(e, p, s));
   if (e->prev_obs && e->off_chobs_pb >= 0) {                    // `obs` = piggy_obs, A * A values per agent
-    const PiggyParams q = piggy_params(e, p);
     const size_t total = (size_t)e->B * e->N * e->A * e->A;
-    hipLaunchKernelGGL(piggy_fill_kernel, dim3(blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, q, total);
-    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, launch_1d<piggy_fill_kernel>(total, s, piggy_params(e, p), total));
   }
   return DIRAL_OK;
 }
@@ -1099,52 +1098,41 @@ int diral_env_observe(DiralEnv* e, const int32_t* actions, const double* chobs_i
 int diral_env_update_velocity(DiralEnv* e, const uint8_t* draws, uint64_t seed, void* stream) {
   if (!e) return DIRAL_ERR_BAD_ARG;
   if (!has(&e->cfg, DIRAL_F_MOBILITY_VARY)) return DIRAL_OK;   // test_env.py:503
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   const size_t bn = (size_t)e->B * e->N;
-  hipLaunchKernelGGL(velocity_kernel, dim3(blocks(bn, 256)), dim3(256), 0, (hipStream_t)stream, (int)bn, draws,
-                     seed, (uint64_t)e->env_offset * (uint64_t)e->N, e->vel);
-  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, launch_1d<velocity_kernel>(bn, (hipStream_t)stream, (int)bn, draws, seed, (uint64_t)e->env_offset * (uint64_t)e->N, e->vel));
   return DIRAL_OK;
 }
 
 int diral_env_sample(DiralEnv* e, int32_t* actions_out, uint64_t seed, void* stream) {
   if (!e || !actions_out) return DIRAL_ERR_BAD_ARG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   const size_t bn = (size_t)e->B * e->N;
-  hipLaunchKernelGGL(sample_kernel, dim3(blocks(bn, 256)), dim3(256), 0, (hipStream_t)stream, (int)bn, e->A, seed,
-                     (uint64_t)e->env_offset * (uint64_t)e->N, actions_out);
-  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, launch_1d<sample_kernel>(bn, (hipStream_t)stream, (int)bn, e->A, seed, (uint64_t)e->env_offset * (uint64_t)e->N, actions_out));
   return DIRAL_OK;
 }
 
 int diral_env_info_age(DiralEnv* e, int64_t t, int32_t* out, void* stream) {
   if (!e || !out) return DIRAL_ERR_BAD_ARG;
   if (!e->la) return DIRAL_ERR_BAD_CONFIG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
-  hipLaunchKernelGGL(info_age_kernel, dim3(e->B), dim3(256), 0, (hipStream_t)stream, e->N, (long long)t, e->la, out);
-  HIP_TRY(e, hipGetLastError());
+  DEVICE_ENTER(e->device);
+  HIP_TRY(e, launch_k<info_age_kernel>(dim3(e->B), dim3(256), 0, (hipStream_t)stream, e->N, (long long)t, e->la, out));
   return DIRAL_OK;
 }
 
 int diral_env_export_state(DiralEnv* e, double* pos_x, double* pos_y, double* vel, int32_t* tab_seq,
                            int32_t* tab_age, double* tab_x, double* tab_y, int32_t* last_arrival, void* stream) {
   if (!e) return DIRAL_ERR_BAD_ARG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   hipStream_t s = (hipStream_t)stream;
   const size_t bn = (size_t)e->B * e->N;
   if (pos_x) HIP_TRY(e, hipMemcpyAsync(pos_x, e->pos_x, bn * 8, hipMemcpyDeviceToDevice, s));
   if (pos_y) HIP_TRY(e, hipMemcpyAsync(pos_y, e->pos_y, bn * 8, hipMemcpyDeviceToDevice, s));
   if (vel) HIP_TRY(e, hipMemcpyAsync(vel, e->vel, bn * 8, hipMemcpyDeviceToDevice, s));
   if (tab_seq || tab_age || tab_x || tab_y) {
-    const size_t total = bn * e->N;
     HIP_TRY(e, ensure_plane(e, s));                               // (sequence numbers and ages too: the packed table of N <= 64)
-    hipLaunchKernelGGL(export_tables_kernel, dim3(blocks(total, 256)), dim3(256), 0, s, e->B, e->N, e->NV, e->NR, e->tkey,
-                       e->tx, e->pos_y, tab_seq, tab_age, tab_x, tab_y);
-    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, launch_1d<export_tables_kernel>(bn * e->N, s, e->B, e->N, e->NV, e->NR, e->tkey, e->tx, e->pos_y, tab_seq, tab_age,
+                                               tab_x, tab_y));
   }
   if (last_arrival) {
     if (!e->la) return DIRAL_ERR_BAD_CONFIG;
@@ -1157,8 +1145,7 @@ int diral_env_import_state(DiralEnv* e, const double* pos_x, const double* pos_y
                            const int32_t* tab_seq, const int32_t* tab_age, const double* tab_x,
                            const int32_t* last_arrival, void* stream) {
   if (!e) return DIRAL_ERR_BAD_ARG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   hipStream_t s = (hipStream_t)stream;
   const size_t bn = (size_t)e->B * e->N;
   if (pos_x) HIP_TRY(e, hipMemcpyAsync(e->pos_x, pos_x, bn * 8, hipMemcpyDeviceToDevice, s));
@@ -1168,12 +1155,9 @@ int diral_env_import_state(DiralEnv* e, const double* pos_x, const double* pos_y
   }
   if (vel) HIP_TRY(e, hipMemcpyAsync(e->vel, vel, bn * 8, hipMemcpyDeviceToDevice, s));
   if (tab_seq || tab_age || tab_x) {
-    const size_t total = bn * e->N;
     HIP_TRY(e, ensure_plane(e, s));                             // (a partial import keeps the other planes)
     e->ring_valid = false;
-    hipLaunchKernelGGL(import_tables_kernel, dim3(blocks(total, 256)), dim3(256), 0, s, e->B, e->N, e->NV, e->NR, tab_seq,
-                       tab_age, tab_x, e->tkey, e->tx);
-    HIP_TRY(e, hipGetLastError());
+    HIP_TRY(e, launch_1d<import_tables_kernel>(bn * e->N, s, e->B, e->N, e->NV, e->NR, tab_seq, tab_age, tab_x, e->tkey, e->tx));
     // the ring again, right away (not at the next step: a step sequence captured into a hipGraph must not
     // contain a rebuild from a plane that later replays find stale)
     if (e->ring) { HIP_TRY(e, ensure_ring(e, s)); HIP_TRY(e, verify_ring(e, s)); }
@@ -1188,8 +1172,7 @@ int diral_env_import_state(DiralEnv* e, const double* pos_x, const double* pos_y
 int diral_env_export_prev_obs(DiralEnv* e, double* prev_obs, void* stream) {
   if (!e || !prev_obs) return DIRAL_ERR_BAD_ARG;
   if (!e->prev_obs) return DIRAL_ERR_BAD_CONFIG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   HIP_TRY(e, hipMemcpyAsync(prev_obs, e->prev_obs, (size_t)e->B * e->N * e->A * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return DIRAL_OK;
 }
@@ -1197,44 +1180,34 @@ int diral_env_export_prev_obs(DiralEnv* e, double* prev_obs, void* stream) {
 int diral_env_import_prev_obs(DiralEnv* e, const double* prev_obs, void* stream) {
   if (!e || !prev_obs) return DIRAL_ERR_BAD_ARG;
   if (!e->prev_obs) return DIRAL_ERR_BAD_CONFIG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   HIP_TRY(e, hipMemcpyAsync(e->prev_obs, prev_obs, (size_t)e->B * e->N * e->A * 8, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return DIRAL_OK;
 }
 
 int diral_env_export_entries(DiralEnv* e, DiralNeighborEntry* entries, void* stream) {
   if (!e || !entries) return DIRAL_ERR_BAD_ARG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   hipStream_t s = (hipStream_t)stream;
-  const size_t total = (size_t)e->B * e->N * e->N;
   HIP_TRY(e, ensure_plane(e, s));
-  hipLaunchKernelGGL(export_entries_kernel, dim3(blocks(total, 256)), dim3(256), 0, s, e->B, e->N, e->NV, e->NR, e->tkey,
-                     e->tx, e->pos_y, entries);
-  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, launch_1d<export_entries_kernel>((size_t)e->B * e->N * e->N, s, e->B, e->N, e->NV, e->NR, e->tkey, e->tx, e->pos_y, entries));
   return DIRAL_OK;
 }
 
 int diral_env_import_entries(DiralEnv* e, const DiralNeighborEntry* entries, void* stream) {
   if (!e || !entries) return DIRAL_ERR_BAD_ARG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   hipStream_t s = (hipStream_t)stream;
-  const size_t total = (size_t)e->B * e->N * e->N;
   e->plane_valid = true;                                        // every entry of the plane is rewritten
   e->ring_valid = false;
-  hipLaunchKernelGGL(import_entries_kernel, dim3(blocks(total, 256)), dim3(256), 0, s, e->B, e->N, e->NV, e->NR, entries,
-                     e->tkey, e->tx);
-  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, launch_1d<import_entries_kernel>((size_t)e->B * e->N * e->N, s, e->B, e->N, e->NV, e->NR, entries, e->tkey, e->tx));
   if (e->ring) { HIP_TRY(e, ensure_ring(e, s)); HIP_TRY(e, verify_ring(e, s)); }   // as in diral_env_import_state
   return DIRAL_OK;
 }
 
 int diral_env_set_trace(DiralEnv* e, const double* x_positions, int T, int per_env, void* stream) {
   if (!e || T < 0) return DIRAL_ERR_BAD_ARG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(e, hipStreamSynchronize(s));               // no launch may still read the old copy
   if (e->trace) { (void)hipFree(e->trace); e->trace = nullptr; }
@@ -1257,12 +1230,9 @@ int diral_env_set_trace(DiralEnv* e, const double* x_positions, int T, int per_e
 
 int diral_env_metrics(DiralEnv* e, double* out, int clear, void* stream) {
   if (!e) return DIRAL_ERR_BAD_ARG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   const int total = e->B * DIRAL_M_COLUMNS;
-  hipLaunchKernelGGL(metrics_kernel, dim3(blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, total, e->metrics,
-                     out, clear);
-  HIP_TRY(e, hipGetLastError());
+  HIP_TRY(e, launch_1d<metrics_kernel>((size_t)total, (hipStream_t)stream, total, e->metrics, out, clear));
   return DIRAL_OK;
 }
 
@@ -1272,8 +1242,7 @@ int diral_env_metrics(DiralEnv* e, double* out, int clear, void* stream) {
 // timestamps [B][waves][8] to a host buffer.
 int diral_env_debug_timing(DiralEnv* e, unsigned long long* host_out, int waves) {
   if (!e || !e->dbg || !host_out) return DIRAL_ERR_BAD_ARG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   if (hipDeviceSynchronize() != hipSuccess) return DIRAL_ERR_HIP;
   if (hipMemcpy(host_out, e->dbg, (size_t)e->B * waves * 8 * 8, hipMemcpyDeviceToHost) != hipSuccess) return DIRAL_ERR_HIP;
   return DIRAL_OK;
@@ -1286,23 +1255,16 @@ int diral_sps_step(int agents, int num_channels, const double* selection_window,
                    int32_t* actions_out, void* stream) {
   if (agents < 1 || num_channels < 1 || !selection_window || !prev_action || !counter || !actions_out)
     return DIRAL_ERR_BAD_ARG;
-  PtrDeviceGuard guard(prev_action);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
-  const hipStream_t st = (hipStream_t)stream;
-  const dim3 g(blocks((size_t)agents, 256)), t(256);
-#define DIRAL_SPS_WAVE(NC)                                                                                           \
-  hipLaunchKernelGGL((sps_step_wave_kernel<NC, double, false>), g, t, 0, st, agents, num_channels, selection_window, \
-                     (const int32_t*)nullptr, prev_action, counter, rssi_threshold, inc_db, keep_prob, draw_counter, \
-                     draw_keep, draw_choice, seed, (const long long*)nullptr, actions_out)
-  if (num_channels <= 64) DIRAL_SPS_WAVE(1);
-  else if (num_channels <= 128) DIRAL_SPS_WAVE(2);
-  else if (num_channels <= kSpsWaveMaxA) DIRAL_SPS_WAVE(4);
-  else                                                            // one thread per agent
-    hipLaunchKernelGGL(sps_step_kernel, dim3(blocks((size_t)agents, 128)), dim3(128), 0, st, agents, num_channels,
-                       selection_window, prev_action, counter, rssi_threshold, inc_db, keep_prob, draw_counter, draw_keep,
-                       draw_choice, seed, actions_out);
-#undef DIRAL_SPS_WAVE
-  return hipGetLastError() == hipSuccess ? DIRAL_OK : DIRAL_ERR_HIP;
+  DEVICE_ENTER(prev_action);
+  const hipStream_t s = (hipStream_t)stream;
+  if (num_channels <= kSpsWaveMaxA)
+    return hip_status(launch_sps_wave<double, false>(agents, num_channels, selection_window, s, (const int32_t*)nullptr, prev_action,
+                                                     counter, rssi_threshold, inc_db, keep_prob, draw_counter, draw_keep,
+                                                     draw_choice, seed, (const long long*)nullptr, actions_out));
+  // one thread per agent
+  return hip_status(launch_k<sps_step_kernel>(dim3(blocks((size_t)agents, 128)), dim3(128), 0, s, agents, num_channels,
+                                              selection_window, prev_action, counter, rssi_threshold, inc_db, keep_prob,
+                                              draw_counter, draw_keep, draw_choice, seed, actions_out));
 }
 
 int diral_driver_shape(int envs, int num_users, int num_channels, const void* reward_in, int dtype,
@@ -1314,53 +1276,32 @@ int diral_driver_shape(int envs, int num_users, int num_channels, const void* re
   if (dtype != DIRAL_F32 && dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
   if ((flags & 4) && (!actions || !pen_counter || !prev_actions)) return DIRAL_ERR_BAD_ARG;
   if ((flags & 2) && (!ia || !sum_ia_prev)) return DIRAL_ERR_BAD_ARG;
-  PtrDeviceGuard guard(reward_in);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
-  if (!ia && !(flags & 2) && num_users >= 8 && num_users <= 64) {
-    // no information-age terms, one wave per env (aux_kernels.hpp)
-    const dim3 gw(blocks((size_t)envs, kShapeWaveBlock / 64)), tw(kShapeWaveBlock);
-    if (dtype == DIRAL_F64)
-      hipLaunchKernelGGL(driver_shape_wave_kernel<double>, gw, tw, 0, (hipStream_t)stream, envs, num_users, num_channels,
-                         static_cast<const double*>(reward_in), actions, pen_counter, prev_actions, flags, ia_penalty_threshold,
-                         ia_penalty_value, static_cast<double*>(reward_out), static_cast<double*>(sum_r_out),
-                         static_cast<double*>(collision_out));
-    else
-      hipLaunchKernelGGL(driver_shape_wave_kernel<float>, gw, tw, 0, (hipStream_t)stream, envs, num_users, num_channels,
-                         static_cast<const float*>(reward_in), actions, pen_counter, prev_actions, flags, ia_penalty_threshold,
-                         ia_penalty_value, static_cast<float*>(reward_out), static_cast<float*>(sum_r_out),
-                         static_cast<float*>(collision_out));
-    return hipGetLastError() == hipSuccess ? DIRAL_OK : DIRAL_ERR_HIP;
-  }
-  const dim3 g(blocks((size_t)envs, kShapeEnvsPerBlock)), t(256);
-  if (dtype == DIRAL_F64)
-    hipLaunchKernelGGL(driver_shape_kernel<double>, g, t, 0, (hipStream_t)stream, envs, num_users, num_channels,
-                       static_cast<const double*>(reward_in), actions, ia, (long long*)sum_ia_prev, pen_counter, prev_actions,
-                       flags, ia_penalty_threshold, ia_penalty_value, static_cast<double*>(reward_out),
-                       static_cast<double*>(sum_r_out), static_cast<double*>(collision_out), (long long*)ia_sum_out,
-                       ia_penalty_out);
-  else
-    hipLaunchKernelGGL(driver_shape_kernel<float>, g, t, 0, (hipStream_t)stream, envs, num_users, num_channels,
-                       static_cast<const float*>(reward_in), actions, ia, (long long*)sum_ia_prev, pen_counter, prev_actions,
-                       flags, ia_penalty_threshold, ia_penalty_value, static_cast<float*>(reward_out),
-                       static_cast<float*>(sum_r_out), static_cast<float*>(collision_out), (long long*)ia_sum_out,
-                       ia_penalty_out);
-  return hipGetLastError() == hipSuccess ? DIRAL_OK : DIRAL_ERR_HIP;
+  DEVICE_ENTER(reward_in);
+  return hip_status(by_dtype(dtype, [&](auto tag) {
+    using T = decltype(tag);
+    const T* in = static_cast<const T*>(reward_in);
+    T *out = static_cast<T*>(reward_out), *sum = static_cast<T*>(sum_r_out), *coll = static_cast<T*>(collision_out);
+    if (!ia && !(flags & 2) && num_users >= 8 && num_users <= 64)   // no information-age terms, one wave per env (aux_kernels.hpp)
+      return launch_k<driver_shape_wave_kernel<T>>(dim3(blocks((size_t)envs, kShapeWaveBlock / 64)), dim3(kShapeWaveBlock), 0,
+                                                   (hipStream_t)stream, envs, num_users, num_channels, in, actions, pen_counter,
+                                                   prev_actions, flags, ia_penalty_threshold, ia_penalty_value, out, sum, coll);
+    return launch_k<driver_shape_kernel<T>>(dim3(blocks((size_t)envs, kShapeEnvsPerBlock)), dim3(256), 0, (hipStream_t)stream, envs,
+                                            num_users, num_channels, in, actions, ia, (long long*)sum_ia_prev, pen_counter,
+                                            prev_actions, flags, ia_penalty_threshold, ia_penalty_value, out, sum, coll,
+                                            (long long*)ia_sum_out, ia_penalty_out);
+  }));
 }
 
 int diral_sps_window_from_chobs(int agents, int num_channels, const void* chobs, int chobs_dtype,
                                 const int32_t* actions, double* window_out, void* stream) {
   if (agents < 1 || num_channels < 1 || !chobs || !actions || !window_out) return DIRAL_ERR_BAD_ARG;
   if (chobs_dtype != DIRAL_F32 && chobs_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
-  PtrDeviceGuard guard(chobs);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(chobs);
   const size_t total = (size_t)agents * num_channels;
-  if (chobs_dtype == DIRAL_F64)
-    hipLaunchKernelGGL(sps_window_kernel<double>, dim3(blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, total,
-                       num_channels, static_cast<const double*>(chobs), actions, window_out);
-  else
-    hipLaunchKernelGGL(sps_window_kernel<float>, dim3(blocks(total, 256)), dim3(256), 0, (hipStream_t)stream, total,
-                       num_channels, static_cast<const float*>(chobs), actions, window_out);
-  return hipGetLastError() == hipSuccess ? DIRAL_OK : DIRAL_ERR_HIP;
+  return hip_status(by_dtype(chobs_dtype, [&](auto tag) {
+    using T = decltype(tag);
+    return launch_1d<sps_window_kernel<T>>(total, (hipStream_t)stream, total, num_channels, static_cast<const T*>(chobs), actions, window_out);
+  }));
 }
 
 static int sps_step_chobs_impl(int agents, int num_channels, const void* chobs, int chobs_dtype, const int32_t* actions,
@@ -1372,25 +1313,12 @@ static int sps_step_chobs_impl(int agents, int num_channels, const void* chobs, 
     return DIRAL_ERR_BAD_ARG;
   if (chobs_dtype != DIRAL_F32 && chobs_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
   if (num_channels > kSpsWaveMaxA) return DIRAL_ERR_UNSUPPORTED;   // use window_from_chobs + sps_step
-  PtrDeviceGuard guard(prev_action);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
-  const hipStream_t st = (hipStream_t)stream;
-  const dim3 g(blocks((size_t)agents, 256)), t(256);
-#define DIRAL_SPS_WAVE(NC, T)                                                                                          \
-  hipLaunchKernelGGL((sps_step_wave_kernel<NC, T, true>), g, t, 0, st, agents, num_channels, static_cast<const T*>(chobs), \
-                     actions, prev_action, counter, rssi_threshold, inc_db, keep_prob, draw_counter, draw_keep,        \
-                     draw_choice, seed, clock, actions_out)
-#define DIRAL_SPS_WAVE_T(T)                          \
-  do {                                               \
-    if (num_channels <= 64) DIRAL_SPS_WAVE(1, T);    \
-    else if (num_channels <= 128) DIRAL_SPS_WAVE(2, T); \
-    else DIRAL_SPS_WAVE(4, T);                       \
-  } while (0)
-  if (chobs_dtype == DIRAL_F64) DIRAL_SPS_WAVE_T(double);
-  else DIRAL_SPS_WAVE_T(float);
-#undef DIRAL_SPS_WAVE_T
-#undef DIRAL_SPS_WAVE
-  return hipGetLastError() == hipSuccess ? DIRAL_OK : DIRAL_ERR_HIP;
+  DEVICE_ENTER(prev_action);
+  return hip_status(by_dtype(chobs_dtype, [&](auto tag) {
+    return launch_sps_wave<decltype(tag), true>(agents, num_channels, chobs, (hipStream_t)stream, actions, prev_action, counter,
+                                                rssi_threshold, inc_db, keep_prob, draw_counter, draw_keep, draw_choice, seed,
+                                                clock, actions_out);
+  }));
 }
 
 int diral_sps_step_chobs(int agents, int num_channels, const void* chobs, int chobs_dtype, const int32_t* actions,
@@ -1411,10 +1339,8 @@ int diral_sps_step_chobs_clocked(int agents, int num_channels, const void* chobs
 
 int diral_clock_add(int64_t* clock, int64_t inc, void* stream) {
   if (!clock) return DIRAL_ERR_BAD_ARG;
-  PtrDeviceGuard guard(clock);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
-  hipLaunchKernelGGL(clock_add_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (long long*)clock, (long long)inc);
-  return hipGetLastError() == hipSuccess ? DIRAL_OK : DIRAL_ERR_HIP;
+  DEVICE_ENTER(clock);
+  return hip_status(launch_k<clock_add_kernel>(dim3(1), dim3(1), 0, (hipStream_t)stream, (long long*)clock, (long long)inc));
 }
 
 int diral_env_set_clock(DiralEnv* e, const int64_t* t_dev) {
@@ -1433,13 +1359,12 @@ int diral_env_set_capture_rotation(DiralEnv* e, int on, int* phase) {
 int diral_env_align_phase(DiralEnv* e, int phase, void* stream) {
   if (!e || phase < 0 || phase > 2) return DIRAL_ERR_BAD_ARG;
   if (!e->slow || (int)(e->slow_launches % 3) == phase) return DIRAL_OK;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   hipStream_t s = (hipStream_t)stream;
   if (stream_is_capturing(s)) { e->capture_violation = true; return DIRAL_ERR_CAPTURE; }
   // the sets a launch of the new phase reads, builds and clears must not hold what launches of another phase left half
   // done (a cleared count under flags that still stand): all three empty = every env runs in dispatch order once
-  if (hipMemsetAsync(e->slow, 0, 3 * slow_set_words(e) * 4, s) != hipSuccess) return DIRAL_ERR_HIP;
+  if (hipMemsetAsync(e->slow, 0, buf_of(e, e->slow).bytes, s) != hipSuccess) return DIRAL_ERR_HIP;
   while ((int)(e->slow_launches % 3) != phase) ++e->slow_launches;
   return DIRAL_OK;
 }
@@ -1447,17 +1372,13 @@ int diral_env_align_phase(DiralEnv* e, int phase, void* stream) {
 int diral_sps_init(int agents, int selection_window, int32_t* prev_action, int32_t* counter, uint64_t seed,
                    void* stream) {
   if (agents < 1 || selection_window < 0 || !prev_action || !counter) return DIRAL_ERR_BAD_ARG;
-  PtrDeviceGuard guard(prev_action);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
-  hipLaunchKernelGGL(sps_init_kernel, dim3(blocks((size_t)agents, 256)), dim3(256), 0, (hipStream_t)stream, agents,
-                     selection_window, seed, prev_action, counter);
-  return hipGetLastError() == hipSuccess ? DIRAL_OK : DIRAL_ERR_HIP;
+  DEVICE_ENTER(prev_action);
+  return hip_status(launch_1d<sps_init_kernel>((size_t)agents, (hipStream_t)stream, agents, selection_window, seed, prev_action, counter));
 }
 
 int diral_env_check(DiralEnv* e, void* stream) {
   if (!e) return DIRAL_ERR_BAD_ARG;
-  DeviceGuard guard(e->device);
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE;
+  DEVICE_ENTER(e->device);
   uint32_t flags = 0;
   HIP_TRY(e, hipMemcpyAsync(&flags, e->err, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
   HIP_TRY(e, hipStreamSynchronize((hipStream_t)stream));
