@@ -89,6 +89,16 @@ struct LargeScratch {
   double* rtx;           // [B][N] reception ratio per colliding transmitter (test_env.py:402-405)
 };
 
+// geometry of the fused step kernel (step_kernel.hpp) for VPL viewers per lane: what lds_layout is called with
+template <int VPL>
+struct Geo {
+  static constexpr int NPAD = 64 * VPL;      // padded viewer count
+  static constexpr int WAVES = 4 * VPL;      // 16 subject columns per wave
+  static constexpr int THREADS = 64 * WAVES;
+  static constexpr int CC = 16 / VPL;        // columns per register chunk (16 key regs)
+  static constexpr int NCH = VPL;            // chunks per wave
+};
+
 // LDS carve of the fused step kernel; byte offsets, doubles first.
 struct LdsLayout {
   uint32_t px, py, npx, vel, rv, rtx, rew, edges, red, mask, act, inr, hist, cnt, mtab, scratch, total;

@@ -14,11 +14,9 @@
 #include "common.hpp"
 #include "launch.hpp"
 #include "observe_kernel.hpp"
-#include "step_kernel.hpp"
-#include "step_fast64.hpp"
-#include "step_wide.hpp"
-#include "posdist_kernel.hpp"
 #include "piggyback_kernel.hpp"
+#include "posdist_kernel.hpp"
+#include "step_params.hpp"
 
 using namespace diral;
 
@@ -73,7 +71,7 @@ struct DiralEnv {
   uint32_t* tage = nullptr;
   uint32_t* tseq = nullptr;
   uint32_t* told = nullptr;
-  // slow envs first (step_fast64.hpp FastParams::slow_*): three rotating sets of [count (16 words) | list | flag per env]
+  // slow envs first (step_params.hpp FastParams::slow_*): three rotating sets of [count (16 words) | list | flag per env]
   uint32_t* slow = nullptr;
   uint64_t slow_launches = 0;   // launches that rotated the sets
   bool capture_rotates = false; // diral_env_set_capture_rotation: captured launches rotate the sets too (graphs of 3 k launches)
@@ -550,7 +548,7 @@ void rotate_slow_sets(DiralEnv* e, FastParams& f, hipStream_t s) {
   // (a CAPTURED launch reads the set it was baked with and builds none: a replayed graph could not rotate the sets -
   // unless the caller keeps every graph at a multiple of three launches and its phase aligned:
   // diral_env_set_capture_rotation.  Eager launches between two replays keep rotating through that set: they leave it
-  // either rebuilt or EMPTY - count and flags, step_fast64.hpp - never half cleared, so the replay runs every env
+  // either rebuilt or EMPTY - count and flags, step_params.hpp - never half cleared, so the replay runs every env
   // exactly once whatever happened in between; the list it reads ages - slow envs stay slow for hundreds of slots,
   // profiles/launch_timeline.py - or is empty, which costs time, not correctness.)
 }

@@ -1,8 +1,17 @@
-// k_fast64.hip - every instantiation of step_fast64_kernel (N <= 64) and its launcher.
+// k_fast64.hip - every instantiation of step_fast64_kernel and step_fast64_slots_kernel (N <= 64; one body, compiled twice) and their launchers.
 #include "launch.hpp"
 #include "step_fast64.hpp"
 
 namespace diral {
+#define DIRAL_FAST_KERNEL step_fast64_kernel
+#include "step_fast64_body.inc"
+#undef DIRAL_FAST_KERNEL
+#define DIRAL_FAST_KERNEL step_fast64_slots_kernel
+#define DIRAL_FAST_KSLOTS 1
+#include "step_fast64_body.inc"
+#undef DIRAL_FAST_KSLOTS
+#undef DIRAL_FAST_KERNEL
+
 namespace {
 struct LaunchFast64 {
   const FastParams& f; const RichParams& r; const PolParams& q; dim3 g; uint32_t lds; hipStream_t s;

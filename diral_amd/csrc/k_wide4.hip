@@ -3,6 +3,10 @@
 #include "step_wide.hpp"
 
 namespace diral {
+#define DIRAL_WIDE_KERNEL step_wide_kernel
+#include "step_wide_body.inc"
+#undef DIRAL_WIDE_KERNEL
+
 namespace {
 constexpr int V = 4;
 struct LaunchWide {

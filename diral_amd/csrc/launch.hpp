@@ -1,6 +1,6 @@
 // launch.hpp - host-side launchers of the step kernels.  Each kernel family lives in its own
-// translation unit (k_fast64.hip, k_wide2.hip, k_wide4.hip, k_wide_slots.hip, k_general.hip) so that hipcc builds
-// them in parallel; diral_env.hip only sees these declarations.
+// translation unit (k_*.hip) so that hipcc builds them in parallel; of the step kernels diral_env.hip only sees these
+// declarations and the parameter structs they take (common.hpp, rich_out.hpp, step_params.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,7 +11,7 @@
 
 namespace diral {
 
-struct FastParams;   // step_fast64.hpp
+struct FastParams;   // step_params.hpp
 struct PolParams;    // policy_device.hpp
 struct ObserveParams;   // observe_kernel.hpp
 

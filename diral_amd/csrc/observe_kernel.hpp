@@ -21,9 +21,9 @@
 // posdist_kernel.hpp, which diral_env_observe launches right after this one, as after a step.
 #pragma once
 #include "common.hpp"
+#include "ref_math.hpp"
 #include "rich_out.hpp"
-#include "step_fast64.hpp"
-#include "step_kernel.hpp"
+#include "wave_ops.hpp"
 
 namespace diral {
 
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(kObserveThreads) void observe_kernel(const ObserveP
       }
       if (u != k && (int)age < p.age_limit && d < p.Rb) {
         bool unsafe;
-        int bin = hist_bin_estimate(v, p.Rb, inv_w, K, unsafe);    // (step_kernel.hpp: the edges are read only near an edge)
+        int bin = hist_bin_estimate(v, p.Rb, inv_w, K, unsafe);    // (ref_math.hpp: the edges are read only near an edge)
         if (unsafe) {
           bin = hist_bin_clamp(bin, K);
           if constexpr (FLAT) {

@@ -28,6 +28,7 @@
 // one-workgroup-per-env kernels, not tuned.
 #pragma once
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace diral {
 
@@ -49,11 +50,6 @@ struct PiggyParams {
   const double* chobs_in;      // observe: [B][N][A * A] f64 copied into the state section (emit not used)
   uint32_t* err;
 };
-
-__device__ inline void piggy_store(void* base, size_t idx, double v, int f64) {
-  if (f64) static_cast<double*>(base)[idx] = v;
-  else static_cast<float*>(base)[idx] = (float)v;
-}
 
 __host__ __device__ inline uint32_t piggy_search_lds_bytes(int N) { return 20u * (uint32_t)N + 16u; }
 // one workgroup per env, one thread per (receiver, resource) pair
@@ -118,9 +114,9 @@ __global__ void piggy_emit_kernel(PiggyParams p) {
       if (pos >= i + A) pos -= A;
       if (t != -2 && pos == i) { val = obs[u * A + i]; break; }  // piggy_obs[user][i] = tx_dist
     }
-    if (p.chobs_out) piggy_store(p.chobs_out, bN * W + e, val, p.out_f64);
+    if (p.chobs_out) store_out(p.chobs_out, bN * W + e, val, p.out_f64);
     if (p.state_out && p.off_chobs >= 0)
-      piggy_store(p.state_out, (bN + u) * (size_t)p.S + p.off_chobs + (e - u * W), val, p.out_f64);
+      store_out(p.state_out, (bN + u) * (size_t)p.S + p.off_chobs + (e - u * W), val, p.out_f64);
   }
   __syncthreads();                                               // every read of prev_obs of this env is done
   for (int e = threadIdx.x; e < N * A; e += blockDim.x) p.prev_obs[bN * A + e] = obs[e];   // test_env.py:260-261
@@ -133,7 +129,7 @@ __global__ void piggy_fill_kernel(PiggyParams p, size_t total) {
   const int W = p.A * p.A;
   const size_t row = e / W;
   const int c = (int)(e - row * W);
-  piggy_store(p.state_out, row * (size_t)p.S + p.off_chobs + c, p.chobs_in ? p.chobs_in[e] : 0.0, p.out_f64);
+  store_out(p.state_out, row * (size_t)p.S + p.off_chobs + c, p.chobs_in ? p.chobs_in[e] : 0.0, p.out_f64);
 }
 
 }  // namespace diral

@@ -4,6 +4,7 @@
 // slot and the three-launch slot decide and round identically.
 #pragma once
 #include "common.hpp"
+#include "wave_ops.hpp"
 
 namespace diral {
 
@@ -91,10 +92,6 @@ __device__ inline double sps_rssi_from_chobs(double d, bool own) {
 // position of every candidate is counted against the candidates' values read lane by lane.
 constexpr int kSpsWaveMaxA = 256;
 
-__device__ inline double sps_readlane(double v, int j) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), j), __builtin_amdgcn_readlane(__double2loint(v), j));
-}
-
 // choose_new_resource (algorithms/v2x_sps.py:24-74) for ONE agent by the whole wave; every argument
 // but `w` / `lane` is wave-uniform, and so is the result.
 template <int NC>
@@ -132,7 +129,7 @@ __device__ inline int sps_choose_wave(const double (&w)[NC], int lane, int A, in
     while (m) {
       const int j = __builtin_ctzll(m);
       m &= m - 1;
-      const double wj = sps_readlane(w[cj], j);
+      const double wj = readlane_f64(w[cj], j);
       const int sj = j + 64 * cj;
 #pragma unroll
       for (int c = 0; c < NC; ++c) rank[c] += (wj < w[c] || (wj == w[c] && sj < lane + 64 * c)) ? 1 : 0;

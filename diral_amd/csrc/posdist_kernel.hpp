@@ -27,7 +27,8 @@
 //   posdist_type1_lanes_kernel   a15 for 64 < N <= 256: 4 or 8 lanes per viewer (32 values each), cross-lane bitonic merge.
 #pragma once
 #include "common.hpp"
-#include "step_kernel.hpp"
+#include "ref_math.hpp"
+#include "wave_ops.hpp"
 
 namespace diral {
 
@@ -181,18 +182,6 @@ __global__ __launch_bounds__(64 * kPdWaves) void posdist_kernel(const PosdistPar
   }
 }
 
-// dist2d with the general case in line (the kernels below): a call inside an unrolled sweep would force the
-// registers of the value array through the calling convention at every call site
-__device__ inline double pd_dist(double x1, double y1, double x2, double y2) {
-  const double dx = x2 - x1, dy = y2 - y1;
-  // |dx| in [2^-500, 2^501) or dx == 0, and dy == 0: sqrt(dx * dx) == |dx| exactly (the same test on the
-  // high word as step_fast64.hpp's fast_dist)
-  const unsigned int hi = (unsigned int)__double2hiint(dx) & 0x7fffffffu;
-  const bool plain = (hi - 0x20b00000u <= 0x3e800000u) || (hi | (unsigned int)__double2loint(dx)) == 0u;
-  if (dy == 0.0 && plain) return __hiloint2double((int)hi, __double2loint(dx));
-  return __builtin_sqrt(dx * dx + dy * dy);
-}
-
 // ---- a16 on a flat highway ------------------------------------------------------------------------
 // v(w) = dist_sign(w, t) (network.py:334-349) is +d for x_w > x_t and -d otherwise, d = dist2d a
 // monotone function of |x_w - x_t| when the y coordinates agree - so v is monotone in x_w, the sorted
@@ -247,12 +236,6 @@ __host__ inline uint32_t posdist_flat_lds_bytes(int N) {
 }
 
 // ---- a15, N <= 64 -----------------------------------------------------------------------------------
-__device__ inline double pd_readlane_f64(double v, int srclane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), srclane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), srclane);
-  return __hiloint2double(hi, lo);
-}
-
 constexpr int kPd1Stride = 65;                         // doubles per row of edge sums: lane t at column t, rows 2 banks apart
 
 __host__ __device__ inline uint32_t posdist_type1_lds_bytes(int K) { return (uint32_t)(8 * (66 + (K + 2) * kPd1Stride)); }
@@ -328,7 +311,7 @@ __global__ __launch_bounds__(64, 3) void posdist_type1_n64_kernel(const PosdistP
       const uint32_t w = tw[c];
       const double x1 = v[k];
       const bool valid = live && k < N && k != lane && (int)(w & 255u) < p.age_limit;
-      const double yk = pd_readlane_f64(yt, k);
+      const double yk = readlane_f64(yt, k);
       const double y1 = (w >> 8) ? yk : 0.0;
       const double d = pd_dist(x1, y1, xt, yt);
       dmax = (valid && d > dmax) ? d : dmax;

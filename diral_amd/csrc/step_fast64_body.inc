@@ -1,4 +1,4 @@
-// step_fast64_body.inc - the body of the fused step kernel of step_fast64.hpp, included TWICE by it (textual inclusion, as
+// step_fast64_body.inc - the body of the fused step kernel of step_fast64.hpp, included TWICE by k_fast64.hip (textual inclusion, as
 // step_wide_pass.inc): once as `step_fast64_kernel` - one slot per launch, the metric's kernel - and once, with
 // DIRAL_FAST_KSLOTS defined, as `step_fast64_slots_kernel` - K slots per launch of the POL instantiation (PolParams::K,
 // diral_env_step_policy with DiralSlotPolicy::slots > 1): the workgroup keeps its env in registers and LDS from slot to
@@ -427,7 +427,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
       if (CH) {
         const double R = (c > 1) ? s_rtx[lane] : 1.0;         // test_env.py:411-429
         const bool plain = (p.reward_design == 2);
-        rw = plain ? ((c > 1) ? -1.0 * (1.0 - R) : 1.0) : fast_ch_reward(p.reward_design, c > 1, R);
+        rw = plain ? ((c > 1) ? -1.0 * (1.0 - R) : 1.0) : ch_reward(p.reward_design, c > 1, R);
         coll = c > 1; sole = !(c > 1); prr = R;
       } else if (c > 1) { rw = (EXTRA && p.design) ? s_rtx[lane] : s_rv[act_own]; coll = 1; } else { rw = 1.0; sole = 1; }   // test_env.py:211-222, 297-301
 #ifdef DIRAL_FAST_KSLOTS
@@ -759,7 +759,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
       // |v| < Rb, so the estimate is in [0, K] and the edge correction needs no bounds
       // tests: edges[0] = -Rb <= v and v < Rb = edges[K] hold by construction
       bool unsafe;
-      int bin = hist_bin_estimate(v, p.Rb, inv_w, K, unsafe);      // (step_kernel.hpp: the edges are read only near an edge)
+      int bin = hist_bin_estimate(v, p.Rb, inv_w, K, unsafe);      // (ref_math.hpp: the edges are read only near an edge)
       if (unsafe) {
         bin = hist_bin_clamp(bin, K);
         if constexpr (FLAT) {

@@ -32,6 +32,8 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "ref_math.hpp"
+#include "wave_ops.hpp"
 
 namespace diral {
 
@@ -43,108 +45,6 @@ namespace diral {
 #ifndef DIRAL_MINWAVES
 #define DIRAL_MINWAVES 1
 #endif
-
-template <int VPL>
-struct Geo {
-  static constexpr int NPAD = 64 * VPL;      // padded viewer count
-  static constexpr int WAVES = 4 * VPL;      // 16 subject columns per wave
-  static constexpr int THREADS = 64 * WAVES;
-  static constexpr int CC = 16 / VPL;        // columns per register chunk (16 key regs)
-  static constexpr int NCH = VPL;            // chunks per wave
-};
-
-// Network.dist (network.py:318-332): sqrt(dx^2 + dy^2) with correctly rounded
-// squares (DESIGN.md on the reference's pow()).  When dy == 0 - every pair in a
-// random topology, where all y are 0 - sqrt(fl(dx*dx)) == |dx| exactly in IEEE
-// binary64 (no over/underflow for 2^-500 <= |dx| <= 2^500), so the sqrt is skipped.
-// rare general paths are kept out of line so the hot code stays compact
-// (the fused kernels were instruction-fetch bound when these were inlined)
-__device__ DIRAL_OUTLINE double dist_general(double dx, double dy) {
-  return __builtin_sqrt(dx * dx + dy * dy);
-}
-__device__ inline double dist2d(double x1, double y1, double x2, double y2) {
-  const double dx = x2 - x1, dy = y2 - y1;
-  const double ax = __builtin_fabs(dx);
-  // (dx == 0 as well: sqrt(0) == 0 - a vehicle measured against itself, as the transmitter search does)
-  if (dy == 0.0 && (ax == 0.0 || (ax >= 0x1p-500 && ax <= 0x1p500))) return ax;
-  return dist_general(dx, dy);
-}
-
-// dist2d for the out-of-line reward functions: the IEEE sqrt is inlined so that they stay LEAF functions - a nested
-// call makes the callee save its return address through a callee-saved VGPR in scratch memory, and a kernel that
-// may reach such a callee carries a private segment (16 B / lane) for every wave it launches
-__device__ inline double dist2d_leaf(double x1, double y1, double x2, double y2) {
-  const double dx = x2 - x1, dy = y2 - y1;
-  const double ax = __builtin_fabs(dx);
-  if (dy == 0.0 && (ax == 0.0 || (ax >= 0x1p-500 && ax <= 0x1p500))) return ax;
-  return __builtin_sqrt(dx * dx + dy * dy);
-}
-
-// Bin of a value of the type-2 histogram, np.histogram(v, K, range=(-Rb, Rb)) (network.py:500): NumPy estimates the bin from
-// (v - first) / (last - first) * K and corrects it by at most one step against the float edges.  The correction can
-// only act when v lies within rounding distance of an edge.  With t = (v + Rb) * inv_w: t, the edges (linspace) and the
-// comparisons are each within 2^-45 bin widths of their exact values (K <= 64), so if the fractional part of t lies in
-// [2^-20, 1 - 2^-20] the value is safely inside bin floor(t) and the edges need not be read - one LDS round trip and two
-// f64 compares less per table entry.  `unsafe` lanes (an exact hit of an edge: integer-valued positions) take the reads.
-// Requires -Rb <= v < Rb (so 0 <= t <= K; t == K rounds in from below: fractional part 0, unsafe - the edge branch
-// clamps the estimate to K - 1 first).
-__device__ inline int hist_bin_estimate(double v, double Rb, double inv_w, int K, bool& unsafe) {
-  const double t = (v + Rb) * inv_w;
-  const int est = (int)t;                        // (t == K: fractional part 0 - the caller's edge branch clamps, hist_bin_clamp)
-  const double fr = __builtin_amdgcn_fract(t);
-  unsafe = !(__builtin_fabs(fr - 0.5) <= 0.5 - 0x1p-20);
-  return est;
-}
-__device__ inline int hist_bin_clamp(int est, int K) { return est > K - 1 ? K - 1 : est; }
-
-// Python float `%` for the position wrap (network.py:203): fast exact path when
-// 0 <= s <= 2L (Sterbenz), generic fmod + sign fix-up otherwise.
-__device__ DIRAL_OUTLINE double py_mod_general(double s, double L) {
-  double m = fmod(s, L);
-  if (m != 0.0) { if ((L < 0) != (m < 0)) m += L; } else { m = copysign(0.0, L); }
-  return m;
-}
-__device__ inline double py_mod_pos(double s, double L) {
-  if (s >= 0.0 && s < L) return s;
-  if (s >= L && s <= 2.0 * L) {
-    const double r = s - L;            // exact
-    return (r >= L) ? r - L : r;       // s == 2L -> 0
-  }
-  return py_mod_general(s, L);
-}
-
-// np.histogram uniform-bin index (numpy/lib/_histograms_impl.py fast path).
-// NumPy estimates the index with a division and then corrects it against the
-// actual edges ("not guaranteed to give exactly consistent results within ~1
-// ULP of the bin edges"), so its result is THE bin with edges[i] <= v <
-// edges[i+1].  Any estimate followed by the same edge correction lands in the
-// same bin; a reciprocal multiply replaces the f64 division.  `edges` are the
-// exact np.linspace values (strictly increasing, checked at create).
-__device__ inline int hist_bin(double v, double first, double inv_width, int K, const double* edges) {
-  int idx = (int)((v - first) * inv_width);
-  idx = idx < 0 ? 0 : (idx > K - 1 ? K - 1 : idx);
-  while (idx > 0 && v < edges[idx]) --idx;
-  while (idx < K - 1 && v >= edges[idx + 1]) ++idx;
-  return idx;
-}
-
-__device__ inline void store_out(void* base, size_t idx, double v, int f64) {
-  if (f64) reinterpret_cast<double*>(base)[idx] = v;
-  else reinterpret_cast<float*>(base)[idx] = (float)v;
-}
-
-// Orders this wave's LDS accesses for the COMPILER only.  The hardware already
-// executes one wave's DS instructions in issue order, so a later ds_read sees an
-// earlier ds_write of the same wave without any wait; a real fence would drain
-// lgkmcnt at every merge step (measured: the dominant cost at N > 64).
-__device__ inline void wave_lds_order() { asm volatile("" ::: "memory"); }
-
-// wave-uniform 64-bit value -> SGPR pair, so branches on it are scalar
-__device__ inline unsigned long long uniform_u64(unsigned long long v) {
-  const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)v);
-  const unsigned int hi = __builtin_amdgcn_readfirstlane((unsigned int)(v >> 32));
-  return ((unsigned long long)hi << 32) | lo;
-}
 
 __device__ inline int popc_masks(const unsigned long long* m, int vpl) {
   int c = 0;
@@ -177,19 +77,7 @@ __device__ inline int reward_weight(const StepParams& p, const unsigned long lon
     }
   }
   const double m = s / (double)cnt;
-  if (p.flags & DIRAL_F_TOY_WEIGHTS) {
-    // calculate_norm (network.py:225-246)
-    double x_min = p.L + 1, x_max = -p.L - 1;
-    int umin = 0, umax = 0;
-    for (int u = 0; u < p.N; ++u) {
-      const double x = s_px[u];
-      if (x < x_min) { x_min = x; umin = u; }
-      if (x > x_max) { x_max = x; umax = u; }
-    }
-    const double norm = dist2d(s_px[umin], s_py[umin], s_px[umax], s_py[umax]);
-    return m == norm;
-  }
-  return m > p.Rc;
+  return weight_from_mean(p, m, s_px, s_py);
 }
 
 // FAST = the configuration BASELINE.json's metric is quoted on (the toy YAML's
@@ -382,7 +270,7 @@ __global__ __launch_bounds__(Geo<VPL>::THREADS, (VPL == 1 ? DIRAL_MINWAVES : 4))
         }
       }
       if (mode == DIRAL_STEP_MY_STEP && c > 1) {
-        // test_env.py:163-199, one value per resource
+        // test_env.py:163-199, one value per resource (collision_value, spelled out: see ref_math.hpp; with the call N = 256 ran 1.1 % slower, profiles/r07/header_refactor.md)
         double rw = 0.0;
         const int rd = p.reward_design;
         if (rd == 1) {
@@ -432,19 +320,10 @@ __global__ __launch_bounds__(Geo<VPL>::THREADS, (VPL == 1 ? DIRAL_MINWAVES : 4))
             sole = 1; prr = 1.0;
           }
         } else if (mode == DIRAL_STEP_MY_STEP_CH) {                           // test_env.py:411-429
-          const int rd = p.reward_design;
-          if (c > 1) {
-            const double R = s_rtx[u];
-            if (rd == 3) r = 1.0 - exp(1.0 - R);
-            else if (rd == 4) r = -1.0 * exp(1.0 - R);
-            else if (rd == 2) r = -1.0 * (1.0 - R);
-            coll = 1; prr = R;
-          } else {
-            if (rd == 3) r = 1.0;
-            else if (rd == 4) r = exp(1.0);
-            else if (rd == 2) r = 1.0;
-            sole = 1; prr = 1.0;
-          }
+          const double R = (c > 1) ? s_rtx[u] : 1.0;
+          r = ch_reward(p.reward_design, c > 1, R);
+          if (c > 1) coll = 1; else sole = 1;
+          prr = R;
         } else {                                                              // test_env.py:297-301, 319-349
           if (c == 1) { r = 1.0; sole = 1; }
           else {

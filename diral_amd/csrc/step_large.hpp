@@ -23,7 +23,8 @@
 // Not tuned like step_fast64 / step_wide: no BASELINE.json configuration runs here.
 #pragma once
 #include "common.hpp"
-#include "step_kernel.hpp"
+#include "ref_math.hpp"
+#include "wave_ops.hpp"
 
 namespace diral {
 
@@ -95,17 +96,7 @@ __device__ inline int large_reward_weight(const StepParams& p, const unsigned sh
     }
   }
   const double m = s / (double)cnt;
-  if (p.flags & DIRAL_F_TOY_WEIGHTS) {
-    double x_min = p.L + 1, x_max = -p.L - 1;      // calculate_norm (network.py:225-246)
-    int umin = 0, umax = 0;
-    for (int u = 0; u < p.N; ++u) {
-      const double x = s_px[u];
-      if (x < x_min) { x_min = x; umin = u; }
-      if (x > x_max) { x_max = x; umax = u; }
-    }
-    return m == dist2d(s_px[umin], s_py[umin], s_px[umax], s_py[umax]);
-  }
-  return m > p.Rc;
+  return weight_from_mean(p, m, s_px, s_py);
 }
 
 __global__ __launch_bounds__(kLargeMaxThreads) void large_search_kernel(const StepParams p, const LargeScratch g) {
@@ -266,21 +257,7 @@ __global__ __launch_bounds__(kLargeMaxThreads) void large_search_kernel(const St
       double rw = 0.0;
       if (mode == DIRAL_STEP_MY_STEP && c > 1) {
         const int rd = p.reward_design;
-        if (rd == 1) {
-          const double R = (double)large_reward_weight(p, lst, c, s_px, s_py) / (double)c;
-          rw = -1.0 * (1.0 - R);
-        } else if (rd == 2) {
-          if (c == 2) rw = 2.0 * (double)large_reward_weight(p, lst, c, s_px, s_py) - (double)c;
-          else rw = 0.0 - (double)c;
-        } else if (rd == 3) {
-          const double R = 1.0 / (double)c;
-          rw = -1.0 * exp(1.0 - R);
-        } else if (rd == 4) {
-          rw = 1.0 / (double)c;
-        } else {
-          if (c == 2) rw = (large_reward_weight(p, lst, c, s_px, s_py) == 1) ? 0.0 : -1.0;
-          else rw = -1.0;
-        }
+        rw = collision_value(rd, c, collision_uses_weight(rd, c) ? large_reward_weight(p, lst, c, s_px, s_py) : 0);
       }
       // the reward of each of its transmitters
       for (int q = lane; q < c; q += 64) {
@@ -303,19 +280,13 @@ __global__ __launch_bounds__(kLargeMaxThreads) void large_search_kernel(const St
             g.rtx[bN + u] = n_in > 0 ? (double)s_rec[u] / (double)n_in : 1.0;     // test_env.py:402-405
           }
         } else if (mode == DIRAL_STEP_MY_STEP_CH) {                     // test_env.py:411-429
-          const int rd = p.reward_design;
+          double R = 1.0;
           if (c > 1) {
             const int n_in = s_inr[u];
-            const double R = n_in > 0 ? (double)s_rec[u] / (double)n_in : 1.0;
+            R = n_in > 0 ? (double)s_rec[u] / (double)n_in : 1.0;
             g.rtx[bN + u] = R;
-            if (rd == 3) r = 1.0 - exp(1.0 - R);
-            else if (rd == 4) r = -1.0 * exp(1.0 - R);
-            else if (rd == 2) r = -1.0 * (1.0 - R);
-          } else {
-            if (rd == 3) r = 1.0;
-            else if (rd == 4) r = exp(1.0);
-            else if (rd == 2) r = 1.0;
           }
+          r = ch_reward(p.reward_design, c > 1, R);
         } else {                                                       // test_env.py:297-301, 319-349
           if (c == 1) r = 1.0;
           else {

@@ -25,15 +25,23 @@
 //     84 VGPRs, three workgroups per CU (52 KB LDS each at N = 256).
 //   * branch-free finalize (signed distance x1 - x2 is the histogram value when
 //     all y are 0; bin = estimate + edge correction).
+//   * xpos ring (see step_fast64.hpp / aux_kernels.hpp): an entry's xpos is a function of (subject, sequence number), the
+//     ring keeps every subject's 8 latest stamps, so the finalize phase fills the rank -> xpos table of a column from the
+//     subject's ring row (8 lanes) instead of having all viewers scatter their old xpos into it, and EVERY entry that lags
+//     at most 7 reads its xpos there.  The per-entry xpos plane - two thirds of the table bytes - is only read for older
+//     entries and only written when an entry reaches lag 7 (or copies an older one).
+// (No kernel in this header: the body, step_wide_body.inc, is compiled by k_wide2.hip, k_wide4.hip and k_wide_slots.hip.)
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
+#include "policy_device.hpp"
+#include "ref_math.hpp"
 #include "rich_out.hpp"
-#include "step_fast64.hpp"
-#include "step_kernel.hpp"
+#include "step_params.hpp"
+#include "wave_ops.hpp"
 
 namespace diral {
-
-constexpr int kWideMaxA = 64;
 
 struct WideLds {
   uint32_t px, npx, rv, edges, red, mask, act, cnt, hist, mtab, scratch, pbytes, lut, slow, total;
@@ -49,9 +57,6 @@ __host__ __device__ constexpr int wide_waves(int vpl) { return vpl == 2 ? 8 : DI
 #ifndef DIRAL_WIDE_PC4
 #define DIRAL_WIDE_PC4 8                 // subject columns per merge pass, N <= 256 (4 until the xpos ring freed the registers: C3 -3.5 %)
 #endif
-// The B operand's table: 256 entries of 8 x bf16 - one 16-byte read per K step; the rows a quarter wave reads are random, half
-// the LDS cycles of the product are bank conflicts.  A 16-entry form of 4 x bf16 (128 bytes, conflict-free) was bit-exact and
-// measured slower (C3 1.33 -> 1.36 ms, C5 +- 0): removed; last at d94e7da.
 // merge scratch per wave: a pass's rank words (one byte per column and viewer), then the
 // rank -> xpos table (256 doubles)
 // (N <= 256: + 64 bytes in front of the lag -> xpos table of the packed form's finalize phase, whose lookup of a
@@ -79,6 +84,7 @@ __host__ __device__ inline WideLds wide_lds_layout(int vpl, int A, int K, bool p
   // the packed form's merge (step_wide_closure.inc), at compile-time addresses as well (DS immediate offsets): the
   // reachability matrix P of the slot as bytes [viewer][lane group][K step] (8 KB at N = 256, 2 KB at N = 128) and the
   // 256-entry bits -> 8 x bf16 table of the product's B operand
+  // (one 16-byte read per K step; a 16-entry form of 4 x bf16 - 128 bytes, conflict-free - was bit-exact and slower: C3 1.33 -> 1.36 ms)
   l.pbytes = l.lut = o;
   // (+ the closure's own rows of P - npad / 16 bytes x 2 waves per viewer - and one row-ready flag per resource: it runs beside P1)
   if (packed) { l.pbytes = o; o += 8u * vpl * npad; l.lut = o; o += 4096u; o += 8u * vpl * npad; o += 4u * (uint32_t)kWideMaxA; }
@@ -141,24 +147,10 @@ __device__ inline void max_u8_words(unsigned int (&a)[NK], const unsigned int (&
   }
 }
 
-// Thermometer codes.  In steady state the lag of an entry behind its subject's
-// own sequence number is tiny (C3: <= 4, C2: <= 5, C5: <= 7 for 98 % of the entries -
-// profiles/lag_distribution.py), so a pass first tries the 8-level code c(lag) = (0xff << lag) & 0xff
-// (0: never heard): the codes form a chain under bit inclusion, the code of the smaller lag is the
-// bitwise OR, and ONE v_or_b32 merges the four columns of a word where the byte ranks take four
-// SDWA maxes.  Exact while every entry of the pass has lag <= 7 or was never heard; otherwise the
-// pass is redone with byte ranks (lag < 255), then with 32-bit keys.
 #ifndef DIRAL_WIDE_INFLIGHT
 #define DIRAL_WIDE_INFLIGHT 16          // table words a lane has in flight while a pass loads its columns
 #endif
-// (thermo_codes(): step_fast64.hpp)
 
-// xpos ring (see step_fast64.hpp / aux_kernels.hpp): an entry's xpos is a function of
-// (subject, sequence number), the ring keeps every subject's 8 latest stamps, so the finalize phase fills
-// the rank -> xpos table of a column from the subject's ring row (8 lanes) instead of having all viewers
-// scatter their old xpos into it, and EVERY entry that lags at most 7 reads its xpos there.  The per-entry
-// xpos plane - two thirds of the table bytes - is only read for older entries and only written when an
-// entry reaches lag 7 (or copies an older one).
 // run f(std::integral_constant<int, wave>) - a copy of f per wave index (wave-uniform switch): the wave's
 // scratch base becomes an immediate offset of the LDS instructions; f(-1): base in a register
 #define DIRAL_WIDE_DISPATCH_WAVE(f)                                      \
@@ -176,18 +168,6 @@ __device__ inline void max_u8_words(unsigned int (&a)[NK], const unsigned int (&
     }                                                                    \
   } while (0)
 
-// An LDS object by its absolute byte address (register + compile-time constant: the constant goes
-// into the DS instruction's immediate offset; going through the `extern __shared__` symbol instead
-// leaves a relocated `+ 0` add in front of every access)
-template <typename T>
-__device__ inline const __attribute__((address_space(3))) T* lds_at(unsigned int byte_addr) {
-  return (const __attribute__((address_space(3))) T*)(size_t)byte_addr;
-}
-
-// LDS byte address of a __shared__ object (what M0-relative DS instructions take)
-__device__ inline unsigned int lds_addr(const void* p) {
-  return (unsigned int)(size_t)(__attribute__((address_space(3))) const void*)p;
-}
 // byte j of the packed gather-source word, shifted left by SH (the LDS byte offset of that
 // viewer's rank words), one SDWA shift each instead of extract + shift
 template <int VPL, unsigned int SH>
@@ -258,6 +238,7 @@ __device__ DIRAL_OUTLINE double wide_collision_reward(int rd, uint32_t flags, do
       wgt = (m > Rc);
     }
   }
+  // (collision_value, spelled out: see ref_math.hpp)
   if (rd == 1) { const double R = (double)wgt / (double)c; return -1.0 * (1.0 - R); }
   if (rd == 2) return (c == 2) ? 2.0 * (double)wgt - (double)c : 0.0 - (double)c;
   if (rd == 3) { const double R = 1.0 / (double)c; return -1.0 * exp(1.0 - R); }
@@ -356,7 +337,6 @@ __device__ __attribute__((noinline)) unsigned int wide_far_guard(const unsigned 
   return stable;
 }
 
-// (uniform_ptr / global_ptr: step_fast64.hpp)
 #ifdef DIRAL_TIMING
 #define DIRAL_WSTAMP(i) do { if (lane == 0 && p.dbg) p.dbg[((size_t)b * WAVES + wave) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
 #define DIRAL_WCLOCK(v) v = __builtin_amdgcn_s_memtime()
@@ -382,6 +362,7 @@ __device__ __attribute__((noinline)) unsigned int wide_far_guard(const unsigned 
 #define DIRAL_WIDE_MINWAVES2P 6          // N <= 128, packed form: 84 VGPRs, three workgroups per CU (43 KB of LDS each)
 #endif
 
+// The template parameters of the kernels in step_wide_body.inc:
 // FULL: N == 64 * VPL (every viewer slot and subject row exists): the u < N / k < N predicates
 // are compiled out (BASELINE.json's 128- and 256-vehicle configurations)
 // CH: my_step_ch (PRR reward, test_env.py:351-443) instead of my_step, as in step_fast64.hpp
@@ -392,9 +373,6 @@ __device__ __attribute__((noinline)) unsigned int wide_far_guard(const unsigned 
 // ranks in place.  Dense topologies (BASELINE configs[2] and [4]) run packed - the coded passes merge as reachability
 // closure + one bf16 product, step_wide_closure.inc -; where most entries lag their subject by more than 7 stamps (sparse
 // topologies) every pass of the packed form would detour through the planes - those handles keep the plane form.
-#define DIRAL_WIDE_KERNEL step_wide_kernel
-#include "step_wide_body.inc"
-#undef DIRAL_WIDE_KERNEL
 
 // The SPS agents of one wave decide for the next slot (step_wide_slots_kernel, k_wide_slots.hip): what
 // sps_step_wave_kernel<1, T, true> does with the rows of the channel observation it loads, for the 64 vehicles

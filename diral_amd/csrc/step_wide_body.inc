@@ -1,4 +1,4 @@
-// step_wide_body.inc - the body of the fused step kernel of step_wide.hpp, included by it as `step_wide_kernel` (one slot
+// step_wide_body.inc - the body of the fused step kernel of step_wide.hpp, included by k_wide2.hip and k_wide4.hip as `step_wide_kernel` (one slot
 // per launch) and, with DIRAL_WIDE_KSLOTS defined, by k_wide_slots.hip as `step_wide_slots_kernel`: K slots per launch
 // (PolParams::K, diral_env_step_policy with DiralSlotPolicy::slots > 1) - every slot the step, then the policy epilogue
 // (the driver's reward shaping, the SPS agents' decisions), then the next slot with the actions chosen.  Between slots
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
     return reinterpret_cast<int*>(smem + lay.scratch + SCR * (u >> 6) + 512u) + (u & 63);
   };
 
-  // which env: blocks = envs in order, or (slow envs first, FastParams::slow_*: step_fast64.hpp) the listed envs in the
+  // which env: blocks = envs in order, or (slow envs first, FastParams::slow_*: step_params.hpp) the listed envs in the
   // first fast_slow_max(B) blocks.  At N <= 128 on a highway of configs[4]'s density one env in ten has broken into
   // clusters that no longer hear each other: nearly all its passes leave the codes (byte ranks through the planes) and
   // its workgroup lives 3-4 times as long as the others' - dispatched in batch order the last of them end the launch late.
@@ -578,7 +578,7 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
   // (the two stores of P2 - reward, position - moved behind P3, so that the table words P3 asks for first do not wait for
   // them: measured, +- 0 at C3 and C5)
   if (tid < NPAD) {
-    const unsigned long long late2 = late_kernarg_base();         // late-bound arguments: see step_fast64.hpp
+    const unsigned long long late2 = late_kernarg_base();         // late-bound arguments: see step_params.hpp
     const int u = tid;
     double rw = 0.0, prr = 0.0;
     int sole = 0, coll = 0;
@@ -590,7 +590,7 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
       if (CH) {
         const double R = (c > 1) ? *rtx_of(u) : 1.0;                          // test_env.py:411-429
         const bool plain = (reward_design == 2);
-        rw = plain ? ((c > 1) ? -1.0 * (1.0 - R) : 1.0) : fast_ch_reward(reward_design, c > 1, R);
+        rw = plain ? ((c > 1) ? -1.0 * (1.0 - R) : 1.0) : ch_reward(reward_design, c > 1, R);
         coll = c > 1; sole = !(c > 1); prr = R;
       } else if (c > 1) { rw = (EXTRA && p.design) ? *rtx_of(u) : s_rv[a]; coll = 1; } else { rw = 1.0; sole = 1; }      // test_env.py:211-222, 297-301
       if (!CH && EXTRA && p.prr) prr = (c > 1) ? *rtx_of(u) : 1.0;            // DIRAL_F_TRACK_PRR: the metric only
@@ -617,7 +617,7 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
       else static_cast<float*>(rew_out2)[bN + u] = (float)rw;
     }
     if (u < N) lp2->pos_x[bN + u] = s_npx[u];
-    // (counts by ballot, the reward sum by DPP moves, the PRR sum on the shuffle tree of the general kernel: step_fast64.hpp)
+    // (counts by ballot, the reward sum by DPP moves, the PRR sum on the shuffle tree of the general kernel: wave_sum_f64, wave_ops.hpp)
     const double vr = wave_sum_f64(rw);
     const int vs = __popcll(__ballot(sole != 0)), vc = __popcll(__ballot(coll != 0));
     double vp = prr;
@@ -695,7 +695,7 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
 #endif /* DIRAL_WIDE_KSLOTS */
     if (ok) {
       bool unsafe;
-      int bin = hist_bin_estimate(v, pRb, inv_w, K, unsafe);        // (step_kernel.hpp: the edges are read only near an edge)
+      int bin = hist_bin_estimate(v, pRb, inv_w, K, unsafe);        // (ref_math.hpp: the edges are read only near an edge)
       if (unsafe) {
         bin = hist_bin_clamp(bin, K);
         if (((unsigned int)__double2hiint(v) & 0x7fffffffu) < 0x20b00000u) {     // |v| below 2^-500 (its square underflows) or 0
@@ -1003,7 +1003,7 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
         if (pos < (unsigned int)fast_slow_max(lp->B)) { lp->slow_list_w[pos] = (unsigned int)b; fl = 1u; }
       }
       flag_w[b] = fl;
-      // the set the launch after the next builds: count AND flags emptied (step_fast64.hpp)
+      // the set the launch after the next builds: count AND flags emptied (step_params.hpp)
       uint32_t* const set_z = lp->slow_cnt_z;
       set_z[16 + fast_slow_max(lp->B) + b] = 0u;
       if (b == 0) *set_z = 0u;
@@ -1011,7 +1011,7 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
     uint8_t* const done_out = lp->done_out;
 #ifndef DIRAL_WIDE_KSLOTS
     if (done_out) {
-      int dn = lp->done_now;                                      // (slot clock: see step_fast64.hpp)
+      int dn = lp->done_now;                                      // (slot clock: see step_params.hpp)
       const long long* const td = lp->t_dev;
       if (td) dn = ((unsigned int)(lp->t + *td) % (unsigned int)lp->episode_interval) == (unsigned int)lp->episode_interval - 1u;
       done_out[b] = (uint8_t)dn;

@@ -1,7 +1,11 @@
 // step_wide_pass.inc - one pass over PC subject columns of the (seq, age) plane `tkey` (round-2 form): load + stamp, merge
-// (thermometer codes, byte ranks, or 32-bit keys), finalize.  Included TWICE by step_wide.hpp - the pass of the plane-form
+// (thermometer codes, byte ranks, or 32-bit keys), finalize.  Included TWICE by step_wide_body.inc - the pass of the plane-form
 // handles, and the flagged pass of the packed form - with DIRAL_PASS_THERMO_FIRST set by the includer; textual inclusion, because
 // a lambda called from the two loops trips a backend error ("illegal VGPR to SGPR copy") in this compiler.
+// In steady state the lag of an entry behind its subject's own sequence number is tiny (C3: <= 4, C2: <= 5, C5: <= 7 for 98 %
+// of the entries - profiles/lag_distribution.py), so a pass first tries thermometer codes (thermo_codes(), wave_ops.hpp): ONE
+// v_or_b32 merges the four columns of a word where the byte ranks take four SDWA maxes.  Exact while every entry of the pass
+// has lag <= 7 or was never heard; otherwise the pass is redone with byte ranks (lag < 255), then with 32-bit keys.
 // Expects `kbase` in scope; leaves `tkov` (lane c: column c's fresh sequence number) behind.
     // One packed pass, ONE body for both packed representations (two copies of it cost 12 more spilled
     // registers): the table words are loaded and turned into clamped lag bytes - 0..7 and 12 = never heard for the

@@ -7,16 +7,17 @@ set -e
 cd "$(dirname "$0")/.."
 NAME=$1; FLAGS=$2; shift 2
 mkdir -p variants_tmp/obj_$NAME
+# the translation units, the compiler and its flags: the build's own (diral_amd/build.py)
+eval "$(python3 -c 'from diral_amd import build as b; print("TUS=\"%s\"; CC=\"%s\"; CFLAGS=\"%s\"" % (" ".join(s[:-4] for s in b.SOURCES), b.hipcc_path(), " ".join(b.HIPCC_FLAGS)))')"
 OBJS=""
-for tu in diral_env k_fast64 k_wide2 k_wide4 k_general k_observe k_large; do
+for tu in $TUS; do
   if [[ " $* " == *" $tu "* ]]; then
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fPIC $FLAGS \
-      -c diral_amd/csrc/$tu.hip -o variants_tmp/obj_$NAME/$tu.o &
+    $CC $CFLAGS $FLAGS -c diral_amd/csrc/$tu.hip -o variants_tmp/obj_$NAME/$tu.o &
     OBJS="$OBJS variants_tmp/obj_$NAME/$tu.o"
   else
     OBJS="$OBJS diral_amd/build/$tu.o"
   fi
 done
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $OBJS -o variants_tmp/lib_$NAME.so
+$CC --offload-arch=gfx950 -shared -fPIC $OBJS -o variants_tmp/lib_$NAME.so
 ls -la variants_tmp/lib_$NAME.so

@@ -4,9 +4,10 @@
 #   bash profiles/resource_usage.sh [out.txt] [extra -D flags...]
 OUT=${1:-/dev/stdout}; shift
 cd "$(dirname "$0")/.."
-for tu in k_fast64 k_wide2 k_wide4 k_general k_observe k_large diral_env; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fPIC "$@" \
-    -Rpass-analysis=kernel-resource-usage -c diral_amd/csrc/$tu.hip -o /dev/null 2>&1 |
+# the translation units, the compiler and its flags: the build's own (diral_amd/build.py)
+eval "$(python3 -c 'from diral_amd import build as b; print("TUS=\"%s\"; CC=\"%s\"; CFLAGS=\"%s\"" % (" ".join(s[:-4] for s in b.SOURCES), b.hipcc_path(), " ".join(b.HIPCC_FLAGS)))')"
+for tu in $TUS; do
+  $CC $CFLAGS "$@" -Rpass-analysis=kernel-resource-usage -c diral_amd/csrc/$tu.hip -o /dev/null 2>&1 |
   python3 -c '
 import re, sys, subprocess
 txt = sys.stdin.read()

@@ -1944,7 +1944,7 @@ def test_graph_replays_on_a_frozen_slow_set_survive_eager_steps_in_between(K, N,
     """A captured rollout whose launch count is NOT a multiple of three cannot rotate the slow-env sets: every captured
     launch is baked with the set the last eager launch before the capture read.  Eager steps between two replays keep
     rotating through that set - one of them clears it, the next rebuilds it.  A set must be either a complete list or
-    EMPTY at every launch boundary (count and flags: step_fast64.hpp), else a replay issued two eager steps after the
+    EMPTY at every launch boundary (count and flags: step_params.hpp), else a replay issued two eager steps after the
     capture finds a zero count under standing flags and steps the flagged envs not at all.  One, two
     and three eager steps between replays; against the same sequence without a graph, bit for bit; every env's slot
     counter advanced by every launch.  Sticky actions keep a third of the envs on the list.  The 128-vehicle case runs
