@@ -457,12 +457,15 @@ StepPlan plan_step(const DiralEnv* e, const StepParams& p, const PolParams* pol)
   // ... and the K-slot form of it runs this configuration's random prefill (diral_env_prefill: my_step_design's
   // reward is computed in P2 there, so the design switch does not count against it)
   const bool prefill_ok = d.use_fast64 && e->flat_y && d.design && !switches && p.N >= 8;
+  // my_step_ch: the K-slot form only (slots > 1 of diral_env_step_policy, and the enable_channel prefill of
+  // diral_env_prefill_mode); a one-slot policy call in this mode keeps its three launches
+  const bool pol_ch_ok = d.use_fast64 && e->flat_y && ch && !extra && p.N >= 8;
   // step_wide_slots_kernel (k_wide_slots.hip) takes K > 1 slots of diral_env_step_policy at 64 < N <= 256; a one-slot
   // call there keeps its three launches
   const bool wide_kslots_ok = d.use_wide && !ch && !extra;
   d.launch = d.use_wide ? StepLaunch::Wide : StepLaunch::Fast64;
-  if (pol && pol->prefill) { if (prefill_ok) d.launch = StepLaunch::Fast64Slots; }
-  else if (pol && pol->K > 1) { if (pol_ok) d.launch = StepLaunch::Fast64Slots; else if (wide_kslots_ok) d.launch = StepLaunch::WideSlots; }
+  if (pol && pol->prefill) { if (prefill_ok || pol_ch_ok) d.launch = StepLaunch::Fast64Slots; }
+  else if (pol && pol->K > 1) { if (pol_ok || pol_ch_ok) d.launch = StepLaunch::Fast64Slots; else if (wide_kslots_ok) d.launch = StepLaunch::WideSlots; }
   else if (pol && pol_ok) d.launch = StepLaunch::Fast64Policy;
   // K slots per launch (DiralSlotPolicy::slots > 1, prefill): blocks = envs in order - over K slots a straggler averages
   // out; the slow-env sets stay as the last one-slot launch left them (complete or empty), unread
@@ -575,7 +578,7 @@ hipError_t launch_step_any(DiralEnv* e, const StepParams& p, const StepPlan& d, 
     case StepLaunch::WideSlots: return launch_wide_slots(f, r, *pol, d.k, e->vpl, p.B, s);
     case StepLaunch::Wide: return e->vpl == 2 ? launch_wide2(f, r, d.k, grid, s) : launch_wide4(f, r, d.k, grid, s);
     // the env stays on the chip from slot to slot: step_fast64_slots_kernel
-    case StepLaunch::Fast64Slots: return launch_fast64_slots(f, r, *pol, d.k.out64, p.B, s);
+    case StepLaunch::Fast64Slots: return launch_fast64_slots(f, r, *pol, d.k.ch, d.k.out64, p.B, s);
     case StepLaunch::Fast64Policy: return launch_fast64_policy(f, r, *pol, d.k.out64, grid, s);
     default: return launch_fast64(f, r, d.k, grid, s);
   }
@@ -1053,17 +1056,22 @@ int diral_env_step_policy(DiralEnv* e, int mode, const int32_t* actions, int64_t
                              pol->draw_choice, pol->seed, (const long long*)pol->seed_clock, pol->actions_out, stream);
 }
 
-int diral_env_prefill(DiralEnv* e, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out, int out_dtype,
-                      int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in, double episode, double epsilon,
-                      void* stream) {
+int diral_env_prefill_mode(DiralEnv* e, int mode, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out,
+                           int out_dtype, int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in,
+                           double episode, double epsilon, void* stream) {
   if (!e || !actions || !actions_next_out || slots < 1) return DIRAL_ERR_BAD_ARG;
+  if (mode != DIRAL_STEP_DESIGN && mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_BAD_ARG;
   if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
-  if (e->prev_obs) return DIRAL_ERR_BAD_CONFIG;                  // State.piggybacking: my_step only (diral_env_step)
+  const bool ch = mode == DIRAL_STEP_MY_STEP_CH;
+  // my_step_ch defines rewards only for reward_design 2,3,4 (test_env.py:413-429)
+  if (ch && (e->cfg.reward_design < 2 || e->cfg.reward_design > 4)) return DIRAL_ERR_BAD_CONFIG;
+  // State.piggybacking: my_step only (diral_env_step) - the loop this launch stands for fails there too
+  if (e->prev_obs) return ch ? DIRAL_ERR_UNSUPPORTED : DIRAL_ERR_BAD_CONFIG;
   // the secondary observation modes are launches of their own behind ONE state vector (posdist_kernel.hpp)
   if (states_out && (has(&e->cfg, DIRAL_F_ADD_POSDIST) || (has(&e->cfg, DIRAL_F_ADD_POSDIST_PIGGY) && e->cfg.posdist_type == 1)))
     return DIRAL_ERR_UNSUPPORTED;
   DEVICE_ENTER(e->device);
-  const StepParams p = call_params(e, DIRAL_STEP_DESIGN, 0, actions, states_out, out_dtype, episode, epsilon);
+  const StepParams p = call_params(e, mode, 0, actions, states_out, out_dtype, episode, epsilon);
   PolParams q;
   std::memset(&q, 0, sizeof(q));
   q.K = slots; q.prefill = 1; q.seed = seed; q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N;
@@ -1072,6 +1080,13 @@ int diral_env_prefill(DiralEnv* e, const int32_t* actions, int32_t slots, uint64
   if (!d.fused) return DIRAL_ERR_UNSUPPORTED;                    // (nothing launched: the caller loops sample + step + observe)
   HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
   return DIRAL_OK;
+}
+
+int diral_env_prefill(DiralEnv* e, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out, int out_dtype,
+                      int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in, double episode, double epsilon,
+                      void* stream) {
+  return diral_env_prefill_mode(e, DIRAL_STEP_DESIGN, actions, slots, seed, states_out, out_dtype, actions_all_out,
+                                actions_next_out, rew_in, episode, epsilon, stream);
 }
 
 int diral_env_observe(DiralEnv* e, const int32_t* actions, const double* chobs_in, const double* rew_in,

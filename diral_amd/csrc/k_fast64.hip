@@ -35,7 +35,7 @@ hipError_t launch_fast64(const FastParams& f, const RichParams& r, const KernelS
   return hipGetLastError();
 }
 
-// the POL instantiations (policy epilogue): the flat highway, my_step, no EXTRA switches, RICH
+// the one-slot POL instantiations (policy epilogue): the flat highway, my_step, no EXTRA switches, RICH
 hipError_t launch_fast64_policy(const FastParams& f, const RichParams& r, const PolParams& q, bool out64, int B, hipStream_t s) {
   const uint32_t lds = fast_lds_layout(f.K, f.A, true, out64, true, false).total;
   if (out64) hipLaunchKernelGGL((step_fast64_kernel<true, true, false, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
@@ -43,11 +43,17 @@ hipError_t launch_fast64_policy(const FastParams& f, const RichParams& r, const 
   return hipGetLastError();
 }
 
-// ... K slots per launch (PolParams::K > 1): step_fast64_slots_kernel, the same body with the env kept on the chip
-hipError_t launch_fast64_slots(const FastParams& f, const RichParams& r, const PolParams& q, bool out64, int B, hipStream_t s) {
-  const uint32_t lds = fast_lds_layout(f.K, f.A, true, out64, true, false, true).total;
-  if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, false, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
-  else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, false, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
+// ... K slots per launch (PolParams::K > 1): step_fast64_slots_kernel, the same body with the env kept on the chip; `ch`:
+// my_step_ch slots (the reception ratios of P1 in LDS next to the policy's arrays)
+hipError_t launch_fast64_slots(const FastParams& f, const RichParams& r, const PolParams& q, bool ch, bool out64, int B, hipStream_t s) {
+  const uint32_t lds = fast_lds_layout(f.K, f.A, true, out64, true, ch, true).total;
+  if (ch) {
+    if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, true, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
+    else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, true, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
+  } else {
+    if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, false, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
+    else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, false, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
+  }
   return hipGetLastError();
 }
 }  // namespace diral

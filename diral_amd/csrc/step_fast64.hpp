@@ -192,5 +192,6 @@ __device__ DIRAL_OUTLINE void fast_sps_decide(const T* stage, int SA, int A, int
 // RICH: the output tail of rich_out.hpp (channel observation output, the cheap State flags)
 // instead of the fixed [one-hot | histogram] state; `r` is only read by these instantiations.
 // POL: the policy epilogue (PolParams: reward shaping + the SPS agents' decisions for the next slot) - RICH instantiations
-// of my_step only; `q` is only read by these.
+// of my_step only (step_fast64_slots_kernel: of my_step_ch too - K slots per launch and the enable_channel prefill); `q` is
+// only read by these.
 }  // namespace diral

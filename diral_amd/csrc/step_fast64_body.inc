@@ -1,8 +1,8 @@
 // step_fast64_body.inc - the body of the fused step kernel of step_fast64.hpp, included TWICE by k_fast64.hip (textual inclusion, as
 // step_wide_pass.inc): once as `step_fast64_kernel` - one slot per launch, the metric's kernel - and once, with
-// DIRAL_FAST_KSLOTS defined, as `step_fast64_slots_kernel` - K slots per launch of the POL instantiation (PolParams::K,
-// diral_env_step_policy with DiralSlotPolicy::slots > 1): the workgroup keeps its env in registers and LDS from slot to
-// slot.  The two differ where `#ifdef DIRAL_FAST_KSLOTS` says so and nowhere else: the one-slot kernel is compiled from
+// DIRAL_FAST_KSLOTS defined, as `step_fast64_slots_kernel` - K slots per launch of the POL instantiations (PolParams::K,
+// diral_env_step_policy with DiralSlotPolicy::slots > 1; my_step and, in this form only, my_step_ch): the workgroup keeps
+// its env in registers and LDS from slot to slot.  The two differ where `#ifdef DIRAL_FAST_KSLOTS` says so and nowhere else: the one-slot kernel is compiled from
 // exactly the text it had before the K-slot form existed (the same statements behind `if (first)` / `if (last)` with
 // compile-time-true conditions cost the metric's instantiation a spilled register).
 template <bool FLAT, bool OUT64, bool CH, bool EXTRA, bool RICH, bool POL = false>
@@ -15,7 +15,12 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES) void DIRAL_FAST_KERNEL(co
 __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL(const FastParams p, const RichParams r,
                                                                                 const PolParams q) {
 #endif
+#ifndef DIRAL_FAST_KSLOTS
   static_assert(!POL || (RICH && !CH), "the policy epilogue needs the staged channel observation of a my_step slot");
+#else /* DIRAL_FAST_KSLOTS */
+  // (K slots: my_step_ch too - its staged observation is 0 / the constant 1, which the SPS agents read as -200 / -40 dBm)
+  static_assert(!POL || (RICH && FLAT && !EXTRA), "the policy epilogue needs the staged channel observation of a my_step / my_step_ch slot");
+#endif /* DIRAL_FAST_KSLOTS */
   extern __shared__ __align__(16) unsigned char smem[];
 #ifndef DIRAL_FAST_KSLOTS
   const FastLds lay = fast_lds_layout(p.K, p.A, RICH, OUT64, FLAT, CH || EXTRA);
@@ -431,7 +436,8 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
         coll = c > 1; sole = !(c > 1); prr = R;
       } else if (c > 1) { rw = (EXTRA && p.design) ? s_rtx[lane] : s_rv[act_own]; coll = 1; } else { rw = 1.0; sole = 1; }   // test_env.py:211-222, 297-301
 #ifdef DIRAL_FAST_KSLOTS
-      if constexpr (POL && FLAT) {
+      // (CH: the enable_channel prefill of main_test.py:101-103 pays my_step_ch's reward, above, like every other slot)
+      if constexpr (POL && FLAT && !CH) {
         if (prefill && c > 1) {
           // my_step_design (test_env.py:297-301, 319-349; network.py:122-157): by the number of transmitters of this resource
           // within 2 Rc of this one - alone 1, else -n (a pair inside 2 Rc: -2)
@@ -1289,6 +1295,9 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   if constexpr (POL) {
     // ---- K slots: what the next slot takes over, Network.update_velocity at an episode end, and the barrier that lets the
     //      next slot's P0 overwrite the LDS of this one
+    // (CH: `s_inr` / `s_rtx` need no barrier of their own.  Wave 0 reads this slot's ratios in P2, in front of its P3 and so
+    //  in front of the barrier behind P3; every wave's P1 of the next slot - the next writer - lies behind that barrier and
+    //  the one below.  Nothing else of my_step_ch crosses a slot: the ratios are rebuilt from the positions every slot.)
     if (KS > 1) {
       mynpx_prev = mynpx;
       tkov_prev = tkov;

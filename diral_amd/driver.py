@@ -122,15 +122,18 @@ class DriverLoop:
     # main_test.py:99-114 as a whole: K random slots, every state kept (what the loop hands to memory.add)
     def prefill(self, slots: int, seed: int):
         """``for k in range(slots): a = env.sample(seed + k); states[k] = prefill_step(a)``: returns
-        ``(states [K, B, N, S], actions [K, B, N])``.  On the HIP env with `enable_channel` off this is ONE launch
-        (`VecV2VEnv.prefill` -> `diral_env_prefill`: the env stays on the chip for the K slots); configurations that
-        launch does not take - and any other env - run the loop."""
+        ``(states [K, B, N, S], actions [K, B, N])``.  On the HIP env this is ONE launch (`VecV2VEnv.prefill` ->
+        `diral_env_prefill_mode`, my_step_design or - `enable_channel` - my_step_ch: the env stays on the chip for the K
+        slots); configurations that launch does not take - and any other env - run the loop."""
         env = self.env
-        if not self.enable_channel and hasattr(env, "prefill"):
+        if hasattr(env, "prefill"):
             from .config import ERR_UNSUPPORTED
             from .vec_env import DiralError
             try:
-                states, acts, _ = env.prefill(env.sample(seed), slots, seed, rew_in=self._rews0)
+                if self.enable_channel:
+                    states, acts, _ = env.prefill(env.sample(seed), slots, seed, rew_in=self._rews0, mode="my_step_ch")
+                else:
+                    states, acts, _ = env.prefill(env.sample(seed), slots, seed, rew_in=self._rews0)
                 return states, acts
             except DiralError as exc:
                 if exc.status != ERR_UNSUPPORTED:

@@ -324,14 +324,19 @@ class VecV2VEnv:
         return out
 
     def prefill(self, actions: torch.Tensor, slots: int, seed: int, rew_in=None, want_states: bool = True,
-                episode: float = 0.0, eps: float = 1.0):
-        """The driver's random prefill (main_test.py:99-114) as ONE launch of `slots` slots (`diral_env_prefill`):
+                episode: float = 0.0, eps: float = 1.0, mode="my_step_design"):
+        """The driver's random prefill (main_test.py:99-114) as ONE launch of `slots` slots (`diral_env_prefill_mode`):
         slot 0 runs `actions` ([B, N] int32, e.g. ``env.sample(seed)``), slot k the draw ``env.sample(seed + k)``
-        would make; every slot is ``my_step_design(a_k, 0)`` followed by ``obtain_state(obs, a_k, rew_in)``.
+        would make; every slot is ``my_step_design(a_k, 0)`` - or, with `mode` = ``"my_step_ch"`` / STEP_MY_STEP_CH, the
+        driver's `enable_channel` branch ``my_step_ch(a_k, 0)`` (PRR reward and PRR metrics, reward_design 2 ... 4) -
+        followed by ``obtain_state(obs, a_k, rew_in)``.
         Returns ``(states [K, B, N, S] or None, actions_all [K, B, N], next_actions [B, N])``; `next_actions` is
         the draw of ``seed + slots`` (pass it, with that seed, to continue).  Bit-equal to the loop of
-        sample + my_step_design + obtain_state calls.  Raises DiralError(ERR_UNSUPPORTED) with nothing launched for
-        configurations the fused kernel does not take (diral_amd.driver.DriverLoop.prefill loops then)."""
+        sample + my_step_design / my_step_ch + obtain_state calls.  Raises DiralError(ERR_UNSUPPORTED) with nothing launched
+        for configurations the fused kernel does not take (diral_amd.driver.DriverLoop.prefill loops then)."""
+        step_mode = _MODES.get(mode)
+        if step_mode not in (STEP_DESIGN, STEP_MY_STEP_CH):
+            raise ValueError("prefill: mode must be 'my_step_design' or 'my_step_ch'")
         K = int(slots)
         a = self._actions(actions)
         states = torch.empty((K, self.B, self.N, self.S), dtype=self.out_dtype, device=self.device) if (want_states and self.S > 0) else None
@@ -339,10 +344,11 @@ class VecV2VEnv:
         a_next = torch.empty((self.B, self.N), dtype=torch.int32, device=self.device)
         rin = None if rew_in is None else self._f64(rew_in, (self.B, self.N))
         self._spec = None
-        st = self.lib.diral_env_prefill(self._h, _ptr(a), K, int(seed) & (2**64 - 1), _ptr(states) if states is not None else None,
-                                        self._dt, _ptr(a_all), _ptr(a_next), _ptr(rin) if rin is not None else None,
-                                        float(episode), float(eps), self._stream())
-        self._ok(st, "diral_env_prefill")
+        st = self.lib.diral_env_prefill_mode(self._h, step_mode, _ptr(a), K, int(seed) & (2**64 - 1),
+                                             _ptr(states) if states is not None else None,
+                                             self._dt, _ptr(a_all), _ptr(a_next), _ptr(rin) if rin is not None else None,
+                                             float(episode), float(eps), self._stream())
+        self._ok(st, "diral_env_prefill_mode")
         if rin is not None:
             torch.cuda.current_stream(self.device).synchronize()   # `rin` may be a temporary
         return states, a_all, a_next
@@ -390,7 +396,9 @@ class VecV2VEnv:
         observation are the LAST slot's (without `want_obs` no slot computes a state vector), `shaped_out` [K, B, N] and
         `sum_r_out` / `collision_out` [K, B] hold every slot's; configs with mobility_vary update the velocities at the
         episode ends inside the launch (`update_velocity(seed=vel_seed + slot // episode_interval)`).  Equal, bit for bit,
-        to K one-slot calls; raises DiralError(UNSUPPORTED) where the fused kernel does not apply."""
+        to K one-slot calls; raises DiralError(UNSUPPORTED) where the fused kernel does not apply.  `mode` = STEP_MY_STEP_CH
+        (the PRR reward of `enable_channel`, reward_design 2 ... 4) runs K > 1 slots in one launch at 8 <= N <= 64 too
+        (profiles/kslots_ch/); with slots = 1 it stays three launches, and 64 < N <= 256 refuses it."""
         from .config import DiralSlotPolicy, ERR_UNSUPPORTED
         K = int(slots)
         if K < 1:

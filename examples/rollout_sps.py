@@ -17,7 +17,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from diral_amd import c2_config  # noqa: E402
-from diral_amd.config import bench_config  # noqa: E402
+from diral_amd.config import STEP_MY_STEP_CH, bench_config  # noqa: E402
 from diral_amd.driver import DriverLoop  # noqa: E402
 from diral_amd.metrics import gather_metrics  # noqa: E402
 from diral_amd.shard import make_sharded_env, rank_world  # noqa: E402
@@ -39,6 +39,9 @@ def main():
     ap.add_argument("--config", choices=["c2", "c5", "c3"], default="c2",
                     help="c2: 64 UE / 32 res (the default); c5: 128 UE / 64 res with mobility_vary; c3: 256 UE / 64 res "
                          "(BASELINE configs[1], [4], [2])")
+    ap.add_argument("--enable-channel", action="store_true",
+                    help="the driver's enable_channel branch: my_step_ch (the PRR reward) instead of my_step; with "
+                         "--one-launch --slots-per-launch K (64 UE) the K slots still run as ONE launch")
     args = ap.parse_args()
     rank, local_rank, world = rank_world()
     torch.cuda.set_device(local_rank)
@@ -50,7 +53,8 @@ def main():
     env, start = make_sharded_env(cfg, args.envs, out_dtype=torch.float32, io_ring=2)
     env.reset_topology(seed=1234)                     # one global seed: the shard offset selects the envs
     loop = DriverLoop(env, global_reward_avg=True, episode_interval=cfg.episode_interval,
-                      fused=args.fused and args.policy == "random")
+                      fused=args.fused and args.policy == "random", enable_channel=args.enable_channel)
+    mode = STEP_MY_STEP_CH if args.enable_channel else None
     pol = SpsPolicy(env.B, env.N, env.A, device=env.device, seed=start)
     state = loop.bootstrap(pol.prev_action)
     actions = pol.prev_action.clone()
@@ -65,13 +69,14 @@ def main():
             for n in range(args.slots // K):
                 # (want_obs=False: a policy-only rollout - no state vector, so no histogram either)
                 env.step_policy(acts[n & 1], n * K, pol, acts[(n + 1) & 1], shaped_out=shaped, global_reward_avg=True,
-                                slots=K, want_obs=False)
+                                slots=K, want_obs=False, mode=mode)
                 if n == args.slots // K // 2:
                     env.metrics(clear=True)
         else:
             shaped = torch.empty((env.B, env.N), dtype=torch.float32, device=env.device)
             for t in range(args.slots):
-                state, _, _ = env.step_policy(acts[t & 1], t, pol, acts[(t + 1) & 1], shaped_out=shaped, global_reward_avg=True)
+                state, _, _ = env.step_policy(acts[t & 1], t, pol, acts[(t + 1) & 1], shaped_out=shaped, global_reward_avg=True,
+                                               mode=mode)
                 if t == args.slots // 2:
                     env.metrics(clear=True)
         args.slots_done = True

@@ -446,7 +446,9 @@ typedef struct DiralSlotPolicy {
   int32_t* actions_out;           /* [B][N] */
   /* K slots in ONE launch (ABI 6).  slots <= 1: one slot, as above.  slots = K > 1 (configurations the fused kernels take -
    * N <= 256 vehicles, my_step, the flat highway, A <= 64, none of the run-time extras (arrival stamps, trace replay, PRR
-   * tracking, static topologies, handles without piggybacked tables), no State.piggybacking; otherwise
+   * tracking, static topologies, handles without piggybacked tables), no State.piggybacking; at 8 <= N <= 64 also
+   * my_step_ch (DIRAL_STEP_MY_STEP_CH with reward_design 2, 3 or 4: the PRR reward and the PRR metric columns every slot;
+   * a ONE-slot call in that mode stays three launches, and 64 < N <= 256 refuses it); otherwise
    * DIRAL_ERR_UNSUPPORTED with nothing launched): the workgroup of an env runs K slots of [env step -> shaping -> SPS
    * decision] back to back (N <= 64 keeps the env on the chip; 64 < N <= 256 leaves its tables in HBM / L2 between
    * slots, as a one-slot launch does), `actions` being slot 0's and the policy's
@@ -481,6 +483,17 @@ int diral_env_step_policy(DiralEnv* env, int mode, const int32_t* actions, int64
 int diral_env_prefill(DiralEnv* env, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out, int out_dtype,
                       int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in, double episode,
                       double epsilon, void* stream);
+/* ... with the step the driver's branch calls (additive within ABI 8): `mode` = DIRAL_STEP_DESIGN is diral_env_prefill;
+ * `mode` = DIRAL_STEP_MY_STEP_CH runs the `enable_channel` prefill of main_test.py:101-103 -
+ *                         obs, _ = my_step_ch(a_k, 0)                            [test_env.py:351-443]
+ * in place of my_step_design: every slot pays the PRR reward and adds to the PRR metric columns, the state rows take
+ * `obs` (0 on the own or an idle resource, else 1) and `rew_in` as above.  Equal, bit for bit, to the loop of
+ * diral_env_sample + diral_env_step(DIRAL_STEP_MY_STEP_CH) + diral_env_observe.  Any other mode: DIRAL_ERR_BAD_ARG;
+ * my_step_ch with reward_design outside 2 ... 4: DIRAL_ERR_BAD_CONFIG (as diral_env_step); the configurations listed
+ * above, vehicles off the lane, static topologies and State.piggybacking: DIRAL_ERR_UNSUPPORTED with nothing launched. */
+int diral_env_prefill_mode(DiralEnv* env, int mode, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out,
+                           int out_dtype, int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in,
+                           double episode, double epsilon, void* stream);
 
 /* ---- slot clock: rollouts captured into a hipGraph ---------------------------------------------
  * A captured sequence of K slots (env step, reward shaping, policy) bakes every by-value argument into its

@@ -1,0 +1,258 @@
+"""K slots per launch of the `my_step_ch` closed loop at N <= 64 (step_fast64_slots_kernel<..., CH, ..., POL>):
+`diral_env_step_policy(DIRAL_STEP_MY_STEP_CH)` with DiralSlotPolicy::slots = K > 1 against K one-slot calls - in this
+mode each of those is three launches (the step with the channel observation, diral_driver_shape, diral_sps_step_chobs) -
+bit for bit, against the CPU oracle, and the refusals."""
+import numpy as np
+import pytest
+import torch
+
+from diral_amd.config import (ERR_BAD_CONFIG, ERR_UNSUPPORTED, KERNEL_CH, KERNEL_FAST64, KERNEL_POLICY, STEP_MY_STEP_CH,
+                              bench_config, c2_config)
+
+pytestmark = pytest.mark.gpu
+
+RICH = dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=True, add_position=True)
+
+
+def _is_ch_slots_kernel(lk):
+    return (lk & 15) == KERNEL_FAST64 and bool(lk & KERNEL_POLICY) and bool(lk & KERNEL_CH)
+
+
+def in_range_counts(x, a, rc):
+    """test_env.py:395-397 on the one-lane highway: for every transmitter of a resource more than one vehicle transmits
+    on, the number of vehicles on OTHER resources closer than `rc`; -1 for a transmitter that is alone.  x, a: [B, N]."""
+    x, a = np.asarray(x, dtype=np.float64), np.asarray(a)
+    same = a[:, :, None] == a[:, None, :]                                  # [B, tx, rx]
+    coll = same.sum(2) > 1
+    near = np.abs(x[:, :, None] - x[:, None, :]) < rc
+    n_in = (near & ~same).sum(2)
+    return np.where(coll, n_in, -1)
+
+
+def _pair(cfg, B, dt, K, t0, *, want_obs=True, keep=0.8, vel_seed=0, pen=False, x0=None, reps=2):
+    """The same slots on two envs: K one-slot calls (side 0) and one K-slot launch (side 1), `reps` times."""
+    from diral_amd.sps import SpsPolicy
+    from diral_amd.vec_env import VecV2VEnv
+    N, A = cfg.num_users, cfg.num_channels
+    vary = cfg.mobility_vary
+    runs = []
+    for fused_k in (False, True):
+        env = VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=dt)
+        if x0 is not None:
+            env.reset_topology(x0, None, np.full(x0.shape, 1.7))
+        else:
+            env.reset_topology(seed=21)
+        pol = SpsPolicy(B, N, A, device="cuda:0", seed=3)
+        pol.keep_prob = keep
+        pn = None
+        if pen:
+            pn = (2, -10.0, torch.zeros((B, N), dtype=torch.int32, device="cuda:0"),
+                  torch.full((B, N), -1, dtype=torch.int32, device="cuda:0"))
+        a = pol.prev_action.clone()
+        nxt = torch.empty_like(a)
+        t = 0
+
+        def one(sh=None, sr=None, co=None):
+            nonlocal a, nxt, t
+            env.step_policy(a, t, pol, nxt, shaped_out=sh, sum_r_out=sr, collision_out=co, mode=STEP_MY_STEP_CH,
+                            want_chobs=True, want_obs=want_obs, stuck_penalty=pn if sh is not None else None)
+            assert env.last_kernel() & KERNEL_POLICY == 0 and env.last_kernel() & KERNEL_CH      # three launches
+            if vary and t % cfg.episode_interval == cfg.episode_interval - 1:
+                env.update_velocity(seed=vel_seed + t // cfg.episode_interval)
+            a, nxt = nxt, a
+            t += 1
+        sh0 = torch.zeros((B, N), dtype=dt, device="cuda:0")
+        for _ in range(t0):                                       # warm-up, one slot per call on both sides
+            one(sh0 if pen else None)
+        start = (env.export_state()["pos_x"].cpu().numpy(), a.cpu().numpy())
+        outs = []
+        for rep in range(reps):
+            sh = torch.zeros((K, B, N), dtype=dt, device="cuda:0")
+            sr = torch.zeros((K, B), dtype=dt, device="cuda:0")
+            co = torch.zeros((K, B), dtype=dt, device="cuda:0")
+            if fused_k:
+                env.step_policy(a, t, pol, nxt, shaped_out=sh, sum_r_out=sr, collision_out=co, slots=K, vel_seed=vel_seed,
+                                mode=STEP_MY_STEP_CH, want_chobs=True, want_obs=want_obs, stuck_penalty=pn)
+                assert _is_ch_slots_kernel(env.last_kernel()), env.last_kernel()
+                a, nxt = nxt, a
+                t += K
+            else:
+                for k in range(K):
+                    one(sh[k], sr[k], co[k])
+            outs.append(dict(shaped=sh, sum_r=sr, coll=co, obs=env._obs.clone() if want_obs else None, rew=env._rew.clone(),
+                             done=env._done.clone(), actions=a.clone(), chobs=env._chobs.clone()))
+        torch.cuda.synchronize()
+        runs.append((env, pol, outs, pn, start))
+    return runs
+
+
+def _compare(runs, want_obs=True):
+    (e1, p1, o1, pn1, _), (e2, p2, o2, pn2, _) = runs
+    for rep in range(len(o1)):
+        for k in ("shaped", "sum_r", "coll", "rew", "done", "chobs", "actions"):
+            assert torch.equal(o1[rep][k], o2[rep][k]), (rep, k, (o1[rep][k] != o2[rep][k]).nonzero()[:4])
+        if want_obs:
+            assert torch.equal(o1[rep]["obs"], o2[rep]["obs"]), (rep, (o1[rep]["obs"] != o2[rep]["obs"]).nonzero()[:4])
+    assert torch.equal(p1.prev_action, p2.prev_action) and torch.equal(p1.counter, p2.counter)
+    sa, sb = e1.export_state(), e2.export_state()
+    for k in sa:
+        assert torch.equal(sa[k], sb[k]), k
+    m1, m2 = e1.metrics(), e2.metrics()
+    assert torch.equal(m1, m2), (m1 != m2).nonzero()[:4]        # the PRR sum and count among them
+    assert float(m1[:, 5].min()) > 0.0                           # DIRAL_M_PRR_CNT: the PRR columns were paid
+    if pn1 is not None:
+        assert torch.equal(pn1[2], pn2[2]) and torch.equal(pn1[3], pn2[3])
+    # ... and the envs go on alike: three plain slots
+    for t in range(3):
+        a = e1.sample(900 + t)
+        q1, r1, _ = e1.step(a, t)
+        q2, r2, _ = e2.step(a, t)
+        assert torch.equal(q1, q2) and torch.equal(r1, r2), t
+    sa, sb = e1.export_state(), e2.export_state()
+    for k in sa:
+        assert torch.equal(sa[k], sb[k]), k
+    assert torch.equal(e1.metrics(), e2.metrics())
+    e1.check()
+    e2.check()
+    return sa
+
+
+CASES = {
+    "c2_rd2_f32": dict(cfg=c2_config(reward_design=2), dt=torch.float32, K=5, t0=3),
+    # episode_interval 25: the episode that ends at t = 24 ends inside both launches' range (t = 10 ... 59)
+    "rd3_f64_vary": dict(cfg=c2_config(reward_design=3, mobility_vary=True), dt=torch.float64, K=25, t0=10, vel_seed=777),
+    "rd4_rich": dict(cfg=c2_config(reward_design=4, State=RICH), dt=torch.float32, K=6, t0=4),
+    # dense: 40 vehicles on 6 resources collide nearly always; a 30 m range leaves some transmitters nobody to reach (R = 1)
+    "dense_40_6": dict(cfg=bench_config(40, 6, 900.0, reward_design=2, communication_range=30.0), dt=torch.float32, K=6, t0=2),
+    "sparse_64_8": dict(cfg=bench_config(64, 8, 9000.0, reward_design=2, communication_range=100.0), dt=torch.float32, K=9,
+                        t0=12),                                  # keyed quads
+    "n8": dict(cfg=bench_config(8, 4, 400.0, reward_design=2), dt=torch.float64, K=6, t0=2),
+    "n33": dict(cfg=bench_config(33, 7, 1200.0, reward_design=3), dt=torch.float32, K=6, t0=2),      # padded lanes
+    "stuck_penalty": dict(cfg=c2_config(reward_design=2), dt=torch.float32, K=6, t0=21, keep=0.95, pen=True),
+    "no_obs": dict(cfg=c2_config(reward_design=2), dt=torch.float32, K=25, t0=3, want_obs=False),
+}
+
+
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_ch_k_slots_equal_k_one_slot_calls(case):
+    """K `my_step_ch` slots in one launch equal K one-slot calls (three launches each): per-slot shaped rewards / sums /
+    collisions, the last slot's state, reward, done and channel observation, the next actions, the policy state, the
+    exported tables, positions, velocities and the metrics - the PRR sum and count included -, then three more plain
+    slots on both handles.  exp()-based rewards (reward_design 3) bit for bit too: both sides are the same device function."""
+    kw = dict(CASES[case])
+    cfg, dt, K, t0 = kw.pop("cfg"), kw.pop("dt"), kw.pop("K"), kw.pop("t0")
+    want_obs = kw.get("want_obs", True)
+    runs = _pair(cfg, 24, dt, K, t0, **kw)
+    if case == "dense_40_6":
+        n_in = in_range_counts(runs[1][4][0], runs[1][4][1], cfg.communication_range)
+        assert (n_in == 0).any() and (n_in > 0).any()             # both sides of `R = received / in_range` ran
+        assert (n_in >= 0).mean() > 0.5                           # most transmitters collide
+    sa = _compare(runs, want_obs=want_obs)
+    if cfg.mobility_vary:
+        assert not torch.equal(sa["vel"], torch.full_like(sa["vel"], 1.7))      # an episode ended inside the launches
+    if case == "stuck_penalty":
+        assert int(runs[1][3][2].max()) > 2
+    if case == "sparse_64_8":
+        seq = sa["seq"]
+        own = torch.diagonal(seq, dim1=1, dim2=2).unsqueeze(1)
+        assert bool(((own - seq >= 8) & (seq > 0)).any()), "no entry fell beyond the codes"
+
+
+# the shape of the oracle anchor: 16 vehicles on 4 resources over 3 km with a 100 m range - nearly every transmitter
+# collides, and about half of them have no vehicle of another resource in range
+ANCHOR = dict(N=16, A=4, L=3000.0, rc=100.0, B=16, K=12, seed=5)
+
+
+def anchor_inputs():
+    c = ANCHOR
+    cfg = bench_config(c["N"], c["A"], c["L"], reward_design=2, communication_range=c["rc"])
+    rng = np.random.default_rng(c["seed"])
+    x0 = rng.integers(0, int(c["L"]), size=(c["B"], c["N"])).astype(np.float64)
+    v0 = rng.uniform(1.1, 2.7, size=(c["B"], c["N"]))
+    a = rng.integers(0, c["A"], size=(c["B"], c["N"])).astype(np.int32)
+    return cfg, x0, v0, a
+
+
+def anchor_oracle(cfg, x0, v0, a, K):
+    """K `my_step_ch` slots of the CPU oracle on constant actions; returns (backend, last reward, last observation,
+    in_range counts of every slot)."""
+    from tests.oracle_backend import OracleBackend
+    ob = OracleBackend(cfg, batch=x0.shape[0])
+    ob.reset_topology(x0, np.zeros_like(x0), v0)
+    n_in = []
+    for t in range(K):
+        n_in.append(in_range_counts(ob.get_x_pos(), a, cfg.communication_range))
+        chobs, rew = ob.my_step_ch(a, t)
+    return ob, rew, chobs, np.stack(n_in)
+
+
+def test_ch_k_slots_against_the_cpu_oracle():
+    """One launch of K = 12 `my_step_ch` slots with keep_prob = 1 (no agent ever re-selects: the actions stay slot 0's, no
+    host SPS needed) against tests/oracle_backend.OracleBackend stepped K times on the same actions: positions and tables
+    bit for bit, the last slot's reward and channel observation bit for bit, the PRR count exact and the PRR sum within
+    the suite's tolerance for that column (test_gpu_parity: rtol 1e-12, atol 1e-9 - the summation order differs)."""
+    from diral_amd.sps import SpsPolicy
+    from diral_amd.vec_env import VecV2VEnv
+    cfg, x0, v0, a_np = anchor_inputs()
+    B, N, A, K = ANCHOR["B"], ANCHOR["N"], ANCHOR["A"], ANCHOR["K"]
+    ob, o_rew, o_chobs, n_in = anchor_oracle(cfg, x0, v0, a_np, K)
+    # neither branch of `R = received / in_range if in_range > 0 else 1` is vacuous
+    assert (n_in == 0).any(axis=(0, 2)).any() and (n_in > 0).any(axis=(0, 2)).any()
+    env = VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=torch.float64)
+    env.reset_topology(x0, 0.0, v0)
+    pol = SpsPolicy(B, N, A, device="cuda:0", seed=1)
+    pol.keep_prob = 1.0
+    a = torch.as_tensor(a_np, device="cuda:0")
+    pol.prev_action.copy_(a)
+    nxt = torch.empty_like(a)
+    env.step_policy(a, 0, pol, nxt, slots=K, mode=STEP_MY_STEP_CH, want_chobs=True)
+    torch.cuda.synchronize()
+    assert _is_ch_slots_kernel(env.last_kernel()), env.last_kernel()
+    assert torch.equal(nxt, a)                                   # nobody re-selected
+    assert np.array_equal(env._rew.cpu().numpy(), o_rew)
+    assert np.array_equal(env._chobs.cpu().numpy(), o_chobs)
+    st = {k: v.cpu().numpy() for k, v in env.export_state().items()}
+    oe = ob.export_state()
+    assert np.array_equal(st["pos_x"], oe["pos_x"])
+    assert np.array_equal(st["seq"], oe["seq"])
+    assert np.array_equal(st["age"], np.minimum(oe["age"], 255))
+    assert np.array_equal(st["x"], oe["x"])
+    m, om = env.metrics().cpu().numpy(), ob.o.metrics()
+    assert np.array_equal(m[:, [0, 2, 3]], om[:, [0, 2, 3]])
+    assert np.array_equal(m[:, 5], om[:, 5])
+    assert np.allclose(m[:, 4], om[:, 4], rtol=1e-12, atol=1e-9)
+    env.check()
+
+
+def test_ch_k_slots_refusals_leave_the_env_untouched():
+    """my_step_ch with slots = 4 and arrival stamps, or vehicles off the lane: DIRAL_ERR_UNSUPPORTED; with reward_design 1:
+    DIRAL_ERR_BAD_CONFIG.  Nothing is launched: export_state() and the policy state are unchanged."""
+    from diral_amd.sps import SpsPolicy
+    from diral_amd.vec_env import DiralError, VecV2VEnv
+    B = 4
+    cases = [("arrival_stamps", c2_config(reward_design=2, track_arrival=True), ERR_UNSUPPORTED),
+             ("reward_design_1", c2_config(reward_design=1), ERR_BAD_CONFIG),
+             ("off_lane", c2_config(reward_design=2), ERR_UNSUPPORTED)]
+    for name, cfg, status in cases:
+        env = VecV2VEnv(cfg, batch=B, device="cuda:0")
+        N, A = cfg.num_users, cfg.num_channels
+        if name == "off_lane":
+            rng = np.random.default_rng(1)
+            env.reset_topology(rng.integers(0, 2000, size=(B, N)).astype(np.float64), rng.uniform(0, 5, size=(B, N)),
+                               np.full((B, N), 1.7))
+        else:
+            env.reset_topology(seed=2)
+        pol = SpsPolicy(B, N, A, device="cuda:0", seed=1)
+        a = pol.prev_action.clone()
+        nxt = torch.empty_like(a)
+        before = {k: v.clone() for k, v in env.export_state().items()}
+        prev, cnt, steps = pol.prev_action.clone(), pol.counter.clone(), pol._t
+        with pytest.raises(DiralError) as ei:
+            env.step_policy(a, 0, pol, nxt, slots=4, mode=STEP_MY_STEP_CH)
+        assert ei.value.status == status, (name, str(ei.value))
+        torch.cuda.synchronize()
+        after = env.export_state()
+        for k in before:
+            assert torch.equal(before[k], after[k]), (name, k)
+        assert torch.equal(pol.prev_action, prev) and torch.equal(pol.counter, cnt) and pol._t == steps, name
+        env.check()
