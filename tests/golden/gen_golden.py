@@ -17,7 +17,18 @@ Reference entry points exercised (all under /root/reference/envs):
 
   SemiPersistentScheduling   algorithms/v2x_sps.py:8-104   (`sps` fixtures)
 
+  Vehicle (a static N-vehicle topology)  vehicle.py:9-33, network.py:302-305, 545
+  Network.dist with pos_y != 0            network.py:318-332   (off-lane fixtures)
+  Network.get_positional_dist / _piggy    network.py:409-471   (at 64 / 80 vehicles)
+  Network.get_information_age, t < last arrival   network.py:566-574 (negative list index)
+
 Usage:  python tests/golden/gen_golden.py        (rewrites tests/golden/*.npz)
+        python tests/golden/gen_golden.py curated | driver | sps | trace | piggyback   (one family)
+        python tests/golden/gen_golden.py fuzz [n_cases [first_seed]]
+            the seeded differential sweep: draw_ref_case(i) for i in first_seed .. first_seed + n_cases - 1
+            (default 320 from 0), each recorded from the reference into a temporary directory, replayed through
+            Oracle(sq_mode=SQ_POW) under the comparison of test_oracle_reproduces_reference_bit_exact, and
+            written as one table row into tests/golden/FUZZ_SWEEP.md.  Nothing is kept but the report.
 """
 import contextlib
 import hashlib
@@ -25,12 +36,15 @@ import io
 import json
 import os
 import sys
+import tempfile
+import time
 from unittest import mock
 
 import numpy as np
 
 REF = "/root/reference/envs"
 OUT = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(OUT))
 
 sys.dont_write_bytecode = True
 os.environ.setdefault("MPLBACKEND", "Agg")
@@ -38,6 +52,8 @@ sys.path.insert(0, REF)
 with contextlib.redirect_stdout(io.StringIO()):
     from test_env import TestEnv  # noqa: E402  (the reference)
     import network as ref_network  # noqa: E402
+sys.path.insert(0, ROOT)
+from tests.golden_util import OUT_KEYS, out_sha  # noqa: E402  (the per-slot hash the replays recompute)
 
 
 # The `EnvironmentTest` block of configs/4ue_3r_toy/*_b20_*_dis_07.yaml:45-71,
@@ -70,6 +86,18 @@ def big_cfg(N, A, L, **kw):
 def make_env(cfg):
     with contextlib.redirect_stdout(io.StringIO()):
         return TestEnv(**json.loads(json.dumps(cfg)))
+
+
+def make_static_env(cfg):
+    """mobility False + enable_design_topology True with num_users vehicles.  The reference's constructor builds
+    the six vehicles of its design test whatever num_users is (network.py:59-60, 69-79), so the N-vehicle static
+    topology is its own mobile network (network.py:54-58, 92-112: N Vehicle objects with N-entry tables) with the
+    two attributes the run-time code reads set to what this config gives them: `mobility` False (update_mobility
+    does nothing, network.py:302-305) and `enable_design_topology_net` True (dist_piggy, network.py:545)."""
+    env = make_env(cfg_with(cfg, mobility=True, enable_design_topology=False))
+    env.mobility = env.network.mobility = False
+    env.enable_design_topology = env.network.enable_design_topology_net = True
+    return env
 
 
 def set_init(env, x0, y0, v0):
@@ -112,15 +140,21 @@ def sha(a):
 
 
 def run_case(name, cfg, init, steps, vel_updates=None, table_every=1,
-             full_tables=True, episode_eps=None, trace=None, trace_after=None, extra=None):
+             full_tables=True, episode_eps=None, trace=None, trace_after=None, extra=None,
+             record_every=1, out_dir=None, quiet=False):
     """steps: list of (mode, actions, t).  vel_updates: {step_index: draws[N]}
-    applied AFTER that step (main_test.py:226-233 order)."""
+    applied AFTER that step (main_test.py:226-233 order).  record_every > 1 thins the fixture: the full per-slot
+    outputs (OUT_KEYS) are kept at every record_every-th slot and the last (`rec_step` lists them), their hashes
+    (`out_sha`) at every slot, like `table_sha`."""
     if trace is not None:
         # trace replay (network.py:171-178): the reference np.load()s `load_file_pos`
-        tpath = "/tmp/diral_golden_trace_%s.npy" % name
+        tpath = os.path.join(out_dir or tempfile.gettempdir(), "diral_golden_trace_%s.npy" % name)
         np.save(tpath, np.asarray(trace, dtype=np.float64))
-        cfg = cfg_with(cfg, load_positions=True, load_file_pos=tpath)
-    env = make_env(cfg)
+        cfg = cfg_with(cfg, load_positions=True, load_file_pos="/tmp/diral_golden_trace_%s.npy" % name)
+    static = not cfg["mobility"] and cfg.get("enable_design_topology") and not isinstance(init, str)
+    env = make_static_env(cfg) if static else make_env(cfg)
+    if trace is not None:
+        env.load_file_positions = tpath
     N, A = env.NUM_USERS, env.NUM_CHANNELS
     if isinstance(init, str) and init == "fixed4":
         env.reset_mobility_env()
@@ -135,9 +169,11 @@ def run_case(name, cfg, init, steps, vel_updates=None, table_every=1,
     rec = dict(rews=[], chobs=[], state=[], pos_x=[], vel=[], ia=[])
     tab = dict(step=[], seq=[], age=[], x=[], y=[], la=[])
     tab_sha = []
+    o_sha, rec_step = [], []
     vel_updates = vel_updates or {}
     for si, (mode, acts, t) in enumerate(steps):
         acts = np.asarray(acts, dtype=np.int32)
+        t = int(t)
         with contextlib.redirect_stdout(io.StringIO()):
             if mode == "step":
                 obs, rews = env.my_step(acts, t)
@@ -149,17 +185,24 @@ def run_case(name, cfg, init, steps, vel_updates=None, table_every=1,
                 raise ValueError(mode)
             ep, eps = (episode_eps[si] if episode_eps else (0, 1))
             st = env.obtain_state(obs, acts, list(rews), ep, eps)
-        rec["rews"].append(np.array(rews, dtype=np.float64))
-        rec["chobs"].append(np.array([obs[u] for u in range(N)], dtype=np.float64))
-        rec["state"].append(np.array([np.asarray(s, dtype=np.float64) for s in st]))
-        rec["pos_x"].append(np.array([float(v.pos_x) for v in env.network.vehicles]))
-        rec["ia"].append(np.array(env.network.get_information_age(t), dtype=np.int64))
+        now = dict(rews=np.array(rews, dtype=np.float64),
+                   chobs=np.array([obs[u] for u in range(N)], dtype=np.float64),
+                   # (action_index "real" alone leaves each agent's state a scalar, test_env.py:543: one column)
+                   state=np.array([np.asarray(s, dtype=np.float64).reshape(-1) for s in st]).reshape(N, -1)
+                   if np.size(st[0]) else np.zeros((N, 0)),
+                   pos_x=np.array([float(v.pos_x) for v in env.network.vehicles]),
+                   ia=np.array(env.network.get_information_age(t), dtype=np.int64))
         if si in vel_updates:
             draws = list(vel_updates[si])
             with mock.patch.object(ref_network.random, "randrange",
                                    side_effect=lambda a, b: draws.pop(0)):
                 env.update_velocity()
-        rec["vel"].append(np.array([float(v.velocity) for v in env.network.vehicles]))
+        now["vel"] = np.array([float(v.velocity) for v in env.network.vehicles])
+        o_sha.append([out_sha(now[k]) for k in OUT_KEYS])
+        if si % record_every == 0 or si == len(steps) - 1:
+            rec_step.append(si)
+            for k in OUT_KEYS:
+                rec[k].append(now[k])
         if trace is not None and si == trace_after:
             with contextlib.redirect_stdout(io.StringIO()):
                 env.load_saved_positions()                      # main_test.py:118
@@ -197,12 +240,17 @@ def run_case(name, cfg, init, steps, vel_updates=None, table_every=1,
     if getattr(env, "piggybacking", False):
         # TestEnv.prev_obs after the last step (test_env.py:260-261): dict user -> ndarray[A]
         out["prev_obs"] = np.array([env.prev_obs[u] for u in range(N)], dtype=np.float64)
+    if record_every > 1:
+        out["rec_step"] = np.array(rec_step, dtype=np.int64)
+        out["out_sha"] = np.array(o_sha)
     for k, v in (extra or {}).items():
         out[k] = np.asarray(v)
-    path = os.path.join(OUT, name + ".npz")
+    path = os.path.join(out_dir or OUT, name + ".npz")
     np.savez_compressed(path, **out)
-    print("%-28s N=%-3d A=%-2d steps=%-3d  %7.1f KB" % (
-        name, N, A, len(steps), os.path.getsize(path) / 1024))
+    if not quiet:
+        print("%-28s N=%-3d A=%-2d steps=%-3d  %7.1f KB" % (
+            name, N, A, len(steps), os.path.getsize(path) / 1024))
+    return path
 
 
 def run_driver_case(name, cfg, init, n_prefill, T, enable_channel, global_reward_avg, ia_averaging,
@@ -507,6 +555,333 @@ def main_driver():
                     rand_init(rng, 16, 600, True), n_prefill=8, T=80, enable_channel=True,
                     global_reward_avg=True, ia_averaging=True, episode_interval=25, seed=73,
                     ia_penalty_enable=True, ia_penalty_threshold=2)
+    # d3: the headline size (64 vehicles / 32 resources) with `enable_channel`: 25 prefill slots of my_step_ch, two
+    # episode ends; no information-age term in the rewards, so that the loop also replays without arrival stamps
+    rng = np.random.default_rng(74)
+    run_driver_case("d3_driver_ch_c2", big_cfg(64, 32, 2000, mobility_vary=True, reward_design=3),
+                    rand_init(rng, 64, 2000, True), n_prefill=25, T=52, enable_channel=True,
+                    global_reward_avg=True, ia_averaging=False, episode_interval=25, seed=75,
+                    ia_penalty_enable=True, ia_penalty_threshold=2)
+    # d4: 100 vehicles (step_wide), information-age averaging and the stuck-action penalty
+    rng = np.random.default_rng(76)
+    run_driver_case("d4_driver_ch_n100", big_cfg(100, 10, 2500, mobility_vary=True, reward_design=2,
+                                                 communication_range=200),
+                    rand_init(rng, 100, 2500, True), n_prefill=6, T=32, enable_channel=True,
+                    global_reward_avg=False, ia_averaging=True, episode_interval=10, seed=77,
+                    ia_penalty_enable=True, ia_penalty_threshold=1)
+
+
+
+def lanes(rng, N):
+    # off-lane vehicles: y in {0, 1, 2} across the highway's height (network.py:31, 104 draws only 0)
+    return rng.integers(0, 3, size=N).astype(np.float64)
+
+
+def sparse_case(name, N, A, seed, T, record_every=1, state=None, y=False, **kw):
+    """A highway that breaks apart and re-merges: about one vehicle per communication range, speeds spread by a
+    velocity update every 10 slots (network.py:208-223), the first vehicles wrapping at the end of the highway
+    (network.py:203) while clusters form, split and merge."""
+    rng = np.random.default_rng(seed)
+    Rc = 40
+    L = N * Rc
+    cfg = big_cfg(N, A, L, mobility_vary=True, communication_range=Rc, state=state, **kw)
+    x0, y0, v0 = rand_init(rng, N, L, True)
+    x0[: max(2, N // 8)] = L - 1 - rng.integers(0, 60, size=max(2, N // 8))     # these wrap within the first slots
+    if y:
+        y0 = lanes(rng, N)
+    steps = rand_steps(rng, "step", T, N, A, sticky=0.3)
+    vu = {si: rng.integers(1, 4, size=N) for si in range(0, T - 1, 10)}
+    run_case(name, cfg, (x0, y0, v0), steps, vel_updates=vu, table_every=T // 3, record_every=record_every)
+
+
+RICH = dict(add_reward=True, add_index=True, add_velocity=True, add_position=True, add_channel_obs=True)
+
+
+def main_curated():
+    """g10+: the cells tests/test_fixture_coverage.py counts, chosen by coverage (65 to 256 vehicles in every step
+    kind and reward design, sparse highways, off-lane vehicles, > 64 resources, > 256 vehicles, saturated table
+    ages, the secondary observation modes, odd histograms, static topology, slot numbers that jump)."""
+    # ---- 65 to 256 vehicles, my_step_ch, reward designs 2 / 3 / 4, >= 20 slots ----
+    rng = np.random.default_rng(1001)
+    run_case("g10_ch_rd2_n96", big_cfg(96, 12, 2400, reward_design=2), rand_init(rng, 96, 2400, False),
+             rand_steps(rng, "ch", 22, 96, 12, sticky=0.5), full_tables=False)
+    rng = np.random.default_rng(1002)
+    run_case("g10_ch_rd3_n130_rich", big_cfg(130, 6, 5200, reward_design=3, communication_range=120,
+                                              enable_fingerprint=True, state=RICH),
+             rand_init(rng, 130, 5200, False), rand_steps(rng, "ch", 20, 130, 6, sticky=0.6), full_tables=False,
+             episode_eps=[(t // 7, 0.99 ** t) for t in range(20)])
+    rng = np.random.default_rng(1003)
+    run_case("g10_ch_rd4_n256", big_cfg(256, 20, 6000, reward_design=4), rand_init(rng, 256, 6000, False),
+             rand_steps(rng, "ch", 20, 256, 20, sticky=0.4), full_tables=False)
+    # ---- my_step_design ----
+    rng = np.random.default_rng(1004)
+    run_case("g10_design_n150", big_cfg(150, 9, 3000, communication_range=150), rand_init(rng, 150, 3000, False),
+             rand_steps(rng, "design", 8, 150, 9), full_tables=False)
+    # ---- my_step, reward designs 1 / 3 / 4 / 5 ----
+    for rd, N, A, seed in ((1, 65, 4, 1011), (3, 128, 6, 1013), (4, 255, 5, 1014), (5, 256, 7, 1015)):
+        rng = np.random.default_rng(seed)
+        run_case("g10_step_rd%d_n%d" % (rd, N), big_cfg(N, A, 12 * N, reward_design=rd, communication_range=200),
+                 rand_init(rng, N, 12 * N, False), rand_steps(rng, "step", 6, N, A), full_tables=False)
+    # ---- rich State flags beyond 64 vehicles: State.type 1 + "real" (every receiver hears every transmitter, or
+    #      test_env.py:230-232 passes tx_id None on, SURVEY Q9), and type 2 (g10_ch_rd3_n130_rich above) ----
+    rng = np.random.default_rng(1020)
+    run_case("g10_rich_type1_n70", big_cfg(70, 5, 600, reward_design=1, communication_range=700,
+                                           enable_fingerprint=True, state=dict(RICH, type=1, action_index="real")),
+             rand_init(rng, 70, 600, False), rand_steps(rng, "step", 8, 70, 5, sticky=0.5), full_tables=False,
+             episode_eps=[(t // 3, 0.9 ** t) for t in range(8)])
+
+    # ---- sparse highways that split and re-merge, velocity updates, wrap-around, >= 150 slots ----
+    sparse_case("g11_sparse_n48", 48, 3, 1101, 150)
+    sparse_case("g11_sparse_n100", 100, 2, 1102, 150, record_every=10)
+    sparse_case("g11_sparse_n200", 200, 2, 1103, 150, record_every=25, state=dict(num_bins=8))
+
+    # ---- table ages past 255 (the device's age byte saturates): my_step_ch so that the information age counts,
+    #      checkpoints at slots 270 and 299, readouts at every slot in between ----
+    rng = np.random.default_rng(1201)
+    run_case("g12_age_past_255", big_cfg(12, 3, 3000, communication_range=60, reward_design=3),
+             rand_init(rng, 12, 3000, False), rand_steps(rng, "ch", 300, 12, 3), table_every=90)
+
+    # ---- off-lane vehicles, with bin_range != 500 and odd bin counts ----
+    rng = np.random.default_rng(1301)
+    x0, _, v0 = rand_init(rng, 40, 900, False)
+    run_case("g13_offlane_n40", big_cfg(40, 5, 900, communication_range=90, bin_range=123.456,
+                                        state=dict(num_bins=7, add_channel_obs=True)),
+             (x0, lanes(rng, 40), v0), rand_steps(rng, "step", 30, 40, 5), table_every=29)
+    rng = np.random.default_rng(1302)
+    x0, _, v0 = rand_init(rng, 90, 1500, False)
+    run_case("g13_offlane_n90", big_cfg(90, 4, 1500, communication_range=120, bin_range=250,
+                                        state=dict(num_bins=33, add_position=True)),
+             (x0, lanes(rng, 90), v0), rand_steps(rng, "step", 12, 90, 4) + rand_steps(rng, "ch", 6, 90, 4),
+             full_tables=False)
+
+    # ---- more than 64 resources (the general kernel) ----
+    rng = np.random.default_rng(1401)
+    run_case("g14_a80_step", big_cfg(20, 80, 700), rand_init(rng, 20, 700, False),
+             rand_steps(rng, "step", 10, 20, 80, sticky=0.5), table_every=9)
+    rng = np.random.default_rng(1402)
+    run_case("g14_a100_ch", big_cfg(30, 100, 900, reward_design=2, communication_range=200),
+             rand_init(rng, 30, 900, False), rand_steps(rng, "ch", 8, 30, 100, sticky=0.5), full_tables=False)
+
+    # ---- more than 256 vehicles (csrc/step_large.hpp): 300 and 512, all three step kinds ----
+    rng = np.random.default_rng(1501)
+    run_case("g15_n300_step_design", big_cfg(300, 8, 6000, reward_design=5), rand_init(rng, 300, 6000, False),
+             rand_steps(rng, "step", 3, 300, 8) + rand_steps(rng, "design", 2, 300, 8), full_tables=False)
+    rng = np.random.default_rng(1502)
+    run_case("g15_n512_ch", big_cfg(512, 40, 9000, reward_design=3), rand_init(rng, 512, 9000, False),
+             rand_steps(rng, "ch", 3, 512, 40), full_tables=False)
+
+    # ---- the secondary observation modes at 64 / 80 vehicles ----
+    rng = np.random.default_rng(1601)
+    run_case("g16_posdist_n64", big_cfg(64, 4, 1600, state=dict(add_positional_dist=True)),
+             rand_init(rng, 64, 1600, False), rand_steps(rng, "step", 5, 64, 4), full_tables=False)
+    rng = np.random.default_rng(1602)
+    run_case("g16_type1hist_n80", big_cfg(80, 6, 1600, mobility_vary=True,
+                                          state=dict(add_positional_dist_type=1, num_bins=12)),
+             rand_init(rng, 80, 1600, True), rand_steps(rng, "step", 8, 80, 6),
+             vel_updates={3: rng.integers(1, 4, size=80)}, full_tables=False)
+
+    # ---- proportional_fair: sticky actions, so that the counters pass pf_threshold (test_env.py:215-222) ----
+    rng = np.random.default_rng(1701)
+    run_case("g17_pf_n32", big_cfg(32, 4, 800, proportional_fair=True), rand_init(rng, 32, 800, False),
+             rand_steps(rng, "step", 36, 32, 4, sticky=0.97), table_every=35)
+
+    # ---- static topology (mobility False, enable_design_topology True: make_static_env) ----
+    rng = np.random.default_rng(1801)
+    run_case("g18_static_n32", big_cfg(32, 5, 900, mobility=False, enable_design_topology=True,
+                                       communication_range=150),
+             rand_init(rng, 32, 900, False),
+             rand_steps(rng, "design", 5, 32, 5) + rand_steps(rng, "step", 5, 32, 5) + rand_steps(rng, "ch", 5, 32, 5),
+             table_every=14)
+
+    # ---- congestion_test weights beyond the toy (network.py:284-290: m == norm) ----
+    rng = np.random.default_rng(1901)
+    run_case("g19_toyweights_n9", cfg_with(num_users=9, num_channels=5, highway_length=300, reward_design=1),
+             rand_init(rng, 9, 300, False), rand_steps(rng, "step", 20, 9, 5), table_every=19)
+
+    # ---- trace replay at 70 vehicles ----
+    rng = np.random.default_rng(2001)
+    N, A, L = 70, 4, 1400
+    tr = np.sort(rng.uniform(0, L, size=(5, N)), axis=1) + rng.normal(0, 3, size=(5, N))
+    run_case("g20_trace_n70", big_cfg(N, A, L, communication_range=140), rand_init(rng, N, L, False),
+             rand_steps(rng, "step", 4, N, A) + [("step", rng.integers(0, A, size=N), t) for t in (4, 9, 17, 2)]
+             + rand_steps(rng, "ch", 3, N, A), trace=tr, trace_after=1, full_tables=False)
+
+    # ---- State.piggybacking with 16 resources (A * A = 256 observation columns) ----
+    rng = np.random.default_rng(2101)
+    run_case("g21_piggyback_a16", big_cfg(6, 16, 200, communication_range=300,
+                                          state=dict(piggybacking=True, add_channel_obs=True)),
+             rand_init(rng, 6, 200, False), rand_steps(rng, "step", 10, 6, 16, sticky=0.4), table_every=9)
+
+    # ---- slot numbers: a start beyond 10^6 and a sequence that jumps forwards and back (the information age of
+    #      a slot before the last arrival is a negative list index, network.py:571-573) ----
+    rng = np.random.default_rng(2201)
+    ts = 1_000_000 + np.array([0, 1, 2, 3, 10, 11, 5, 6, 40, 41, 42, 20, 21, 22, 23, 24])
+    run_case("g22_tjump_n20", big_cfg(20, 4, 500, reward_design=2, communication_range=150),
+             rand_init(rng, 20, 500, False),
+             [("ch", rng.integers(0, 4, size=20), int(t)) for t in ts], table_every=15)
+
+
+# ---- the seeded differential sweep (`fuzz`) ------------------------------------------------
+
+FUZZ_BUDGET = 2.5e7          # dictionary operations of the reference per case: ~10 s of CPU
+
+
+def draw_ref_case(i):
+    """Case i of the sweep: a configuration both the reference and EnvConfig.validate() accept, its topology,
+    its steps.  Combinations the reference cannot run are remapped; each remap names the reference line."""
+    rng = np.random.default_rng(50000 + i)
+    N = int(rng.choice([63, 64, 65, 128, 255, 256, 257]) if rng.random() < 0.4 else
+            rng.choice([rng.integers(1, 9), rng.integers(9, 65), rng.integers(65, 257), rng.integers(257, 601)]))
+    A = int(rng.choice([rng.integers(1, 9), rng.integers(9, 65), rng.integers(65, 131)], p=[0.4, 0.4, 0.2]))
+    K = int(rng.integers(1, 65))
+    kind = str(rng.choice(["step", "step", "ch", "design", "mixed"]))
+    rd = int(rng.choice([2, 3, 4])) if kind in ("ch", "mixed") else int(rng.integers(1, 6))
+    #   (my_step_ch with reward design 1 or 5 only prints "This is not defined", test_env.py:419-420, 428-429)
+    L = int(rng.choice([4, 10, 25, 40]) * N + rng.integers(20, 200))
+    Rc = float(rng.choice([L + 10.0, 250.0, 120.0, 3.0 * L / N, 1.2 * L / N]))
+    st = dict(type=int(rng.choice([1, 2])), add_reward=bool(rng.random() < 0.3), add_action=bool(rng.random() < 0.8),
+              add_index=bool(rng.random() < 0.3), add_velocity=bool(rng.random() < 0.3),
+              action_index=str(rng.choice(["binary", "real"])), piggybacking=False,
+              add_position=bool(rng.random() < 0.3), add_positional_dist=bool(rng.random() < 0.2),
+              add_positional_dist_piggy=bool(rng.random() < 0.8), add_positional_dist_type=int(rng.choice([1, 2, 2])),
+              add_channel_obs=bool(rng.random() < 0.4), num_bins=K)
+    mobility = bool(rng.random() < 0.85)
+    offlane = bool(rng.random() < 0.25)
+    if st["type"] == 1 and st["add_positional_dist_piggy"] and Rc * Rc <= (L * L + 4.0):
+        # test_env.py:230-232 hands tx_id None to received_update when no transmitter is in range
+        # (network.py:583: self.vehicles[None], TypeError) - SURVEY Q9
+        st["type"] = 2
+    if kind == "step" and rng.random() < 0.1 and A <= 20:
+        # State.piggybacking: type 2 with add_channel_obs (EnvConfig.validate: no fixed state vector otherwise),
+        # my_step only (my_step_ch / my_step_design return A columns where get_state_space counts A * A,
+        # test_env.py:71-72, 316, 443), and every receiver in range of a transmitter (prev_obs[None], test_env.py:243)
+        st.update(piggybacking=True, type=2, add_channel_obs=True)
+        Rc = L + 10.0
+    if not mobility and st["add_positional_dist"]:
+        st["add_positional_dist"] = False      # network.py:341-344: dist_sign reads pos_of_nodes, which is empty
+    if st["add_positional_dist"] and N < 3:
+        st["add_positional_dist"] = False      # network.py:429: two vehicles on one spot divide by max_dist 0
+    vary = bool(rng.random() < 0.4)
+    cfg = cfg_with(num_users=N, num_channels=A, highway_length=L,
+                   reward_design=rd, mobility=mobility, enable_design_topology=not mobility, mobility_vary=vary,
+                   enable_fingerprint=bool(rng.random() < 0.3), proportional_fair=bool(rng.random() < 0.2),
+                   congestion_test=bool(rng.random() < 0.2), communication_range=Rc,
+                   bin_range=float(rng.choice([50.0, 123.456, 250.0, 500.0, 1000.0])), state=st)
+    # the reference's cost per slot: tables N * N, received_update N * N * min(A, N); my_step_ch adds N^3 / A
+    per_slot = float(N) * N * (4 + min(A, N)) + (float(N) ** 3 / A if kind in ("ch", "mixed") else 0.0)
+    T = int(max(2, min(40, FUZZ_BUDGET // per_slot)))
+    x0, y0, v0 = rand_init(rng, N, L, vary)
+    if offlane:
+        y0 = lanes(rng, N)
+    sticky = float(rng.choice([0.0, 0.5, 0.9]))
+    acts = rng.integers(0, A, size=N)
+    t = int(rng.choice([0, 0, 7, 10 ** 6]))
+    steps = []
+    for si in range(T):
+        acts = np.where(rng.random(N) < sticky, acts, rng.integers(0, A, size=N))
+        mode = kind if kind != "mixed" else str(rng.choice(["step", "ch", "design"]))
+        steps.append((mode, acts.copy(), t))
+        # mostly t + 1; now and then a jump forwards or back (back by < 100: network.py:571-573 indexes a list
+        # of 100 with t - last_arrival)
+        t = max(0, t + (1 if rng.random() < 0.85 else int(rng.integers(-30, 60))))
+    vu = {si: rng.integers(1, 4, size=N) for si in range(4, T, 5)} if vary else None
+    trace = trace_after = None
+    if mobility and rng.random() < 0.1:
+        trace = np.sort(rng.uniform(0, L, size=(int(rng.integers(1, 6)), N)), axis=1) + rng.normal(0, 3, size=(1, N))
+        trace_after = int(rng.integers(0, T))
+    eps = [(si // 3, 0.97 ** si) for si in range(T)]
+    return dict(cfg=cfg, init=(x0, y0, v0), steps=steps, vel_updates=vu, trace=trace, trace_after=trace_after,
+                episode_eps=eps, kind=kind, offlane=offlane)
+
+
+def fuzz_one(i):
+    """One sweep case -> its report row (a dict)."""
+    import traceback
+    from tests.golden_util import Golden
+    from tests.test_oracle_golden import compare_with_reference
+    c = draw_ref_case(i)
+    cfg, st = c["cfg"], c["cfg"]["State"]
+    flags = [k[4:] for k in ("add_reward", "add_index", "add_velocity", "add_position", "add_positional_dist",
+                             "add_channel_obs") if st[k]]
+    flags += ["type%d" % st["type"], st["action_index"] if st["add_action"] else "noaction",
+              ("hist%d" % st["add_positional_dist_type"]) if st["add_positional_dist_piggy"] else "notables"]
+    flags += [k for k in ("mobility_vary", "enable_fingerprint", "proportional_fair", "congestion_test") if cfg[k]]
+    flags += (["piggybacking"] if st["piggybacking"] else []) + (["static"] if not cfg["mobility"] else []) \
+        + (["offlane"] if c["offlane"] else []) + (["trace"] if c["trace"] is not None else [])
+    row = dict(seed=i, N=cfg["num_users"], A=cfg["num_channels"], K=st["num_bins"], T=len(c["steps"]), mode=c["kind"],
+               rd=cfg["reward_design"], Rc=cfg["communication_range"], L=cfg["highway_length"],
+               bin_range=cfg["bin_range"], t0=c["steps"][0][2], flags=" ".join(flags))
+    t0 = time.time()
+    with tempfile.TemporaryDirectory() as tmp:
+        try:
+            path = run_case("fuzz%d" % i, cfg, c["init"], c["steps"], vel_updates=c["vel_updates"], trace=c["trace"],
+                            trace_after=c["trace_after"], episode_eps=c["episode_eps"],
+                            table_every=max(1, len(c["steps"]) - 1), out_dir=tmp, quiet=True)
+        except Exception as ex:                  # a finding, written down with the reference's own line
+            tb = traceback.extract_tb(ex.__traceback__)
+            where = [f for f in tb if f.filename.startswith(REF)]
+            row["verdict"] = "REFERENCE RAISED %s at %s" % (type(ex).__name__, "%s:%d" % (
+                os.path.basename(where[-1].filename), where[-1].lineno) if where else "generator")
+            row["seconds"] = time.time() - t0
+            return row
+        row["ref_s"] = time.time() - t0
+        try:
+            compare_with_reference(Golden("fuzz%d" % i, path=path))
+            row["verdict"] = "ok"
+        except AssertionError as ex:
+            a = ex.args[0] if ex.args else ("?", -1)
+            row["verdict"] = "MISMATCH %s %s" % (a[0], a[1]) if isinstance(a, tuple) else "MISMATCH %s" % (a,)
+    # what the device build says to this configuration without a GPU: diral_env_validate's documented refusals
+    try:
+        import ctypes
+        from diral_amd import _lib
+        from diral_amd.config import EnvConfig
+        rc = _lib.load().diral_env_validate(ctypes.byref(EnvConfig.from_dict(cfg).to_c()))
+        row["device"] = {0: "ok", -3: "DIRAL_ERR_UNSUPPORTED"}.get(rc, "status %d" % rc)
+    except Exception as ex:
+        row["device"] = "validate() raised %s" % type(ex).__name__
+    row["seconds"] = time.time() - t0
+    return row
+
+
+def main_fuzz(n=320, first=0, procs=None):
+    import multiprocessing
+    t0 = time.time()
+    with multiprocessing.Pool(procs or min(8, os.cpu_count() or 1)) as pool:
+        rows = pool.map(fuzz_one, range(first, first + n), chunksize=1)
+    bad = [r for r in rows if r["verdict"].startswith("MISMATCH")]
+    raised = [r for r in rows if r["verdict"].startswith("REFERENCE")]
+    refused = [r for r in rows if r.get("device", "ok") != "ok"]
+    cols = ("seed", "N", "A", "K", "T", "mode", "rd", "L", "Rc", "bin_range", "t0", "flags", "seconds", "device",
+            "verdict")
+    lines = ["# Differential sweep: the reference against the CPU oracle", "",
+             "Written by `python tests/golden/gen_golden.py fuzz %d %d`; do not edit by hand." % (n, first), "",
+             "Each row is `draw_ref_case(seed)`: recorded from the reference with `run_case`, replayed through",
+             "`Oracle(sq_mode=SQ_POW)` and compared like `test_oracle_reproduces_reference_bit_exact` (every output",
+             "of every slot bit for bit, the table planes by hash at every slot and in full at the first and last).",
+             "`device` is what `diral_env_validate` answers to the configuration (no GPU takes part in the sweep).",
+             "The `seconds` column is the only one that changes from run to run.", "",
+             "## Summary", "",
+             "- seeds %d to %d: %d cases, %d ok, %d MISMATCH, %d REFERENCE RAISED (%.1f %%; the cap is 5 %%)" % (
+                 first, first + n - 1, n, n - len(bad) - len(raised), len(bad), len(raised), 100.0 * len(raised) / n),
+             "- sizes: N %d to %d (%d cases beyond 64 vehicles, %d beyond 256), A %d to %d (%d beyond 64 resources)" % (
+                 min(r["N"] for r in rows), max(r["N"] for r in rows), sum(r["N"] > 64 for r in rows),
+                 sum(r["N"] > 256 for r in rows), min(r["A"] for r in rows), max(r["A"] for r in rows),
+                 sum(r["A"] > 64 for r in rows)),
+             "- step kinds: " + ", ".join("%s %d" % (k, sum(r["mode"] == k for r in rows))
+                                          for k in ("step", "ch", "design", "mixed")),
+             "- configurations the device build refuses (documented `DIRAL_ERR_UNSUPPORTED`): " +
+             (", ".join("seed %d (N=%d A=%d K=%d %s)" % (r["seed"], r["N"], r["A"], r["K"], r["device"])
+                        for r in refused) or "none"),
+             "- mismatches: " + (", ".join("seed %d: %s" % (r["seed"], r["verdict"]) for r in bad) or "none"),
+             "- reference exceptions: " + (", ".join("seed %d: %s" % (r["seed"], r["verdict"]) for r in raised) or "none"),
+             "", "## Cases", "", "| " + " | ".join(cols) + " |", "|" + "---|" * len(cols)]
+    for r in rows:
+        lines.append("| " + " | ".join(("%.1f" % r[c]) if c == "seconds" else ("%g" % r[c]) if isinstance(r.get(c), float)
+                                       else str(r.get(c, "-")) for c in cols) + " |")
+    with open(os.path.join(OUT, "FUZZ_SWEEP.md"), "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("%d cases in %.0f s: %d mismatches, %d reference exceptions" % (n, time.time() - t0, len(bad), len(raised)))
 
 
 def run_sps_case(name, n_agents, A, T, threshold, seed, level_lo, level_hi, tie_step, keep_lo=0.0):
@@ -612,8 +987,13 @@ if __name__ == "__main__":
         main_trace()
     elif len(sys.argv) > 1 and sys.argv[1] == "piggyback":
         main_piggyback()
+    elif len(sys.argv) > 1 and sys.argv[1] == "curated":
+        main_curated()
+    elif len(sys.argv) > 1 and sys.argv[1] == "fuzz":
+        main_fuzz(*[int(a) for a in sys.argv[2:4]])
     else:
         main()
+        main_curated()
         main_piggyback()
         main_trace()
         main_driver()

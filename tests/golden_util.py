@@ -5,6 +5,7 @@ draws) and the reference's outputs for the same (rews, chobs, state, positions,
 table planes).  tests/golden/gen_golden.py recorded them from the reference.
 """
 import glob
+import hashlib
 import json
 import os
 
@@ -22,10 +23,25 @@ def golden_names(prefix="g"):
                   for p in glob.glob(os.path.join(GOLDEN_DIR, prefix + "*.npz")))
 
 
+OUT_KEYS = ("rews", "chobs", "state", "pos_x", "vel", "ia")     # the per-slot outputs run_case records
+
+
+def out_sha(a):
+    """The per-slot hash of a thinned fixture's outputs (gen_golden.py `record_every`): sha256 of the array's bytes,
+    float arrays with -0.0 folded onto 0.0 (the comparison of the full arrays takes the two as equal too)."""
+    a = np.ascontiguousarray(a)
+    if a.dtype.kind == "f":
+        a = a.astype(np.float64) + 0.0
+    else:
+        a = a.astype(np.int64)
+    return hashlib.sha256(a.tobytes()).hexdigest()
+
+
 class Golden:
-    def __init__(self, name):
+    def __init__(self, name, path=None):
         self.name = name
-        self.d = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
+        self.d = np.load(path or os.path.join(GOLDEN_DIR, name + ".npz"))
+        self._cache = {}
         self.cfg_dict = json.loads(str(self.d["cfg"]))
         self.cfg = EnvConfig.from_dict(self.cfg_dict, track_arrival=True)
         self.N = self.cfg.num_users
@@ -38,8 +54,24 @@ class Golden:
         self.trace = self.d["trace"] if "trace" in self.d and self.d["trace"].shape[0] else None
         self.trace_after = int(self.d["trace_after"]) if "trace_after" in self.d else -1
 
+        # thinned fixtures (run_case(record_every=...)): the full per-slot outputs exist at the slots `rec_step`
+        # lists, their hashes (`out_sha`, one column per OUT_KEYS) at every slot
+        self.kept = {int(s): j for j, s in enumerate(self.d["rec_step"])} if "rec_step" in self.d.files else None
+
     def __getitem__(self, k):
-        return self.d[k]
+        if k not in self._cache:                  # (an .npz member is inflated anew on every access)
+            self._cache[k] = self.d[k]
+        return self._cache[k]
+
+    def out(self, key, i):
+        """The recorded output `key` of slot i; None where a thinned fixture holds only its hash."""
+        if self.kept is None:
+            return self[key][i]
+        j = self.kept.get(i)
+        return None if j is None else self[key][j]
+
+    def out_sha(self, key, i):
+        return str(self["out_sha"][i][OUT_KEYS.index(key)])
 
     def steps(self):
         for i in range(self.T):

@@ -21,7 +21,7 @@ def load(name):
     return d, cfg, json.loads(str(d["opts"]))
 
 
-def run(env, d, opts, exact, fused=False):
+def run(env, d, opts, exact, fused=False, want_ia=True):
     loop = DriverLoop(env, fused=fused, enable_channel=opts["enable_channel"], global_reward_avg=opts["global_reward_avg"],
                       ia_averaging=opts["ia_averaging"], ia_penalty_enable=opts["ia_penalty_enable"],
                       ia_penalty_threshold=opts["ia_penalty_threshold"], ia_penalty_value=opts["ia_penalty_value"],
@@ -45,14 +45,15 @@ def run(env, d, opts, exact, fused=False):
         same(st[0], d["pre_states"][i], ("prefill", i))
     for t in range(opts["T"]):
         assert loop.episode == (0 if t == 0 else int(d["episode"][t - 1]))
-        out = loop.slot(d["actions"][t], t, want_ia=True)
+        out = loop.slot(d["actions"][t], t, want_ia=want_ia)
         same(out["next_state"][0], d["states"][t], ("state", t))
         same(out["raw_reward"][0], d["raw_reward"][t], ("raw reward", t))
         same(out["reward"][0], d["shaped_reward"][t], ("shaped reward", t))
         same(out["sum_r"][0], d["sum_r"][t], ("sum_r", t))
         same(out["collision"][0], d["collision"][t], ("collision", t))
-        assert np.array_equal(np_(out["ia"])[0], d["ia"][t]), ("ia", t)
-        assert int(np_(out["ia_sum"])[0]) == int(d["ia_sum"][t])
+        if want_ia:
+            assert np.array_equal(np_(out["ia"])[0], d["ia"][t]), ("ia", t)
+            assert int(np_(out["ia_sum"])[0]) == int(d["ia_sum"][t])
         if opts["ia_averaging"]:
             assert int(np_(out["ia_penalty"])[0]) == int(d["ia_pen"][t])
         assert bool(out["episode_end"]) == bool(d["episode_end"][t])
@@ -80,6 +81,16 @@ def test_driver_loop_reproduces_reference_sequence_gpu(name):
     run(VecV2VEnv(cfg, batch=1, out_dtype=torch.float64), d, opts, exact=False)
     if not cfg.State.add_reward:       # one fused launch per slot gives the same sequence
         run(VecV2VEnv(cfg, batch=1, out_dtype=torch.float64), d, opts, exact=False, fused=True)
+    if name == "d3_driver_ch_c2":
+        # the recorded closed loop once more on the handle the K-slot my_step_ch launches are built for (no arrival
+        # stamps, so no information age: d3's rewards carry none): DriverLoop(enable_channel=True, fused=True) is the
+        # one-slot my_step_ch launch those K-slot launches are tested against - here against the reference
+        from diral_amd.config import KERNEL_CH, KERNEL_FAST64
+        assert opts["enable_channel"] and not opts["ia_averaging"]
+        for fused in (False, True):
+            env = VecV2VEnv(cfg.replace(track_arrival=False), batch=1, out_dtype=torch.float64)
+            run(env, d, opts, exact=False, fused=fused, want_ia=False)
+            assert (env.last_kernel() & 15) == KERNEL_FAST64 and env.last_kernel() & KERNEL_CH
 
 
 def test_ia_penalty_helper_matches_utils_misc():

@@ -1,0 +1,94 @@
+"""The reference fixtures from g10 on as ONE env of a batch of different envs.
+
+tests/test_gpu_parity.py::test_golden_replay_on_gpu replays a fixture on identical replicas, so an indexing slip
+across the envs of a batch cannot show against the reference.  Here the fixture is env 2 of 5; the other four are
+different seeded topologies and action streams of the same configuration.  Env 2 is held to the reference's record
+under the rules of test_golden_replay_on_gpu, all five to the oracle (IEEE squares, bit for bit).  Fixtures that the
+specialised kernels (step_fast64 / step_wide) or the three-launch form (step_large.hpp) serve."""
+import numpy as np
+import pytest
+
+import tests.test_gpu_parity as tp
+from diral_amd.config import KERNEL_FAST64, KERNEL_LARGE, KERNEL_WIDE
+from tests.golden_util import Golden, golden_names
+
+pytestmark = pytest.mark.gpu
+
+B, REF = 5, 2
+
+
+def _names():
+    out = []
+    for n in golden_names():
+        if int(n[1:n.index("_")]) < 10:
+            continue
+        g = Golden(n)
+        c = g.cfg
+        # (the general kernel serves more than 64 resources, and vehicles off the y = 0 lane at 65 to 256 vehicles)
+        if c.num_users > 256 or (c.num_channels <= 64 and (c.num_users <= 64 or not np.any(g["y0"] != 0))):
+            out.append(n)
+    return out
+
+
+@pytest.mark.parametrize("name", _names())
+def test_reference_fixture_as_one_env_of_a_mixed_batch(name):
+    from oracle.oracle import Oracle, SQ_IEEE
+    g = Golden(name)
+    cfg, N, A = g.cfg, g.N, g.A
+    rng = np.random.default_rng(sum(map(ord, name)))
+    L = int(cfg.highway_length)
+    x0 = rng.integers(0, L, size=(B, N)).astype(np.float64)
+    y0 = rng.integers(0, 3, size=(B, N)).astype(np.float64) if np.any(g["y0"] != 0) else np.zeros((B, N))
+    v0 = np.full((B, N), 1.7) if cfg.mobility_vary else rng.uniform(1.1, 2.7, size=(B, N))
+    x0[REF], y0[REF], v0[REF] = g["x0"], g["y0"], g["v0"]
+    env = tp.make_env(cfg, B)
+    env.reset_topology(x0, y0, v0)
+    orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=5)
+    orc.reset(x0, y0, v0)
+    ck = g.table_checkpoints()
+    fam = KERNEL_LARGE if N > 256 else (KERNEL_FAST64 if N <= 64 else KERNEL_WIDE)
+    acts = rng.integers(0, A, size=(B, N))
+    for i, mode, ref_acts, t, (ep, eps) in g.steps():
+        acts = np.where(rng.random((B, N)) < 0.5, acts, rng.integers(0, A, size=(B, N))).astype(np.int32)
+        acts[REF] = ref_acts
+        obs, rew, chobs, _ = tp.gpu_step(env, mode, acts, t, ep, eps)
+        assert (env.last_kernel() & 15) == fam, env.last_kernel()
+        o_rew, o_chobs = orc.step(mode, acts, t)
+        o_state = orc.obtain_state(acts, o_chobs, o_rew, ep, eps)
+        if tp.uses_exp(cfg, mode):
+            assert tp.exp_close(rew, o_rew), (name, i)
+        else:
+            assert np.array_equal(rew, o_rew), (name, i, np.argwhere(rew != o_rew)[:5])
+        assert np.array_equal(chobs, o_chobs), (name, i)
+        if cfg.State.add_reward and tp.uses_exp(cfg, mode):
+            assert tp.exp_close(obs, o_state), (name, i)
+        else:
+            assert np.array_equal(obs, o_state), (name, i, np.argwhere(obs != o_state)[:5])
+        tp.assert_slot_matches_reference(g, i, mode, rew[REF], chobs[REF], obs[REF])
+        if i in g.vel_updates:
+            draws = rng.integers(1, 4, size=(B, N)).astype(np.uint8)
+            draws[REF] = g.vel_updates[i]
+            env.update_velocity(draws)
+            orc.update_velocity(draws)
+        if g.trace is not None and i == g.trace_after:
+            env.load_saved_positions(g.trace)              # (one trace for the five envs; their tables still differ)
+            orc.set_trace(g.trace)
+        ia = env.info_age(t).cpu().numpy()
+        assert np.array_equal(ia, orc.info_age(t)), (name, i)
+        tables = i in ck or i == g.T - 1
+        st = {k: v.cpu().numpy() for k, v in env.export_state(tables=tables).items()}
+        oe = orc.export()
+        assert np.array_equal(st["pos_x"], oe["pos_x"]) and np.array_equal(st["vel"], oe["vel"]), (name, i)
+        tp.assert_moves_match_reference(g, i, st["pos_x"][REF], st["vel"][REF], ia[REF])
+        if tables:
+            assert np.array_equal(st["seq"], oe["seq"]), (name, i)
+            assert np.array_equal(st["age"], np.minimum(oe["age"], 255)), (name, i)
+            assert np.array_equal(st["x"], oe["x"]) and np.array_equal(st["y"], oe["y"]), (name, i)
+            assert np.array_equal(st["la"].astype(np.int64), oe["la"]), (name, i)
+        if i in ck:
+            j = ck[i]
+            assert np.array_equal(st["seq"][REF], g["tab_seq"][j])
+            assert np.array_equal(st["age"][REF], np.minimum(g["tab_age"][j], 255))
+            assert np.array_equal(st["x"][REF], g["tab_x"][j]) and np.array_equal(st["y"][REF], g["tab_y"][j])
+            assert np.array_equal(st["la"][REF], g["tab_la"][j])
+    env.check()

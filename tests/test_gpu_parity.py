@@ -15,7 +15,7 @@ import torch
 
 from diral_amd.config import (EnvConfig, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config,
                               c2_config)
-from tests.golden_util import Golden, golden_names, ulp_diff
+from tests.golden_util import Golden, golden_names, out_sha, ulp_diff
 
 pytestmark = pytest.mark.gpu
 
@@ -47,6 +47,40 @@ def exp_close(a, b):
     return bool(np.all(np.abs(np.asarray(a) - np.asarray(b)) <= EXP_ATOL))
 
 
+def assert_slot_matches_reference(g, i, mode, rew, chobs, obs):
+    """One env's outputs of slot i against what the reference recorded (tests/golden/*.npz): rewards exact (exp()
+    designs within EXP_ATOL), distances within DIST_ULP, the type-2 histogram bins exact.  A thinned fixture
+    (gen_golden.py `record_every`) holds the arrays at some slots and a hash at every slot: the hash is compared
+    wherever this bar is "exact", so a slot without arrays still pins its rewards."""
+    cfg, name = g.cfg, g.name
+    ref_rew, ref_chobs, ref_state = g.out("rews", i), g.out("chobs", i), g.out("state", i)
+    if not uses_exp(cfg, mode) and g.kept is not None:
+        assert out_sha(rew) == g.out_sha("rews", i), (name, i)
+    if ref_rew is None:
+        return
+    assert exp_close(rew, ref_rew) if uses_exp(cfg, mode) else np.array_equal(rew, ref_rew), (name, i)
+    assert ulp_diff(chobs, ref_chobs) <= DIST_ULP, (name, i)
+    assert ulp_diff(obs, ref_state) <= DIST_ULP or (cfg.State.add_reward and exp_close(obs, ref_state)), (name, i)
+    if cfg.State.add_positional_dist_piggy:
+        K = cfg.State.num_bins
+        off = (cfg.num_channels if cfg.State.action_index == "binary" else 1) if cfg.State.add_action else 0
+        off += cfg.chobs_width if cfg.State.add_channel_obs else 0
+        off += cfg.num_users - 1 if cfg.State.add_positional_dist else 0
+        if cfg.State.add_positional_dist_type == 2:
+            assert np.array_equal(obs[:, off:off + K], ref_state[:, off:off + K]), "histogram bins"
+
+
+def assert_moves_match_reference(g, i, pos_x, vel, ia):
+    """Positions, speeds and the information-age histogram after slot i: exact (by hash where a thinned fixture
+    dropped the arrays)."""
+    for key, got in (("pos_x", pos_x), ("vel", vel), ("ia", ia)):
+        ref = g.out(key, i)
+        if ref is None:
+            assert out_sha(got) == g.out_sha(key, i), (g.name, key, i)
+        else:
+            assert np.array_equal(got, ref), (g.name, key, i)
+
+
 @pytest.mark.parametrize("name", [n for n in golden_names() if n not in UNBUILT])
 def test_golden_replay_on_gpu(name):
     """Every reference fixture replayed through libdiral_env.so (B=3 replicas)."""
@@ -76,17 +110,7 @@ def test_golden_replay_on_gpu(name):
             else:
                 assert np.array_equal(obs[b], o_state[0]), (name, i, np.argwhere(obs[b] != o_state[0])[:5])
             # --- vs the reference fixture
-            ref_rew, ref_chobs, ref_state = g["rews"][i], g["chobs"][i], g["state"][i]
-            assert exp_close(rew[b], ref_rew) if uses_exp(cfg, mode) else np.array_equal(rew[b], ref_rew), (name, i)
-            assert ulp_diff(chobs[b], ref_chobs) <= DIST_ULP, (name, i)
-            assert ulp_diff(obs[b], ref_state) <= DIST_ULP or (cfg.State.add_reward and exp_close(obs[b], ref_state)), (name, i)
-            if cfg.State.add_positional_dist_piggy:
-                K = cfg.State.num_bins
-                off = (cfg.num_channels if cfg.State.action_index == "binary" else 1) if cfg.State.add_action else 0
-                off += cfg.chobs_width if cfg.State.add_channel_obs else 0
-                off += cfg.num_users - 1 if cfg.State.add_positional_dist else 0
-                if cfg.State.add_positional_dist_type == 2:
-                    assert np.array_equal(obs[b][:, off:off + K], ref_state[:, off:off + K]), "histogram bins"
+            assert_slot_matches_reference(g, i, mode, rew[b], chobs[b], obs[b])
             assert done[b] == ((t % cfg.episode_interval) == cfg.episode_interval - 1)
         if i in g.vel_updates:
             env.update_velocity(g.vel_updates[i])
@@ -98,9 +122,7 @@ def test_golden_replay_on_gpu(name):
         st = {k: v.cpu().numpy() for k, v in env.export_state().items()}
         oe = orc.export()
         for b in range(B):
-            assert np.array_equal(st["pos_x"][b], g["pos_x"][i]), (name, i)
-            assert np.array_equal(st["vel"][b], g["vel"][i]), (name, i)
-            assert np.array_equal(ia[b], g["ia"][i]), (name, i)
+            assert_moves_match_reference(g, i, st["pos_x"][b], st["vel"][b], ia[b])
             assert np.array_equal(st["seq"][b], oe["seq"][0]), (name, i)
             assert np.array_equal(st["age"][b], np.minimum(oe["age"][0], 255)), (name, i)
             assert np.array_equal(st["x"][b], oe["x"][0]), (name, i)
@@ -1277,11 +1299,16 @@ def test_reference_fixtures_replayed_on_the_specialised_kernels(name):
         torch.cuda.synchronize()
         obs, rew = obs.cpu().numpy(), rew.cpu().numpy()
         for b in range(B):
+            if g.out("rews", i) is None:                                # a thinned fixture: the hashes (exact outputs)
+                if not (uses_exp(cfg, mode) and mode != STEP_DESIGN):
+                    assert out_sha(rew[b]) == g.out_sha("rews", i), (name, i)
+                assert out_sha(obs[b]) == g.out_sha("state", i), (name, i)
+                continue
             if uses_exp(cfg, mode) and mode != STEP_DESIGN:
                 assert exp_close(rew[b], g["rews"][i]), (name, i)
             else:
-                assert np.array_equal(rew[b], g["rews"][i]), (name, i)
-            assert np.array_equal(obs[b], g["state"][i]), (name, i)     # one-hot + histogram: exact
+                assert np.array_equal(rew[b], g.out("rews", i)), (name, i)
+            assert np.array_equal(obs[b], g.out("state", i)), (name, i)     # one-hot + histogram: exact
         if i in g.vel_updates:
             env.update_velocity(g.vel_updates[i])
         if g.trace is not None and i == g.trace_after:
@@ -1289,8 +1316,7 @@ def test_reference_fixtures_replayed_on_the_specialised_kernels(name):
         ia = env.info_age(t).cpu().numpy()
         st = {k: v.cpu().numpy() for k, v in env.export_state().items()}
         for b in range(B):
-            assert np.array_equal(st["pos_x"][b], g["pos_x"][i]), (name, i)
-            assert np.array_equal(ia[b], g["ia"][i]), (name, i)
+            assert_moves_match_reference(g, i, st["pos_x"][b], st["vel"][b], ia[b])
             if i in ck:
                 j = ck[i]
                 assert np.array_equal(st["seq"][b], g["tab_seq"][j])

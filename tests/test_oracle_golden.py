@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from oracle.oracle import Oracle, SQ_IEEE, SQ_POW
-from tests.golden_util import Golden, golden_names, ulp_diff
+from tests.golden_util import Golden, golden_names, out_sha, ulp_diff
 
 
 def sha(a):
@@ -41,32 +41,45 @@ def replay(g, sq_mode, batch=1):
     return o, out
 
 
-@pytest.mark.parametrize("name", golden_names())
-def test_oracle_reproduces_reference_bit_exact(name):
-    g = Golden(name)
+def compare_with_reference(g):
+    """The oracle in its reference-faithful mode against one recorded fixture: every output of every slot bit for
+    bit (a thinned fixture: by its per-slot hashes where it dropped the arrays), the table planes by hash at every
+    slot and in full at the checkpoints.  AssertionError((key, slot)) on the first difference; also what
+    tests/golden/gen_golden.py `fuzz` runs on every drawn case."""
     o, out = replay(g, SQ_POW)
-    assert o.S == int(g["state_space"])
+    assert o.S == int(g["state_space"]), ("state_space", -1)
     ck = g.table_checkpoints()
     for i in range(g.T):
         for key in ("rews", "chobs", "state", "pos_x", "vel"):
             got = out[key][i][0]
-            ref = g[key][i]
+            ref = g.out(key, i)
+            if ref is None:
+                assert out_sha(got) == g.out_sha(key, i), (key, i)
+                continue
             assert got.shape == ref.shape, (key, i)
             assert np.array_equal(got.view(np.int64), ref.view(np.int64)) or \
-                np.array_equal(got, ref), "%s step %d differs (max ulp %d)" % (
-                    key, i, ulp_diff(got, ref))
-        assert np.array_equal(out["ia"][i][0], g["ia"][i]), ("ia", i)
+                np.array_equal(got, ref), (key, i, "max ulp %d" % ulp_diff(got, ref))
+        if g.kept is not None:                  # the hashes cover the kept slots as well
+            for key in ("rews", "chobs", "state", "pos_x", "vel"):
+                assert out_sha(out[key][i][0]) == g.out_sha(key, i), (key, i)
+            assert out_sha(out["ia"][i][0]) == g.out_sha("ia", i), ("ia", i)
+        if g.out("ia", i) is not None:
+            assert np.array_equal(out["ia"][i][0], g.out("ia", i)), ("ia", i)
         e = out["exp"][i]
         shas = [sha(e["seq"][0].astype(np.int64)), sha(e["age"][0].astype(np.int64)),
                 sha(e["x"][0]), sha(e["y"][0]), sha(e["la"][0])]
-        assert shas == list(g["table_sha"][i]), "table planes differ at step %d" % i
+        assert shas == list(g["table_sha"][i]), ("table_sha", i)
         if i in ck:
             j = ck[i]
-            assert np.array_equal(e["seq"][0], g["tab_seq"][j])
-            assert np.array_equal(e["age"][0], g["tab_age"][j])
-            assert np.array_equal(e["x"][0], g["tab_x"][j])
-            assert np.array_equal(e["y"][0], g["tab_y"][j])
-            assert np.array_equal(e["la"][0], g["tab_la"][j])
+            for k in ("seq", "age", "x", "y", "la"):
+                assert np.array_equal(e[k][0], g["tab_" + k][j]), ("tab_" + k, i)
+    return o
+
+
+@pytest.mark.parametrize("name", golden_names())
+def test_oracle_reproduces_reference_bit_exact(name):
+    g = Golden(name)
+    o = compare_with_reference(g)
     if g.cfg.State.piggybacking:
         # TestEnv.prev_obs after the last slot (test_env.py:260-261)
         assert np.array_equal(o.prev_obs()[0], g["prev_obs"])
@@ -190,14 +203,27 @@ def test_fixtures_carry_the_keys_the_generator_writes():
     sps_keys = {"A", "threshold", "tie_step", "init_prev", "init_counter", "codes", "draw_counter", "draw_keep",
                 "draw_choice", "actions", "counters", "prev_actions", "reselections"}
     names = sorted(os.path.basename(f)[:-4] for f in glob.glob(os.path.join(gdir, "*.npz")))
-    assert len([n for n in names if n[0] == "g"]) == 38 and len([n for n in names if n[0] == "s"]) == 7
+    assert len([n for n in names if n[0] == "g"]) == 65 and len([n for n in names if n[0] == "s"]) == 7
+    assert len([n for n in names if n[0] == "d"]) == 4
     for n in names:
         keys = set(np.load(os.path.join(gdir, n + ".npz")).files)
         if n[0] == "g":
             # State.piggybacking fixtures also hold TestEnv.prev_obs; the KeyError one the slot that raised
             more = {"prev_obs"} if "piggyback" in n else set()
             more |= {"keyerror_actions", "keyerror_t"} if n.endswith("keyerror") else set()
+            # a thinned fixture (run_case(record_every=...)): the slots whose outputs it keeps, and every slot's hashes
+            thinned = n in ("g11_sparse_n100", "g11_sparse_n200")
+            more |= {"rec_step", "out_sha"} if thinned else set()
             assert keys == case_keys | more, (n, keys ^ (case_keys | more))
+            g = np.load(os.path.join(gdir, n + ".npz"))
+            T = len(g["modes"])
+            assert g["table_sha"].shape == (T, 5)
+            if thinned:
+                rs = g["rec_step"]
+                assert g["out_sha"].shape == (T, 6) and 1 < len(rs) < T and rs[0] == 0 and rs[-1] == T - 1
+                assert all(len(g[k]) == len(rs) for k in ("rews", "chobs", "state", "pos_x", "vel", "ia"))
+            else:
+                assert all(len(g[k]) == T for k in ("rews", "chobs", "state", "pos_x", "vel", "ia"))
         elif n[0] == "s":
             assert keys == sps_keys, (n, keys ^ sps_keys)
             g = np.load(os.path.join(gdir, n + ".npz"))
