@@ -8,9 +8,9 @@ from oracle.oracle import Oracle, SQ_POW
 
 
 class OracleBackend:
-    def __init__(self, cfg, batch=1):
+    def __init__(self, cfg, batch=1, sq_mode=SQ_POW):
         self.cfg, self.B, self.N, self.A = cfg, batch, cfg.num_users, cfg.num_channels
-        self.o = Oracle(cfg, batch=batch, sq_mode=SQ_POW)
+        self.o = Oracle(cfg, batch=batch, sq_mode=sq_mode)
 
     def get_total_users(self):
         return self.N

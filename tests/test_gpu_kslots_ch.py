@@ -187,8 +187,8 @@ def anchor_oracle(cfg, x0, v0, a, K):
 
 
 def test_ch_k_slots_against_the_cpu_oracle():
-    """One launch of K = 12 `my_step_ch` slots with keep_prob = 1 (no agent ever re-selects: the actions stay slot 0's, no
-    host SPS needed) against tests/oracle_backend.OracleBackend stepped K times on the same actions: positions and tables
+    """One launch of K = 12 `my_step_ch` slots with keep_prob = 1 (no agent ever re-selects: the actions stay slot 0's; the
+    loop with agents that do re-select is checked against a host SPS in tests/test_gpu_closed_loop_host.py) against tests/oracle_backend.OracleBackend stepped K times on the same actions: positions and tables
     bit for bit, the last slot's reward and channel observation bit for bit, the PRR count exact and the PRR sum within
     the suite's tolerance for that column (test_gpu_parity: rtol 1e-12, atol 1e-9 - the summation order differs)."""
     from diral_amd.sps import SpsPolicy
