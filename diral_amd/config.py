@@ -140,6 +140,25 @@ class DiralSlotPolicy(ctypes.Structure):
     ]
 
 
+class DiralRollout(ctypes.Structure):
+    """ctypes image of ``struct DiralRollout`` (include/diral_env.h): the shaping and velocity fields of
+    ``diral_env_rollout``."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("shape_flags", ctypes.c_int32),
+        ("pen_threshold", ctypes.c_int32),
+        ("reserved0", ctypes.c_int32),
+        ("pen_value", ctypes.c_double),
+        ("shaped_out", ctypes.c_void_p),
+        ("sum_r_out", ctypes.c_void_p),
+        ("collision_out", ctypes.c_void_p),
+        ("pen_counter", ctypes.c_void_p),
+        ("pen_prev_actions", ctypes.c_void_p),
+        ("vel_seed", ctypes.c_uint64),
+    ]
+
+
 class ConfigError(ValueError):
     """A config the reference itself cannot run, or one this build rejects."""
 

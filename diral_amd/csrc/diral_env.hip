@@ -402,7 +402,7 @@ hipError_t alloc_large_scratch(DiralEnv* e) {
 size_t slow_set_words(const DiralEnv* e) { return 16 + (size_t)fast_slow_max(e->B) + (size_t)e->B; }
 
 // What one step call launches: decided in ONE place and without side effects, from the handle, the call's parameters
-// and its policy request (`pol`: diral_env_step_policy / diral_env_prefill, else null) - for the launch itself
+// and its policy request (`pol`: diral_env_step_policy / diral_env_prefill / diral_env_rollout, else null) - for the launch itself
 // (launch_step_any) and for everyone who must know the outcome before anything is launched (`fused`).
 enum class StepLaunch { Large, General, Fast64, Wide, Fast64Policy, Fast64Slots, WideSlots };
 struct StepPlan {
@@ -465,6 +465,16 @@ StepPlan plan_step(const DiralEnv* e, const StepParams& p, const PolParams* pol)
   const bool wide_kslots_ok = d.use_wide && !ch && !extra;
   d.launch = d.use_wide ? StepLaunch::Wide : StepLaunch::Fast64;
   if (pol && pol->prefill) { if (prefill_ok || pol_ch_ok) d.launch = StepLaunch::Fast64Slots; }
+  else if (pol && pol->rollout) {
+    // an open-loop rollout (diral_env_rollout): any K >= 1 on the two slot loops - every slot's state vector only where
+    // the env stays on the chip (N <= 64); the secondary observation modes are launches of their own behind ONE state
+    // vector (posdist_kernel.hpp), State.piggybacking's A * A observation is piggy_emit_kernel's
+    const bool secondary = p.state_out && ((p.flags & DIRAL_F_ADD_POSDIST) || ((p.flags & DIRAL_F_ADD_POSDIST_PIGGY) && p.posdist_type == 1));
+    if (!secondary && !e->prev_obs) {
+      if (pol_ok || pol_ch_ok) d.launch = StepLaunch::Fast64Slots;
+      else if (wide_kslots_ok && !(pol->rollout & 2)) d.launch = StepLaunch::WideSlots;
+    }
+  }
   else if (pol && pol->K > 1) { if (pol_ok || pol_ch_ok) d.launch = StepLaunch::Fast64Slots; else if (wide_kslots_ok) d.launch = StepLaunch::WideSlots; }
   else if (pol && pol_ok) d.launch = StepLaunch::Fast64Policy;
   // K slots per launch (DiralSlotPolicy::slots > 1, prefill): blocks = envs in order - over K slots a straggler averages
@@ -1036,7 +1046,7 @@ int diral_env_step_policy(DiralEnv* e, int mode, const int32_t* actions, int64_t
   const int slots = pol->slots > 1 ? pol->slots : 1;
   q.K = slots; q.vel_vary = has(&e->cfg, DIRAL_F_MOBILITY_VARY) ? 1 : 0; q.vel_seed = pol->vel_seed;
   q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N; q.vel_w = e->vel;
-  q.prefill = 0; q.actions_all = nullptr; q.rew_in = nullptr;
+  q.prefill = 0; q.actions_all = nullptr; q.rew_in = nullptr; q.rollout = 0; q.actions_seq = nullptr;
   if (slots > 1 && (pol->draw_counter || pol->draw_keep || pol->draw_choice)) return DIRAL_ERR_BAD_ARG;
   // (decided before anything is launched: a caller without a channel-observation buffer can retry with one)
   const StepPlan d = plan_step(e, p, &q);
@@ -1078,6 +1088,33 @@ int diral_env_prefill_mode(DiralEnv* e, int mode, const int32_t* actions, int32_
   q.actions_out = actions_next_out; q.actions_all = actions_all_out; q.rew_in = rew_in; q.vel_w = e->vel;
   const StepPlan d = plan_step(e, p, &q);
   if (!d.fused) return DIRAL_ERR_UNSUPPORTED;                    // (nothing launched: the caller loops sample + step + observe)
+  HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
+  return DIRAL_OK;
+}
+
+int diral_env_rollout(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
+                      int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro, void* stream) {
+  if (!e || !actions_seq || !ro || ro->struct_bytes != sizeof(DiralRollout) || slots < 1) return DIRAL_ERR_BAD_ARG;
+  if (mode != DIRAL_STEP_MY_STEP && mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_BAD_ARG;
+  if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
+  if ((ro->shape_flags & ~5) != 0) return DIRAL_ERR_BAD_ARG;                  // global_reward_avg | stuck-action penalty
+  if (ro->shaped_out && !rew_out) return DIRAL_ERR_BAD_ARG;                   // (the wide slot loop shapes what rew_out holds)
+  if (ro->shaped_out && (ro->shape_flags & 4) && (!ro->pen_counter || !ro->pen_prev_actions)) return DIRAL_ERR_BAD_ARG;
+  // my_step_ch defines rewards only for reward_design 2,3,4 (test_env.py:413-429)
+  if (mode == DIRAL_STEP_MY_STEP_CH && (e->cfg.reward_design < 2 || e->cfg.reward_design > 4)) return DIRAL_ERR_BAD_CONFIG;
+  DEVICE_ENTER(e->device);
+  StepParams p = call_params(e, mode, t, actions_seq, states_out, out_dtype, 0.0, 1.0);
+  p.rew_out = rew_out; p.done_out = done_out;
+  PolParams q;
+  std::memset(&q, 0, sizeof(q));
+  q.shape_flags = ro->shape_flags; q.pen_threshold = ro->pen_threshold; q.pen_value = ro->pen_value;
+  q.shaped_out = ro->shaped_out; q.sum_r_out = ro->sum_r_out; q.coll_out = ro->collision_out;
+  q.pen_counter = ro->pen_counter; q.pen_prev = ro->pen_prev_actions;
+  q.K = slots; q.vel_vary = has(&e->cfg, DIRAL_F_MOBILITY_VARY) ? 1 : 0; q.vel_seed = ro->vel_seed;
+  q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N; q.vel_w = e->vel;
+  q.rollout = 1 | ((states_all && p.state_out) ? 2 : 0); q.actions_seq = actions_seq;
+  const StepPlan d = plan_step(e, p, &q);
+  if (!d.fused) return DIRAL_ERR_UNSUPPORTED;                    // (nothing launched: the caller loops step + shape)
   HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
   return DIRAL_OK;
 }

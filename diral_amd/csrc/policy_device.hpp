@@ -43,6 +43,10 @@ struct PolParams {
   int prefill;
   int32_t* actions_all;          // [K][B][N] the actions slot ks ran with, or null
   const double* rew_in;          // [B][N] or null (null: the slot's own reward)
+  // An open-loop rollout (diral_env_rollout): the agents of slot ks run actions_seq[ks] - nothing is decided inside the
+  // launch, no SPS state is read or written; the shaping and the velocity updates are the closed loop's.
+  int rollout;                   // 0: off; bit 0: on; bit 1: every slot's state vector leaves ([K][B][N][S], as the prefill's)
+  const int32_t* actions_seq;    // [K][B][N]
 };
 
 // counter-based generator (splitmix64 finaliser over seed/stream/index); the

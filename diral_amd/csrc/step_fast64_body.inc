@@ -1,7 +1,7 @@
 // step_fast64_body.inc - the body of the fused step kernel of step_fast64.hpp, included TWICE by k_fast64.hip (textual inclusion, as
 // step_wide_pass.inc): once as `step_fast64_kernel` - one slot per launch, the metric's kernel - and once, with
 // DIRAL_FAST_KSLOTS defined, as `step_fast64_slots_kernel` - K slots per launch of the POL instantiations (PolParams::K,
-// diral_env_step_policy with DiralSlotPolicy::slots > 1; my_step and, in this form only, my_step_ch): the workgroup keeps
+// diral_env_step_policy with DiralSlotPolicy::slots > 1, the prefill, diral_env_rollout; my_step and, in this form only, my_step_ch): the workgroup keeps
 // its env in registers and LDS from slot to slot.  The two differ where `#ifdef DIRAL_FAST_KSLOTS` says so and nowhere else: the one-slot kernel is compiled from
 // exactly the text it had before the K-slot form existed (the same statements behind `if (first)` / `if (last)` with
 // compile-time-true conditions cost the metric's instantiation a spilled register).
@@ -119,11 +119,20 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
 #define p (*p_ks)
   const bool first = !POL || ks == 0, last = !POL || ks == KS - 1;
   // the driver's random prefill (PolParams::prefill): every slot writes its state vector, the agents act at random
-  int prefill_i = 0;
-  if constexpr (POL) prefill_i = ((LatePolArgs)(late_kernarg_base() + kPolArgOffset))->prefill;
+  int prefill_i = 0, rollout_i = 0;
+  if constexpr (POL) {
+    const LatePolArgs lq0 = (LatePolArgs)(late_kernarg_base() + kPolArgOffset);
+    prefill_i = lq0->prefill; rollout_i = lq0->rollout;
+  }
   const bool prefill = prefill_i != 0;
+  // an open-loop rollout (PolParams::rollout, diral_env_rollout): slot ks + 1 runs actions_seq[ks + 1]; with bit 1 every
+  // slot's state vector leaves, as the prefill's
+  const bool rollout = rollout_i != 0;
+  const bool every = prefill || (rollout_i & 2) != 0;
+  // (a rollout keeps the velocities on the chip even for one slot: an episode end behind it updates them in this launch)
+  const bool kvel_on = KS > 1 || prefill || rollout;
   // the histogram (tally, P4) is wanted only where a state vector leaves: every slot of a one-slot launch, the last of K
-  const bool tally_on = !POL || ((last || prefill) && p.state_out != nullptr);
+  const bool tally_on = !POL || ((last || every) && p.state_out != nullptr);
 #endif /* DIRAL_FAST_KSLOTS */
   // ---- P0: per-vehicle state straight into registers (every wave, lane = vehicle)
   // (unconditional, index-clamped loads pinned ahead of the table loads: vmcnt
@@ -156,7 +165,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     }
     // the velocities this slot starts with, for the velocity column of the last slot's state vector (State.add_velocity:
     // P4 reads them by vehicle index, four barriers from here; every wave holds the same `myvel`)
-    if ((KS > 1 || prefill) && (last || prefill) && wave == 0) s_kvel[lane] = myvel;
+    if (kvel_on && (last || every) && wave == 0) s_kvel[lane] = myvel;
   }
 #endif /* DIRAL_FAST_KSLOTS */
   // this wave's 16 subject columns (rows are padded to a multiple of 16, viewers
@@ -556,12 +565,20 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
 #ifndef DIRAL_FAST_KSLOTS
     if (wave == 3 && live) {
 #else /* DIRAL_FAST_KSLOTS */
-    if (wave == 3 && live && first && !prefill) {
+    if (wave == 3 && live && first && !prefill && !rollout) {
 #endif /* DIRAL_FAST_KSLOTS */
       const LatePolArgs lq = (LatePolArgs)(late_kernarg_base() + kPolArgOffset);
       pol_action = lq->sps_prev[bN + lane];
       pol_cnt = lq->sps_counter[bN + lane];
     }
+#ifdef DIRAL_FAST_KSLOTS
+    // (a rollout: the next slot's actions, asked for HERE - the round trip to memory runs under P3, nothing waits for it
+    // before wave 3 hands them over behind the merge)
+    if (wave == 3 && live && rollout && !last) {
+      const LatePolArgs lq = (LatePolArgs)(late_kernarg_base() + kPolArgOffset);
+      pol_action = lq->actions_seq[((size_t)(ks + 1) * (size_t)p.B) * N + bN + lane];
+    }
+#endif /* DIRAL_FAST_KSLOTS */
   }
   DIRAL_FSTAMP(3);
 
@@ -1061,7 +1078,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
         // TestEnv.sample (test_env.py:116-122) for the next slot, as sample_kernel draws it with seed + ks + 1
         pol_action = (int)(rng_u64(qp->seed + (uint64_t)ks + 1ull, 3, qp->idx0 + (uint64_t)bN + (uint64_t)lane) % (uint64_t)A);
         if (last && live) qp->actions_out[bN + lane] = pol_action;
-      } else {
+      } else if (!rollout) {                                      // (a rollout: `pol_action` is actions_seq[ks + 1], loaded in front of P3)
         fast_sps_decide<out_t>(s_stage, SA, A, N, bN, lane, s_act[lane], pol_action, pol_cnt, qp, ks, last);
       }
       if (!last) s_nact[lane] = pol_action;                       // the next slot's actions, for all four waves
@@ -1155,8 +1172,8 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
 #ifndef DIRAL_FAST_KSLOTS
   void* const state_out = ((LateFastArgs)late)->state_out;
 #else /* DIRAL_FAST_KSLOTS */
-  void* state_out = (last || prefill) ? ((LateFastArgs)late)->state_out : nullptr;   // (K slots: the last slot's state vector)
-  if (prefill && state_out) {                                        // (prefill: every slot's, [K][B][N][S])
+  void* state_out = (last || every) ? ((LateFastArgs)late)->state_out : nullptr;   // (K slots: the last slot's state vector)
+  if (every && state_out) {                                          // (prefill, rollout with states_all: every slot's, [K][B][N][S])
     const size_t S_row = RICH ? (size_t)((LateRichArgs)(late + kRichArgOffset))->S : (size_t)(A + K);
     state_out = static_cast<out_t*>(state_out) + (size_t)ks * (size_t)p.B * (size_t)N * S_row;
   }
@@ -1197,7 +1214,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
 #else /* DIRAL_FAST_KSLOTS */
           // (K slots: Network.update_velocity ran INSIDE the launch at the episode ends in front of this slot - the velocities
           // live in `myvel`, e->vel is written behind the last slot: the column comes from the copy P0 of this slot staged)
-          [&](int u) { return FLAT ? 0.0 : s_py[u]; }, [&](int u) { return (POL && (KS > 1 || prefill)) ? s_kvel[u] : rr.vel[bN + u]; });
+          [&](int u) { return FLAT ? 0.0 : s_py[u]; }, [&](int u) { return (POL && kvel_on) ? s_kvel[u] : rr.vel[bN + u]; });
 #endif /* DIRAL_FAST_KSLOTS */
     }
     // the reference's call pattern on the toy YAML's flags (my_step* with `obs` + obtain_state):
@@ -1298,7 +1315,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     // (CH: `s_inr` / `s_rtx` need no barrier of their own.  Wave 0 reads this slot's ratios in P2, in front of its P3 and so
     //  in front of the barrier behind P3; every wave's P1 of the next slot - the next writer - lies behind that barrier and
     //  the one below.  Nothing else of my_step_ch crosses a slot: the ratios are rebuilt from the positions every slot.)
-    if (KS > 1) {
+    if (KS > 1 || rollout) {
       mynpx_prev = mynpx;
       tkov_prev = tkov;
       if (q.vel_vary) {

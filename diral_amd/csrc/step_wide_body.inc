@@ -100,7 +100,9 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
 #pragma unroll 1
   for (int ks = 0; ks < KS; ++ks) {
   const bool last = ks == KS - 1;
-  const int32_t* const acts_ks = ks == 0 ? p.actions : q.actions_out;
+  // (an open-loop rollout, PolParams::rollout: slot ks runs actions_seq[ks]; nothing is decided in the epilogue)
+  const bool rollout = q.rollout != 0;
+  const int32_t* const acts_ks = rollout ? q.actions_seq + ((size_t)ks * (size_t)p.B) * N : (ks == 0 ? p.actions : q.actions_out);
   // the positional histogram is wanted only where a state vector leaves: the last slot, with state_out
   const bool tally_on = last && ((LateFastArgs)late_kernarg_base())->state_out != nullptr;
 #endif /* DIRAL_WIDE_KSLOTS */
@@ -1213,9 +1215,11 @@ __global__ __launch_bounds__(64 * wide_waves(VPL), VPL == 2 ? (PACKED ? DIRAL_WI
     const LateFastArgs le = (LateFastArgs)late_kernarg_base();
     const PolParams* const qp = reinterpret_cast<const PolParams*>(late_kernarg_base() + kPolArgOffset);
     if (wave < VPL) {
+      if (!rollout) {
       // the SPS agents of this slot (algorithms/v2x_sps.py:76-104), lane = vehicle 64 wave + lane
       const bool dist_obs = ((LateRichArgs)(late_kernarg_base() + kRichArgOffset))->state_type == 2;
       wide_sps_decide<out_t, VPL, MT>(qp, s_act, s_px, s_mtab, actw, dist_obs, N, A, bN, wave, lane, ks);
+      }
     } else if (wave == WAVES - 1) {
       // the driver's reward shaping (main_test.py:171, 178, 194-206; diral_driver_shape without the information-age
       // terms) from this slot's rewards as rew_out holds them (P2, two barriers ago), np.sum in NumPy's order: the rewards

@@ -221,6 +221,54 @@ class DriverLoop:
                    episode_end=episode_end, episode=self.episode, eps=self.eps)
         return out
 
+    # K slots of main_test.py:119-236 with the actions given in advance (a replayed log, a fixed schedule)
+    def rollout(self, actions_seq, t: int, states: Optional[str] = "last", vel_seed: int = 0) -> Dict[str, Any]:
+        """``for k in range(K): out = slot(actions_seq[k], t + k)`` and, behind a slot that ends an episode,
+        ``env.update_velocity(seed=vel_seed + (t + k) // episode_interval)``: returns ``states`` (the last slot's
+        [B, N, S]; `states` = ``"all"``: every slot's [K, B, N, S]; None: none), ``reward`` [B, N] (as the env returned it)
+        and ``done`` [B] of the last slot, ``shaped`` [K, B, N], ``sum_r`` / ``collision`` [K, B].  On the HIP env this is
+        ONE launch (`VecV2VEnv.rollout` -> `diral_env_rollout`); configurations that launch does not take, the
+        information-age terms - and any other env - run the loop.  The loop's episode counter and epsilon stay where they
+        are (`end_episode` is the caller's): every slot's fingerprint columns carry the current ones."""
+        env = self.env
+        seq = self._t(actions_seq)
+        K = int(seq.shape[0])
+        if hasattr(env, "rollout") and not self.ia_averaging:
+            from .config import ERR_UNSUPPORTED
+            from .vec_env import DiralError
+            pen = None
+            if self.ia_penalty_enable:
+                if self._pen_counter is None:
+                    self._pen_counter = torch.zeros((env.B, env.N), dtype=torch.int32, device=env.device)
+                    self._prev_actions = torch.full((env.B, env.N), -1, dtype=torch.int32, device=env.device)
+                pen = (int(self.ia_penalty_threshold), float(self.ia_penalty_value), self._pen_counter, self._prev_actions)
+            try:
+                out = env.rollout(seq, t, mode="my_step_ch" if self.enable_channel else "my_step", states=states,
+                                  global_reward_avg=self.global_reward_avg, stuck_penalty=pen, vel_seed=vel_seed)
+                if out["states"] is not None and env.cfg.enable_fingerprint:     # test_env.py:577-579
+                    out["states"][..., env.S - 2] = self.episode
+                    out["states"][..., env.S - 1] = self.eps
+                return out
+            except DiralError as exc:
+                if exc.status != ERR_UNSUPPORTED:
+                    raise
+        kept, shaped, sum_r, coll = [], [], [], []
+        out: Dict[str, Any] = {}
+        for k in range(K):
+            out = self.slot(seq[k], t + k)
+            if states == "all":
+                kept.append(self._t(out["next_state"]).clone())
+            shaped.append(self._t(out["reward"]).clone())
+            sum_r.append(self._t(out["sum_r"]).clone())
+            coll.append(self._t(out["collision"]).clone())
+            if out["episode_end"]:
+                env.update_velocity(seed=vel_seed + (t + k) // self.episode_interval)
+        raw = self._t(out["raw_reward"])
+        done = torch.full((raw.shape[0],), 1 if out["episode_end"] else 0, dtype=torch.uint8, device=raw.device)
+        st = None if states is None else (torch.stack(kept) if states == "all" else self._t(out["next_state"]))
+        return dict(states=st, reward=raw, done=done, shaped=torch.stack(shaped), sum_r=torch.stack(sum_r),
+                    collision=torch.stack(coll))
+
     def _shape_on_device(self, reward: torch.Tensor, a: torch.Tensor, ia: Optional[torch.Tensor]):
         """main_test.py:171-206 through `diral_driver_shape` (one launch)."""
         env = self.env

@@ -482,6 +482,75 @@ class VecV2VEnv:
         self._keep_policy = (q, actions, actions_out, shaped_out, sum_r_out, collision_out, clock, stuck_penalty)
         return self._obs, self._rew, self._done
 
+    def rollout(self, actions_seq, t: Optional[int] = None, mode="my_step", states: Optional[str] = "last",
+                global_reward_avg: bool = False, stuck_penalty: Optional[tuple] = None, vel_seed: int = 0
+                ) -> Dict[str, Optional[torch.Tensor]]:
+        """K slots of a GIVEN action sequence as ONE launch (`diral_env_rollout`): slot k runs ``my_step(actions_seq[k],
+        t + k)`` (`mode` = ``"my_step_ch"``: ``my_step_ch``, reward_design 2 ... 4), then the driver's reward shaping
+        (main_test.py:171-206 without the information-age terms, `diral_driver_shape` with the same flags) and, in configs
+        with mobility_vary, ``update_velocity(seed=vel_seed + (t + k) // episode_interval)`` behind every slot that ends an
+        episode.  A replayed action log, a fixed schedule, action repeat, the candidate sequences of a search.
+
+        `actions_seq`: [K, B, N] int32 (or [K, N], every env alike).  `states`: ``"last"`` - the last slot's state vectors
+        [B, N, S]; ``"all"`` - every slot's, [K, B, N, S] (N <= 64); ``None`` - none, and no slot computes the positional
+        histogram.  `stuck_penalty` = (threshold, value, counter, prev_actions) as in `step_policy`.
+
+        Returns a dict: ``states``, ``reward`` [B, N] and ``done`` [B] of the LAST slot (owned by the env, like `step`'s),
+        ``shaped`` [K, B, N], ``sum_r`` [K, B], ``collision`` [K, B] of every slot (fresh tensors).  Bit-equal to the loop of
+        K `step` + `diral_driver_shape` (+ `update_velocity`) calls; the env's slot counter moves on by K.  Raises
+        DiralError(ERR_UNSUPPORTED) with nothing launched and the env untouched where the slot loops do not apply
+        (include/diral_env.h lists them; diral_amd.driver.DriverLoop.rollout loops then)."""
+        from .config import DiralRollout
+        step_mode = _MODES.get(mode)
+        if step_mode not in (STEP_MY_STEP, STEP_MY_STEP_CH):
+            raise ValueError("rollout: mode must be 'my_step' or 'my_step_ch'")
+        if states not in ("last", "all", None):
+            raise ValueError("rollout: states must be 'last', 'all' or None")
+        seq = torch.as_tensor(actions_seq, device=self.device)
+        if seq.dtype != torch.int32:
+            seq = seq.to(torch.int32)
+        if seq.dim() == 2:
+            seq = seq.unsqueeze(1).expand(seq.shape[0], self.B, self.N)
+        if seq.dim() != 3 or seq.shape[0] < 1 or tuple(seq.shape[1:]) != (self.B, self.N):
+            raise ValueError("rollout: actions_seq must have shape [K >= 1, B=%d, N=%d], got %s" % (self.B, self.N, tuple(seq.shape)))
+        seq = seq.contiguous()
+        K = int(seq.shape[0])
+        if t is None:
+            t = self.t
+        ri = (self._ri + K) % self.io_ring
+        slot = self._ring[ri]
+        want_states = states is not None and self.S > 0
+        if states == "all" and want_states:
+            st_out = torch.empty((K, self.B, self.N, self.S), dtype=self.out_dtype, device=self.device)
+        else:
+            st_out = slot["obs"] if want_states else None
+        o = dict(dtype=self.out_dtype, device=self.device)
+        shaped, sum_r, coll = torch.empty((K, self.B, self.N), **o), torch.empty((K, self.B), **o), torch.empty((K, self.B), **o)
+        q = DiralRollout()
+        q.struct_bytes = ctypes.sizeof(DiralRollout)
+        q.shape_flags = 1 if global_reward_avg else 0
+        if stuck_penalty is not None:
+            thr, val, cnt, prev = stuck_penalty
+            for name, a in (("counter", cnt), ("prev_actions", prev)):
+                if not isinstance(a, torch.Tensor) or a.dtype != torch.int32 or tuple(a.shape) != (self.B, self.N) \
+                        or not a.is_contiguous() or a.device != self.device:
+                    raise ValueError("rollout: stuck_penalty %s must be a contiguous int32 tensor [%d, %d] on %s" %
+                                     (name, self.B, self.N, self.device))
+            q.shape_flags |= 4
+            q.pen_threshold, q.pen_value = int(thr), float(val)
+            q.pen_counter, q.pen_prev_actions = _ptr(cnt), _ptr(prev)
+        q.shaped_out, q.sum_r_out, q.collision_out = _ptr(shaped), _ptr(sum_r), _ptr(coll)
+        q.vel_seed = int(vel_seed) & (2**64 - 1)
+        st = self.lib.diral_env_rollout(self._h, step_mode, _ptr(seq), K, int(t), _ptr(st_out), 1 if states == "all" else 0,
+                                        _ptr(slot["rew"]), _ptr(slot["done"]), self._dt, ctypes.byref(q), self._stream())
+        self._ok(st, "diral_env_rollout")            # (a refused call has launched nothing: the bookkeeping below stays as it was)
+        self._ri = ri
+        self._obs, self._rew, self._done, self._chobs = slot["obs"], slot["rew"], slot["done"], slot["chobs"]
+        self._spec = None
+        self.t = int(t) + K
+        self._keep_rollout = (q, seq, stuck_penalty)
+        return dict(states=st_out, reward=self._rew, done=self._done, shaped=shaped, sum_r=sum_r, collision=coll)
+
     def step(self, actions, t: Optional[int] = None, episode: float = 0.0, epsilon: float = 1.0
              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """``step(actions[B,N]) -> (obs[B,N,S], reward[B,N], done[B])``.

@@ -495,6 +495,43 @@ int diral_env_prefill_mode(DiralEnv* env, int mode, const int32_t* actions, int3
                            int out_dtype, int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in,
                            double episode, double epsilon, void* stream);
 
+/* An open-loop rollout: K slots of a GIVEN action sequence as ONE launch (additive within ABI 8; the slot loops of
+ * step_fast64_slots_kernel / step_wide_slots_kernel with the actions read from `actions_seq` instead of decided on the chip):
+ *   for k = 0 .. K - 1:   obs, rews = my_step(actions_seq[k], t + k)            [mode DIRAL_STEP_MY_STEP_CH: my_step_ch]
+ *                         shaped_out[k], sum_r_out[k], collision_out[k] = diral_driver_shape(rews, actions_seq[k], ...)
+ *                         diral_env_update_velocity(env, NULL, vel_seed + (t + k) / episode_interval)   [at an episode end]
+ * Equal, bit for bit, to that loop of diral_env_step + diral_driver_shape (+ diral_env_update_velocity) calls: states,
+ * rewards, shaped rewards, sums, collisions, done, tables, ring, positions, velocities, metrics, penalty state.  A replayed
+ * action log, a fixed schedule (TDMA), action repeat, B candidate sequences of a search.
+ *   actions_seq [K][B][N]     slots >= 1
+ *   states_out                NULL: no slot computes the positional histogram; states_all = 0: [B][N][S] of the LAST slot;
+ *                             states_all = 1: [K][B][N][S], row k = obtain_state(obs_k, actions_seq[k], rews_k)
+ *   rew_out [B][N], done_out [B]   of the LAST slot (each may be NULL; shaped_out needs rew_out)
+ *   shaped_out [K][B][N], sum_r_out [K][B], collision_out [K][B]   out dtype, slot-major; shaped_out NULL = no shaping;
+ *     shape_flags: bit 0 global_reward_avg, bit 2 stuck-action penalty (then pen_counter / pen_prev_actions are mandatory);
+ *     shape_flags = 0: shaped_out[k] is the reward as the step returns it
+ * Configurations the slot loops take: 8 <= N <= 256, A <= 64, the one-lane highway, piggybacked tables, no arrival / PRR
+ * tracking, no trace replay, no static topology, no State.piggybacking, no secondary observation mode behind a state
+ * vector; my_step_ch and states_all = 1 at N <= 64 only.  Otherwise DIRAL_ERR_UNSUPPORTED with nothing launched and the env
+ * untouched (loop over the calls instead: diral_amd.driver.DriverLoop.rollout does).  my_step_ch with reward_design
+ * outside 2 ... 4: DIRAL_ERR_BAD_CONFIG (as diral_env_step). */
+typedef struct DiralRollout {
+  uint32_t struct_bytes;          /* = sizeof(DiralRollout) */
+  int32_t  shape_flags;
+  int32_t  pen_threshold;
+  int32_t  reserved0;
+  double   pen_value;
+  void*    shaped_out;            /* [K][B][N] out dtype or NULL */
+  void*    sum_r_out;             /* [K][B] or NULL */
+  void*    collision_out;         /* [K][B] or NULL */
+  int32_t* pen_counter;           /* [B][N] (shape_flags bit 2) */
+  int32_t* pen_prev_actions;      /* [B][N] */
+  uint64_t vel_seed;              /* as DiralSlotPolicy::vel_seed */
+} DiralRollout;
+int diral_env_rollout(DiralEnv* env, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
+                      int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* rollout,
+                      void* stream);
+
 /* ---- slot clock: rollouts captured into a hipGraph ---------------------------------------------
  * A captured sequence of K slots (env step, reward shaping, policy) bakes every by-value argument into its
  * kernel nodes; what has to move on from replay to replay - the slot number behind `done`, arrival stamps and
