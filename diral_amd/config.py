@@ -64,6 +64,7 @@ KERNEL_POLICY = 512
 MAX_USERS = 4096
 MAX_CHANNELS = 4096
 MAX_BINS = 1024
+MAX_SLOTS = 16777214         # DIRAL_MAX_SLOTS: steps between resets, the last sequence number a table entry may carry
 SMALL_MAX_USERS = 256        # the one-workgroup kernels; beyond: csrc/step_large.hpp (KERNEL_LARGE)
 SMALL_MAX_CHANNELS = 256
 SMALL_MAX_BINS = 64

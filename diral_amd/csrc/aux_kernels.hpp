@@ -169,8 +169,12 @@ __global__ void unpack_codes_kernel(int B, int N, int NV, int NR, const uint32_t
   }
 }
 
+// A sequence number the 24-bit field of the table word cannot hold, or the one past the last a step accepts
+// (outside [0, kSeqMax]), is not truncated into a legal-looking one: it raises kErrSeq in the sticky error
+// word (diral_env_check: DIRAL_ERR_SEQ_OVERFLOW) and the entry is stored as never heard.
+constexpr uint32_t kSeqMax = (1u << 24) - 2u;   // DIRAL_MAX_SLOTS
 __global__ void import_tables_kernel(int B, int N, int NV, int NR, const int32_t* seq, const int32_t* age,
-                                     const double* x, uint32_t* tkey, double* tx) {
+                                     const double* x, uint32_t* tkey, double* tx, uint32_t* err) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t total = (size_t)B * N * N;
   if (i >= total) return;
@@ -181,6 +185,7 @@ __global__ void import_tables_kernel(int B, int N, int NV, int NR, const int32_t
   if (seq || age) {
     uint32_t w = tkey[dst];
     uint32_t s = seq ? (uint32_t)seq[i] : (w >> 8);
+    if (s > kSeqMax) { atomicOr(err, kErrSeq); s = 0u; }      // (a negative number lands here too)
     int a = age ? age[i] : (int)(w & 255u);
     if (a > 255) a = 255;
     if (a < 0) a = 0;
@@ -209,7 +214,7 @@ __global__ void export_entries_kernel(int B, int N, int NV, int NR, const uint32
 }
 
 __global__ void import_entries_kernel(int B, int N, int NV, int NR, const DiralNeighborEntry* in, uint32_t* tkey,
-                                      double* tx) {
+                                      double* tx, uint32_t* err) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)B * N * N) return;
   const int k = (int)(i % N);
@@ -218,7 +223,9 @@ __global__ void import_entries_kernel(int B, int N, int NV, int NR, const DiralN
   const size_t dst = ((size_t)b * NR + k) * NV + u;
   const DiralNeighborEntry r = in[i];
   const int a = r.last_update > 255 ? 255 : (r.last_update < 0 ? 0 : r.last_update);
-  tkey[dst] = ((uint32_t)r.seq_num << 8) | (uint32_t)a;
+  uint32_t s = (uint32_t)r.seq_num;
+  if (s > kSeqMax) { atomicOr(err, kErrSeq); s = 0u; }        // as in import_tables_kernel
+  tkey[dst] = (s << 8) | (uint32_t)a;
   tx[dst] = (double)r.pos_x;
 }
 

@@ -1207,7 +1207,7 @@ int diral_env_import_state(DiralEnv* e, const double* pos_x, const double* pos_y
   if (tab_seq || tab_age || tab_x) {
     HIP_TRY(e, ensure_plane(e, s));                             // (a partial import keeps the other planes)
     e->ring_valid = false;
-    HIP_TRY(e, launch_1d<import_tables_kernel>(bn * e->N, s, e->B, e->N, e->NV, e->NR, tab_seq, tab_age, tab_x, e->tkey, e->tx));
+    HIP_TRY(e, launch_1d<import_tables_kernel>(bn * e->N, s, e->B, e->N, e->NV, e->NR, tab_seq, tab_age, tab_x, e->tkey, e->tx, e->err));
     // the ring again, right away (not at the next step: a step sequence captured into a hipGraph must not
     // contain a rebuild from a plane that later replays find stale)
     if (e->ring) { HIP_TRY(e, ensure_ring(e, s)); HIP_TRY(e, verify_ring(e, s)); }
@@ -1250,7 +1250,7 @@ int diral_env_import_entries(DiralEnv* e, const DiralNeighborEntry* entries, voi
   hipStream_t s = (hipStream_t)stream;
   e->plane_valid = true;                                        // every entry of the plane is rewritten
   e->ring_valid = false;
-  HIP_TRY(e, launch_1d<import_entries_kernel>((size_t)e->B * e->N * e->N, s, e->B, e->N, e->NV, e->NR, entries, e->tkey, e->tx));
+  HIP_TRY(e, launch_1d<import_entries_kernel>((size_t)e->B * e->N * e->N, s, e->B, e->N, e->NV, e->NR, entries, e->tkey, e->tx, e->err));
   if (e->ring) { HIP_TRY(e, ensure_ring(e, s)); HIP_TRY(e, verify_ring(e, s)); }   // as in diral_env_import_state
   return DIRAL_OK;
 }

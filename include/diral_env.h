@@ -47,7 +47,11 @@ typedef enum DiralStatus {
   DIRAL_ERR_NO_DEVICE = -5,    /* no gfx950 device / device index out of range */
   DIRAL_ERR_ACTION_RANGE = -6, /* an action outside [0, A) was seen (sticky flag
                                   raised by the step kernel; test_env.py:592)   */
-  DIRAL_ERR_SEQ_OVERFLOW = -7, /* more than DIRAL_MAX_SLOTS steps since reset   */
+  DIRAL_ERR_SEQ_OVERFLOW = -7, /* more than DIRAL_MAX_SLOTS steps since reset, or an
+                                  imported sequence number outside [0, DIRAL_MAX_SLOTS]
+                                  (sticky flag, reported once by diral_env_check; what
+                                  the handle computes after it was raised is undefined
+                                  until diral_env_reset)                         */
   DIRAL_ERR_CAPTURE = -8,      /* the call would launch a ring <-> plane conversion
                                   (first step after a kernel-path switch, export /
                                   observe after ring steps) while `stream` is being
@@ -308,7 +312,11 @@ int diral_env_set_trace(DiralEnv* env, const double* x_positions, int T, int per
  * plane, N > 64 routes xpos through a rank-indexed table; export / observe /
  * other consumers see the plane completed first (no caller-visible difference).
  * An import that violates the requirement is detected: the next
- * diral_env_check() returns DIRAL_ERR_TABLE_CONFLICT.  A call that needs the
+ * diral_env_check() returns DIRAL_ERR_TABLE_CONFLICT.  So is a sequence number
+ * the 24-bit table words cannot carry: tab_seq outside [0, DIRAL_MAX_SLOTS]
+ * (negative ones included) is never truncated into a legal-looking number; the
+ * next diral_env_check() returns DIRAL_ERR_SEQ_OVERFLOW, and the handle's outputs
+ * are undefined until diral_env_reset.  A call that needs the
  * plane <-> ring conversion launch (the first step after a kernel-path switch,
  * export / observe after ring steps) while `stream` is being captured into a
  * hipGraph returns DIRAL_ERR_CAPTURE and launches nothing: a captured
@@ -337,7 +345,8 @@ int diral_env_import_prev_obs(DiralEnv* env, const double* prev_obs, void* strea
  * [env][viewer][subject].  export narrows the f64 positions to f32 (round to
  * nearest); import widens pos_x exactly, ignores pos_y (an entry's ypos is the
  * subject's lane) and saturates last_update at 255 like
- * diral_env_import_state, whose reachability note applies. */
+ * diral_env_import_state, whose reachability note and range of seq_num
+ * ([0, DIRAL_MAX_SLOTS], else DIRAL_ERR_SEQ_OVERFLOW at the next check) apply. */
 typedef struct DiralNeighborEntry {
   float pos_x, pos_y;
   int32_t seq_num, last_update;

@@ -95,3 +95,70 @@ def ulp_diff(a, b):
     if a.size == 0:
         return 0
     return int(np.max(np.abs(ai - bi)))
+
+
+HORIZON_LAGS = ("never", "fresh", "handover", "mid", "byte", "ancient")
+
+
+def horizon_tables(rng, B, N, L, own_seq, lags=HORIZON_LAGS):
+    """Neighbour tables of a run that has been going for `own_seq` slots, for import_state: every vehicle's own entry
+    carries `own_seq` (a number, or a [B, N] array: one number per vehicle), age 0 and the vehicle's position; an entry
+    about subject k lags k's own number by a draw from the classes named in `lags`, chosen so that every representation
+    of an entry meets its neighbour:
+      never     never heard (number 0);
+      fresh     lag 1 ... 3;
+      handover  lag exactly 6, 7, 8 - where the thermometer codes / the xpos ring of N <= 256 hand over to the keys;
+      mid       lag 9 ... 40;
+      byte      lag exactly 253, 254, 255 - the last ranks a byte holds;
+      ancient   lag >= 2^20 (beyond the 20-bit rank of the large path), where the subject's own number allows it.
+    The entries beyond the byte ranks ("far": lag >= 254, the `byte` draws of 254 / 255 and the `ancient` ones alike) are
+    arranged per column (env, subject), a quarter of the columns each:
+      0  as drawn - the only columns where lags of exactly 254 / 255 sit next to ancient numbers;
+      1  none (they become `mid`): a column without far entries;
+      2  all far entries of the column share ONE number (the one-far-number shortcut of the 2-values-per-lane wide kernel);
+      3  exactly two different far numbers (its 32-bit fallback).
+    The shared numbers of 2 and 3 are ancient (lag >= 2^20) when `ancient` is among `lags`, else lags 254 / 255 and up to
+    299 more: with `ancient`, about a sixth of all entries are ancient and a quarter of the columns hold none.
+    xpos is a function of (subject, number) - equal numbers about one subject carry equal xpos, what every run produces and
+    what import_state asks for -, ages are min(lag, 255).  An entry whose number would not be positive is never heard.
+    Returns dict(pos_x, vel [B, N] float64; seq, age [B, N, N] int32; x [B, N, N] float64), indexed [env][viewer][subject]."""
+    own = np.broadcast_to(np.asarray(own_seq, dtype=np.int64), (B, N))
+    pos_x = rng.integers(0, int(L), size=(B, N)).astype(np.float64)
+    vel = rng.uniform(1.1, 2.7, size=(B, N))
+    shape = (B, N, N)
+    draws = {
+        "never": np.zeros(shape, np.int64),
+        "fresh": rng.integers(1, 4, size=shape),
+        "handover": rng.integers(6, 9, size=shape),
+        "mid": rng.integers(9, 41, size=shape),
+        "byte": rng.integers(253, 256, size=shape),
+        "ancient": rng.integers(1 << 20, 1_200_000, size=shape),
+    }
+    names = list(lags)
+    kind = rng.integers(0, len(names), size=shape)
+    lag = np.zeros(shape, np.int64)
+    for i, name in enumerate(names):
+        lag = np.where(kind == i, draws[name], lag)
+    heard = kind != (names.index("never") if "never" in names else -1)
+    col = rng.integers(0, 4, size=(B, 1, N))                          # the column's arrangement of far entries
+    far = heard & (lag >= 254)
+    if "ancient" in names:
+        far_a = rng.integers(1 << 20, 1_200_000, size=(B, 1, N))
+    else:
+        far_a = rng.integers(254, 256, size=(B, 1, N))
+    far_b = far_a + rng.integers(1, 300, size=(B, 1, N))
+    lag = np.where(far & (col == 1), draws["mid"], lag)
+    lag = np.where(far & (col == 2), far_a, lag)
+    lag = np.where(far & (col == 3), np.where(rng.integers(0, 2, size=shape) == 0, far_a, far_b), lag)
+    seq = np.where(heard, own[:, None, :] - lag, 0)
+    heard = seq > 0
+    seq = np.where(heard, seq, 0)
+    lag = np.where(heard, lag, 0)
+    kk = np.arange(N)[None, None, :]
+    x = np.where(heard, (kk * 7919 + seq * 31) % int(L), 0).astype(np.float64)
+    age = np.minimum(lag, 255)
+    d = np.arange(N)
+    seq[:, d, d] = own
+    age[:, d, d] = 0
+    x[:, d, d] = pos_x
+    return dict(pos_x=pos_x, vel=vel, seq=seq.astype(np.int32), age=age.astype(np.int32), x=x)

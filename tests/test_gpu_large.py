@@ -13,7 +13,7 @@ import torch
 
 import tests.test_gpu_parity as tp
 from diral_amd.config import (KERNEL_LARGE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config, c2_config)
-from tests.golden_util import golden_names
+from tests.golden_util import golden_names, horizon_tables
 
 pytestmark = pytest.mark.gpu
 
@@ -122,21 +122,10 @@ def test_entries_a_million_stamps_old_take_the_64_bit_merge(N, A, L):
     cfg = bench_config(N, A, L)
     B = 2
     rng = np.random.default_rng(4242 + N)
-    pos_x = rng.integers(0, int(L), size=(B, N)).astype(np.float64)
-    vel = rng.uniform(1.1, 2.7, size=(B, N))
     T0 = 1_300_000
-    kind = rng.integers(0, 4, size=(B, N, N))                       # 0 never heard, 1 fresh, 2 a few stamps old, 3 ancient
-    lag = np.where(kind == 1, rng.integers(1, 4, size=(B, N, N)), np.where(kind == 2, rng.integers(4, 40, size=(B, N, N)),
-                                                                            rng.integers(1 << 20, 1_200_000, size=(B, N, N))))
-    seq = np.where(kind == 0, 0, T0 - lag).astype(np.int32)
-    # equal (subject, number) => equal xpos (what a run produces and import_state asks for): xpos a function of both
-    kk = np.broadcast_to(np.arange(N)[None, None, :], (B, N, N))
-    x = np.where(seq > 0, (kk * 7919 + seq.astype(np.int64) * 31) % int(L), 0).astype(np.float64)
-    age = np.where(kind == 0, 0, np.minimum(lag, 255)).astype(np.int32)
-    for u in range(N):
-        seq[:, u, u] = T0
-        age[:, u, u] = 0
-        x[:, u, u] = pos_x[:, u]
+    tab = horizon_tables(rng, B, N, L, T0)
+    pos_x, vel, seq, age, x = (tab[k] for k in ("pos_x", "vel", "seq", "age", "x"))
+    assert ((seq > 0) & (T0 - seq >= 1 << 20)).any(axis=1).mean() > 0.5     # most columns hold entries beyond the 20-bit rank
     env = tp.make_env(cfg, B)
     env.force_large_path()
     env.reset_topology(pos_x, 0.0, vel)
