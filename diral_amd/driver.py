@@ -20,6 +20,9 @@ from typing import Any, Dict, Optional
 
 import torch
 
+from .config import ERR_UNSUPPORTED, STEP_MY_STEP, STEP_MY_STEP_CH
+from .vec_env import DiralError, driver_shape
+
 
 def calculate_ia_penalty(ia: torch.Tensor) -> torch.Tensor:
     """utils/misc.py:1-12: sum over bins of (i+1)*ia[i] (bins with ia > 0);
@@ -94,6 +97,7 @@ class DriverLoop:
         self._sum_ia_prev: Optional[torch.Tensor] = None
         self._pen_counter: Optional[torch.Tensor] = None
         self._prev_actions: Optional[torch.Tensor] = None
+        self._keep: tuple = ()                # what the last `diral_driver_shape` launch's raw pointers refer to
 
     @staticmethod
     def _t(x) -> torch.Tensor:
@@ -127,8 +131,6 @@ class DriverLoop:
         slots); configurations that launch does not take - and any other env - run the loop."""
         env = self.env
         if hasattr(env, "prefill"):
-            from .config import ERR_UNSUPPORTED
-            from .vec_env import DiralError
             try:
                 if self.enable_channel:
                     states, acts, _ = env.prefill(env.sample(seed), slots, seed, rew_in=self._rews0, mode="my_step_ch")
@@ -150,7 +152,6 @@ class DriverLoop:
         env = self.env
         fused_state = None
         if self.fused:
-            from .config import STEP_MY_STEP, STEP_MY_STEP_CH
             mode = STEP_MY_STEP_CH if self.enable_channel else STEP_MY_STEP
             fused_state, reward, _ = env._step(mode, env._actions(action), time_step, self.episode, self.eps)
             obs = None
@@ -187,35 +188,32 @@ class DriverLoop:
                 next_state = next_state.clone()
         a = self._actions(action).to(reward.device)
         if self.device_shaping:
-            shaped, sum_r, collision, pen, ia_sum = self._shape_on_device(reward, a, out.get("ia"))
+            reward, sum_r, collision, pen, ia_sum = self._shape_on_device(reward, a, out.get("ia"))
             if ia_sum is not None:
                 out["ia_sum"] = ia_sum
             if pen is not None:
                 out["ia_penalty"] = pen
-            episode_end = (time_step % self.episode_interval) == self.episode_interval - 1   # :226
-            out.update(next_state=next_state, reward=shaped, raw_reward=raw, sum_r=sum_r, collision=collision,
-                       episode_end=episode_end, episode=self.episode, eps=self.eps)
-            return out
-        sum_r = np_sum_lastdim(reward)                                       # :171 (NumPy's summation order)
-        collision = self.A - sum_r                                           # :178
-        if ia_penalty is not None:
-            reward = reward + ia_penalty.unsqueeze(-1)                       # :190-192
-        if self.ia_penalty_enable:                                           # :194-203
-            if self._pen_counter is None:
-                self._pen_counter = torch.zeros_like(a, dtype=torch.int64)
-                self._prev_actions = torch.full_like(a, -1)
-            stuck = (reward < 1) & (a == self._prev_actions)
-            self._pen_counter = torch.where(stuck, self._pen_counter + 1, torch.zeros_like(self._pen_counter))
-            reward = torch.where(self._pen_counter > self.ia_penalty_threshold,
-                                 torch.as_tensor(float(self.ia_penalty_value), dtype=reward.dtype, device=reward.device),
-                                 reward)
-            self._prev_actions = a.clone()
-        if self.global_reward_avg:
-            # (tensor / tensor: a true IEEE division like Python's `sum_r / len(reward)`; tensor / Python scalar
-            # is computed on the GPU as a multiplication by the rounded reciprocal - one ulp off unless N is a
-            # power of two)
-            n_t = torch.as_tensor(float(self.N), dtype=reward.dtype, device=reward.device)
-            reward = reward + (sum_r / n_t).unsqueeze(-1)                    # :205-206
+        else:
+            sum_r = np_sum_lastdim(reward)                                       # :171 (NumPy's summation order)
+            collision = self.A - sum_r                                           # :178
+            if ia_penalty is not None:
+                reward = reward + ia_penalty.unsqueeze(-1)                       # :190-192
+            if self.ia_penalty_enable:                                           # :194-203
+                if self._pen_counter is None:
+                    self._pen_counter = torch.zeros_like(a, dtype=torch.int64)
+                    self._prev_actions = torch.full_like(a, -1)
+                stuck = (reward < 1) & (a == self._prev_actions)
+                self._pen_counter = torch.where(stuck, self._pen_counter + 1, torch.zeros_like(self._pen_counter))
+                reward = torch.where(self._pen_counter > self.ia_penalty_threshold,
+                                     torch.as_tensor(float(self.ia_penalty_value), dtype=reward.dtype, device=reward.device),
+                                     reward)
+                self._prev_actions = a.clone()
+            if self.global_reward_avg:
+                # (tensor / tensor: a true IEEE division like Python's `sum_r / len(reward)`; tensor / Python scalar
+                # is computed on the GPU as a multiplication by the rounded reciprocal - one ulp off unless N is a
+                # power of two)
+                n_t = torch.as_tensor(float(self.N), dtype=reward.dtype, device=reward.device)
+                reward = reward + (sum_r / n_t).unsqueeze(-1)                    # :205-206
         episode_end = (time_step % self.episode_interval) == self.episode_interval - 1   # :226
         out.update(next_state=next_state, reward=reward, raw_reward=raw, sum_r=sum_r, collision=collision,
                    episode_end=episode_end, episode=self.episode, eps=self.eps)
@@ -234,8 +232,6 @@ class DriverLoop:
         seq = self._t(actions_seq)
         K = int(seq.shape[0])
         if hasattr(env, "rollout") and not self.ia_averaging:
-            from .config import ERR_UNSUPPORTED
-            from .vec_env import DiralError
             pen = None
             if self.ia_penalty_enable:
                 if self._pen_counter is None:
@@ -246,8 +242,8 @@ class DriverLoop:
                 out = env.rollout(seq, t, mode="my_step_ch" if self.enable_channel else "my_step", states=states,
                                   global_reward_avg=self.global_reward_avg, stuck_penalty=pen, vel_seed=vel_seed)
                 if out["states"] is not None and env.cfg.enable_fingerprint:     # test_env.py:577-579
-                    out["states"][..., env.S - 2] = self.episode
-                    out["states"][..., env.S - 1] = self.eps
+                    out["states"][..., env._fp_offset] = self.episode
+                    out["states"][..., env._fp_offset + 1] = self.eps
                 return out
             except DiralError as exc:
                 if exc.status != ERR_UNSUPPORTED:
@@ -271,7 +267,6 @@ class DriverLoop:
 
     def _shape_on_device(self, reward: torch.Tensor, a: torch.Tensor, ia: Optional[torch.Tensor]):
         """main_test.py:171-206 through `diral_driver_shape` (one launch)."""
-        env = self.env
         B, N = reward.shape
         dev = reward.device
         reward = reward.contiguous()
@@ -290,18 +285,11 @@ class DriverLoop:
         # (the information-age term only when this slot fetched the histogram: slot(..., want_ia=False) with
         # ia_averaging skips it, exactly like the torch statement in slot())
         use_ia = self.ia_averaging and ia is not None
-        flags = (1 if self.global_reward_avg else 0) | (2 if use_ia else 0) | (4 if self.ia_penalty_enable else 0)
-
-        def p(t):
-            return None if t is None else t.data_ptr()
-        st = env.lib.diral_driver_shape(B, N, self.A, p(reward), 1 if reward.dtype == torch.float64 else 0, p(a32), p(ia32),
-                                        p(self._sum_ia_prev) if use_ia else None,
-                                        p(self._pen_counter) if self.ia_penalty_enable else None,
-                                        p(self._prev_actions) if self.ia_penalty_enable else None, flags,
-                                        int(self.ia_penalty_threshold), float(self.ia_penalty_value), p(shaped), p(sum_r),
-                                        p(coll), p(ia_sum), p(pen), env._stream())
-        if st != 0:
-            raise RuntimeError("diral_driver_shape failed with status %d" % st)
+        pen_on = self.ia_penalty_enable
+        driver_shape(self.env, reward, a32, shaped=shaped, sum_r=sum_r, collision=coll, global_reward_avg=self.global_reward_avg,
+                     ia=ia32, sum_ia_prev=self._sum_ia_prev if use_ia else None, ia_sum=ia_sum, ia_penalty=pen,
+                     pen_counter=self._pen_counter if pen_on else None, prev_actions=self._prev_actions if pen_on else None,
+                     pen_threshold=self.ia_penalty_threshold, pen_value=self.ia_penalty_value)
         self._keep = (reward, a32, ia32)
         return shaped, sum_r, coll, (pen.to(reward.dtype) if pen is not None else None), ia_sum
 

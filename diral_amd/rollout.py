@@ -30,7 +30,7 @@ import torch
 
 from .config import STEP_MY_STEP, STEP_MY_STEP_CH
 from .sps import SpsPolicy
-from .vec_env import DiralError, VecV2VEnv
+from .vec_env import VecV2VEnv, driver_shape
 
 
 @contextlib.contextmanager
@@ -64,12 +64,7 @@ class SlotClock:
 def shape_rewards(env: VecV2VEnv, reward: torch.Tensor, actions: torch.Tensor, out: torch.Tensor, sum_r: torch.Tensor,
                   coll: torch.Tensor, global_reward_avg: bool) -> None:
     """main_test.py:171-206 without the information-age terms: `diral_driver_shape`, one launch, caller-owned outputs."""
-    B, N = reward.shape
-    st = env.lib.diral_driver_shape(B, N, env.A, reward.data_ptr(), 1 if reward.dtype == torch.float64 else 0,
-                                    actions.data_ptr(), None, None, None, None, 1 if global_reward_avg else 0, 0, 0.0,
-                                    out.data_ptr(), sum_r.data_ptr(), coll.data_ptr(), None, None, env._stream())
-    if st != 0:
-        raise DiralError(st, "diral_driver_shape")
+    driver_shape(env, reward, actions, shaped=out, sum_r=sum_r, collision=coll, global_reward_avg=global_reward_avg)
 
 
 class GraphRollout:
@@ -141,15 +136,14 @@ class GraphRollout:
     def _run_slots(self, eager: bool) -> None:
         for k in range(self.K):
             self._one_slot(k)
-        st = self.env.lib.diral_clock_add(ctypes.c_void_p(self.clock.ptr()), self.K, self.env._stream())
-        if st != 0:
-            raise DiralError(st, "diral_clock_add")
+        self.env._ok(self.env.lib.diral_clock_add(ctypes.c_void_p(self.clock.ptr()), self.K, self.env._stream()),
+                     "diral_clock_add")
         if eager:
             self._slots_run += self.K
 
     def run(self, replays: int = 1) -> None:
         """`replays` x K slots (enqueued on the current stream; no host sync)."""
-        if self.graph is not None and getattr(self, "_phase", None) is not None and replays > 0:
+        if self.graph is not None and self._phase is not None and replays > 0:
             self.env.align_phase(self._phase)        # (eager steps since the last replay may have moved it)
         for _ in range(replays):
             if self.graph is not None:

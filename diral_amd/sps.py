@@ -18,11 +18,8 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .vec_env import DiralError
-
-
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
+from ._tensors import _ptr, check_tensor, dtype_code, policy_seed, seed64
+from .vec_env import check_status
 
 
 class SpsPolicy:
@@ -37,16 +34,35 @@ class SpsPolicy:
         self.prev_action = torch.zeros((batch, num_users), dtype=torch.int32, device=self.device)
         self.counter = torch.zeros((batch, num_users), dtype=torch.int32, device=self.device)
         self._t = 0
+        self._keep: tuple = ()                          # what the last launch's raw pointers refer to
         # v2x_sps.py:14: randint(0, selection_window) is inclusive; A-1 keeps actions in range
         window = num_channels - 1 if selection_window is None else selection_window
-        st = self.lib.diral_sps_init(batch * num_users, int(window), _ptr(self.prev_action), _ptr(self.counter),
-                                     int(seed) & (2**64 - 1), self._stream())
-        if st != 0:
-            raise DiralError(st, "diral_sps_init")
+        check_status(self.lib.diral_sps_init(batch * num_users, int(window), _ptr(self.prev_action), _ptr(self.counter),
+                                             seed64(seed), self._stream()), "diral_sps_init")
         self.seed = seed
 
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _draws(self, draw_counter, draw_keep, draw_choice):
+        def opt(t, dt):
+            return None if t is None else torch.as_tensor(t, dtype=dt, device=self.device).reshape(self.B, self.N).contiguous()
+        return opt(draw_counter, torch.int32), opt(draw_keep, torch.float64), opt(draw_choice, torch.int32)
+
+    def _out(self, out: Optional[torch.Tensor]) -> torch.Tensor:
+        return torch.empty((self.B, self.N), dtype=torch.int32, device=self.device) if out is None else out
+
+    def _chobs_in(self, chobs: torch.Tensor, actions: torch.Tensor):
+        """The channel observation [B, N, A] (float32 / float64) and the actions as the `*_chobs` launches take them."""
+        c = chobs.contiguous()
+        check_tensor("chobs", c, torch.float64 if c.dtype == torch.float64 else torch.float32, (self.B, self.N, self.A),
+                     c.device, "%(name)s must be float32/float64 [B, N, A]")
+        return c, actions.to(device=self.device, dtype=torch.int32).contiguous()
+
+    def _launched(self, st: int, where: str, out: torch.Tensor, *keep) -> torch.Tensor:
+        check_status(st, where)
+        self._keep = keep
+        return out
 
     def step(self, selection_window: torch.Tensor, draw_counter=None, draw_keep=None, draw_choice=None,
              out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -54,26 +70,13 @@ class SpsPolicy:
         w = selection_window.to(device=self.device, dtype=torch.float64).contiguous()
         if tuple(w.shape) != (self.B, self.N, self.A):
             raise ValueError("selection_window must be [B, N, A]")
-        if out is None:
-            out = torch.empty((self.B, self.N), dtype=torch.int32, device=self.device)
-
-        def opt(t, dt):
-            return None if t is None else torch.as_tensor(t, dtype=dt, device=self.device).reshape(self.B, self.N).contiguous()
-        dc, dk, dch = opt(draw_counter, torch.int32), opt(draw_keep, torch.float64), opt(draw_choice, torch.int32)
+        out = self._out(out)
+        dc, dk, dch = self._draws(draw_counter, draw_keep, draw_choice)
         self._t += 1
         st = self.lib.diral_sps_step(self.B * self.N, self.A, _ptr(w), _ptr(self.prev_action), _ptr(self.counter),
                                      self.threshold, self.inc_db, self.keep_prob, _ptr(dc), _ptr(dk), _ptr(dch),
-                                     (int(self.seed) * 1000003 + self._t) & (2**64 - 1), _ptr(out), self._stream())
-        if st != 0:
-            raise DiralError(st, "diral_sps_step")
-        self._keep = (w, dc, dk, dch)
-        return out
-
-
-    def _draws(self, draw_counter, draw_keep, draw_choice):
-        def opt(t, dt):
-            return None if t is None else torch.as_tensor(t, dtype=dt, device=self.device).reshape(self.B, self.N).contiguous()
-        return opt(draw_counter, torch.int32), opt(draw_keep, torch.float64), opt(draw_choice, torch.int32)
+                                     policy_seed(self.seed, self._t), _ptr(out), self._stream())
+        return self._launched(st, "diral_sps_step", out, w, dc, dk, dch)
 
     def window_from_chobs(self, chobs: torch.Tensor, actions: torch.Tensor) -> torch.Tensor:
         """`diral_sps_window_from_chobs`: the RSSI-like window [B, N, A] float64 from the env's channel
@@ -82,10 +85,8 @@ class SpsPolicy:
         c = chobs.contiguous()
         a = actions.to(device=self.device, dtype=torch.int32).contiguous()
         out = torch.empty((self.B, self.N, self.A), dtype=torch.float64, device=self.device)
-        st = self.lib.diral_sps_window_from_chobs(self.B * self.N, self.A, _ptr(c), 1 if c.dtype == torch.float64 else 0,
-                                                  _ptr(a), _ptr(out), self._stream())
-        if st != 0:
-            raise DiralError(st, "diral_sps_window_from_chobs")
+        check_status(self.lib.diral_sps_window_from_chobs(self.B * self.N, self.A, _ptr(c), dtype_code(c), _ptr(a), _ptr(out),
+                                                          self._stream()), "diral_sps_window_from_chobs")
         return out
 
     def step_from_chobs(self, chobs: torch.Tensor, actions: torch.Tensor, draw_counter=None, draw_keep=None,
@@ -93,43 +94,29 @@ class SpsPolicy:
         """One SPS step straight from the env's channel observation [B, N, A] (float32 / float64) and
         the actions of the slot that produced it: `window_from_chobs` + `step` in ONE launch, with the
         window built only for the agents that re-select (`diral_sps_step_chobs`).  A <= 256."""
-        if chobs.dtype not in (torch.float32, torch.float64) or tuple(chobs.shape) != (self.B, self.N, self.A):
-            raise ValueError("chobs must be float32/float64 [B, N, A]")
-        c = chobs.contiguous()
-        a = actions.to(device=self.device, dtype=torch.int32).contiguous()
-        if out is None:
-            out = torch.empty((self.B, self.N), dtype=torch.int32, device=self.device)
+        c, a = self._chobs_in(chobs, actions)
+        out = self._out(out)
         dc, dk, dch = self._draws(draw_counter, draw_keep, draw_choice)
         self._t += 1
-        st = self.lib.diral_sps_step_chobs(self.B * self.N, self.A, _ptr(c), 1 if c.dtype == torch.float64 else 0, _ptr(a),
+        st = self.lib.diral_sps_step_chobs(self.B * self.N, self.A, _ptr(c), dtype_code(c), _ptr(a),
                                            _ptr(self.prev_action), _ptr(self.counter), self.threshold, self.inc_db,
                                            self.keep_prob, _ptr(dc), _ptr(dk), _ptr(dch),
-                                           (int(self.seed) * 1000003 + self._t) & (2**64 - 1), _ptr(out), self._stream())
-        if st != 0:
-            raise DiralError(st, "diral_sps_step_chobs")
-        self._keep = (c, a, dc, dk, dch)
-        return out
+                                           policy_seed(self.seed, self._t), _ptr(out), self._stream())
+        return self._launched(st, "diral_sps_step_chobs", out, c, a, dc, dk, dch)
 
     def step_from_chobs_clocked(self, chobs: torch.Tensor, actions: torch.Tensor, clock, offset: int = 0,
                                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """`step_from_chobs` with device draws seeded by (seed, offset) + the value of a device slot counter
         (`diral_sps_step_chobs_clocked`): the by-value arguments of a captured launch stay fixed while the draws move on
         with the counter (diral_amd/rollout.py).  `clock`: a rollout.SlotClock or an int64 device tensor."""
-        if chobs.dtype not in (torch.float32, torch.float64) or tuple(chobs.shape) != (self.B, self.N, self.A):
-            raise ValueError("chobs must be float32/float64 [B, N, A]")
-        c = chobs.contiguous()
-        a = actions.to(device=self.device, dtype=torch.int32).contiguous()
-        if out is None:
-            out = torch.empty((self.B, self.N), dtype=torch.int32, device=self.device)
+        c, a = self._chobs_in(chobs, actions)
+        out = self._out(out)
         ct = clock.t if hasattr(clock, "t") else clock
-        st = self.lib.diral_sps_step_chobs_clocked(self.B * self.N, self.A, _ptr(c), 1 if c.dtype == torch.float64 else 0, _ptr(a),
+        st = self.lib.diral_sps_step_chobs_clocked(self.B * self.N, self.A, _ptr(c), dtype_code(c), _ptr(a),
                                                    _ptr(self.prev_action), _ptr(self.counter), self.threshold, self.inc_db,
-                                                   self.keep_prob, (int(self.seed) * 1000003 + int(offset)) & (2**64 - 1),
-                                                   _ptr(ct), _ptr(out), self._stream())
-        if st != 0:
-            raise DiralError(st, "diral_sps_step_chobs_clocked")
-        self._keep = (c, a, ct)
-        return out
+                                                   self.keep_prob, policy_seed(self.seed, offset), _ptr(ct), _ptr(out),
+                                                   self._stream())
+        return self._launched(st, "diral_sps_step_chobs_clocked", out, c, a, ct)
 
 
 def rssi_from_channel_obs(chobs: torch.Tensor, actions: torch.Tensor) -> torch.Tensor:

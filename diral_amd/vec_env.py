@@ -18,8 +18,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .config import (DT_F32, DT_F64, ERR_HIP, M_COLUMNS, OK, OPT_ENV_OFFSET, OPT_KERNEL_PATH, PATH_AUTO,
-                     PATH_GENERAL, PATH_LARGE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, ConfigError, EnvConfig)
+from ._tensors import MSG_OUT, _ptr, check_tensor, dtype_code, policy_seed, seed64
+from .config import (DT_F32, DT_F64, ERR_HIP, ERR_UNSUPPORTED, M_COLUMNS, OK, OPT_ENV_OFFSET, OPT_KERNEL_PATH, PATH_AUTO,
+                     PATH_GENERAL, PATH_LARGE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, ConfigError, DiralRollout,
+                     DiralSlotPolicy, EnvConfig)
 
 # MA_NeighborTableEntry (envs/ma_messages_pb2.py:195-230) as a host view of DiralNeighborEntry
 ENTRY_DTYPE = np.dtype([("pos_x", "<f4"), ("pos_y", "<f4"), ("seq_num", "<i4"), ("last_update", "<i4")])
@@ -47,8 +49,23 @@ class DiralError(RuntimeError):
         super().__init__(msg)
 
 
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
+def check_status(st: int, where: str, detail: str = "") -> None:
+    if st != OK:
+        raise DiralError(st, where, detail)
+
+
+def driver_shape(env, reward: torch.Tensor, actions: torch.Tensor, *, shaped: torch.Tensor, sum_r: torch.Tensor,
+                 collision: torch.Tensor, global_reward_avg: bool = False, ia=None, sum_ia_prev=None, ia_sum=None,
+                 ia_penalty=None, pen_counter=None, prev_actions=None, pen_threshold: int = 0, pen_value: float = 0.0) -> None:
+    """main_test.py:171-206 as one launch of `diral_driver_shape` (include/diral_env.h) on `env`'s current stream; the
+    tensors are the caller's, contiguous.  `sum_ia_prev` switches the information-age term on (flag bit 1, with `ia`
+    [B, 100] int32), `pen_counter` / `prev_actions` the stuck penalty (flag bit 2)."""
+    B, N = reward.shape
+    flags = (1 if global_reward_avg else 0) | (2 if sum_ia_prev is not None else 0) | (4 if pen_counter is not None else 0)
+    st = env.lib.diral_driver_shape(B, N, env.A, _ptr(reward), dtype_code(reward), _ptr(actions), _ptr(ia), _ptr(sum_ia_prev),
+                                    _ptr(pen_counter), _ptr(prev_actions), flags, int(pen_threshold), float(pen_value),
+                                    _ptr(shaped), _ptr(sum_r), _ptr(collision), _ptr(ia_sum), _ptr(ia_penalty), env._stream())
+    check_status(st, "diral_driver_shape")
 
 
 class VecV2VEnv:
@@ -140,8 +157,8 @@ class VecV2VEnv:
                 tns = out_buffers.get(k)
                 if tns is None and k == "chobs":
                     continue
-                if tns is None or tuple(tns.shape) != shape or tns.dtype != dt or tns.device != self.device or not tns.is_contiguous():
-                    raise ValueError("out_buffers[%r] must be a contiguous %s %s tensor on %s" % (k, shape, dt, self.device))
+                check_tensor("out_buffers[%r]" % k, tns, dt, shape, self.device,
+                             "%(name)s must be a contiguous %(shape)s %(dtype)s tensor on %(device)s")
             self._ring = [dict(obs=out_buffers["obs"], rew=out_buffers["rew"], done=out_buffers["done"],
                                chobs=out_buffers.get("chobs"))]
         else:
@@ -161,6 +178,11 @@ class VecV2VEnv:
         self._spec: Optional[tuple] = None      # what the speculative state of the last my_step* is valid for
         self._vel_calls = 0                     # default-seed counter of update_velocity()
         self._clock: Optional[torch.Tensor] = None   # device slot clock installed by set_clock(); kept alive here
+        self._keep: Dict[str, tuple] = {}       # per call name: what the last launch's raw pointers refer to
+        self._last_actions: Optional[torch.Tensor] = None
+        self._policy_needs_chobs = False        # step_policy met a configuration that does not run fused
+        # section order of obtain_state (test_env.py:527-583): ... velocity, fingerprint last
+        self._fp_offset = self.S - 2
 
     # ---- lifetime -------------------------------------------------------------
     def close(self) -> None:
@@ -188,12 +210,42 @@ class VecV2VEnv:
     def _stream(self) -> ctypes.c_void_p:
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
-    def _ok(self, st: int, where: str) -> None:
+    def _ok(self, st: int, where: str, advanced: int = 0) -> None:
+        """Raise on a bad status; `advanced`: by how many sets the call had rotated the output ring (`_bind_slot`) - a
+        refused call has launched nothing, so the ring goes back to where it was."""
         if st != OK:
-            detail = ""
-            if st == ERR_HIP:
-                detail = self.lib.diral_env_last_hip_error(self._h).decode()
-            raise DiralError(st, where, detail)
+            if advanced:
+                self._bind_slot(-advanced, False)
+            check_status(st, where, self.lib.diral_env_last_hip_error(self._h).decode() if st == ERR_HIP else "")
+
+    def _bind_slot(self, advance: int, want_chobs: bool) -> None:
+        """Rotate the output ring by `advance` sets and bind `_obs` / `_rew` / `_done` / `_chobs` to the set it lands on
+        (its channel-observation tensor is allocated when first asked for); the speculative state is void from here."""
+        if self.io_ring > 1:
+            self._ri = (self._ri + advance) % self.io_ring
+        slot = self._ring[self._ri]
+        if want_chobs and slot["chobs"] is None:
+            slot["chobs"] = torch.zeros((self.B, self.N, self.CW), dtype=self.out_dtype, device=self.device)
+        self._obs, self._rew, self._done, self._chobs = slot["obs"], slot["rew"], slot["done"], slot["chobs"]
+        self._spec = None
+
+    def _shaping(self, q, where: str, global_reward_avg: bool, stuck_penalty: Optional[tuple], shaped, sum_r, collision,
+                 vel_seed: int):
+        """The fields DiralSlotPolicy and DiralRollout share: flags, the stuck penalty (its tensors checked), outputs."""
+        q.struct_bytes = ctypes.sizeof(q)
+        q.shape_flags = 1 if global_reward_avg else 0
+        if stuck_penalty is not None:
+            thr, val, cnt, prev = stuck_penalty
+            for name, a in (("counter", cnt), ("prev_actions", prev)):
+                check_tensor("%s: stuck_penalty %s" % (where, name), a, torch.int32, (self.B, self.N), self.device)
+            if shaped is None:
+                raise ValueError("%s: stuck_penalty needs shaped_out" % where)
+            q.shape_flags |= 4
+            q.pen_threshold, q.pen_value = int(thr), float(val)
+            q.pen_counter, q.pen_prev_actions = _ptr(cnt), _ptr(prev)
+        q.shaped_out, q.sum_r_out, q.collision_out = _ptr(shaped), _ptr(sum_r), _ptr(collision)
+        q.vel_seed = seed64(vel_seed)
+        return q
 
     def _f64(self, a, shape) -> Optional[torch.Tensor]:
         if a is None:
@@ -237,9 +289,9 @@ class VecV2VEnv:
         (`diral_env_set_clock`).  The env keeps a reference to the tensor: the C handle only stores its raw
         address, and a freed block would be handed out again by the caching allocator."""
         if clock is not None:
-            if (not isinstance(clock, torch.Tensor) or clock.dtype != torch.int64 or clock.numel() != 1
-                    or clock.device != self.device or not clock.is_contiguous()):
-                raise ValueError("the slot clock must be a contiguous int64 tensor of one element on %s" % (self.device,))
+            one = isinstance(clock, torch.Tensor) and clock.numel() == 1       # (of any rank)
+            check_tensor("the slot clock", clock, torch.int64, tuple(clock.shape) if one else None, self.device,
+                         "%(name)s must be a contiguous int64 tensor of one element on %(device)s")
         self._ok(self.lib.diral_env_set_clock(self._h, ctypes.c_void_p(clock.data_ptr()) if clock is not None else None),
                  "diral_env_set_clock")
         self._clock = clock
@@ -283,8 +335,8 @@ class VecV2VEnv:
         when x0/y0/v0 are given."""
         shape = (self.B, self.N)
         x0, y0, v0 = self._f64(x0, shape), self._f64(y0, shape), self._f64(v0, shape)
-        self._keep = (x0, y0, v0)
-        self._ok(self.lib.diral_env_reset(self._h, _ptr(x0), _ptr(y0), _ptr(v0), int(seed) & (2**64 - 1),
+        self._keep["reset"] = (x0, y0, v0)
+        self._ok(self.lib.diral_env_reset(self._h, _ptr(x0), _ptr(y0), _ptr(v0), seed64(seed),
                                           self._stream()), "diral_env_reset")
         self.t = 0
         self._spec = None
@@ -319,7 +371,7 @@ class VecV2VEnv:
         out = torch.empty((self.B, self.N), dtype=torch.int32, device=self.device)
         if seed is None:
             seed = int(torch.randint(0, 2**62, (1,)).item())
-        self._ok(self.lib.diral_env_sample(self._h, _ptr(out), int(seed) & (2**64 - 1), self._stream()),
+        self._ok(self.lib.diral_env_sample(self._h, _ptr(out), seed64(seed), self._stream()),
                  "diral_env_sample")
         return out
 
@@ -344,9 +396,8 @@ class VecV2VEnv:
         a_next = torch.empty((self.B, self.N), dtype=torch.int32, device=self.device)
         rin = None if rew_in is None else self._f64(rew_in, (self.B, self.N))
         self._spec = None
-        st = self.lib.diral_env_prefill_mode(self._h, step_mode, _ptr(a), K, int(seed) & (2**64 - 1),
-                                             _ptr(states) if states is not None else None,
-                                             self._dt, _ptr(a_all), _ptr(a_next), _ptr(rin) if rin is not None else None,
+        st = self.lib.diral_env_prefill_mode(self._h, step_mode, _ptr(a), K, seed64(seed), _ptr(states),
+                                             self._dt, _ptr(a_all), _ptr(a_next), _ptr(rin),
                                              float(episode), float(eps), self._stream())
         self._ok(st, "diral_env_prefill_mode")
         if rin is not None:
@@ -355,19 +406,13 @@ class VecV2VEnv:
 
     def _step(self, mode: int, actions: torch.Tensor, t: int, episode: float = 0.0, eps: float = 1.0,
               want_chobs: bool = False, want_obs: bool = True, stream: Optional[ctypes.c_void_p] = None):
-        if self.io_ring > 1:
-            self._ri = (self._ri + 1) % self.io_ring
-        slot = self._ring[self._ri]
-        if want_chobs and slot["chobs"] is None:
-            slot["chobs"] = torch.zeros((self.B, self.N, self.CW), dtype=self.out_dtype, device=self.device)
-        self._obs, self._rew, self._done, self._chobs = slot["obs"], slot["rew"], slot["done"], slot["chobs"]
-        self._spec = None
+        self._bind_slot(1, want_chobs)
         st = self.lib.diral_env_step(self._h, mode, _ptr(actions), int(t),
                                      _ptr(self._obs) if (want_obs and self.S > 0) else None,
                                      _ptr(self._rew), _ptr(self._done),
                                      _ptr(self._chobs) if want_chobs else None,
                                      self._dt, float(episode), float(eps), self._stream() if stream is None else stream)
-        self._ok(st, "diral_env_step")
+        self._ok(st, "diral_env_step", 1)
         return self._obs, self._rew, self._done
 
     def step_policy(self, actions: torch.Tensor, t: int, policy, actions_out: torch.Tensor, shaped_out=None, sum_r_out=None,
@@ -399,87 +444,56 @@ class VecV2VEnv:
         to K one-slot calls; raises DiralError(UNSUPPORTED) where the fused kernel does not apply.  `mode` = STEP_MY_STEP_CH
         (the PRR reward of `enable_channel`, reward_design 2 ... 4) runs K > 1 slots in one launch at 8 <= N <= 64 too
         (profiles/kslots_ch/); with slots = 1 it stays three launches, and 64 < N <= 256 refuses it."""
-        from .config import DiralSlotPolicy, ERR_UNSUPPORTED
         K = int(slots)
         if K < 1:
             raise ValueError("step_policy: slots must be >= 1")
         # raw pointers cross the C-ABI: what they point at is checked here (an int64 or strided tensor would be read as
         # garbage; `actions_out` aliasing `actions` lets the fused kernel's policy wave overwrite actions the
         # three-launch form still reads)
-        for name, a in (("actions", actions), ("actions_out", actions_out)):
-            if not isinstance(a, torch.Tensor) or a.dtype != torch.int32 or tuple(a.shape) != (self.B, self.N) \
-                    or not a.is_contiguous() or a.device != self.device:
-                raise ValueError("step_policy: %s must be a contiguous int32 tensor [%d, %d] on %s" %
-                                 (name, self.B, self.N, self.device))
+        check_tensor("step_policy: actions", actions, torch.int32, (self.B, self.N), self.device)
+        check_tensor("step_policy: actions_out", actions_out, torch.int32, (self.B, self.N), self.device)
         if actions_out.data_ptr() == actions.data_ptr():
             raise ValueError("step_policy: actions_out must not alias actions")
         lead = (K,) if K > 1 else ()
-        for name, a, shape in (("shaped_out", shaped_out, lead + (self.B, self.N)), ("sum_r_out", sum_r_out, lead + (self.B,)),
-                               ("collision_out", collision_out, lead + (self.B,))):
-            if a is not None and (a.dtype != self.out_dtype or tuple(a.shape) != shape or not a.is_contiguous()
-                                  or a.device != self.device):
-                raise ValueError("step_policy: %s must be a contiguous %s tensor %s on %s" %
-                                 (name, self.out_dtype, shape, self.device))
-        if self.io_ring > 1:
-            self._ri = (self._ri + 1) % self.io_ring
-        slot = self._ring[self._ri]
+        for name, a, shape in (("step_policy: shaped_out", shaped_out, lead + (self.B, self.N)),
+                               ("step_policy: sum_r_out", sum_r_out, lead + (self.B,)),
+                               ("step_policy: collision_out", collision_out, lead + (self.B,))):
+            if a is not None:
+                check_tensor(name, a, self.out_dtype, shape, self.device, MSG_OUT)
+        q = self._shaping(DiralSlotPolicy(), "step_policy", global_reward_avg, stuck_penalty, shaped_out, sum_r_out,
+                          collision_out, vel_seed)
+        q.sps_prev_action = _ptr(policy.prev_action); q.sps_counter = _ptr(policy.counter)
+        q.rssi_threshold, q.inc_db, q.keep_prob = policy.threshold, policy.inc_db, policy.keep_prob
+        if clock is not None:
+            q.seed = policy_seed(policy.seed, seed_offset or 0)
+            q.seed_clock = _ptr(clock.t if hasattr(clock, "t") else clock)
+        else:
+            q.seed = policy_seed(policy.seed, policy._t + 1)
+        q.actions_out = _ptr(actions_out)
+        q.slots = K
         # (whether the slot runs fused is the library's decision - kernel family, step mode, run-time extras; a call
         # without a channel-observation buffer that cannot run fused comes back DIRAL_ERR_UNSUPPORTED before anything
         # is launched, and is repeated with the buffer from then on)
         # K > 1 runs fused or not at all (DIRAL_ERR_UNSUPPORTED): no channel-observation buffer unless asked for - at
         # 64 < N <= 256 the K-slot kernel would otherwise write [B, N, A] for nothing on every launch
-        fusable = K > 1 or ((self.N <= 64 and self.N >= 8 and self.A <= 64) and not getattr(self, "_policy_needs_chobs", False))
-        if (want_chobs or not fusable) and slot["chobs"] is None:
-            slot["chobs"] = torch.zeros((self.B, self.N, self.CW), dtype=self.out_dtype, device=self.device)
-        self._obs, self._rew, self._done, self._chobs = slot["obs"], slot["rew"], slot["done"], slot["chobs"]
-        self._spec = None
-        q = DiralSlotPolicy()
-        q.struct_bytes = ctypes.sizeof(DiralSlotPolicy)
-        q.shape_flags = 1 if global_reward_avg else 0
-        if stuck_penalty is not None:
-            thr, val, cnt, prev = stuck_penalty
-            for name, a in (("counter", cnt), ("prev_actions", prev)):
-                if not isinstance(a, torch.Tensor) or a.dtype != torch.int32 or tuple(a.shape) != (self.B, self.N) \
-                        or not a.is_contiguous() or a.device != self.device:
-                    raise ValueError("step_policy: stuck_penalty %s must be a contiguous int32 tensor [%d, %d] on %s" %
-                                     (name, self.B, self.N, self.device))
-            if shaped_out is None:
-                raise ValueError("step_policy: stuck_penalty needs shaped_out")
-            q.shape_flags |= 4
-            q.pen_threshold, q.pen_value = int(thr), float(val)
-            q.pen_counter, q.pen_prev_actions = _ptr(cnt), _ptr(prev)
-        q.shaped_out = _ptr(shaped_out); q.sum_r_out = _ptr(sum_r_out); q.collision_out = _ptr(collision_out)
-        q.sps_prev_action = _ptr(policy.prev_action); q.sps_counter = _ptr(policy.counter)
-        q.rssi_threshold, q.inc_db, q.keep_prob = policy.threshold, policy.inc_db, policy.keep_prob
-        if clock is not None:
-            ct = clock.t if hasattr(clock, "t") else clock
-            q.seed = (int(policy.seed) * 1000003 + int(seed_offset or 0)) & (2**64 - 1)
-            q.seed_clock = _ptr(ct)
-        else:
-            q.seed = (int(policy.seed) * 1000003 + policy._t + 1) & (2**64 - 1)
-        q.actions_out = _ptr(actions_out)
-        q.slots = K
-        q.vel_seed = int(vel_seed) & (2**64 - 1)
-        use_chobs = self._chobs if (want_chobs or not fusable) else None
+        fusable = K > 1 or ((self.N <= 64 and self.N >= 8 and self.A <= 64) and not self._policy_needs_chobs)
+        use_chobs = want_chobs or not fusable
+        self._bind_slot(1, use_chobs)
 
         def call(chobs):
             return self.lib.diral_env_step_policy(self._h, self.step_mode if mode is None else mode, _ptr(actions), int(t),
                                                   _ptr(self._obs) if (want_obs and self.S > 0) else None, _ptr(self._rew),
                                                   _ptr(self._done), _ptr(chobs), self._dt, ctypes.byref(q), self._stream())
-        st = call(use_chobs)
-        if st == ERR_UNSUPPORTED and use_chobs is None and K == 1:  # not a fused configuration, nothing launched
+        st = call(self._chobs if use_chobs else None)
+        if st == ERR_UNSUPPORTED and not use_chobs and K == 1:  # not a fused configuration, nothing launched
             self._policy_needs_chobs = True
-            if slot["chobs"] is None:
-                slot["chobs"] = torch.zeros((self.B, self.N, self.CW), dtype=self.out_dtype, device=self.device)
-            self._chobs = slot["chobs"]
+            self._bind_slot(0, True)
             st = call(self._chobs)
-        if st != OK and self.io_ring > 1:
-            self._ri = (self._ri - 1) % self.io_ring            # nothing was launched: the ring slot is not consumed either
-        self._ok(st, "diral_env_step_policy")
+        self._ok(st, "diral_env_step_policy", 1)
         if clock is None:
             policy._t += K        # only once the call is in: slot k drew with seed + k, what K one-slot calls are given; a
                                   # refused call (DIRAL_ERR_UNSUPPORTED: nothing launched) leaves the draw counter alone
-        self._keep_policy = (q, actions, actions_out, shaped_out, sum_r_out, collision_out, clock, stuck_penalty)
+        self._keep["step_policy"] = (q, actions, actions_out, shaped_out, sum_r_out, collision_out, clock, stuck_penalty)
         return self._obs, self._rew, self._done
 
     def rollout(self, actions_seq, t: Optional[int] = None, mode="my_step", states: Optional[str] = "last",
@@ -500,7 +514,6 @@ class VecV2VEnv:
         K `step` + `diral_driver_shape` (+ `update_velocity`) calls; the env's slot counter moves on by K.  Raises
         DiralError(ERR_UNSUPPORTED) with nothing launched and the env untouched where the slot loops do not apply
         (include/diral_env.h lists them; diral_amd.driver.DriverLoop.rollout loops then)."""
-        from .config import DiralRollout
         step_mode = _MODES.get(mode)
         if step_mode not in (STEP_MY_STEP, STEP_MY_STEP_CH):
             raise ValueError("rollout: mode must be 'my_step' or 'my_step_ch'")
@@ -517,38 +530,20 @@ class VecV2VEnv:
         K = int(seq.shape[0])
         if t is None:
             t = self.t
-        ri = (self._ri + K) % self.io_ring
-        slot = self._ring[ri]
+        o = dict(dtype=self.out_dtype, device=self.device)
+        shaped, sum_r, coll = torch.empty((K, self.B, self.N), **o), torch.empty((K, self.B), **o), torch.empty((K, self.B), **o)
+        q = self._shaping(DiralRollout(), "rollout", global_reward_avg, stuck_penalty, shaped, sum_r, coll, vel_seed)
+        self._bind_slot(K, False)
         want_states = states is not None and self.S > 0
         if states == "all" and want_states:
             st_out = torch.empty((K, self.B, self.N, self.S), dtype=self.out_dtype, device=self.device)
         else:
-            st_out = slot["obs"] if want_states else None
-        o = dict(dtype=self.out_dtype, device=self.device)
-        shaped, sum_r, coll = torch.empty((K, self.B, self.N), **o), torch.empty((K, self.B), **o), torch.empty((K, self.B), **o)
-        q = DiralRollout()
-        q.struct_bytes = ctypes.sizeof(DiralRollout)
-        q.shape_flags = 1 if global_reward_avg else 0
-        if stuck_penalty is not None:
-            thr, val, cnt, prev = stuck_penalty
-            for name, a in (("counter", cnt), ("prev_actions", prev)):
-                if not isinstance(a, torch.Tensor) or a.dtype != torch.int32 or tuple(a.shape) != (self.B, self.N) \
-                        or not a.is_contiguous() or a.device != self.device:
-                    raise ValueError("rollout: stuck_penalty %s must be a contiguous int32 tensor [%d, %d] on %s" %
-                                     (name, self.B, self.N, self.device))
-            q.shape_flags |= 4
-            q.pen_threshold, q.pen_value = int(thr), float(val)
-            q.pen_counter, q.pen_prev_actions = _ptr(cnt), _ptr(prev)
-        q.shaped_out, q.sum_r_out, q.collision_out = _ptr(shaped), _ptr(sum_r), _ptr(coll)
-        q.vel_seed = int(vel_seed) & (2**64 - 1)
+            st_out = self._obs if want_states else None
         st = self.lib.diral_env_rollout(self._h, step_mode, _ptr(seq), K, int(t), _ptr(st_out), 1 if states == "all" else 0,
-                                        _ptr(slot["rew"]), _ptr(slot["done"]), self._dt, ctypes.byref(q), self._stream())
-        self._ok(st, "diral_env_rollout")            # (a refused call has launched nothing: the bookkeeping below stays as it was)
-        self._ri = ri
-        self._obs, self._rew, self._done, self._chobs = slot["obs"], slot["rew"], slot["done"], slot["chobs"]
-        self._spec = None
+                                        _ptr(self._rew), _ptr(self._done), self._dt, ctypes.byref(q), self._stream())
+        self._ok(st, "diral_env_rollout", K)            # (a refused call has launched nothing: the ring is back where it was)
         self.t = int(t) + K
-        self._keep_rollout = (q, seq, stuck_penalty)
+        self._keep["rollout"] = (q, seq, stuck_penalty)
         return dict(states=st_out, reward=self._rew, done=self._done, shaped=shaped, sum_r=sum_r, collision=coll)
 
     def step(self, actions, t: Optional[int] = None, episode: float = 0.0, epsilon: float = 1.0
@@ -622,14 +617,9 @@ class VecV2VEnv:
             self._write_fingerprint(float(episode), float(eps))
         return self._obs
 
-    def _fp_offset(self) -> int:
-        # section order of obtain_state (test_env.py:527-583): ... velocity, fingerprint last
-        return self.S - 2
-
     def _write_fingerprint(self, episode: float, eps: float) -> None:
-        o = self._fp_offset()
-        self._obs[:, :, o] = episode
-        self._obs[:, :, o + 1] = eps
+        self._obs[:, :, self._fp_offset] = episode
+        self._obs[:, :, self._fp_offset + 1] = eps
 
     def obtain_state(self, obs, acts, rewards, episode_number: float = 0, epsilon: float = 1) -> torch.Tensor:
         """test_env.py:527-583 on the current tables/positions; [B, N, S]."""
@@ -656,7 +646,7 @@ class VecV2VEnv:
             self._vel_calls += 1
             seed = self._vel_calls * 2654435761 + 12345
         self._spec = None
-        self._ok(self.lib.diral_env_update_velocity(self._h, _ptr(d), int(seed) & (2**64 - 1), self._stream()),
+        self._ok(self.lib.diral_env_update_velocity(self._h, _ptr(d), seed64(seed), self._stream()),
                  "diral_env_update_velocity")
 
     def load_saved_positions(self, x_positions=None) -> None:
@@ -672,7 +662,6 @@ class VecV2VEnv:
             self._ok(self.lib.diral_env_set_trace(self._h, None, 0, 0, self._stream()), "diral_env_set_trace")
             return
         if isinstance(x_positions, str):
-            import numpy as np
             x_positions = np.load(x_positions)
         tr = torch.as_tensor(x_positions, dtype=torch.float64, device=self.device).contiguous()
         if tr.dim() == 2 and tr.shape[1] == self.N:

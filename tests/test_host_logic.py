@@ -286,3 +286,23 @@ def test_byte_models_of_the_roofline_bookkeeping():
     assert m2["resident_bytes"] < INFINITY_CACHE_BYTES < m4["resident_bytes"] < m3["resident_bytes"]
     assert m2["reads_served_by"].startswith("infinity cache") and m4["reads_served_by"].startswith("hbm")
     assert m2["output_bytes"] == 4096 * (4 * 64 + 4 * 64 * 52 + 4 * 64 * 32)
+
+
+def test_tensor_contract_checker_and_policy_seed():
+    """The one check of a tensor whose raw address crosses the C-ABI (diral_amd/_tensors.py), as `step_policy` calls it
+    for `actions`: wrong dtype, wrong shape, strided view, wrong device - each the ValueError `step_policy` has always
+    raised, word for word; and the seed of the SPS policy's draw number k."""
+    import torch
+    from diral_amd._tensors import check_tensor, policy_seed
+    fmt = "step_policy: %s must be a contiguous int32 tensor [%d, %d] on %s"
+    cpu, gpu = torch.device("cpu"), torch.device("cuda", 0)          # (the GPU device is only compared, never used)
+    good = torch.zeros((2, 3), dtype=torch.int32)
+    bad = [(good.long(), cpu), (torch.zeros((3, 2), dtype=torch.int32), cpu), (torch.zeros((3, 2), dtype=torch.int32).t(), cpu),
+           (good, gpu)]
+    for t, dev in bad:
+        with pytest.raises(ValueError) as exc:
+            check_tensor("step_policy: actions", t, torch.int32, (2, 3), dev)
+        assert str(exc.value) == fmt % ("actions", 2, 3, dev)
+    assert check_tensor("step_policy: actions", good, torch.int32, (2, 3), cpu) is None
+    for seed, k in ((0, 0), (2**63, 5), (-1, 0)):
+        assert policy_seed(seed, k) == (seed * 1000003 + k) & (2**64 - 1)
