@@ -14,9 +14,10 @@
 //     ds_bpermute_b32 costs ~5.5 LDS cycles; one env-slot needs ~1800).
 // So here:
 //   * closest-transmitter search without LDS: lane = vehicle, a transmitter's
-//     position is broadcast with v_readlane; each wave owns the resources
-//     i == wave (mod 4) and walks their transmitters in ascending id with a
-//     strict '<' (the reference's lowest-id tie-break, network.py:387-392);
+//     position is broadcast with v_readlane; each wave owns the groups of four
+//     resources g == wave (mod 4), g = i / 4, and walks their transmitters in
+//     ascending id with a strict '<' (the reference's lowest-id tie-break,
+//     network.py:387-392);
 //   * gossip merge key[u] = max(key[u], key[m_i(u)]): one ds_bpermute + max per
 //     (resource, column PAIR): two columns travel as 16-bit (rank, source) keys in
 //     one register (exactness argument and fallback at the merge loop);
@@ -50,16 +51,16 @@ struct FastLds {
 };
 // row stride (elements) of the channel-observation staging array [vehicle][resource] of the RICH
 // instantiations: a multiple of 4 elements, so that the write-out reads a 16-byte piece of a row
-// with ONE ds_read_b128 (f32) / ds_read_b128 of two doubles; the 4 extra elements skew the rows
-// over the banks (the column writes of P1, lane = vehicle, then conflict 4-way: 8 cheap writes
-// per wave)
+// with ONE ds_read_b128 (f32) / ds_read_b128 of two doubles - and P1 (lane = vehicle) writes a group of
+// four resources with one ds_write_b128 (fast_stage_store4); the 4 extra elements skew the rows over
+// the banks
 __host__ __device__ constexpr int fast_stage_stride(int A) { return (A <= 32 ? 32 : 64) + 4; }
 // histogram row stride (words): odd (lane = row: conflict-free increments) and at least K + 1 - slot K of a row is a
 // spare that takes the increments of entries that do not count (the column loop needs no exec-mask branch then)
 __host__ __device__ constexpr int fast_hist_stride(int K) { return (K + 1) | 1; }
 // gather-source table [vehicle][resource], one BYTE per entry (source lane * 4, the ds_bpermute address, <= 252): the
 // merge reads the sources of FOUR consecutive resources with one ds_read_b32; the row stride of a32 + 4 bytes = 9 / 17
-// words puts the 64 lanes' words - and the byte writes of P1, lane = row - on distinct banks
+// words puts the 64 lanes' words - read by the merge, written by P1 a group at a time, lane = row - on distinct banks
 __host__ __device__ constexpr int fast_mtab_stride(int A) { return (A <= 32 ? 32 : 64) + 4; }
 __host__ __device__ inline FastLds fast_lds_layout(int K, int A, bool rich, bool out64, bool flat, bool ratios = true, bool pol = false) {
   FastLds l;
@@ -174,6 +175,16 @@ __device__ DIRAL_OUTLINE void fast_sps_decide(const T* stage, int SA, int A, int
     q->sps_counter[i] = cnt;
     q->actions_out[i] = action;
   }
+}
+
+// Four consecutive staged observations of one vehicle (P1, a group of four resources) into its row of the staging
+// array: one ds_write_b128 (float), two (double).  `row4` is 16-byte aligned (fast_stage_stride: a multiple of 4).
+__device__ __forceinline__ void fast_stage_store4(float* row4, const float (&v)[4]) {
+  *reinterpret_cast<float4*>(row4) = make_float4(v[0], v[1], v[2], v[3]);
+}
+__device__ __forceinline__ void fast_stage_store4(double* row4, const double (&v)[4]) {
+  *reinterpret_cast<double2*>(row4) = make_double2(v[0], v[1]);
+  *reinterpret_cast<double2*>(row4 + 2) = make_double2(v[2], v[3]);
 }
 
 #ifdef DIRAL_TIMING

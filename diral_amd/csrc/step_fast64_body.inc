@@ -280,8 +280,13 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
 #endif /* DIRAL_FAST_KSLOTS */
   DIRAL_FSTAMP(1);
 
-  // ---- P1: per owned resource i = wave + 4*s: transmitter set, closest in-range
-  // transmitter per vehicle, gather sources, collision reward ----------------------
+  // ---- P1: per owned resource: transmitter set, closest in-range transmitter per vehicle, gather sources, collision
+  // reward.  Resources are dealt to waves in GROUPS of four - group g = resources 4g .. 4g + 3, wave w owns the groups
+  // w, w + 4, ... - the way the merge reads the gather table (one ds_read_b32 per vehicle and group): what a group leaves
+  // goes out packed, one ds_write_b32 of four source bytes and one ds_write_b128 (two for float64) of four staged
+  // observations per lane, and the four resources of a group are unrolled - no loop or address work per resource.
+  // Everything else P1 leaves is keyed by resource (s_rv) or by transmitter (s_inr, s_rtx, the arrival stamps) and a
+  // vehicle transmits on one resource: it does not matter which wave owns it. ----------------------
   const bool dist_obs = RICH && (p.chobs_mode & 2) != 0;
   const bool rd2_lanes = FLAT && !CH && p.reward_design == 2 && !(p.flags & DIRAL_F_TOY_WEIGHTS) && !(EXTRA && p.design);
 #ifndef DIRAL_FAST_KSLOTS
@@ -292,8 +297,17 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   const bool need_rw = !CH && !(EXTRA && p.design) && !rd2_lanes;      // collision reward per resource, here (uniform)
   mtab_t* const mtab_row = s_mtab + lane * MS;               // this vehicle's rows of the gather table / the staging array
   out_t* const stage_row = s_stage + lane * SA;
+  const int NG = (A + 3) >> 2;
 #pragma unroll 1
-  for (int i = wave; i < A; i += 4) {
+  for (int g = wave; g < NG; g += 4) {
+  // (columns >= A of a partial last group: nobody transmits there - `myact` < A -, so they take the row's identity
+  // `lane << 2` and a staged 0 without a search; rows are A + 4 wide, the words stay inside them, and neither the
+  // merge nor the write-out reads a column >= A)
+  unsigned int src4 = 0u;                                  // the group's four gather sources (lane * 4), a byte each
+  out_t ob4[4];                                            // ... and its four staged observations
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = 4 * g + j;
     const unsigned long long mk = __ballot(myact == i);     // tx set (test_env.py:153-157)
     const int c = __popcll(mk);
     // Network.find_closest_tx (network.py:378-398): ascending id, strict '<'.  `bid` starts as the own lane: a
@@ -364,16 +378,20 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     const bool self = !live || myact == i;                  // padded lanes and the transmitters of i gather from themselves
     const int src_lane = self ? lane : bid;
     const bool got = src_lane != lane;
-    mtab_row[i] = (mtab_t)(src_lane << 2);
+    // (packed and converted HERE, behind an opaque asm: left alone the compiler keeps every resource's float64 distance,
+    // source lane and transmitter mask alive to the end of the group and packs there - 12 registers and 16 SGPRs more)
+    src4 |= (unsigned int)src_lane << (8 * j + 2);
+    asm volatile("" : "+v"(src4));
     if constexpr (RICH) {
+      // `obs[user][i]` of the reference step (test_env.py:143, 206, 228, 240, 306, 432): 0 on the own
+      // resource or an unused one; my_step with State.type 2: the distance to the closest in-range
+      // transmitter, 100000 (network.py:385) when none is in range; otherwise the constant 1.
+      // Straight from the registers of the search into the staging array (lane = row), four resources
+      // at a time; rows leave coalesced after the barrier.
       if (emit_chobs || POL) {
-        // `obs[user][i]` of the reference step (test_env.py:143, 206, 228, 240, 306, 432): 0 on the own
-        // resource or an unused one; my_step with State.type 2: the distance to the closest in-range
-        // transmitter, 100000 (network.py:385) when none is in range; otherwise the constant 1.
-        // Straight from the registers of the search into the staging array (lane = row); rows leave
-        // coalesced after the barrier.
         const double ob = (myact == i || c == 0) ? 0.0 : (dist_obs ? best : 1.0);
-        stage_row[i] = (out_t)ob;
+        ob4[j] = (out_t)ob;
+        asm volatile("" : "+v"(ob4[j]));
       }
     }
     if (EXTRA && CH && p.la && got) p.la[(bN + bid) * N + lane] = (int32_t)(p.t + (p.t_dev ? *p.t_dev : 0ll));   // test_env.py:436
@@ -402,6 +420,11 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
         if (lane == 0) s_rv[i] = rw;
       }
     }
+  }
+  *reinterpret_cast<unsigned int*>(mtab_row + 4 * g) = src4;              // MS % 4 == 0
+  if constexpr (RICH) {
+    if (emit_chobs || POL) fast_stage_store4(stage_row + 4 * g, ob4);     // 16-byte aligned: SA % 4 == 0
+  }
   }
   DIRAL_FSTAMP(2);
   __syncthreads();
