@@ -3,7 +3,9 @@
 * G7: histogram values exactly on / one ulp around every bin edge on the HIP
   path - the kernels estimate the bin with a reciprocal multiply and correct it against the
   np.linspace edges (csrc/ref_math.hpp hist_bin, hist_bin_estimate); NumPy
-  (np.histogram, network.py:500) and the oracle are the references;
+  (np.histogram, network.py:500) and the oracle are the references (this is the type-2 histogram of the fused
+  step; the type-1 weighted histogram and the sorted true distances have their sweep in
+  tests/test_gpu_posdist_edges.py);
 * the device-RNG branch of update_velocity (network.py:208-223): a fresh draw per call;
 * shard invariance of every device draw (DIRAL_OPT_ENV_OFFSET) and one C4-shard-sized run
   (BASELINE.json configs[3]: 32768 envs per GPU)."""
