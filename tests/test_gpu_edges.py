@@ -4,8 +4,8 @@
   path - the kernels estimate the bin with a reciprocal multiply and correct it against the
   np.linspace edges (csrc/ref_math.hpp hist_bin, hist_bin_estimate); NumPy
   (np.histogram, network.py:500) and the oracle are the references (this is the type-2 histogram of the fused
-  step; the type-1 weighted histogram and the sorted true distances have their sweep in
-  tests/test_gpu_posdist_edges.py);
+  step, every viewer at post-move x == 0 - with the viewers off the origin: tests/test_gpu_hist_edges.py; the type-1
+  weighted histogram and the sorted true distances have their sweep in tests/test_gpu_posdist_edges.py);
 * the device-RNG branch of update_velocity (network.py:208-223): a fresh draw per call;
 * shard invariance of every device draw (DIRAL_OPT_ENV_OFFSET) and one C4-shard-sized run
   (BASELINE.json configs[3]: 32768 envs per GPU)."""
@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from diral_amd.config import KERNEL_FAST64, KERNEL_GENERAL, KERNEL_RING, KERNEL_WIDE, STEP_MY_STEP, bench_config
+from tests.hist_edge_cases import numpy_hist
 from tests.test_gpu_parity import make_env
 
 pytestmark = pytest.mark.gpu
@@ -93,15 +94,12 @@ def test_histogram_bin_edges_sweep_on_the_hip_path(K, rb, N, path):
         got = obs.cpu().numpy()
         assert np.array_equal(got, o_state if dt == torch.float64 else o_state.astype(np.float32)), (K, rb, N, path)
         env.check()
-    # ... and against NumPy itself (network.py:500) for every viewer
+    # ... and against NumPy itself (network.py:500) for every viewer: x1 - x2 with x2 (own post-move x) == 0
     hist = envs[torch.float64]._obs.cpu().numpy()[:, :, A:]
+    off = ~np.eye(N, dtype=bool)
     for b in range(B):
         for u in range(N):
-            dx = cand[b, u]                                        # x1 - x2 with x2 (own post-move x) == 0
-            d = np.sqrt(dx * dx)                                   # Network.dist (network.py:318-332): tiny dx underflow to 0
-            vals = [(d[k] if dx[k] > 0 else -d[k])                 # dist_piggy sign: +1 iff x1 - x2 > 0 (network.py:552-556)
-                    for k in range(N) if k != u and age[b, u, k] + 1 < 20 and d[k] < rb]
-            ref = np.histogram(sorted(vals), K, range=(-rb, rb))[0] / float(len(vals)) if vals else np.zeros(K)
+            ref = numpy_hist(cand[b, u], np.zeros(N), off[u] & (age[b, u] + 1 < 20), K, rb)
             assert np.array_equal(hist[b, u], ref), (K, rb, N, path, b, u)
 
 
