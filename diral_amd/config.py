@@ -83,6 +83,7 @@ ERR_SEQ_OVERFLOW = -7
 ERR_CAPTURE = -8
 ERR_TABLE_CONFLICT = -9
 ERR_PIGGY_NO_TX = -10
+ERR_ENV_INDEX = -11
 
 
 class DiralCfg(ctypes.Structure):

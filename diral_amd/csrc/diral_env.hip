@@ -3,15 +3,18 @@
 // types anywhere; every data pointer in the ABI is a device pointer.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "aux_kernels.hpp"
 #include "common.hpp"
+#include "copy_envs_kernel.hpp"
 #include "launch.hpp"
 #include "observe_kernel.hpp"
 #include "piggyback_kernel.hpp"
@@ -332,6 +335,21 @@ hipError_t ensure_ring(DiralEnv* e, hipStream_t s) {
   }
   e->ring_valid = st == hipSuccess;
   return st;
+}
+
+// What diral_env_copy_envs moves: the per-env slabs of every buffer that is STATE - the positions and velocities, and
+// whatever diral_env_reset refills (tables in every stored form, arrival stamps, pf counters, metric sums, prev_obs) except
+// the slow-first sets, a scheduling hint with a list / flag consistency of its own that no result depends on
+// (step_params.hpp).  Taken from the records of `own`, in the order of its calls: two handles of one config and one table
+// form give the same list.  false: more than kCopyMaxSlabs such buffers (a bug in this file).
+bool copy_slabs(const DiralEnv* e, std::vector<std::pair<char*, uint32_t>>& out) {
+  out.clear();
+  for (const DevBuf& b : e->bufs) {
+    const bool pos = b.p == e->pos_x || b.p == e->pos_y || b.p == e->vel;
+    if (!pos && (!b.reset_bytes || b.p == e->slow)) continue;
+    out.push_back({(char*)b.p, (uint32_t)((pos ? b.bytes : b.reset_bytes) / (size_t)e->B)});
+  }
+  return out.size() <= (size_t)kCopyMaxSlabs;
 }
 
 // The RICH output-tail description of one call: section layout of the state vector, and which of its columns
@@ -709,6 +727,7 @@ const char* diral_env_strerror(int status) {
     case DIRAL_ERR_CAPTURE: return "call needs a ring <-> plane conversion and the stream is being captured into a hipGraph";
     case DIRAL_ERR_TABLE_CONFLICT: return "imported tables hold entries about one subject with equal sequence numbers but different xpos";
     case DIRAL_ERR_PIGGY_NO_TX: return "State.piggybacking: a receiver heard no transmitter on a used resource (the reference's prev_obs[None] KeyError)";
+    case DIRAL_ERR_ENV_INDEX: return "diral_env_copy_envs: an env index outside its handle (that pair was skipped)";
     default: return "unknown status";
   }
 }
@@ -1219,6 +1238,44 @@ int diral_env_import_state(DiralEnv* e, const double* pos_x, const double* pos_y
   return DIRAL_OK;
 }
 
+int diral_env_copy_envs(DiralEnv* dst, const int32_t* dst_index, DiralEnv* src, const int32_t* src_index, int32_t count,
+                        void* stream) {
+  if (!dst || !src || count < 1) return DIRAL_ERR_BAD_ARG;
+  if ((!dst_index && count > dst->B) || (!src_index && count > src->B)) return DIRAL_ERR_BAD_ARG;
+  if (dst->device != src->device) return DIRAL_ERR_UNSUPPORTED;
+  if (std::memcmp(&dst->cfg, &src->cfg, sizeof(DiralCfg)) != 0) return DIRAL_ERR_BAD_CONFIG;
+  std::vector<std::pair<char*, uint32_t>> from, to;
+  if (!copy_slabs(src, from) || !copy_slabs(dst, to)) return DIRAL_ERR_UNSUPPORTED;
+  if (from.size() != to.size()) return DIRAL_ERR_BAD_CONFIG;      // (a wide handle made under another DIRAL_TABLE_FORM)
+  CopyPlan plan;
+  std::memset(&plan, 0, sizeof(plan));
+  for (size_t i = 0; i < from.size(); ++i) {
+    if (from[i].second != to[i].second) return DIRAL_ERR_BAD_CONFIG;
+    plan.slab[i] = {from[i].first, to[i].first, from[i].second, plan.units};
+    plan.units += copy_units(from[i].second);
+  }
+  plan.slabs = (int32_t)from.size();
+  DEVICE_ENTER(dst->device);
+  hipStream_t s = (hipStream_t)stream;
+  // Host flags only: behind the copy `dst` is valid in a form only if both handles were.  Where that would leave neither
+  // form, both handles complete their planes first - the one launch this call ever adds (refused inside a capture).
+  if (!(dst->plane_valid && src->plane_valid) && !(dst->ring_valid && src->ring_valid)) {
+    for (DiralEnv* h : {dst, src}) {
+      const hipError_t st = ensure_plane(h, s);
+      if (st == hipSuccess) continue;
+      if (h->capture_violation) { h->capture_violation = false; dst->capture_violation = true; }
+      return note_hip(dst, st, "diral_env_copy_envs: ensure_plane");
+    }
+  }
+  const uint32_t chunks = (plan.units + kCopyChunk - 1) / kCopyChunk;
+  HIP_TRY(dst, launch_k<copy_envs_kernel>(dim3(chunks, (uint32_t)std::min(count, 65535)), dim3(kCopyThreads), 0, s, plan, src_index,
+                                          dst_index, (int)count, src->B, dst->B, dst == src ? 1 : 0, dst->err));
+  dst->plane_valid = dst->plane_valid && src->plane_valid;
+  dst->ring_valid = dst->ring_valid && src->ring_valid;
+  dst->flat_y = dst->flat_y && src->flat_y;                       // (the non-flat instantiations are correct for flat data)
+  return DIRAL_OK;
+}
+
 int diral_env_export_prev_obs(DiralEnv* e, double* prev_obs, void* stream) {
   if (!e || !prev_obs) return DIRAL_ERR_BAD_ARG;
   if (!e->prev_obs) return DIRAL_ERR_BAD_CONFIG;
@@ -1437,6 +1494,7 @@ int diral_env_check(DiralEnv* e, void* stream) {
   if (flags & kErrSeq) return DIRAL_ERR_SEQ_OVERFLOW;
   if (flags & kErrTable) return DIRAL_ERR_TABLE_CONFLICT;
   if (flags & kErrPiggy) return DIRAL_ERR_PIGGY_NO_TX;
+  if (flags & kErrEnvIndex) return DIRAL_ERR_ENV_INDEX;
   return DIRAL_OK;
 }
 

@@ -181,6 +181,8 @@ class VecV2VEnv:
         self._keep: Dict[str, tuple] = {}       # per call name: what the last launch's raw pointers refer to
         self._last_actions: Optional[torch.Tensor] = None
         self._policy_needs_chobs = False        # step_policy met a configuration that does not run fused
+        self._kernel_path = PATH_AUTO           # what force_general_kernel / force_large_path chose (twin() repeats it)
+        self._snap_twin: Optional["VecV2VEnv"] = None   # the handle snapshot() copies into, made at its first call
         # section order of obtain_state (test_env.py:527-583): ... velocity, fingerprint last
         self._fp_offset = self.S - 2
 
@@ -275,12 +277,14 @@ class VecV2VEnv:
         """Tests / A-B timing: run every step on the general kernel (csrc/step_kernel.hpp)."""
         self._ok(self.lib.diral_env_set_option(self._h, OPT_KERNEL_PATH, PATH_GENERAL if on else PATH_AUTO),
                  "diral_env_set_option")
+        self._kernel_path = PATH_GENERAL if on else PATH_AUTO
 
     def force_large_path(self, on: bool = True) -> None:
         """Tests: run every step / observe on the three launches of csrc/step_large.hpp, the form that serves
         num_users > 256, num_channels > 256 or num_bins > 64 (there it is the only path and this is a no-op)."""
         self._ok(self.lib.diral_env_set_option(self._h, OPT_KERNEL_PATH, PATH_LARGE if on else PATH_AUTO),
                  "diral_env_set_option")
+        self._kernel_path = PATH_LARGE if on else PATH_AUTO
 
     def set_clock(self, clock: Optional[torch.Tensor]) -> None:
         """Install (or, with None, remove) a device slot clock: an int64 tensor of one element on this env's device.
@@ -672,6 +676,73 @@ class VecV2VEnv:
             raise ValueError("x_positions must be [T, N] or [B, T, N]")
         self._ok(self.lib.diral_env_set_trace(self._h, _ptr(tr), int(T), per_env, self._stream()),
                  "diral_env_set_trace")
+
+    # ---- env copies: fork, snapshot / restore, the candidates of a search -----------------------
+    def twin(self, batch: Optional[int] = None) -> "VecV2VEnv":
+        """A new handle with this one's config, device, `out_dtype`, `step_mode` and kernel path, `batch` envs (default:
+        as many as this one) in the state of a fresh handle: the other side of `copy_envs_from`."""
+        other = VecV2VEnv(self.cfg, batch=self.B if batch is None else int(batch), device=self.device, out_dtype=self.out_dtype,
+                          step_mode=self.step_mode, speculate_state=self.speculate_state)
+        if self._kernel_path == PATH_GENERAL:
+            other.force_general_kernel()
+        elif self._kernel_path == PATH_LARGE:
+            other.force_large_path()
+        return other
+
+    def _index(self, idx) -> Optional[torch.Tensor]:
+        """An index array of `copy_envs_from` as a contiguous int32 tensor on this device; a tensor that already is one is
+        passed through untouched (no upload, no synchronisation: the call stays capturable)."""
+        if idx is None:
+            return None
+        if isinstance(idx, torch.Tensor) and idx.dtype == torch.int32 and idx.device == self.device and idx.is_contiguous():
+            t = idx
+        else:
+            t = torch.as_tensor(np.asarray(idx.cpu() if isinstance(idx, torch.Tensor) else idx, dtype=np.int32), device=self.device)
+        if t.dim() != 1:
+            raise ValueError("copy_envs_from: an index array must be one-dimensional, got %s" % (tuple(t.shape),))
+        return t
+
+    def copy_envs_from(self, src: "VecV2VEnv", src_index=None, dst_index=None, count: Optional[int] = None) -> None:
+        """``for i in range(count): self[dst_index[i]] = src[src_index[i]]`` (a missing index array = i) as ONE launch over
+        the handles' own storage (`diral_env_copy_envs`, include/diral_env.h): positions, velocities, the tables in every
+        stored form, arrival stamps, proportional-fair counters, metric sums, `prev_obs` - everything a later call can
+        observe of an env.  `src` may be this handle (the caller keeps the pairs disjoint) or another one of the same
+        config, device and table form; batch sizes and kernel paths may differ.  int32 device tensors are passed straight
+        through - enqueue-only and capturable as long as no ring <-> plane conversion is due (DiralError(ERR_CAPTURE)
+        otherwise) -, lists and arrays are uploaded first.  `count` defaults to the length of an index array, else to the
+        smaller batch.  The slot counter `t` stays where it is; an index outside its handle skips that pair and makes the
+        next `check()` raise ERR_ENV_INDEX."""
+        if not isinstance(src, VecV2VEnv):
+            raise TypeError("copy_envs_from: src must be a VecV2VEnv")
+        si, di = src._index(src_index), self._index(dst_index)
+        if count is None:
+            lens = [int(t.numel()) for t in (si, di) if t is not None]
+            count = min(lens) if lens else min(self.B, src.B)
+        count = int(count)
+        for t in (si, di):
+            if t is not None and t.numel() < count:
+                raise ValueError("copy_envs_from: an index array is shorter than count = %d" % count)
+        self._spec = None
+        self._last_actions = None
+        self._keep["copy_envs"] = (si, di, src)
+        st = self.lib.diral_env_copy_envs(self._h, _ptr(di), src._h, _ptr(si), count, self._stream())
+        self._ok(st, "diral_env_copy_envs")
+
+    def snapshot(self) -> "VecV2VEnv":
+        """Every env of this handle as it is now, copied into a twin (made at the first call, reused afterwards), with the
+        slot counter and the default-seed counter of `update_velocity`.  Returns the twin: `restore(snap)` brings the
+        handle back, e.g. behind a look-ahead."""
+        if self._snap_twin is None:
+            self._snap_twin = self.twin()
+        snap = self._snap_twin
+        snap.copy_envs_from(self)
+        snap.t, snap._vel_calls = self.t, self._vel_calls
+        return snap
+
+    def restore(self, snap: "VecV2VEnv") -> None:
+        """Undo everything since ``snap = env.snapshot()``: envs, `t`, the velocity-draw counter."""
+        self.copy_envs_from(snap)
+        self.t, self._vel_calls = snap.t, snap._vel_calls
 
     # ---- state access ---------------------------------------------------------
     def get_x_pos(self) -> torch.Tensor:

@@ -61,10 +61,12 @@ typedef enum DiralStatus {
                                   run of the reference produces that (an entry IS the
                                   subject's stamp at that number, vehicle.py:35-63);
                                   raised by diral_env_check after an import      */
-  DIRAL_ERR_PIGGY_NO_TX = -10  /* State.piggybacking: a receiver found no transmitter in range
+  DIRAL_ERR_PIGGY_NO_TX = -10, /* State.piggybacking: a receiver found no transmitter in range
                                   on a used resource - the reference's `self.prev_obs[tx_id]`
                                   with tx_id None, a KeyError (test_env.py:243; sticky flag
                                   raised by the step, reported by diral_env_check)      */
+  DIRAL_ERR_ENV_INDEX = -11    /* diral_env_copy_envs met an env index outside its handle (sticky flag on dst,
+                                  reported by diral_env_check; that pair was skipped) */
 } DiralStatus;
 
 /* ---- config flags: the booleans of the `EnvironmentTest` YAML block -------- */
@@ -354,13 +356,48 @@ typedef struct DiralNeighborEntry {
 int diral_env_export_entries(DiralEnv* env, DiralNeighborEntry* entries, void* stream);
 int diral_env_import_entries(DiralEnv* env, const DiralNeighborEntry* entries, void* stream);
 
+/* ---- env copies between handles: fork, snapshot / restore, the candidates of a search --------------
+ * (additive within ABI 8; csrc/copy_envs_kernel.hpp)
+ *   for i in [0, count):  env dst_index[i] of `dst`  :=  env src_index[i] of `src`     (a NULL index array = i)
+ * as ONE gather launch over the handles' own storage - no conversion to the reference-shaped planes of
+ * diral_env_export_state / diral_env_import_state, no launch per buffer.  dst_index / src_index: [count] int32 device
+ * arrays.  Only ENQUEUES: no host synchronisation, no allocation.
+ *   What "an env" is: everything a later call can observe of it - positions and velocities; the tables in every stored
+ *     form the handle has (the (seq, age) plane and the xpos plane, the xpos ring, the packed codes / ages / own sequence
+ *     numbers / old-quad flags), whole slabs whichever form is current; arrival stamps (DIRAL_F_TRACK_ARRIVAL), the
+ *     proportional-fair counters, the metric sums, prev_obs (DIRAL_F_PIGGYBACKING).  i.e. the positions plus whatever
+ *     diral_env_reset refills, except the slow-first sets (a dispatch-order hint; no result depends on them).
+ *   What does NOT travel, being the handle's and not the env's: the slot number `t` of the caller, the replay trace, the
+ *     env offset, the device clock, the options.  Device random draws are a function of the GLOBAL env index, so a copied
+ *     env draws what its new position draws; arrival stamps stay in the source's slot numbering.
+ *   The two handles must be on one device (else DIRAL_ERR_UNSUPPORTED), have byte-equal DiralCfg and own the same set of
+ *     state buffers (else DIRAL_ERR_BAD_CONFIG: e.g. a wide handle created under another DIRAL_TABLE_FORM).  Batch sizes
+ *     and kernel paths may differ.
+ *   DIRAL_ERR_BAD_ARG, checked first and without touching a device: a NULL handle; count < 1; a NULL index array with
+ *     count larger than THAT handle's B.
+ *   dst == src is allowed: the caller promises that no env is both read and written by different pairs; a pair with
+ *     equal indices is skipped.  Broadcasting env b over a handle: src_index = [b] * B, dst_index = NULL.
+ *   Duplicate entries in dst_index: which pair wins is unspecified.
+ *   An index outside [0, B) of its handle: that pair is skipped, the others are copied, and the sticky flag behind
+ *     DIRAL_ERR_ENV_INDEX is raised on `dst` (diral_env_check).
+ *   Table forms: the validity of ring and plane is a pair of HOST flags per handle; behind the copy `dst` is valid in a
+ *     form only if both handles were.  Where that would leave neither form (one handle last stepped on the ring, the
+ *     other on another kernel path), both handles complete their planes first: the only launch the call ever adds,
+ *     and - like every such conversion - refused inside a stream capture with DIRAL_ERR_CAPTURE and nothing copied.
+ *     Likewise `dst` keeps its "every y == 0" flag only if `src` has it.
+ *   A CAPTURED copy bakes the host flags of capture time into the graph: replay it only while both handles are in the
+ *     forms (ring / plane validity, flat y) they had when it was captured. */
+int diral_env_copy_envs(DiralEnv* dst, const int32_t* dst_index, DiralEnv* src, const int32_t* src_index,
+                        int32_t count, void* stream);
+
 /* ---- metrics ------------------------------------------------------------------ */
 
 /* out [B][DIRAL_M_COLUMNS] float64 device array; clear != 0 zeroes the
  * accumulators afterwards. */
 int diral_env_metrics(DiralEnv* env, double* out, int clear, void* stream);
 
-/* Sticky device-side error flags (action range, sequence overflow, piggybacking without a transmitter) raised by
+/* Sticky device-side error flags (action range, sequence overflow, piggybacking without a transmitter, an env index
+ * outside its handle in diral_env_copy_envs) raised by
  * kernels since the last call.  SYNCHRONISES `stream`.  Returns DIRAL_OK or the
  * first error. */
 int diral_env_check(DiralEnv* env, void* stream);

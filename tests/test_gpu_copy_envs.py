@@ -1,0 +1,561 @@
+"""`diral_env_copy_envs` / `VecV2VEnv.copy_envs_from`: whole envs from handle to handle in their stored form.
+
+Two independent statements of what a copy must do:
+
+(a) twin determinism, bit for bit.  Envs are independent, so behind ``dst.copy_envs_from(src, si, di)`` env ``di[i]`` of
+    `dst` returns on every later call exactly what env ``si[i]`` of `src` returns for the same actions - state, reward,
+    channel observation, done, export_state, metrics, info_age, prev_obs - and every other env of `dst` what a twin of
+    `dst` returns that never received the copy (`ref`, driven like `dst` from the start).  Velocity draws are given.
+(b) the CPU oracle.  Two `Oracle` objects follow `src` and `dst`; the copy on their side is `import_state` of host-indexed
+    `export()` arrays; the GPU's outputs and exported tables of 8 further slots are compared with the suite's bars
+    (against the oracle's IEEE-square mode: everything bit for bit, exp() rewards within EXP_ATOL).
+
+What keeps them from being vacuous is asserted on the host: `src` and `dst` start from different topologies and have run
+13 and 6 slots (own sequence numbers, ages, ring slots, positions differ - checked on the oracle's exports at copy time, and
+on the GPU as "every copied env of `dst` differs from `ref` in every exported array"); and one case per buffer class in
+which only that buffer can carry the difference: a handle filled through export_state -> import_state from the same
+source (the route that carries positions and tables only) steps DIFFERENTLY from the source, the copied one identically.
+"""
+import numpy as np
+import pytest
+import torch
+
+from diral_amd.config import (ERR_BAD_ARG, ERR_BAD_CONFIG, ERR_CAPTURE, ERR_ENV_INDEX, KERNEL_FAST64, KERNEL_GENERAL,
+                              KERNEL_LARGE, KERNEL_RING, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config)
+from diral_amd.vec_env import DiralError
+from tests import call_programs as P
+from tests.call_programs import EXP_ATOL, FAMILIES, uses_exp
+from tests.test_gpu_parity import make_env
+
+pytestmark = pytest.mark.gpu
+
+# N = 9: pos_x is 72 bytes per env, metrics 48 - the 4-byte path of the gather; unequal batches
+NARROW = dict(cfg=lambda: bench_config(9, 5, 300.0), B=5, B_dst=7, f64=True, mode=STEP_MY_STEP, form=None)
+CASES = dict(FAMILIES, narrow=NARROW)
+SLOTS_SRC, SLOTS_DST = 13, 6
+
+
+def dev(a):
+    return torch.as_tensor(np.ascontiguousarray(a), device="cuda:0")
+
+
+def topo(cfg, B, seed):
+    rng = np.random.default_rng([seed, B, cfg.num_users])
+    return P._positions(rng, B, cfg.num_users, cfg.highway_length), P._speeds(rng, B, cfg.num_users, cfg.mobility_vary)
+
+
+def draw_acts(rng, B, cfg):
+    return rng.integers(0, cfg.num_channels, size=(B, cfg.num_users)).astype(np.int32)
+
+
+def new_env(f, cfg, B, seed, y0=None, f64=None):
+    f64 = f["f64"] if f64 is None else f64
+    env = make_env(cfg, B, mode=f["mode"], dtype=torch.float64 if f64 else torch.float32)
+    x0, v0 = topo(cfg, B, seed)
+    env.reset_topology(x0, y0, v0)
+    return env
+
+
+def run(envs, n, seed, t0=0, sticky=False):
+    """`n` slots of the same random actions on every handle of `envs` (equal batches)."""
+    cfg, B = envs[0].cfg, envs[0].B
+    rng = np.random.default_rng([seed, 77])
+    a = dev(draw_acts(rng, B, cfg))
+    for k in range(n):
+        if not sticky and k:
+            a = dev(draw_acts(rng, B, cfg))
+        for e in envs:
+            e.step(a, t0 + k)
+    return t0 + n
+
+
+def slot(env, a, t):
+    obs, rew, done = env._step(env.step_mode, dev(a), t, want_chobs=True)
+    return dict(state=obs.cpu().numpy().copy(), reward=rew.cpu().numpy().copy(), done=done.cpu().numpy().copy(),
+                chobs=env._chobs.cpu().numpy().copy())
+
+
+def everything(env, t):
+    out = {k: v.cpu().numpy() for k, v in env.export_state().items()}
+    out["metrics"] = env.metrics().cpu().numpy()
+    if env.cfg.track_arrival:
+        out["info_age"] = env.info_age(t).cpu().numpy()
+    if env.cfg.State.piggybacking:
+        out["prev_obs"] = env.prev_obs().cpu().numpy()
+    return out
+
+
+def pick_pairs(Bs, Bd, seed):
+    """Distinct sources to distinct destinations, at least one env of `dst` left out."""
+    rng = np.random.default_rng([seed, Bs, Bd])
+    n = min(Bs, Bd - 1)
+    return rng.permutation(Bs)[:n].astype(np.int32), rng.permutation(Bd)[:n].astype(np.int32)
+
+
+def assert_follows(src, dst, ref, si, di, t, seed, slots=3, differ=(), after_first=None):
+    """Statement (a) behind a copy: `slots` slots, everything a call can read, two more slots.  `ref` may be `src` itself
+    (a copy within one handle: `dst` is the handle, `ref` its never-copied twin, and the sources are read from `ref`)."""
+    cfg = dst.cfg
+    si, di = np.asarray(si, dtype=np.int64), np.asarray(di, dtype=np.int64)
+    rest = np.setdiff1d(np.arange(dst.B), di)
+    rng = np.random.default_rng([seed, 99])
+    handles = [dst, ref] + ([src] if src is not ref else [])
+
+    def same(tag, s, d, r):
+        for k in d:
+            assert np.array_equal(d[k][di], s[k][si]), "%s: %s of the copied envs differs from the source's" % (tag, k)
+            assert np.array_equal(d[k][rest], r[k][rest]), "%s: %s of an env outside the copy changed" % (tag, k)
+
+    def step_all(t):
+        a_dst = draw_acts(rng, dst.B, cfg)
+        if src is ref:
+            a_dst[di] = a_dst[si]
+            a_src = a_dst
+        else:
+            a_src = draw_acts(rng, src.B, cfg)
+            a_dst[di] = a_src[si]
+        outs = {id(h): slot(h, a_src if h is src else a_dst, t) for h in handles}
+        same("slot %d" % t, outs[id(src)], outs[id(dst)], outs[id(ref)])
+        if cfg.mobility_vary:                                        # explicit draws: a device draw follows the env's position
+            d_dst = rng.integers(1, 4, size=(dst.B, cfg.num_users)).astype(np.uint8)
+            d_src = d_dst if src is ref else rng.integers(1, 4, size=(src.B, cfg.num_users)).astype(np.uint8)
+            d_dst[di] = d_src[si]
+            for h in handles:
+                h.update_velocity(d_src if h is src else d_dst)
+
+    for k in range(slots):
+        step_all(t + k)
+        if k == 0 and after_first:
+            after_first()
+    t += slots
+    s, d, r = everything(src, t), everything(dst, t), everything(ref, t)
+    same("export", s, d, r)
+    for k in differ:                                                 # the copy changed this buffer of EVERY copied env
+        for i in di:
+            assert not np.array_equal(d[k][i], r[k][i]), "%s of env %d is what it would have been without the copy" % (k, i)
+    for k in range(2):
+        step_all(t + k)
+    for h in handles:
+        h.check()
+
+
+def trio(name, monkeypatch, src_seed=1, dst_seed=2, src_slots=SLOTS_SRC, dst_slots=SLOTS_DST, f64=None):
+    f = CASES[name]
+    if f["form"]:
+        monkeypatch.setenv("DIRAL_TABLE_FORM", f["form"])
+    cfg = f["cfg"]()
+    Bs, Bd = f["B"], f.get("B_dst", f["B"])
+    src = new_env(f, cfg, Bs, src_seed, f64=f64)
+    dst, ref = new_env(f, cfg, Bd, dst_seed, f64=f64), new_env(f, cfg, Bd, dst_seed, f64=f64)
+    assert not np.array_equal(topo(cfg, Bs, src_seed)[0][:min(Bs, Bd)], topo(cfg, Bd, dst_seed)[0][:min(Bs, Bd)])
+    assert src_slots != dst_slots and (src_slots & 7) != (dst_slots & 7)        # own sequence numbers in different ring slots
+    run([src], src_slots, 11)
+    run([dst, ref], dst_slots, 12)
+    return f, cfg, src, dst, ref
+
+
+DIFFER = ("pos_x", "vel", "seq", "age", "x", "metrics")
+
+
+# ---- (a) on every kernel family ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(CASES))
+def test_copied_envs_follow_their_source_and_the_others_their_twin(name, monkeypatch):
+    f, cfg, src, dst, ref = trio(name, monkeypatch)
+    si, di = pick_pairs(src.B, dst.B, 5)
+    # (lists are uploaded; device tensors pass straight through)
+    if name in ("f64_full", "w2_packed", "narrow"):
+        dst.copy_envs_from(src, dev(si), dev(di))
+    else:
+        dst.copy_envs_from(src, si.tolist(), di.tolist())
+    assert dst.t == SLOTS_DST                                        # the slot counter is the handle's, not the env's
+    differ = DIFFER                                                  # (arrival stamps: my_step_ch only, test_arrival_stamps_travel)
+    ring = cfg.num_channels <= 64
+
+    def still_on_the_ring():                                         # ring-only -> ring-only: no conversion was needed
+        assert not ring or dst.last_kernel() & KERNEL_RING, dst.last_kernel()
+    assert_follows(src, dst, ref, si, di, SLOTS_SRC, 21, differ=differ, after_first=still_on_the_ring)
+
+
+# ---- (b) against the CPU oracle ------------------------------------------------------------------------------------
+def oracle_pair(f, cfg, Bs, Bd, src_seed, dst_seed, src_slots, dst_slots):
+    from oracle.oracle import SQ_IEEE, Oracle
+    out = []
+    for B, seed, slots, aseed in ((Bs, src_seed, src_slots, 11), (Bd, dst_seed, dst_slots, 12)):
+        o = Oracle(cfg, batch=B, sq_mode=SQ_IEEE)
+        x0, v0 = topo(cfg, B, seed)
+        o.reset(x0, np.zeros_like(x0), v0)
+        rng = np.random.default_rng([aseed, 77])                     # (what `run` draws)
+        for k in range(slots):
+            o.step(f["mode"], draw_acts(rng, B, cfg), k)
+        out.append(o)
+    return out
+
+
+def oracle_copy(o_src, o_dst, si, di):
+    s, d = o_src.export(), o_dst.export()
+    for k in ("pos_x", "pos_y", "vel", "seq", "age", "x", "y", "la"):
+        d[k][di] = s[k][si]
+    o_dst.import_state(**{k: d[k] for k in ("pos_x", "pos_y", "vel", "seq", "age", "x", "y", "la")})
+    return s, d
+
+
+def lag_census(e):
+    """Per env: does it hold a heard entry (seq > 0) more than 7 stamps behind its subject's own sequence number?"""
+    own = np.diagonal(e["seq"], axis1=1, axis2=2)[:, None, :]
+    return ((e["seq"] > 0) & (own - e["seq"] > 7)).any(axis=(1, 2))
+
+
+def compare_with_oracle(env, orc, f, cfg, t, rng_seed, slots=8):
+    rng = np.random.default_rng([rng_seed, 55])
+    exp = uses_exp(cfg, f["mode"])
+    for k in range(slots):
+        a = draw_acts(rng, env.B, cfg)
+        got = slot(env, a, t + k)
+        rew, chobs = orc.step(f["mode"], a, t + k)
+        state = orc.obtain_state(a, chobs, rew)
+        assert np.array_equal(got["chobs"], chobs), "slot %d: channel observation" % (t + k)
+        if exp:
+            assert np.abs(got["reward"] - rew).max() <= EXP_ATOL
+            assert np.abs(got["state"] - state).max() <= (EXP_ATOL if cfg.State.add_reward else 0.0)
+        else:
+            assert np.array_equal(got["reward"], rew), "slot %d: reward" % (t + k)
+            assert np.array_equal(got["state"], state), "slot %d: state" % (t + k)
+        if cfg.mobility_vary:
+            d = rng.integers(1, 4, size=(env.B, cfg.num_users)).astype(np.uint8)
+            env.update_velocity(d)
+            orc.update_velocity(d)
+    st, e = env.export_state(), orc.export()
+    for k in ("pos_x", "pos_y", "vel", "seq", "x"):
+        assert np.array_equal(st[k].cpu().numpy(), e[k]), "export %s" % k
+    assert np.array_equal(st["age"].cpu().numpy(), np.minimum(e["age"], 255))
+    if cfg.track_arrival:
+        assert np.array_equal(st["la"].cpu().numpy().astype(np.int64), e["la"])
+        assert np.array_equal(env.info_age(t + slots).cpu().numpy(), orc.info_age(t + slots))
+    env.check()
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_copy_against_the_oracle(name, monkeypatch):
+    f, cfg, src, dst, _ = trio(name, monkeypatch, f64=True)
+    o_src, o_dst = oracle_pair(f, cfg, src.B, dst.B, 1, 2, SLOTS_SRC, SLOTS_DST)
+    si, di = pick_pairs(src.B, dst.B, 6)
+    s, d_before = o_src.export(), o_dst.export()
+    for i, j in zip(si, di):                                         # at copy time every pair differs in every buffer class
+        assert s["seq"][i].diagonal().min() == SLOTS_SRC and d_before["seq"][j].diagonal().max() == SLOTS_DST
+        for k in ("pos_x", "vel", "seq", "age", "x"):
+            assert not np.array_equal(s[k][i], d_before[k][j]), k
+    oracle_copy(o_src, o_dst, si, di)
+    dst.copy_envs_from(src, dev(si), dev(di))
+    compare_with_oracle(dst, o_dst, f, cfg, SLOTS_SRC, 31)
+    compare_with_oracle(src, o_src, f, cfg, SLOTS_SRC, 32)
+
+
+@pytest.mark.parametrize("name", ["f64_sparse", "w4_sparse"])
+def test_old_entries_beyond_the_ring_travel_with_the_planes(name, monkeypatch):
+    """told / tkey / tx: after 30 slots on a sparse highway some envs hold entries older than the 7 stamps the ring and the
+    codes reach - their xpos lives in the plane slabs only, and the packed form flags their row-quads - and some hold none."""
+    f, cfg, src, dst, ref = trio(name, monkeypatch, src_seed=6, dst_seed=7, src_slots=30, dst_slots=4, f64=True)
+    o_src, o_dst = oracle_pair(f, cfg, src.B, dst.B, 6, 7, 30, 4)
+    si = np.arange(src.B, dtype=np.int32)
+    di = si[::-1].copy()
+    old_src, old_dst = lag_census(o_src.export()), lag_census(o_dst.export())
+    assert old_src[si[:-1]].any() and not old_dst.any(), (old_src, old_dst)
+    # both directions: envs with old entries into a handle that has none, and back
+    oracle_copy(o_src, o_dst, si[:-1], di[:-1])
+    dst.copy_envs_from(src, dev(si[:-1]), dev(di[:-1]))
+    after = lag_census(o_dst.export())
+    assert after.any() and not after.all(), after                    # copied envs with such entries, and one env with none
+    compare_with_oracle(dst, o_dst, f, cfg, 30, 41)
+    oracle_copy(o_dst, o_src, di[-1:], si[:1])
+    src.copy_envs_from(dst, dev(di[-1:]), dev(si[:1]))
+    compare_with_oracle(src, o_src, f, cfg, 38, 42)
+
+
+# ---- one case per buffer class: only that buffer carries the difference ----------------------------------------------
+def via_export_import(src):
+    """The route without the copy: positions, velocities, tables and arrival stamps only."""
+    imp = src.twin()
+    st = src.export_state()
+    imp.import_state(st["pos_x"], st["pos_y"], st["vel"], seq=st["seq"], age=st["age"], x=st["x"], la=st.get("la"))
+    return imp
+
+
+def test_proportional_fair_counters_travel():
+    cfg = bench_config(20, 4, 340.0, reward_design=1, proportional_fair=True)
+    f = dict(mode=STEP_MY_STEP, f64=True)
+    src = new_env(f, cfg, 5, 1)
+    t = run([src], 14, 3, sticky=True)                               # the same collisions 14 slots in a row: past pf_threshold = 10
+    imp, dst = via_export_import(src), src.twin()
+    dst.copy_envs_from(src)
+    a = draw_acts(np.random.default_rng([3, 77]), 5, cfg)            # the sticky actions once more
+    want, got, lost = slot(src, a, t), slot(dst, a, t), slot(imp, a, t)
+    penalty = cfg.to_c().pf_penalty                                  # test_env.py:90
+    assert penalty == -10.0 and (want["reward"] == penalty).any() and not (lost["reward"] == penalty).any()
+    assert np.array_equal(lost["chobs"], want["chobs"])              # tables and positions alike: only the counters differ
+    for k in want:
+        assert np.array_equal(got[k], want[k]), k
+    assert_follows(src, dst, dst.twin(), np.arange(5), np.arange(5), t + 1, 7)
+
+
+def test_arrival_stamps_travel():
+    cfg = bench_config(33, 9, 1200.0, reward_design=3, track_arrival=True)
+    f = dict(mode=STEP_MY_STEP_CH, f64=True)
+    src = new_env(f, cfg, 5, 1)
+    t = run([src], 13, 3)
+    dst, blank = src.twin(), src.twin()
+    st = src.export_state()
+    blank.import_state(st["pos_x"], st["pos_y"], st["vel"], seq=st["seq"], age=st["age"], x=st["x"])     # everything but `la`
+    dst.copy_envs_from(src)
+    want = src.info_age(t).cpu().numpy()
+    assert np.array_equal(dst.info_age(t).cpu().numpy(), want)
+    assert not np.array_equal(blank.info_age(t).cpu().numpy(), want)
+    ref = new_env(f, cfg, 5, 2)
+    assert_follows(src, dst, ref, np.arange(5), np.arange(5), t, 8, differ=DIFFER + ("la", "info_age"))
+
+
+def test_prev_obs_travels():
+    cfg = bench_config(20, 5, 300.0, communication_range=301.0, State=dict(piggybacking=True, add_channel_obs=True))
+    f = dict(mode=STEP_MY_STEP, f64=True)
+    src = new_env(f, cfg, 5, 1)
+    t = run([src], 13, 3)
+    imp, dst = via_export_import(src), src.twin()
+    dst.copy_envs_from(src)
+    assert np.array_equal(dst.prev_obs().cpu().numpy(), src.prev_obs().cpu().numpy()) and src.prev_obs().any()
+    a = draw_acts(np.random.default_rng(4), 5, cfg)
+    want, got, lost = slot(src, a, t), slot(dst, a, t), slot(imp, a, t)
+    assert not np.array_equal(lost["chobs"], want["chobs"]) and np.array_equal(lost["reward"], want["reward"])
+    for k in want:
+        assert np.array_equal(got[k], want[k]), k
+    assert_follows(src, dst, dst.twin(), np.arange(5), np.arange(5), t + 1, 9)
+
+
+def test_metric_sums_travel():
+    f = FAMILIES["f64_ch"]
+    cfg = f["cfg"]()
+    src = new_env(f, cfg, 6, 1)
+    run([src], 13, 3)
+    imp, dst = via_export_import(src), src.twin()
+    dst.copy_envs_from(src, [5, 0], [0, 5])
+    m, d = src.metrics().cpu().numpy(), dst.metrics().cpu().numpy()
+    assert m[:, 0].min() == 13 and m[:, 4].min() > 0 and not imp.metrics().any()
+    assert np.array_equal(d[[0, 5]], m[[5, 0]]) and not d[1:5].any()
+
+
+# ---- form transitions ---------------------------------------------------------------------------------------------
+def set_path(env, path):
+    if path == "general":
+        env.force_general_kernel()
+    elif path == "large":
+        env.force_large_path()
+
+
+@pytest.mark.parametrize("N,A,L,src_path,dst_path", [
+    (64, 32, 2000.0, "general", "auto"),       # the conversion branch: neither form would be left valid
+    (64, 32, 2000.0, "auto", "general"),
+    (24, 6, 500.0, "large", "large"),
+    (24, 6, 500.0, "large", "auto"),
+    (128, 16, 4000.0, "general", "auto"),
+])
+def test_copy_between_handles_on_different_kernel_paths(N, A, L, src_path, dst_path):
+    cfg = bench_config(N, A, L)
+    f = dict(mode=STEP_MY_STEP, f64=True)
+    src, dst, ref = new_env(f, cfg, 5, 1), new_env(f, cfg, 4, 2), new_env(f, cfg, 4, 2)
+    set_path(src, src_path)
+    for e in (dst, ref):
+        set_path(e, dst_path)
+    run([src], SLOTS_SRC, 11)
+    run([dst, ref], SLOTS_DST, 12)
+    want = {"general": KERNEL_GENERAL, "large": KERNEL_LARGE, "auto": None}
+    assert want[src_path] is None or (src.last_kernel() & 15) == want[src_path]
+    if dst_path == "auto":
+        assert dst.last_kernel() & KERNEL_RING
+    si, di = pick_pairs(5, 4, 3)
+    dst.copy_envs_from(src, si.tolist(), di.tolist())
+
+    def back_on_its_path():
+        if dst_path == "auto":
+            assert dst.last_kernel() & KERNEL_RING
+        else:
+            assert (dst.last_kernel() & 15) == want[dst_path]
+    assert_follows(src, dst, ref, si, di, SLOTS_SRC, 22, differ=DIFFER, after_first=back_on_its_path)
+
+
+def test_fresh_reset_into_a_stepped_handle_and_back():
+    f = FAMILIES["f64_full"]
+    cfg = f["cfg"]()
+    src, dst, ref = new_env(f, cfg, 6, 1), new_env(f, cfg, 6, 2), new_env(f, cfg, 6, 2)
+    run([dst, ref], SLOTS_DST, 12)
+    si, di = pick_pairs(6, 6, 4)
+    dst.copy_envs_from(src, si.tolist(), di.tolist())
+    assert_follows(src, dst, ref, si, di, SLOTS_DST, 23, differ=DIFFER)
+    # ... and stepped envs into a freshly reset handle
+    fresh, fresh_ref = new_env(f, cfg, 6, 3), new_env(f, cfg, 6, 3)
+    fresh.copy_envs_from(dst, di.tolist(), si.tolist())
+    assert_follows(dst, fresh, fresh_ref, di, si, SLOTS_DST + 5, 24, differ=DIFFER)
+
+
+def test_vehicles_off_the_lane_into_a_flat_handle():
+    """`dst` loses its "every y == 0" flag with the copy: its next steps run the non-flat instantiation, for the envs that
+    still are flat too."""
+    f = FAMILIES["f64_full"]
+    cfg = f["cfg"]()
+    y0 = np.random.default_rng(8).choice(np.array([0.0, 0.0, 1.0, 2.0]), size=(6, cfg.num_users))
+    y0[:, 0] = 1.0
+    src, dst, ref = new_env(f, cfg, 6, 1, y0=y0), new_env(f, cfg, 6, 2), new_env(f, cfg, 6, 2)
+    run([src], SLOTS_SRC, 11)
+    run([dst, ref], SLOTS_DST, 12)
+    si, di = pick_pairs(6, 6, 9)
+    dst.copy_envs_from(src, dev(si), dev(di))
+    with pytest.raises(DiralError):                                  # (K-slot launches need the flat lane: the flag did travel)
+        dst.rollout(dev(np.zeros((2, 6, cfg.num_users), np.int32)), SLOTS_SRC)
+    assert_follows(src, dst, ref, si, di, SLOTS_SRC, 25, differ=DIFFER + ("pos_y",),
+                   after_first=lambda: (dst.last_kernel() & 15) == KERNEL_FAST64 or pytest.fail("left the fast path"))
+
+
+# ---- copies within one handle ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["f64_full", "w2_plane", "narrow"])
+def test_broadcast_of_one_env_over_its_handle(name, monkeypatch):
+    f = CASES[name]
+    if f["form"]:
+        monkeypatch.setenv("DIRAL_TABLE_FORM", f["form"])
+    cfg, B = f["cfg"](), f["B"]
+    one, two = new_env(f, cfg, B, 1), new_env(f, cfg, B, 1)
+    t = run([one, two], SLOTS_SRC, 11)
+    other = two.twin()
+    run([other], SLOTS_DST, 12)
+    idx = dev(np.full(B, 2, np.int32))
+    one.copy_envs_from(one, src_index=idx)                           # within the handle
+    other.copy_envs_from(two, src_index=idx)                         # the same env across handles
+    rng = np.random.default_rng(5)
+    for k in range(4):                                               # B copies of env 2, different actions each
+        a = draw_acts(rng, B, cfg)
+        x, y = slot(one, a, t + k), slot(other, a, t + k)
+        for key in x:
+            assert np.array_equal(x[key], y[key]), key
+        solo = slot(two, np.repeat(a[2:3], B, axis=0), t + k)
+        assert np.array_equal(solo["state"][2], x["state"][2])
+    x, y = everything(one, t + 4), everything(other, t + 4)
+    for key in x:
+        assert np.array_equal(x[key], y[key]), key
+    assert not np.array_equal(x["seq"][0], x["seq"][1])              # (they did go different ways)
+    one.check()
+
+
+def test_disjoint_permutation_within_one_handle():
+    f = FAMILIES["f64_sparse"]
+    cfg = f["cfg"]()
+    h, ref = new_env(f, cfg, 6, 1), new_env(f, cfg, 6, 1)
+    t = run([h, ref], SLOTS_SRC, 11)
+    si, di = np.array([0, 2, 4], np.int32), np.array([5, 1, 3], np.int32)
+    h.copy_envs_from(h, dev(si), dev(di))
+    h.copy_envs_from(h, [1, 3], [1, 3])                              # equal indices: skipped
+    assert_follows(ref, h, ref, si, di, t, 26, differ=DIFFER)
+
+
+# ---- refusals ------------------------------------------------------------------------------------------------------
+def status_of(call):
+    with pytest.raises(DiralError) as ei:
+        call()
+    return ei.value.status
+
+
+def test_mismatched_handles_and_counts_are_refused(monkeypatch):
+    f = dict(mode=STEP_MY_STEP, f64=True)
+    cfg = bench_config(16, 4, 300.0)
+    a, b = new_env(f, cfg, 4, 1), new_env(f, bench_config(16, 4, 300.0, communication_range=251.0), 4, 1)
+    assert status_of(lambda: a.copy_envs_from(b)) == ERR_BAD_CONFIG
+    c = new_env(f, cfg, 6, 2)
+    assert status_of(lambda: a.copy_envs_from(c, count=5)) == ERR_BAD_ARG          # a NULL index with count > THAT handle's B
+    assert status_of(lambda: c.copy_envs_from(a, count=5)) == ERR_BAD_ARG
+    assert status_of(lambda: c.copy_envs_from(a, dst_index=[0, 1, 2, 3, 4])) == ERR_BAD_ARG
+    c.copy_envs_from(a, src_index=[0, 1, 2, 3, 0, 1])                # (indexed: count may exceed the source's B)
+    wide = bench_config(128, 16, 4000.0)
+    monkeypatch.setenv("DIRAL_TABLE_FORM", "plane")
+    p = new_env(f, wide, 4, 1)
+    monkeypatch.setenv("DIRAL_TABLE_FORM", "packed")
+    q = new_env(f, wide, 4, 1)
+    assert status_of(lambda: p.copy_envs_from(q)) == ERR_BAD_CONFIG
+    assert status_of(lambda: q.copy_envs_from(p)) == ERR_BAD_CONFIG
+    for e in (a, c, p, q):
+        e.check()
+
+
+@pytest.mark.parametrize("bad_src,bad_dst", [(6, 1), (-1, 1), (0, 6), (0, -2)])
+def test_an_index_outside_its_handle_skips_that_pair_only(bad_src, bad_dst):
+    f = FAMILIES["f64_full"]
+    cfg = f["cfg"]()
+    src, dst, ref = new_env(f, cfg, 6, 1), new_env(f, cfg, 6, 2), new_env(f, cfg, 6, 2)
+    run([src], SLOTS_SRC, 11)
+    run([dst, ref], SLOTS_DST, 12)
+    dst.copy_envs_from(src, [4, bad_src, 2], [0, bad_dst, 5])
+    assert status_of(dst.check) == ERR_ENV_INDEX
+    dst.check()                                                      # reported once
+    src.check()                                                      # ... and on `dst` only
+    assert_follows(src, dst, ref, [4, 2], [0, 5], SLOTS_SRC, 27, differ=DIFFER)
+
+
+def test_a_copy_that_needs_the_conversion_is_refused_inside_a_capture():
+    f = FAMILIES["f64_full"]
+    cfg = f["cfg"]()
+    src, dst, ref = new_env(f, cfg, 6, 1), new_env(f, cfg, 6, 2), new_env(f, cfg, 6, 2)
+    src.force_general_kernel()
+    run([src], SLOTS_SRC, 11)                                        # plane only
+    run([dst, ref], SLOTS_DST, 12)                                   # ring only
+    idx = dev(np.arange(6, dtype=np.int32))
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(s):
+        g.capture_begin()
+        try:
+            keep = idx + 0                                           # (the captured graph is not empty)
+            assert status_of(lambda: dst.copy_envs_from(src, idx, idx)) == ERR_CAPTURE
+        finally:
+            g.capture_end()
+    torch.cuda.synchronize()
+    # nothing was copied, launched or recorded: `dst` goes on like its twin, still on the ring
+    assert_follows(src, dst, ref, [], [], SLOTS_DST, 28, after_first=lambda: dst.last_kernel() & KERNEL_RING or pytest.fail("off the ring"))
+    dst.copy_envs_from(src, idx, idx)                                # outside the capture the same call converts and copies
+    assert_follows(src, dst, dst.twin(), np.arange(6), np.arange(6), SLOTS_SRC, 29)
+
+
+# ---- a captured fork + rollout ---------------------------------------------------------------------------------------
+def test_captured_fork_and_rollout_replays_against_the_moved_env():
+    from diral_amd.rollout import no_finalizers_during_capture
+    from diral_amd.search import candidate_index
+    f = FAMILIES["f64_full"]
+    cfg = f["cfg"]()
+    B, C, K, N = 4, 3, 3, cfg.num_users
+    env, env2 = new_env(f, cfg, B, 1), new_env(f, cfg, B, 1)
+    t = run([env, env2], 5, 11)
+    work, work2 = env.twin(B * C), env2.twin(B * C)
+    gather = candidate_index(B, C, "cuda:0")
+    seq = dev(np.random.default_rng(6).integers(0, cfg.num_channels, size=(K, B * C, N)).astype(np.int32))
+    t_roll = 40                                                      # (baked into the graph; no episode end inside)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        work.copy_envs_from(env, src_index=gather)                   # warm-up: both handles end in ring form
+        work.rollout(seq, t_roll, states=None)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with no_finalizers_during_capture():
+        with torch.cuda.graph(g, stream=s):
+            work.copy_envs_from(env, src_index=gather)
+            out = work.rollout(seq, t_roll, states=None)
+    for rounds in (2, 3):                                            # the env moves on by ring steps between the replays
+        t = run([env, env2], rounds, 13 + rounds, t0=t)
+        assert env.last_kernel() & KERNEL_RING
+        g.replay()
+        torch.cuda.synchronize()
+        work2.copy_envs_from(env2, src_index=gather)
+        want = work2.rollout(seq, t_roll, states=None)
+        for k in ("sum_r", "collision", "shaped", "reward", "done"):
+            assert np.array_equal(out[k].cpu().numpy(), want[k].cpu().numpy()), k
+    # (only now: an export completes the planes and says so in the host flags, which a replay would not take back)
+    x, y = everything(work, t_roll + K), everything(work2, t_roll + K)
+    for k in x:
+        assert np.array_equal(x[k], y[k]), k
+    assert x["metrics"][:, 0].min() == t + K                         # the env's slots and the rollout's
+    work.check()
