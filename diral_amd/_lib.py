@@ -27,7 +27,7 @@ SYMBOLS = [
     "diral_env_set_clock", "diral_clock_add", "diral_sps_step_chobs_clocked", "diral_env_step_policy",
     "diral_env_set_capture_rotation", "diral_env_align_phase",
     "diral_env_export_prev_obs", "diral_env_import_prev_obs", "diral_env_prefill", "diral_env_prefill_mode",
-    "diral_env_rollout", "diral_env_copy_envs",
+    "diral_env_rollout", "diral_env_copy_envs", "diral_env_rollout_ia", "diral_env_step_policy_ia",
 ]
 
 _lib = None
@@ -98,6 +98,8 @@ def load() -> ctypes.CDLL:
         "diral_env_prefill_mode": (I, [P, I, P, I, U64, P, I, P, P, P, D, D, P]),
         "diral_env_rollout": (I, [P, I, P, I, I64, P, I, P, P, I, P, P]),
         "diral_env_copy_envs": (I, [P, P, P, P, I, P]),
+        "diral_env_rollout_ia": (I, [P, I, P, I, I64, P, I, P, P, I, P, P, P]),
+        "diral_env_step_policy_ia": (I, [P, I, P, I64, P, P, P, P, I, P, P, P]),
     }
     for name in SYMBOLS:
         try:

@@ -161,6 +161,20 @@ class DiralRollout(ctypes.Structure):
     ]
 
 
+class DiralSlotInfoAge(ctypes.Structure):
+    """ctypes image of ``struct DiralSlotInfoAge`` (include/diral_env.h): the information-age block of
+    ``diral_env_rollout_ia`` / ``diral_env_step_policy_ia``."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("flags", ctypes.c_int32),
+        ("ia_out", ctypes.c_void_p),
+        ("ia_sum_out", ctypes.c_void_p),
+        ("ia_pen_out", ctypes.c_void_p),
+        ("sum_ia_prev", ctypes.c_void_p),
+    ]
+
+
 class ConfigError(ValueError):
     """A config the reference itself cannot run, or one this build rejects."""
 

@@ -468,7 +468,10 @@ StepPlan plan_step(const DiralEnv* e, const StepParams& p, const PolParams* pol)
   d.nomove = !(p.flags & DIRAL_F_MOBILITY);                  // static (design) topology: network.py:302-305
   d.la = (p.flags & DIRAL_F_TRACK_ARRIVAL) ? p.la : nullptr;
   d.trace = d.nomove ? nullptr : p.trace;
-  const bool switches = d.la != nullptr || d.trace != nullptr || d.prr || d.notab || d.nomove;
+  // (a my_step_ch call that carries the information-age block - diral_env_rollout_ia / diral_env_step_policy_ia - runs its
+  // stamps in the slot loop of step_fast64: they do not ask for an EXTRA instantiation there)
+  const bool la_in_slots = pol && pol->ia_on && ch;
+  const bool switches = (d.la != nullptr && !la_in_slots) || d.trace != nullptr || d.prr || d.notab || d.nomove;
   const bool extra = d.design || switches;
   // the POL instantiation of step_fast64 (policy epilogue inside the launch) takes this call
   const bool pol_ok = d.use_fast64 && e->flat_y && !ch && !extra && p.N >= 8;
@@ -1039,9 +1042,27 @@ static int sps_step_chobs_impl(int agents, int num_channels, const void* chobs, 
                                const int32_t* draw_choice, uint64_t seed, const long long* clock, int32_t* actions_out,
                                void* stream);
 
-int diral_env_step_policy(DiralEnv* e, int mode, const int32_t* actions, int64_t t, void* state_out, void* rew_out,
-                          uint8_t* done_out, void* chobs_out, int out_dtype, const DiralSlotPolicy* pol, void* stream) {
+// The information-age block of a K-slot my_step_ch call (DiralSlotInfoAge): its own argument checks ...
+static int ia_block_check(const DiralSlotInfoAge* ia, const void* shaped_out) {
+  if (ia->struct_bytes != sizeof(DiralSlotInfoAge) || (ia->flags & ~1) != 0) return DIRAL_ERR_BAD_ARG;
+  if ((ia->flags & 1) && (!ia->sum_ia_prev || !shaped_out)) return DIRAL_ERR_BAD_ARG;
+  return DIRAL_OK;
+}
+// ... and what the slot loop is handed (PolParams::ia_on: bit 0 the block, bit 1 a histogram pass every slot)
+static void ia_block_params(const DiralSlotInfoAge* ia, PolParams& q) {
+  q.ia_on = 0; q.ia_flags = 0; q.ia_out = nullptr; q.ia_sum_out = nullptr; q.ia_pen_out = nullptr; q.sum_ia_prev = nullptr;
+  if (!ia) return;
+  const bool hist = ia->ia_out || ia->ia_sum_out || (ia->flags & 1);
+  q.ia_on = 1 | (hist ? 2 : 0); q.ia_flags = ia->flags;
+  q.ia_out = ia->ia_out; q.ia_sum_out = (long long*)ia->ia_sum_out; q.ia_pen_out = ia->ia_pen_out;
+  q.sum_ia_prev = (long long*)ia->sum_ia_prev;
+}
+
+static int step_policy_impl(DiralEnv* e, int mode, const int32_t* actions, int64_t t, void* state_out, void* rew_out,
+                            uint8_t* done_out, void* chobs_out, int out_dtype, const DiralSlotPolicy* pol,
+                            const DiralSlotInfoAge* ia, void* stream) {
   if (!e || !actions || !pol || pol->struct_bytes != sizeof(DiralSlotPolicy)) return DIRAL_ERR_BAD_ARG;
+  if (ia && ia_block_check(ia, pol->shaped_out) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
   if (!pol->sps_prev_action || !pol->sps_counter || !pol->actions_out) return DIRAL_ERR_BAD_ARG;
   if (mode != DIRAL_STEP_MY_STEP && mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_BAD_ARG;
   if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
@@ -1049,6 +1070,12 @@ int diral_env_step_policy(DiralEnv* e, int mode, const int32_t* actions, int64_t
   if (pol->shaped_out && !rew_out) return DIRAL_ERR_BAD_ARG;                 // (the three-launch form shapes rew_out)
   if ((pol->shape_flags & ~5) != 0) return DIRAL_ERR_BAD_ARG;                // global_reward_avg | stuck-action penalty
   if (pol->shaped_out && (pol->shape_flags & 4) && (!pol->pen_counter || !pol->pen_prev_actions)) return DIRAL_ERR_BAD_ARG;
+  if (ia) {
+    if (pol->slots > 1 && (pol->draw_counter || pol->draw_keep || pol->draw_choice)) return DIRAL_ERR_BAD_ARG;
+    if (!e->la) return DIRAL_ERR_BAD_CONFIG;                     // (as diral_env_info_age)
+    // my_step's only stamp effect is the -1 of network.py:394; there is no fused one-slot my_step_ch launch
+    if (mode != DIRAL_STEP_MY_STEP_CH || pol->slots <= 1) return DIRAL_ERR_UNSUPPORTED;
+  }
   if (e->A > kSpsWaveMaxA) return DIRAL_ERR_UNSUPPORTED;
   if (e->prev_obs) return DIRAL_ERR_UNSUPPORTED;                // State.piggybacking: the SPS agents sense A values, not A * A
   DEVICE_ENTER(e->device);
@@ -1066,10 +1093,12 @@ int diral_env_step_policy(DiralEnv* e, int mode, const int32_t* actions, int64_t
   q.K = slots; q.vel_vary = has(&e->cfg, DIRAL_F_MOBILITY_VARY) ? 1 : 0; q.vel_seed = pol->vel_seed;
   q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N; q.vel_w = e->vel;
   q.prefill = 0; q.actions_all = nullptr; q.rew_in = nullptr; q.rollout = 0; q.actions_seq = nullptr;
+  ia_block_params(ia, q);
   if (slots > 1 && (pol->draw_counter || pol->draw_keep || pol->draw_choice)) return DIRAL_ERR_BAD_ARG;
   // (decided before anything is launched: a caller without a channel-observation buffer can retry with one)
   const StepPlan d = plan_step(e, p, &q);
   if (!d.fused && (!chobs_out || slots > 1)) return DIRAL_ERR_UNSUPPORTED;
+  if (ia && d.launch != StepLaunch::Fast64Slots) return DIRAL_ERR_UNSUPPORTED;   // (only that slot loop keeps the stamps)
   HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
   HIP_TRY(e, launch_posdist_if_needed(e, p, (hipStream_t)stream));
   if (d.fused) return DIRAL_OK;
@@ -1083,6 +1112,17 @@ int diral_env_step_policy(DiralEnv* e, int mode, const int32_t* actions, int64_t
   return sps_step_chobs_impl(e->B * e->N, e->A, chobs_out, out_dtype, actions, pol->sps_prev_action, pol->sps_counter,
                              pol->rssi_threshold, pol->inc_db, pol->keep_prob, pol->draw_counter, pol->draw_keep,
                              pol->draw_choice, pol->seed, (const long long*)pol->seed_clock, pol->actions_out, stream);
+}
+
+int diral_env_step_policy(DiralEnv* e, int mode, const int32_t* actions, int64_t t, void* state_out, void* rew_out,
+                          uint8_t* done_out, void* chobs_out, int out_dtype, const DiralSlotPolicy* pol, void* stream) {
+  return step_policy_impl(e, mode, actions, t, state_out, rew_out, done_out, chobs_out, out_dtype, pol, nullptr, stream);
+}
+
+int diral_env_step_policy_ia(DiralEnv* e, int mode, const int32_t* actions, int64_t t, void* state_out, void* rew_out,
+                             uint8_t* done_out, void* chobs_out, int out_dtype, const DiralSlotPolicy* pol,
+                             const DiralSlotInfoAge* ia, void* stream) {
+  return step_policy_impl(e, mode, actions, t, state_out, rew_out, done_out, chobs_out, out_dtype, pol, ia, stream);
 }
 
 int diral_env_prefill_mode(DiralEnv* e, int mode, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out,
@@ -1111,9 +1151,11 @@ int diral_env_prefill_mode(DiralEnv* e, int mode, const int32_t* actions, int32_
   return DIRAL_OK;
 }
 
-int diral_env_rollout(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
-                      int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro, void* stream) {
+static int rollout_impl(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
+                        int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro,
+                        const DiralSlotInfoAge* ia, void* stream) {
   if (!e || !actions_seq || !ro || ro->struct_bytes != sizeof(DiralRollout) || slots < 1) return DIRAL_ERR_BAD_ARG;
+  if (ia && ia_block_check(ia, ro->shaped_out) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
   if (mode != DIRAL_STEP_MY_STEP && mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_BAD_ARG;
   if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
   if ((ro->shape_flags & ~5) != 0) return DIRAL_ERR_BAD_ARG;                  // global_reward_avg | stuck-action penalty
@@ -1121,6 +1163,10 @@ int diral_env_rollout(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t
   if (ro->shaped_out && (ro->shape_flags & 4) && (!ro->pen_counter || !ro->pen_prev_actions)) return DIRAL_ERR_BAD_ARG;
   // my_step_ch defines rewards only for reward_design 2,3,4 (test_env.py:413-429)
   if (mode == DIRAL_STEP_MY_STEP_CH && (e->cfg.reward_design < 2 || e->cfg.reward_design > 4)) return DIRAL_ERR_BAD_CONFIG;
+  if (ia) {
+    if (!e->la) return DIRAL_ERR_BAD_CONFIG;                     // (as diral_env_info_age)
+    if (mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_UNSUPPORTED;   // my_step's only stamp effect is the -1 of network.py:394
+  }
   DEVICE_ENTER(e->device);
   StepParams p = call_params(e, mode, t, actions_seq, states_out, out_dtype, 0.0, 1.0);
   p.rew_out = rew_out; p.done_out = done_out;
@@ -1132,10 +1178,23 @@ int diral_env_rollout(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t
   q.K = slots; q.vel_vary = has(&e->cfg, DIRAL_F_MOBILITY_VARY) ? 1 : 0; q.vel_seed = ro->vel_seed;
   q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N; q.vel_w = e->vel;
   q.rollout = 1 | ((states_all && p.state_out) ? 2 : 0); q.actions_seq = actions_seq;
+  ia_block_params(ia, q);
   const StepPlan d = plan_step(e, p, &q);
   if (!d.fused) return DIRAL_ERR_UNSUPPORTED;                    // (nothing launched: the caller loops step + shape)
+  if (ia && d.launch != StepLaunch::Fast64Slots) return DIRAL_ERR_UNSUPPORTED;   // (only that slot loop keeps the stamps)
   HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
   return DIRAL_OK;
+}
+
+int diral_env_rollout(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
+                      int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro, void* stream) {
+  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, nullptr, stream);
+}
+
+int diral_env_rollout_ia(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
+                         int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro,
+                         const DiralSlotInfoAge* ia, void* stream) {
+  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, ia, stream);
 }
 
 int diral_env_prefill(DiralEnv* e, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out, int out_dtype,

@@ -46,8 +46,12 @@ hipError_t launch_fast64_policy(const FastParams& f, const RichParams& r, const 
 // ... K slots per launch (PolParams::K > 1): step_fast64_slots_kernel, the same body with the env kept on the chip; `ch`:
 // my_step_ch slots (the reception ratios of P1 in LDS next to the policy's arrays)
 hipError_t launch_fast64_slots(const FastParams& f, const RichParams& r, const PolParams& q, bool ch, bool out64, int B, hipStream_t s) {
-  const uint32_t lds = fast_lds_layout(f.K, f.A, true, out64, true, ch, true).total;
-  if (ch) {
+  const bool ia = ch && q.ia_on != 0;       // the information-age block: the IA instantiations (arrival stamps, histogram pass, term)
+  const uint32_t lds = fast_lds_layout(f.K, f.A, true, out64, true, ch, true, ia).total;
+  if (ia) {
+    if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, true, false, true, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
+    else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, true, false, true, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
+  } else if (ch) {
     if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, true, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
     else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, true, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
   } else {

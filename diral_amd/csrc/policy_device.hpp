@@ -47,6 +47,15 @@ struct PolParams {
   // launch, no SPS state is read or written; the shaping and the velocity updates are the closed loop's.
   int rollout;                   // 0: off; bit 0: on; bit 1: every slot's state vector leaves ([K][B][N][S], as the prefill's)
   const int32_t* actions_seq;    // [K][B][N]
+  // The information-age block of a my_step_ch slot loop (diral_env_rollout_ia / diral_env_step_policy_ia, DiralSlotInfoAge;
+  // step_fast64_slots_kernel only): P1 keeps the arrival stamps FastParams::la from slot to slot, a pass behind P1's barrier
+  // builds Network.get_information_age(t + ks) in LDS, the shaping adds the ia_averaging term (main_test.py:151-160, 190-192)
+  int ia_on;                     // the call carries the block (plan_step: the stamps then do not ask for an EXTRA instantiation)
+  int ia_flags;                  // bit 0: ia_averaging
+  int32_t* ia_out;               // [K][B][100] or null
+  long long* ia_sum_out;         // [K][B] or null
+  int32_t* ia_pen_out;           // [K][B] or null (written with bit 0)
+  long long* sum_ia_prev;        // [B] in/out (bit 0)
 };
 
 // counter-based generator (splitmix64 finaliser over seed/stream/index); the

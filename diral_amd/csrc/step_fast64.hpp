@@ -47,7 +47,7 @@ namespace diral {
 #endif
 
 struct FastLds {
-  uint32_t rv, edges, mask, act, hist, cnt, slow, inv, mtab, rtx, inr, px, py, npx, rew, stage, nact, kvel, total;
+  uint32_t rv, edges, mask, act, hist, cnt, slow, inv, mtab, rtx, inr, px, py, npx, rew, stage, nact, kvel, ia, total;
 };
 // row stride (elements) of the channel-observation staging array [vehicle][resource] of the RICH
 // instantiations: a multiple of 4 elements, so that the write-out reads a 16-byte piece of a row
@@ -62,7 +62,8 @@ __host__ __device__ constexpr int fast_hist_stride(int K) { return (K + 1) | 1; 
 // merge reads the sources of FOUR consecutive resources with one ds_read_b32; the row stride of a32 + 4 bytes = 9 / 17
 // words puts the 64 lanes' words - read by the merge, written by P1 a group at a time, lane = row - on distinct banks
 __host__ __device__ constexpr int fast_mtab_stride(int A) { return (A <= 32 ? 32 : 64) + 4; }
-__host__ __device__ inline FastLds fast_lds_layout(int K, int A, bool rich, bool out64, bool flat, bool ratios = true, bool pol = false) {
+__host__ __device__ inline FastLds fast_lds_layout(int K, int A, bool rich, bool out64, bool flat, bool ratios = true, bool pol = false,
+                                                     bool ia = false) {
   FastLds l;
   uint32_t o = 0;
   const uint32_t a32 = A <= 32 ? 32u : 64u;
@@ -91,6 +92,9 @@ __host__ __device__ inline FastLds fast_lds_layout(int K, int A, bool rich, bool
   l.nact = o;  o += pol ? 4u * 64 : 0u;     // POL: the agents' actions of the next slot (K slots per launch)
   o = align_up(o, 8);
   l.kvel = o;  o += pol ? 8u * 64 : 0u;     // K slots per launch: the velocities the last slot's state vector reports (they live in registers)
+  // the information-age block of a my_step_ch slot loop (PolParams::ia_on), and only then: the caller's sum_ia_prev (8 bytes)
+  // and the 100 bins of Network.get_information_age
+  l.ia = o;    o += ia ? 8u + 4u * 100 : 0u;
   l.total = align_up(o, 16);
   return l;
 }

@@ -5,7 +5,16 @@
 // its env in registers and LDS from slot to slot.  The two differ where `#ifdef DIRAL_FAST_KSLOTS` says so and nowhere else: the one-slot kernel is compiled from
 // exactly the text it had before the K-slot form existed (the same statements behind `if (first)` / `if (last)` with
 // compile-time-true conditions cost the metric's instantiation a spilled register).
+#ifndef DIRAL_FAST_KSLOTS
+#define DIRAL_FAST_STAMPS EXTRA
 template <bool FLAT, bool OUT64, bool CH, bool EXTRA, bool RICH, bool POL = false>
+#else /* DIRAL_FAST_KSLOTS */
+// IA: the my_step_ch slot loop of a call that carries the information-age block (PolParams::ia_on) - arrival stamps kept from
+// slot to slot, the histogram pass, the ia_averaging term.  Instantiations of their own: as run-time branches of the two CH
+// slot loops they cost the calls without the block 3 to 5 % (profiles/kslots_ia/)
+#define DIRAL_FAST_STAMPS (EXTRA || IA)
+template <bool FLAT, bool OUT64, bool CH, bool EXTRA, bool RICH, bool POL = false, bool IA = false>
+#endif /* DIRAL_FAST_KSLOTS */
 #ifndef DIRAL_FAST_KSLOTS
 __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES) void DIRAL_FAST_KERNEL(const FastParams p, const RichParams r,
                                                                                 const PolParams q) {
@@ -20,12 +29,13 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
 #else /* DIRAL_FAST_KSLOTS */
   // (K slots: my_step_ch too - its staged observation is 0 / the constant 1, which the SPS agents read as -200 / -40 dBm)
   static_assert(!POL || (RICH && FLAT && !EXTRA), "the policy epilogue needs the staged channel observation of a my_step / my_step_ch slot");
+  static_assert(!IA || (POL && CH), "the information-age block belongs to the my_step_ch slot loop");
 #endif /* DIRAL_FAST_KSLOTS */
   extern __shared__ __align__(16) unsigned char smem[];
 #ifndef DIRAL_FAST_KSLOTS
   const FastLds lay = fast_lds_layout(p.K, p.A, RICH, OUT64, FLAT, CH || EXTRA);
 #else /* DIRAL_FAST_KSLOTS */
-  const FastLds lay = fast_lds_layout(p.K, p.A, RICH, OUT64, FLAT, CH || EXTRA, POL);
+  const FastLds lay = fast_lds_layout(p.K, p.A, RICH, OUT64, FLAT, CH || EXTRA, POL, IA);
 #endif /* DIRAL_FAST_KSLOTS */
   double* s_rv = reinterpret_cast<double*>(smem + lay.rv);
   double* s_edges = reinterpret_cast<double*>(smem + lay.edges);
@@ -90,6 +100,9 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   const int KS = POL ? q.K : 1;
   int* const s_nact = reinterpret_cast<int*>(smem + lay.nact);   // POL only
   double* const s_kvel = reinterpret_cast<double*>(smem + lay.kvel);   // POL only
+  // the information-age block (IA): the caller's sum_ia_prev and the 100 bins of this slot
+  long long* const s_iaprev = reinterpret_cast<long long*>(smem + lay.ia);
+  int* const s_ia = reinterpret_cast<int*>(smem + lay.ia + 8);
   // what a slot carries over to the next one (POL, KS > 1)
   double mynpx_prev = 0.0;
   unsigned int tkov_prev = 0u, told_next = 0u;
@@ -125,6 +138,9 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     prefill_i = lq0->prefill; rollout_i = lq0->rollout;
   }
   const bool prefill = prefill_i != 0;
+  // the information-age histogram of this slot is wanted (an output of the block, or its ia_averaging term)
+  bool ia_hist = false;
+  if constexpr (IA) ia_hist = (((LatePolArgs)(late_kernarg_base() + kPolArgOffset))->ia_on & 2) != 0;
   // an open-loop rollout (PolParams::rollout, diral_env_rollout): slot ks + 1 runs actions_seq[ks + 1]; with bit 1 every
   // slot's state vector leaves, as the prefill's
   const bool rollout = rollout_i != 0;
@@ -266,6 +282,15 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   if (tally_on) {
     for (int j = tid; j < KP * 64; j += 256) s_hist[j] = 0u;
   }
+  if constexpr (IA) {
+    if (ia_hist) {
+      if (tid < 100) s_ia[tid] = 0;
+      if (first && tid == 128) {
+        const long long* const sp = ((LatePolArgs)(late_kernarg_base() + kPolArgOffset))->sum_ia_prev;
+        s_iaprev[0] = sp ? sp[b] : 0ll;
+      }
+    }
+  }
   if (first) {
 #endif /* DIRAL_FAST_KSLOTS */
   if constexpr (!OUT64) {
@@ -337,7 +362,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
         }
         // find_closest_tx side effect (network.py:394): an out-of-range transmitter's arrival
         // stamp at this receiver becomes -1
-        if (EXTRA && p.la && live && (myact != i) && !inr) p.la[(bN + w) * N + lane] = -1;
+        if (DIRAL_FAST_STAMPS && p.la && live && (myact != i) && !inr) p.la[(bN + w) * N + lane] = -1;
         if (EXTRA && !CH && p.design && c > 1) {
           // my_step_design: reward by the number of transmitters of this resource within 2 Rc
           // of this one (network.py:122-157): alone 1, else -n (a pair inside 2 Rc gets -2)
@@ -394,7 +419,12 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
         asm volatile("" : "+v"(ob4[j]));
       }
     }
+#ifndef DIRAL_FAST_KSLOTS
     if (EXTRA && CH && p.la && got) p.la[(bN + bid) * N + lane] = (int32_t)(p.t + (p.t_dev ? *p.t_dev : 0ll));   // test_env.py:436
+#else /* DIRAL_FAST_KSLOTS */
+    // (slot ks of the launch: the slot number its one-slot call would be handed)
+    if (DIRAL_FAST_STAMPS && CH && p.la && got) p.la[(bN + bid) * N + lane] = (int32_t)(p.t + ks + (p.t_dev ? *p.t_dev : 0ll));   // test_env.py:436
+#endif /* DIRAL_FAST_KSLOTS */
     if (CH || (EXTRA && p.prr)) {
       if (c > 1) {
         // received[tx] = #rx whose nearest in-range tx is tx; R = received / in_range (test_env.py:398-405)
@@ -428,6 +458,40 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   }
   DIRAL_FSTAMP(2);
   __syncthreads();
+#ifdef DIRAL_FAST_KSLOTS
+  if constexpr (IA) {
+    // ---- Network.get_information_age(t + ks) (network.py:560-574, info_age_kernel's rules) of this env, all four waves:
+    // the stamps of this slot were stored by P1 of every wave - they are read BEHIND the barrier above, whose release /
+    // acquire fences at workgroup scope (s_waitcnt vmcnt(0) in front of s_barrier: the stores have reached the CU's vector
+    // cache, which the waves of a workgroup share) make them visible; the bins are read behind the barrier that ends P3
+    if (ia_hist) {
+      const LateFastArgs lp = (LateFastArgs)late_kernarg_base();
+      const int32_t* const lrow = lp->la + bN * N;               // [tx][rx] of this env, contiguous
+      const long long tt = lp->t + ks + (lp->t_dev ? *lp->t_dev : 0ll);
+      const int NN = N * N;
+      const unsigned int mg = (1u << 20) / (unsigned int)N + 1u;   // i / N == (i * mg) >> 20 for i < 2^13, 8 <= N <= 64
+      for (int i0 = tid; i0 < NN; i0 += 1024) {
+        int v[4];                                                  // four loads in flight per lane
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const int i = i0 + 256 * j; v[j] = lrow[i < NN ? i : 0]; }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int i = i0 + 256 * j;
+          const int tx = (int)(((unsigned int)i * mg) >> 20);
+          long long ia = tt - (long long)v[j];
+          const bool cnt = i < NN && i != tx * (N + 1) && v[j] != -1 && ia < 100;   // tx != rx; never arrived; beyond the list
+          if (ia < 0) ia += 100;                                   // Python's negative index
+          // (a stamp of this very slot - most of them, where the agents keep transmitting - is counted with a ballot: 64
+          // increments of ONE LDS word would be served one after the other)
+          const bool hit = cnt && ia >= 0, now = hit && ia == 0;
+          const int n0 = __popcll(__ballot(now));
+          if (n0 != 0 && lane == 0) atomicAdd(&s_ia[0], n0);
+          if (hit && !now) atomicAdd(&s_ia[(int)ia], 1);
+        }
+      }
+    }
+  }
+#endif /* DIRAL_FAST_KSLOTS */
 
   // ---- P2 (wave 0): reward per transmitter, metrics -------------------------------
   // Nothing of it is needed before the state vectors are written unless they carry the rewards (the RICH tail) or the
@@ -1139,6 +1203,42 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     if (wave == 1) {
       const LatePolArgs lq = (LatePolArgs)(late_kernarg_base() + kPolArgOffset);
       void* const shaped_out = lq->shaped_out;
+#ifdef DIRAL_FAST_KSLOTS
+      // the information-age block: this slot's histogram leaves, utils/misc.calculate_ia_penalty of it, and the
+      // ia_averaging term (main_test.py:151-160) against the sum of the slot before
+      int ia_term = 0;
+      bool ia_avg = false;
+      if constexpr (IA) {
+        if (ia_hist) {
+          const size_t sBi = (size_t)ks * (size_t)p.B + (size_t)b;
+          const int v0 = s_ia[lane], v1 = lane < 36 ? s_ia[64 + lane] : 0;
+          int32_t* const io = lq->ia_out;
+          if (io) {
+            io[sBi * 100 + lane] = v0;
+            if (lane < 36) io[sBi * 100 + 64 + lane] = v1;
+          }
+          // (counts are never negative; N (N - 1) entries of weight <= 100: the sum fits 32 bits)
+          int acc = (lane + 1) * v0 + (lane + 65) * v1;
+#pragma unroll
+          for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+          const long long sum = (long long)acc;
+          long long* const so = lq->ia_sum_out;
+          if (so && lane == 0) so[sBi] = sum;
+          ia_avg = (lq->ia_flags & 1) != 0;
+          if (ia_avg) {
+            const long long prev = s_iaprev[0];
+            ia_term = sum > prev ? -1 : (sum < prev ? 1 : 0);
+            wave_lds_order();
+            if (lane == 0) {
+              s_iaprev[0] = sum;
+              if (last) lq->sum_ia_prev[b] = sum;
+              int32_t* const po = lq->ia_pen_out;
+              if (po) po[sBi] = ia_term;
+            }
+          }
+        }
+      }
+#endif /* DIRAL_FAST_KSLOTS */
       if (shaped_out) {
 #ifdef DIRAL_FAST_KSLOTS
         // (K slots: shaped_out [K][B][N], sum_r_out / coll_out [K][B], slot-major)
@@ -1160,6 +1260,9 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
         }
         if (live) {
           out_t rr = a;
+#ifdef DIRAL_FAST_KSLOTS
+          if (ia_avg) rr = rr + (out_t)ia_term;                  // (in front of the stuck-action test, as driver_shape_kernel)
+#endif /* DIRAL_FAST_KSLOTS */
           if (sflags & 4) {
             int32_t* const pc = lq->pen_counter;
             int32_t* const pp = lq->pen_prev;
@@ -1357,3 +1460,4 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
 #undef p
 #endif /* DIRAL_FAST_KSLOTS */
 }
+#undef DIRAL_FAST_STAMPS

@@ -226,21 +226,35 @@ class DriverLoop:
         [B, N, S]; `states` = ``"all"``: every slot's [K, B, N, S]; None: none), ``reward`` [B, N] (as the env returned it)
         and ``done`` [B] of the last slot, ``shaped`` [K, B, N], ``sum_r`` / ``collision`` [K, B].  On the HIP env this is
         ONE launch (`VecV2VEnv.rollout` -> `diral_env_rollout`); configurations that launch does not take, the
-        information-age terms - and any other env - run the loop.  The loop's episode counter and epsilon stay where they
-        are (`end_episode` is the caller's): every slot's fingerprint columns carry the current ones."""
+        information-age terms of a my_step driver - and any other env - run the loop.  The loop's episode counter and
+        epsilon stay where they are (`end_episode` is the caller's): every slot's fingerprint columns carry the current ones.
+
+        `enable_channel` on a HIP env with `track_arrival` (the driver reads the information age behind every slot,
+        main_test.py:150): the launch carries the information-age block (`diral_env_rollout_ia`) - `ia_averaging` included -
+        and the result gains ``ia`` [K, B, 100], ``ia_sum`` [K, B] and, with `ia_averaging`, ``ia_penalty`` [K, B]; the loop
+        behind a refused launch stacks what ``slot(want_ia=True)`` returns."""
         env = self.env
         seq = self._t(actions_seq)
         K = int(seq.shape[0])
-        if hasattr(env, "rollout") and not self.ia_averaging:
+        hip = hasattr(env, "lib") and hasattr(env, "_stream")
+        with_ia = bool(self.enable_channel and getattr(getattr(env, "cfg", None), "track_arrival", False))
+        if hasattr(env, "rollout") and ((with_ia and hip) or not self.ia_averaging):
             pen = None
             if self.ia_penalty_enable:
                 if self._pen_counter is None:
                     self._pen_counter = torch.zeros((env.B, env.N), dtype=torch.int32, device=env.device)
                     self._prev_actions = torch.full((env.B, env.N), -1, dtype=torch.int32, device=env.device)
                 pen = (int(self.ia_penalty_threshold), float(self.ia_penalty_value), self._pen_counter, self._prev_actions)
+            ia_kw = {}
+            if with_ia and hip:
+                if self.ia_averaging and self._sum_ia_prev is None:
+                    self._sum_ia_prev = torch.zeros((env.B,), dtype=torch.int64, device=env.device)
+                ia_kw = dict(info_age=True, sum_ia_prev=self._sum_ia_prev if self.ia_averaging else None)
             try:
                 out = env.rollout(seq, t, mode="my_step_ch" if self.enable_channel else "my_step", states=states,
-                                  global_reward_avg=self.global_reward_avg, stuck_penalty=pen, vel_seed=vel_seed)
+                                  global_reward_avg=self.global_reward_avg, stuck_penalty=pen, vel_seed=vel_seed, **ia_kw)
+                if "ia_penalty" in out:                                          # (as slot() reports it)
+                    out["ia_penalty"] = out["ia_penalty"].to(out["shaped"].dtype)
                 if out["states"] is not None and env.cfg.enable_fingerprint:     # test_env.py:577-579
                     out["states"][..., env._fp_offset] = self.episode
                     out["states"][..., env._fp_offset + 1] = self.eps
@@ -249,9 +263,15 @@ class DriverLoop:
                 if exc.status != ERR_UNSUPPORTED:
                     raise
         kept, shaped, sum_r, coll = [], [], [], []
+        ia_keys = ("ia", "ia_sum", "ia_penalty")
+        ia_kept: Dict[str, list] = {k: [] for k in ia_keys}
         out: Dict[str, Any] = {}
         for k in range(K):
-            out = self.slot(seq[k], t + k)
+            out = self.slot(seq[k], t + k, want_ia=True if with_ia else None)
+            if with_ia:
+                for key in ia_keys:
+                    if key in out:
+                        ia_kept[key].append(self._t(out[key]).clone())
             if states == "all":
                 kept.append(self._t(out["next_state"]).clone())
             shaped.append(self._t(out["reward"]).clone())
@@ -263,7 +283,7 @@ class DriverLoop:
         done = torch.full((raw.shape[0],), 1 if out["episode_end"] else 0, dtype=torch.uint8, device=raw.device)
         st = None if states is None else (torch.stack(kept) if states == "all" else self._t(out["next_state"]))
         return dict(states=st, reward=raw, done=done, shaped=torch.stack(shaped), sum_r=torch.stack(sum_r),
-                    collision=torch.stack(coll))
+                    collision=torch.stack(coll), **{key: torch.stack(v) for key, v in ia_kept.items() if v})
 
     def _shape_on_device(self, reward: torch.Tensor, a: torch.Tensor, ia: Optional[torch.Tensor]):
         """main_test.py:171-206 through `diral_driver_shape` (one launch)."""

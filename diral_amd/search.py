@@ -45,11 +45,14 @@ class CandidateSearch:
         self._gather = candidate_index(env.B, C, env.device)        # built once, on the device
         self._K = 0
 
-    def evaluate(self, seqs, t: Optional[int] = None, mode="my_step", global_reward_avg: bool = False, vel_seed: int = 0
-                 ) -> Dict[str, torch.Tensor]:
+    def evaluate(self, seqs, t: Optional[int] = None, mode="my_step", global_reward_avg: bool = False, vel_seed: int = 0,
+                 info_age: bool = False) -> Dict[str, torch.Tensor]:
         """Run every candidate: `seqs` [K, B, C, N] int32, ``seqs[k, b, c]`` the actions of env b's candidate c in slot
         ``t + k`` (`t` defaults to ``env.t``).  Returns ``returns`` [B, C] (the sum of `sum_r` over the K slots, float64),
-        ``sum_r`` and ``collision`` [K, B, C] (main_test.py:171, 178) - and leaves `env` as it was."""
+        ``sum_r`` and ``collision`` [K, B, C] (main_test.py:171, 178) - and leaves `env` as it was.  `info_age` (`mode` =
+        ``"my_step_ch"`` on a `track_arrival` handle): the rollout of `work` keeps the arrival stamps (`copy_envs_from`
+        carries them) and ``ia_sum`` [K, B, C] int64 - utils/misc.calculate_ia_penalty of every candidate's information-age
+        histogram behind every slot - is returned beside ``returns``: candidates can be scored by information age."""
         env, work, C = self.env, self.work, self.C
         seq = torch.as_tensor(seqs, device=env.device)
         if seq.dim() != 4 or tuple(seq.shape[1:]) != (env.B, C, env.N) or seq.shape[0] < 1:
@@ -60,30 +63,37 @@ class CandidateSearch:
             t = env.t
         work.copy_envs_from(env, src_index=self._gather)
         try:
-            out = work.rollout(seq, t, mode=mode, states=None, global_reward_avg=global_reward_avg, vel_seed=vel_seed)
-            sum_r, coll = out["sum_r"], out["collision"]
+            out = work.rollout(seq, t, mode=mode, states=None, global_reward_avg=global_reward_avg, vel_seed=vel_seed,
+                               info_age=True if info_age else None)
+            sum_r, coll, ia_sum = out["sum_r"], out["collision"], out.get("ia_sum")
         except DiralError as exc:
             if exc.status != ERR_UNSUPPORTED:                       # (refused: nothing launched, `work` untouched)
                 raise
-            sum_r, coll = self._loop(seq, int(t), _MODES[mode], global_reward_avg, vel_seed)
+            sum_r, coll, ia_sum = self._loop(seq, int(t), _MODES[mode], global_reward_avg, vel_seed, info_age)
         self._K = K
-        return dict(returns=sum_r.to(torch.float64).sum(0).view(env.B, C), sum_r=sum_r.view(K, env.B, C),
-                    collision=coll.view(K, env.B, C))
+        res = dict(returns=sum_r.to(torch.float64).sum(0).view(env.B, C), sum_r=sum_r.view(K, env.B, C),
+                   collision=coll.view(K, env.B, C))
+        if info_age:
+            res["ia_sum"] = ia_sum.view(K, env.B, C)
+        return res
 
-    def _loop(self, seq: torch.Tensor, t: int, step_mode: int, global_reward_avg: bool, vel_seed: int):
+    def _loop(self, seq: torch.Tensor, t: int, step_mode: int, global_reward_avg: bool, vel_seed: int, info_age: bool = False):
         """What `rollout` is equal to, slot by slot (as diral_amd.driver.DriverLoop.rollout loops)."""
         work = self.work
         K, EI = int(seq.shape[0]), work.cfg.episode_interval
         o = dict(dtype=work.out_dtype, device=work.device)
         shaped = torch.empty((work.B, work.N), **o)
         sum_r, coll = torch.empty((K, work.B), **o), torch.empty((K, work.B), **o)
+        ia_sum = torch.empty((K, work.B), dtype=torch.int64, device=work.device) if info_age else None
         for k in range(K):
             _, rew, _ = work._step(step_mode, seq[k], t + k, want_obs=False)
-            driver_shape(work, rew, seq[k], shaped=shaped, sum_r=sum_r[k], collision=coll[k], global_reward_avg=global_reward_avg)
+            ia = work.info_age(t + k) if info_age else None
+            driver_shape(work, rew, seq[k], shaped=shaped, sum_r=sum_r[k], collision=coll[k], global_reward_avg=global_reward_avg,
+                         ia=ia, ia_sum=None if ia is None else ia_sum[k])
             if (t + k) % EI == EI - 1:
                 work.update_velocity(seed=vel_seed + (t + k) // EI)
         work.t = t + K
-        return sum_r, coll
+        return sum_r, coll, ia_sum
 
     def commit(self, choice) -> None:
         """Keep candidate ``choice[b]`` of every env b ([B] integer tensor, e.g. ``returns.argmax(1)``): `env` becomes

@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from ._tensors import MSG_OUT, _ptr, check_tensor, dtype_code, policy_seed, seed64
 from .config import (DT_F32, DT_F64, ERR_HIP, ERR_UNSUPPORTED, M_COLUMNS, OK, OPT_ENV_OFFSET, OPT_KERNEL_PATH, PATH_AUTO,
-                     PATH_GENERAL, PATH_LARGE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, ConfigError, DiralRollout,
+                     PATH_GENERAL, PATH_LARGE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, ConfigError, DiralRollout, DiralSlotInfoAge,
                      DiralSlotPolicy, EnvConfig)
 
 # MA_NeighborTableEntry (envs/ma_messages_pb2.py:195-230) as a host view of DiralNeighborEntry
@@ -249,6 +249,28 @@ class VecV2VEnv:
         q.vel_seed = seed64(vel_seed)
         return q
 
+    def _info_age_block(self, where: str, info_age, sum_ia_prev, K: int):
+        """The information-age block of a K-slot my_step_ch call (DiralSlotInfoAge) and the tensors it fills: `info_age` =
+        True / ``"hist"`` - every slot's histogram and its sum; ``"stamps"`` - the arrival stamps are kept, nothing else;
+        `sum_ia_prev` ([B] int64, updated in place) switches the `ia_averaging` term on."""
+        if info_age is True:
+            info_age = "hist"
+        if info_age not in ("hist", "stamps"):
+            raise ValueError("%s: info_age must be None, True, 'hist' or 'stamps'" % where)
+        blk = DiralSlotInfoAge()
+        blk.struct_bytes = ctypes.sizeof(blk)
+        out = {}
+        if info_age == "hist":
+            out["ia"] = torch.empty((K, self.B, 100), dtype=torch.int32, device=self.device)
+            out["ia_sum"] = torch.empty((K, self.B), dtype=torch.int64, device=self.device)
+            blk.ia_out, blk.ia_sum_out = _ptr(out["ia"]), _ptr(out["ia_sum"])
+        if sum_ia_prev is not None:
+            check_tensor("%s: sum_ia_prev" % where, sum_ia_prev, torch.int64, (self.B,), self.device)
+            out["ia_penalty"] = torch.empty((K, self.B), dtype=torch.int32, device=self.device)
+            blk.flags = 1
+            blk.ia_pen_out, blk.sum_ia_prev = _ptr(out["ia_penalty"]), _ptr(sum_ia_prev)
+        return blk, out
+
     def _f64(self, a, shape) -> Optional[torch.Tensor]:
         if a is None:
             return None
@@ -422,7 +444,7 @@ class VecV2VEnv:
     def step_policy(self, actions: torch.Tensor, t: int, policy, actions_out: torch.Tensor, shaped_out=None, sum_r_out=None,
                     collision_out=None, global_reward_avg: bool = True, want_chobs: bool = False, clock=None,
                     seed_offset: Optional[int] = None, mode: Optional[int] = None, slots: int = 1, vel_seed: int = 0,
-                    want_obs: bool = True, stuck_penalty: Optional[tuple] = None):
+                    want_obs: bool = True, stuck_penalty: Optional[tuple] = None, info_age=None, sum_ia_prev=None):
         """One slot of a policy-only rollout as ONE launch (`diral_env_step_policy`): env step (state, reward, done,
         optionally the channel observation) + the driver's reward shaping (main_test.py:171-206 without the
         information-age terms) + the SPS agents' decisions for the next slot (algorithms/v2x_sps.py:76-104), the
@@ -447,7 +469,13 @@ class VecV2VEnv:
         episode ends inside the launch (`update_velocity(seed=vel_seed + slot // episode_interval)`).  Equal, bit for bit,
         to K one-slot calls; raises DiralError(UNSUPPORTED) where the fused kernel does not apply.  `mode` = STEP_MY_STEP_CH
         (the PRR reward of `enable_channel`, reward_design 2 ... 4) runs K > 1 slots in one launch at 8 <= N <= 64 too
-        (profiles/kslots_ch/); with slots = 1 it stays three launches, and 64 < N <= 256 refuses it."""
+        (profiles/kslots_ch/); with slots = 1 it stays three launches, and 64 < N <= 256 refuses it.
+
+        `info_age` (K > 1 slots of my_step_ch on a `track_arrival` handle, 8 <= N <= 64; `diral_env_step_policy_ia`):
+        ``True`` / ``"hist"`` - the launch keeps the arrival stamps and returns, as a fourth value, a dict with ``ia``
+        [K, B, 100] int32 (`info_age(t + k)` behind slot k) and ``ia_sum`` [K, B] int64; ``"stamps"`` - the stamps only
+        (an empty dict); `sum_ia_prev` ([B] int64, updated in place) adds the `ia_averaging` term (main_test.py:151-160)
+        to the shaped rewards and ``ia_penalty`` [K, B] int32 to the dict.  ``None``: today's call, three values."""
         K = int(slots)
         if K < 1:
             raise ValueError("step_policy: slots must be >= 1")
@@ -484,10 +512,15 @@ class VecV2VEnv:
         use_chobs = want_chobs or not fusable
         self._bind_slot(1, use_chobs)
 
+        blk, ia_out = (None, None) if info_age is None else self._info_age_block("step_policy", info_age, sum_ia_prev, K)
+
         def call(chobs):
-            return self.lib.diral_env_step_policy(self._h, self.step_mode if mode is None else mode, _ptr(actions), int(t),
-                                                  _ptr(self._obs) if (want_obs and self.S > 0) else None, _ptr(self._rew),
-                                                  _ptr(self._done), _ptr(chobs), self._dt, ctypes.byref(q), self._stream())
+            args = (self._h, self.step_mode if mode is None else mode, _ptr(actions), int(t),
+                    _ptr(self._obs) if (want_obs and self.S > 0) else None, _ptr(self._rew),
+                    _ptr(self._done), _ptr(chobs), self._dt, ctypes.byref(q))
+            if blk is None:
+                return self.lib.diral_env_step_policy(*args, self._stream())
+            return self.lib.diral_env_step_policy_ia(*args, ctypes.byref(blk), self._stream())
         st = call(self._chobs if use_chobs else None)
         if st == ERR_UNSUPPORTED and not use_chobs and K == 1:  # not a fused configuration, nothing launched
             self._policy_needs_chobs = True
@@ -497,12 +530,15 @@ class VecV2VEnv:
         if clock is None:
             policy._t += K        # only once the call is in: slot k drew with seed + k, what K one-slot calls are given; a
                                   # refused call (DIRAL_ERR_UNSUPPORTED: nothing launched) leaves the draw counter alone
-        self._keep["step_policy"] = (q, actions, actions_out, shaped_out, sum_r_out, collision_out, clock, stuck_penalty)
+        self._keep["step_policy"] = (q, actions, actions_out, shaped_out, sum_r_out, collision_out, clock, stuck_penalty,
+                                     blk, ia_out, sum_ia_prev)
+        if blk is not None:
+            return self._obs, self._rew, self._done, ia_out
         return self._obs, self._rew, self._done
 
     def rollout(self, actions_seq, t: Optional[int] = None, mode="my_step", states: Optional[str] = "last",
-                global_reward_avg: bool = False, stuck_penalty: Optional[tuple] = None, vel_seed: int = 0
-                ) -> Dict[str, Optional[torch.Tensor]]:
+                global_reward_avg: bool = False, stuck_penalty: Optional[tuple] = None, vel_seed: int = 0,
+                info_age=None, sum_ia_prev=None) -> Dict[str, Optional[torch.Tensor]]:
         """K slots of a GIVEN action sequence as ONE launch (`diral_env_rollout`): slot k runs ``my_step(actions_seq[k],
         t + k)`` (`mode` = ``"my_step_ch"``: ``my_step_ch``, reward_design 2 ... 4), then the driver's reward shaping
         (main_test.py:171-206 without the information-age terms, `diral_driver_shape` with the same flags) and, in configs
@@ -517,7 +553,13 @@ class VecV2VEnv:
         ``shaped`` [K, B, N], ``sum_r`` [K, B], ``collision`` [K, B] of every slot (fresh tensors).  Bit-equal to the loop of
         K `step` + `diral_driver_shape` (+ `update_velocity`) calls; the env's slot counter moves on by K.  Raises
         DiralError(ERR_UNSUPPORTED) with nothing launched and the env untouched where the slot loops do not apply
-        (include/diral_env.h lists them; diral_amd.driver.DriverLoop.rollout loops then)."""
+        (include/diral_env.h lists them; diral_amd.driver.DriverLoop.rollout loops then).
+
+        `info_age` (`mode` = ``"my_step_ch"`` on a `track_arrival` handle, 8 <= N <= 64; `diral_env_rollout_ia`): ``True`` /
+        ``"hist"`` - the launch keeps the arrival stamps and the result gains ``ia`` [K, B, 100] int32 (`info_age(t + k)`
+        behind slot k) and ``ia_sum`` [K, B] int64; ``"stamps"`` - the stamps only; `sum_ia_prev` ([B] int64, updated in
+        place) adds the `ia_averaging` term (main_test.py:151-160, 190-192) to the shaped rewards, in front of the stuck
+        penalty, and ``ia_penalty`` [K, B] int32 to the result.  ``None``: today's call - a tracking handle is refused."""
         step_mode = _MODES.get(mode)
         if step_mode not in (STEP_MY_STEP, STEP_MY_STEP_CH):
             raise ValueError("rollout: mode must be 'my_step' or 'my_step_ch'")
@@ -543,12 +585,18 @@ class VecV2VEnv:
             st_out = torch.empty((K, self.B, self.N, self.S), dtype=self.out_dtype, device=self.device)
         else:
             st_out = self._obs if want_states else None
-        st = self.lib.diral_env_rollout(self._h, step_mode, _ptr(seq), K, int(t), _ptr(st_out), 1 if states == "all" else 0,
-                                        _ptr(self._rew), _ptr(self._done), self._dt, ctypes.byref(q), self._stream())
+        args = (self._h, step_mode, _ptr(seq), K, int(t), _ptr(st_out), 1 if states == "all" else 0,
+                _ptr(self._rew), _ptr(self._done), self._dt, ctypes.byref(q))
+        blk, ia_out = None, {}
+        if info_age is None:
+            st = self.lib.diral_env_rollout(*args, self._stream())
+        else:
+            blk, ia_out = self._info_age_block("rollout", info_age, sum_ia_prev, K)
+            st = self.lib.diral_env_rollout_ia(*args, ctypes.byref(blk), self._stream())
         self._ok(st, "diral_env_rollout", K)            # (a refused call has launched nothing: the ring is back where it was)
         self.t = int(t) + K
-        self._keep["rollout"] = (q, seq, stuck_penalty)
-        return dict(states=st_out, reward=self._rew, done=self._done, shaped=shaped, sum_r=sum_r, collision=coll)
+        self._keep["rollout"] = (q, seq, stuck_penalty, blk, sum_ia_prev)
+        return dict(states=st_out, reward=self._rew, done=self._done, shaped=shaped, sum_r=sum_r, collision=coll, **ia_out)
 
     def step(self, actions, t: Optional[int] = None, episode: float = 0.0, epsilon: float = 1.0
              ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

@@ -491,7 +491,8 @@ typedef struct DiralSlotPolicy {
   const int64_t* seed_clock;      /* NULL, or a device counter added to the seed */
   int32_t* actions_out;           /* [B][N] */
   /* K slots in ONE launch (ABI 6).  slots <= 1: one slot, as above.  slots = K > 1 (configurations the fused kernels take -
-   * N <= 256 vehicles, my_step, the flat highway, A <= 64, none of the run-time extras (arrival stamps, trace replay, PRR
+   * N <= 256 vehicles, my_step, the flat highway, A <= 64, none of the run-time extras (arrival stamps - but see
+   * diral_env_step_policy_ia -, trace replay, PRR
    * tracking, static topologies, handles without piggybacked tables), no State.piggybacking; at 8 <= N <= 64 also
    * my_step_ch (DIRAL_STEP_MY_STEP_CH with reward_design 2, 3 or 4: the PRR reward and the PRR metric columns every slot;
    * a ONE-slot call in that mode stays three launches, and 64 < N <= 256 refuses it); otherwise
@@ -556,8 +557,8 @@ int diral_env_prefill_mode(DiralEnv* env, int mode, const int32_t* actions, int3
  *   shaped_out [K][B][N], sum_r_out [K][B], collision_out [K][B]   out dtype, slot-major; shaped_out NULL = no shaping;
  *     shape_flags: bit 0 global_reward_avg, bit 2 stuck-action penalty (then pen_counter / pen_prev_actions are mandatory);
  *     shape_flags = 0: shaped_out[k] is the reward as the step returns it
- * Configurations the slot loops take: 8 <= N <= 256, A <= 64, the one-lane highway, piggybacked tables, no arrival / PRR
- * tracking, no trace replay, no static topology, no State.piggybacking, no secondary observation mode behind a state
+ * Configurations the slot loops take: 8 <= N <= 256, A <= 64, the one-lane highway, piggybacked tables, no arrival (but
+ * see diral_env_rollout_ia) / PRR tracking, no trace replay, no static topology, no State.piggybacking, no secondary observation mode behind a state
  * vector; my_step_ch and states_all = 1 at N <= 64 only.  Otherwise DIRAL_ERR_UNSUPPORTED with nothing launched and the env
  * untouched (loop over the calls instead: diral_amd.driver.DriverLoop.rollout does).  my_step_ch with reward_design
  * outside 2 ... 4: DIRAL_ERR_BAD_CONFIG (as diral_env_step). */
@@ -577,6 +578,43 @@ typedef struct DiralRollout {
 int diral_env_rollout(DiralEnv* env, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
                       int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* rollout,
                       void* stream);
+
+/* Information age inside the K-slot my_step_ch launches (additive within ABI 8; step_fast64_slots_kernel, 8 <= N <= 64).
+ * The reference's driver reads Network.get_information_age(time_step) behind EVERY slot (main_test.py:150) and, with
+ * `ia_averaging`, turns the movement of utils/misc.calculate_ia_penalty of it into a -1 / 0 / +1 reward term
+ * (main_test.py:151-160, 190-192).  The arrival stamps are my_step_ch's (test_env.py:436, network.py:394): the two entry
+ * points below are diral_env_rollout / diral_env_step_policy with one more argument, the block, and on a handle created
+ * with DIRAL_F_TRACK_ARRIVAL the slot loop then
+ *   - keeps the arrival stamps from slot to slot (slot k stamps t + k, plus the slot clock when one is set),
+ *   - writes behind slot k   ia_out[k] = diral_env_info_age(env, t + k),  ia_sum_out[k] = sum (i + 1) ia[i] over ia[i] > 0,
+ *   - with flags bit 0 adds  term = -1 / +1 / 0 (ia_sum rose above / fell below / equals sum_ia_prev) to slot k's rewards
+ *     in front of the stuck-action test and the global average (diral_driver_shape's order with `ia` and flag bit 1),
+ *     writes it to ia_pen_out[k] and leaves ia_sum in sum_ia_prev; the state vector's reward column stays the raw reward.
+ * Equal, bit for bit, to the loop of diral_env_step(DIRAL_STEP_MY_STEP_CH) + diral_env_info_age + diral_driver_shape
+ * (+ diral_env_update_velocity) calls.  All three outputs NULL and flags 0: the stamps are kept, no histogram is built.
+ *   `ia` NULL: exactly diral_env_rollout / diral_env_step_policy, refusals included (a tracking handle stays refused).
+ *   DIRAL_ERR_BAD_ARG (checked first, no device needed): struct_bytes, flags & ~1, bit 0 without sum_ia_prev or without
+ *     shaped_out, and everything the base entry point rejects;
+ *   DIRAL_ERR_BAD_CONFIG: a handle without DIRAL_F_TRACK_ARRIVAL (as diral_env_info_age); reward_design outside 2 ... 4;
+ *   DIRAL_ERR_UNSUPPORTED, nothing launched, env untouched: mode != DIRAL_STEP_MY_STEP_CH, N < 8 or N > 64, a one-slot
+ *     diral_env_step_policy_ia call (slots <= 1), and every configuration the my_step_ch slot loop refuses (PRR tracking,
+ *     trace replay, static topology, no piggybacked tables, vehicles off the lane, State.piggybacking, secondary observation
+ *     modes behind a state vector).
+ * Enqueue-only, like the other slot launches. */
+typedef struct DiralSlotInfoAge {
+  uint32_t struct_bytes;          /* = sizeof(DiralSlotInfoAge) */
+  int32_t  flags;                 /* bit 0: ia_averaging - add the -1 / 0 / +1 term to every slot's shaped rewards */
+  int32_t* ia_out;                /* [K][B][100] Network.get_information_age(t + k) behind slot k, or NULL */
+  int64_t* ia_sum_out;            /* [K][B] utils/misc.calculate_ia_penalty of it, or NULL */
+  int32_t* ia_pen_out;            /* [K][B] the term (written with bit 0), or NULL */
+  int64_t* sum_ia_prev;           /* [B] in/out, the caller's (as pen_counter is); mandatory with bit 0 */
+} DiralSlotInfoAge;
+int diral_env_rollout_ia(DiralEnv* env, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
+                         int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* rollout,
+                         const DiralSlotInfoAge* ia, void* stream);
+int diral_env_step_policy_ia(DiralEnv* env, int mode, const int32_t* actions, int64_t t, void* state_out, void* rew_out,
+                             uint8_t* done_out, void* chobs_out, int out_dtype, const DiralSlotPolicy* policy,
+                             const DiralSlotInfoAge* ia, void* stream);
 
 /* ---- slot clock: rollouts captured into a hipGraph ---------------------------------------------
  * A captured sequence of K slots (env step, reward shaping, policy) bakes every by-value argument into its
