@@ -562,6 +562,7 @@ FastParams fast_params(const DiralEnv* e, const StepParams& p, const StepPlan& d
   f.B = p.B;
   f.f32_m16 = d.use_fast64 ? f32_margin16(p.L, p.Rb, p.K, e->hooks.f32_margin) : 0;
   f.f32_xmax = (float)p.L;
+  f.wo = writeout_params(p.A, p.K, p.out_f64 != 0);
   f.slow_cnt_r = nullptr; f.slow_list_r = nullptr; f.slow_flag_r = nullptr;
   f.slow_cnt_w = nullptr; f.slow_list_w = nullptr; f.slow_flag_w = nullptr; f.slow_cnt_z = nullptr;
   return f;

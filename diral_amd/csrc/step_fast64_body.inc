@@ -627,11 +627,13 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
       constexpr int CV = OUT64 ? 2 : 4;
       out_t* const co = static_cast<out_t*>(chobs_out) + bN * A;
       if ((A % CV) == 0) {
-        const int qpr = A / CV, total = N * qpr;
-        const int du = 256 / qpr, dq = 256 - du * qpr;
-        int u = tid / qpr, qr = tid - u * qpr;
+        // (row and piece of the first trip, and what a trip advances by: the host's divisions, WriteoutParams)
+        const WriteoutParams wo = load_writeout_args(late_kernarg_base());
+        const int qpr = A >> (OUT64 ? 1 : 2), total = N * qpr;
+        const int du = wo.co_du, dq = wo.co_dq;
+        int u = (int)(__umul24((unsigned int)tid, (unsigned int)wo.qa_mul) >> wo.qa_shift), qr = tid - (int)__umul24((unsigned int)u, (unsigned int)qpr);
         for (int q = tid; q < total; q += 256) {
-          const out_t* src = s_stage + u * SA + qr * CV;        // 16-byte aligned: SA % 4 == 0
+          const out_t* src = s_stage + __umul24((unsigned int)u, (unsigned int)SA) + qr * CV;   // 16-byte aligned: SA % 4 == 0
           if constexpr (OUT64) stream_store2(co + 2 * q, *reinterpret_cast<const double2*>(src));
           else stream_store4(co + 4 * q, *reinterpret_cast<const float4*>(src));
           u += du; qr += dq;
@@ -846,7 +848,8 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   // (the own position folded into the addend: t16 = xpos * (inv_w 2^16) + (Rb - npx) * inv_w 2^16 - one v_fma_f32 per entry
   // instead of a subtraction and the fma; the host's bound FastParams::f32_m16 covers this form: csrc/diral_env.hip)
   const float cfix16f = (float)((p.Rb - mynpx) * inv_w * 65536.0);
-  const unsigned int k16m = ((unsigned int)K << 16) + 2u * (unsigned int)m16;   // -m16 <= t16 < K * 2^16 + m16
+  const unsigned int m16x2 = 2u * (unsigned int)m16;
+  const unsigned int k16m = ((unsigned int)K << 16) + m16x2;                    // -m16 <= t16 < K * 2^16 + m16
   unsigned int* const hrow = s_hist + lane * KP;
   // Network.dist_piggy + get_positional_dist_2_piggy (network.py:538-558, 473-513) of one entry:
   // d = dist(entry, own post-move position), kept if d < Rb, value d * sign(x1 - x2)
@@ -947,7 +950,8 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
             const int src = ((int)((__builtin_ctz((cnq >> (8 * cc)) | 0x100u)) & 7) << 2) + (((4 * q + cc) & 7) << 5);
             const float xf = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(q >= 2 ? ringf1 : ringf0)));
             const int t16 = cvt_i32_f32_sat(__builtin_fmaf(xf, invw16f, cfix16f));
-            return (unsigned int)(t16 + m16) < k16m && (((unsigned int)(t16 - m16)) & 0xffffu) >= 65536u - 2u * (unsigned int)m16;
+            const unsigned int s = (unsigned int)t16 + (unsigned int)m16;     // (the same two tests on the same sum as column32)
+            return s < k16m && (s & 0xffffu) < m16x2;
           };
           auto column = [&](auto cc_tag) {
             constexpr int cc = decltype(cc_tag)::value;
@@ -989,7 +993,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
           // inv_w * 2^16 truncated - its integer part is the bin, and |v| < Rb is 0 <= t16 < K * 2^16, unless the 16 fraction bits
           // are within m16 of an integer (everything float32 lost is below m16 / 65536 bin widths).  Lanes inside that
           // band are left for the float64 body, which then runs once more for the quad (a uniform test: rare)
-          bool redo = false;                                        // an entry of this lane is left for float64
+          unsigned long long redo_m = 0ull;                         // the lanes with an entry left for float64
           auto column32 = [&](auto cc_tag) {
             constexpr int cc = decltype(cc_tag)::value;
             const int c = 4 * q + cc;
@@ -997,19 +1001,28 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
             const float xf = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(q >= 2 ? ringf1 : ringf0)));
             const int t16 = cvt_i32_f32_sat(__builtin_fmaf(xf, invw16f, cfix16f));
             const bool agev = ((agt >> (8 * cc)) & 255u) < (unsigned int)p.age_limit;
-            const bool mm = agev && (unsigned int)(t16 + m16) < k16m;
-            const bool band = (((unsigned int)(t16 - m16)) & 0xffffu) >= 65536u - 2u * (unsigned int)m16;
-            const bool cnt = mm && !band;
-            redo = redo || (mm && band);
-            atomicAdd(&hrow[cnt ? (t16 >> 16) : K], 1u);
-            mycnt += cnt ? 1u : 0u;
+            // ONE sum serves both tests and the bin.  s = t16 + m16: the range test is s < K 2^16 + 2 m16 as before; the
+            // fraction of t16 lies within m16 of an integer iff (t16 - m16) mod 2^16 >= 2^16 - 2 m16, and since
+            // t16 - m16 = s - 2 m16 (mod 2^16) that is (s mod 2^16) < 2 m16 - one compare of the low half, its complement
+            // taken on the mask.  A counted entry has m16 <= frac(t16) < 2^16 - m16, so adding m16 carries nothing into the
+            // bin: s >> 16 == t16 >> 16 (both identities swept in tests/test_gpu_writeout.py)
+            // The results stay lane masks (every lane is active here): counted = in range and not in the band, left for
+            // float64 = in range and in the band - scalar instructions - and the select and the count take the mask as it is
+            // (select_lane_mask / add_lane_mask read the masks of ALL lanes: this must stay outside any lane-divergent branch)
+            const unsigned int s = (unsigned int)t16 + (unsigned int)m16;
+            const unsigned long long mm = __builtin_amdgcn_ballot_w64(agev) & __builtin_amdgcn_ballot_w64(s < k16m);
+            const unsigned long long band = __builtin_amdgcn_ballot_w64((s & 0xffffu) < m16x2);
+            const unsigned long long cnt = mm & ~band;
+            redo_m |= mm & band;
+            atomicAdd(&hrow[select_lane_mask(cnt, (int)(s >> 16), K)], 1u);
+            mycnt = add_lane_mask(mycnt, cnt);
           };
           if (f32_ok) {                                             // (uniform)
             column32(std::integral_constant<int, 0>{});
             column32(std::integral_constant<int, 1>{});
             column32(std::integral_constant<int, 2>{});
             column32(std::integral_constant<int, 3>{});
-            if (__ballot(redo) == 0ull) continue;
+            if (redo_m == 0ull) continue;
           }
           column(std::integral_constant<int, 0>{});
           column(std::integral_constant<int, 1>{});
@@ -1359,8 +1372,17 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     double* out = static_cast<double*>(state_out) + bN * S;
     if (((A | K) & 1) == 0) {
       const int q_per_row = S >> 1, total = N * q_per_row;
+#ifndef DIRAL_FAST_KSLOTS
+      // (row and piece of the first trip, and what a trip advances by: the host's divisions, WriteoutParams)
+      const WriteoutParams wo = load_writeout_args(late);
+      const int du = late_p2 ? wo.p4_du3 : wo.p4_du4, dq = late_p2 ? wo.p4_dq3 : wo.p4_dq4;
+      int u = (int)(__umul24((unsigned int)t4, (unsigned int)wo.qs_mul) >> wo.qs_shift), qr = t4 - (int)__umul24((unsigned int)u, (unsigned int)q_per_row);
+#else /* DIRAL_FAST_KSLOTS */
+      // (K slots: the division stays in the kernel - with the host's reciprocal the float32 my_step slot loop went from 37 to
+      // 58 spilled VGPRs, profiles/writeout)
       const int du = T4 / q_per_row, dq = T4 - du * q_per_row;
       int u = t4 / q_per_row, qr = t4 - u * q_per_row;
+#endif /* DIRAL_FAST_KSLOTS */
       for (int q = t4; q < total; q += T4) {
         const int s0 = qr << 1;
         double2 v;
@@ -1369,7 +1391,11 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
           v = make_double2(a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0);
         } else {
           const unsigned int n = s_cnt[u];
+#ifndef DIRAL_FAST_KSLOTS
+          const unsigned int* h = s_hist + __umul24((unsigned int)u, (unsigned int)KP) + (s0 - A);
+#else /* DIRAL_FAST_KSLOTS */
           const unsigned int* h = s_hist + u * KP + (s0 - A);
+#endif /* DIRAL_FAST_KSLOTS */
           const double dn = (double)n;
           v = n ? make_double2((double)h[0] / dn, (double)h[1] / dn) : make_double2(0.0, 0.0);
         }
@@ -1394,9 +1420,16 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   const double* const inv_tab = reinterpret_cast<const double*>(smem + lay.inv);
   if (((A | K) & 3) == 0) {
     const int q_per_row = S >> 2, total = N * q_per_row;
-    // (row, quad) advance incrementally: one integer division per thread instead of one per store
+#ifndef DIRAL_FAST_KSLOTS
+    // (row, quad) advance incrementally; the first trip's and the advance by the host's divisions (WriteoutParams)
+    const WriteoutParams wo = load_writeout_args(late);
+    const int du = late_p2 ? wo.p4_du3 : wo.p4_du4, dq = late_p2 ? wo.p4_dq3 : wo.p4_dq4;
+    int u = (int)(__umul24((unsigned int)t4, (unsigned int)wo.qs_mul) >> wo.qs_shift), qr = t4 - (int)__umul24((unsigned int)u, (unsigned int)q_per_row);
+#else /* DIRAL_FAST_KSLOTS */
+    // (row, quad) advance incrementally: one integer division per thread instead of one per store (K slots: in the kernel)
     const int du = T4 / q_per_row, dq = T4 - du * q_per_row;
     int u = t4 / q_per_row, qr = t4 - u * q_per_row;
+#endif /* DIRAL_FAST_KSLOTS */
     for (int q = t4; q < total; q += T4) {
       const int s0 = qr << 2;
       float4 v;
@@ -1405,7 +1438,11 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
         v = make_float4(a == 0 ? 1.f : 0.f, a == 1 ? 1.f : 0.f, a == 2 ? 1.f : 0.f, a == 3 ? 1.f : 0.f);
       } else {
         const unsigned int n = s_cnt[u];
+#ifndef DIRAL_FAST_KSLOTS
+        const unsigned int* h = s_hist + __umul24((unsigned int)u, (unsigned int)KP) + (s0 - A);
+#else /* DIRAL_FAST_KSLOTS */
         const unsigned int* h = s_hist + u * KP + (s0 - A);
+#endif /* DIRAL_FAST_KSLOTS */
         // (float)((double)h * fl(1.0 / n)) == (float)((double)h / (double)n) == the correctly rounded float
         // quotient for every 0 <= h <= n <= 255 (checked exhaustively; the quotient of two small integers
         // is never within 2^-50 of a float rounding boundary): one table load instead of four IEEE divisions

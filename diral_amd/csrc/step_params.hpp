@@ -10,6 +10,39 @@ namespace diral {
 constexpr int kFastMaxA = 64;           // LDS is sized by the actual A (rounded up to 32): A <= 32 keeps 8 workgroups per CU
 constexpr int kWideMaxA = 64;
 
+// Index arithmetic of the write-out loops of step_fast64 in 16-byte pieces (CV = 4 floats or 2 doubles): the channel
+// observation, qa = A / CV pieces per row, and the state rows of P4, qs = (A + K) / CV.  Every operand is uniform and known
+// to the host, so the divisions are done there, once per launch.  i / q is (i * mul) >> shift with mul = ceil(2^shift / q),
+// shift = 16 + ceil(log2 q): with e = mul * q - 2^shift < q <= 2^(shift - 16) the quotient is exact while i * e < 2^shift,
+// that is for every i < 2^16; both factors stay below 2^24 and the product below 2^32 for i < 2^15 (q <= 2^12): a full-rate
+// v_mul_u32_u24.  The kernel divides a thread index < 256.
+struct WriteoutParams {
+  int qa_mul, qa_shift;          // i / qa
+  int co_du, co_dq;              // 256 / qa and 256 % qa: what a thread of the channel-observation loop advances by
+  int qs_mul, qs_shift;          // i / qs
+  int p4_du3, p4_dq3;            // 192 / qs and 192 % qs: P4 by waves 1-3 (`late_p2`)
+  int p4_du4, p4_dq4;            // 256 / qs and 256 % qs: P4 by all four waves
+};
+__host__ __device__ inline void writeout_reciprocal(int q, int& mul, int& shift) {
+  mul = 0; shift = 16;
+  if (q <= 0) return;
+  while ((1 << (shift - 16)) < q) ++shift;
+  mul = (int)(((1ll << shift) + q - 1) / q);
+}
+// (A, or A and K, that are no multiples of CV: that loop writes element by element and reads none of these)
+__host__ __device__ inline WriteoutParams writeout_params(int A, int K, bool out_f64) {
+  const int cv = out_f64 ? 2 : 4;
+  const int qa = (A % cv) == 0 ? A / cv : 0;
+  const int qs = (A % cv) == 0 && (K % cv) == 0 ? (A + K) / cv : 0;
+  WriteoutParams w;
+  writeout_reciprocal(qa, w.qa_mul, w.qa_shift);
+  w.co_du = qa ? 256 / qa : 0; w.co_dq = qa ? 256 % qa : 0;
+  writeout_reciprocal(qs, w.qs_mul, w.qs_shift);
+  w.p4_du3 = qs ? 192 / qs : 0; w.p4_dq3 = qs ? 192 % qs : 0;
+  w.p4_du4 = qs ? 256 / qs : 0; w.p4_dq4 = qs ? 256 % qs : 0;
+  return w;
+}
+
 struct FastParams {
   int N, A, K, NR;               // NR: padded subject rows (multiple of 16); viewer stride is 64
   int NV;                        // viewer stride (step_wide.hpp; 64 for step_fast64)
@@ -80,6 +113,7 @@ struct FastParams {
   uint32_t* slow_list_w;
   uint32_t* slow_flag_w;
   uint32_t* slow_cnt_z;           // the set [count | list | flags] the launch after the next will build: emptied here
+  WriteoutParams wo;              // step_fast64 only, read late (LateFastArgs) where the write-out loops start
 };
 // listed envs per launch (an env beyond that keeps its place in dispatch order): a quarter of the batch, 16 ... 4096
 #ifndef DIRAL_SLOW_SHIFT
@@ -98,6 +132,14 @@ __device__ inline unsigned long long late_kernarg_base() {
   unsigned long long a = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
   asm volatile("" : "+s"(a));
   return a;
+}
+__device__ inline WriteoutParams load_writeout_args(unsigned long long kernarg_base) {
+  const LateFastArgs a = (LateFastArgs)kernarg_base;
+  WriteoutParams w;
+  w.qa_mul = a->wo.qa_mul; w.qa_shift = a->wo.qa_shift; w.co_du = a->wo.co_du; w.co_dq = a->wo.co_dq;
+  w.qs_mul = a->wo.qs_mul; w.qs_shift = a->wo.qs_shift; w.p4_du3 = a->wo.p4_du3; w.p4_dq3 = a->wo.p4_dq3;
+  w.p4_du4 = a->wo.p4_du4; w.p4_dq4 = a->wo.p4_dq4;
+  return w;
 }
 // byte offset of the second kernel argument (RichParams) in the kernarg segment
 constexpr unsigned long long kRichArgOffset = (sizeof(FastParams) + alignof(RichParams) - 1) / alignof(RichParams) * alignof(RichParams);

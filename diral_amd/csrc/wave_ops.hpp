@@ -63,6 +63,23 @@ __device__ inline double wave_sum_f64(double v) {
 // lgkmcnt at every merge step (measured: the dominant cost at N > 64).
 __device__ inline void wave_lds_order() { asm volatile("" ::: "memory"); }
 
+// Lane masks as values (a compare's result taken with __builtin_amdgcn_ballot_w64 while every lane of the wave is active):
+// combined on the scalar side (and, andn2, or) and handed back to the vector side as the mask operand itself.
+// x + 1 in the lanes of `m`, x elsewhere: ONE v_addc_co_u32 with the mask as its carry-in (from a bool the compiler makes
+// v_cndmask_b32 0 / 1 and v_add)
+__device__ inline unsigned int add_lane_mask(unsigned int x, unsigned long long m) {
+  unsigned int r;
+  unsigned long long carry_out;
+  asm("v_addc_co_u32 %0, %1, 0, %2, %3" : "=v"(r), "=s"(carry_out) : "v"(x), "s"(m));
+  return r;
+}
+// a in the lanes of `m`, b elsewhere
+__device__ inline int select_lane_mask(unsigned long long m, int a, int b) {
+  int r;
+  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
+  return r;
+}
+
 // An LDS object by its absolute byte address (register + compile-time constant: the constant goes
 // into the DS instruction's immediate offset; going through the `extern __shared__` symbol instead
 // leaves a relocated `+ 0` add in front of every access)

@@ -14,11 +14,12 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 # the kernel-trace pass profiles the SAME command the driver runs (default steps/warmup), minus the host-side extras
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python $R/bench.py --lean "$@" > $OUT/trace.log 2>&1
+# (every pass under a time limit of its own; a pass that fails, faults or hangs ends the script: nothing more is started on that GPU)
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- python $R/bench.py --lean "$@" > $OUT/trace.log 2>&1 || { echo "trace pass failed: rc $?"; exit 1; }
 pmc() { # name counters...
   local name=$1; shift
-  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$name -o $name -- \
-    python $R/bench.py --steps 40 --warmup 0 --lean ${EXTRA:-} > $OUT/$name.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$name -o $name -- \
+    python $R/bench.py --steps 40 --warmup 0 --lean ${EXTRA:-} > $OUT/$name.log 2>&1 || { echo "$name failed: rc $?"; exit 1; }
 }
 EXTRA="$*"
 pmc pmc_sq1 SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS
