@@ -28,6 +28,7 @@ SYMBOLS = [
     "diral_env_set_capture_rotation", "diral_env_align_phase",
     "diral_env_export_prev_obs", "diral_env_import_prev_obs", "diral_env_prefill", "diral_env_prefill_mode",
     "diral_env_rollout", "diral_env_copy_envs", "diral_env_rollout_ia", "diral_env_step_policy_ia",
+    "diral_env_rollout_replay", "diral_env_step_policy_replay",
 ]
 
 _lib = None
@@ -100,6 +101,8 @@ def load() -> ctypes.CDLL:
         "diral_env_copy_envs": (I, [P, P, P, P, I, P]),
         "diral_env_rollout_ia": (I, [P, I, P, I, I64, P, I, P, P, I, P, P, P]),
         "diral_env_step_policy_ia": (I, [P, I, P, I64, P, P, P, P, I, P, P, P]),
+        "diral_env_rollout_replay": (I, [P, I, P, I, I64, P, I, P, P, I, P, P, P, P]),
+        "diral_env_step_policy_replay": (I, [P, I, P, I64, P, P, P, P, I, P, P, P, P]),
     }
     for name in SYMBOLS:
         try:

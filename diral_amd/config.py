@@ -175,6 +175,20 @@ class DiralSlotInfoAge(ctypes.Structure):
     ]
 
 
+class DiralSlotReplay(ctypes.Structure):
+    """ctypes image of ``struct DiralSlotReplay`` (include/diral_env.h): the recorded-mobility block of
+    ``diral_env_rollout_replay`` / ``diral_env_step_policy_replay``."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("flags", ctypes.c_int32),
+        ("x_positions", ctypes.c_void_p),
+        ("T", ctypes.c_int32),
+        ("per_env", ctypes.c_int32),
+        ("xpos_out", ctypes.c_void_p),
+    ]
+
+
 class ConfigError(ValueError):
     """A config the reference itself cannot run, or one this build rejects."""
 

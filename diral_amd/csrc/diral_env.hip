@@ -1059,10 +1059,25 @@ static void ia_block_params(const DiralSlotInfoAge* ia, PolParams& q) {
   q.sum_ia_prev = (long long*)ia->sum_ia_prev;
 }
 
+// The recorded-mobility block of a K-slot call (DiralSlotReplay): its own argument checks ...
+static int replay_block_check(const DiralSlotReplay* rp) {
+  if (rp->struct_bytes != sizeof(DiralSlotReplay) || rp->flags != 0) return DIRAL_ERR_BAD_ARG;
+  if (rp->x_positions ? rp->T < 1 : rp->T != 0) return DIRAL_ERR_BAD_ARG;
+  return DIRAL_OK;
+}
+// ... and what the slot loop is handed; false: the block is absent or empty - the call is its _ia entry point's
+static bool replay_block_params(const DiralSlotReplay* rp, PolParams& q) {
+  q.rp_on = 0; q.rp_T = 0; q.rp_per_env = 0; q.rp_x = nullptr; q.rp_xout = nullptr;
+  if (!rp || (!rp->x_positions && !rp->xpos_out)) return false;
+  q.rp_on = 1; q.rp_T = rp->T; q.rp_per_env = rp->per_env ? 1 : 0; q.rp_x = rp->x_positions; q.rp_xout = rp->xpos_out;
+  return true;
+}
+
 static int step_policy_impl(DiralEnv* e, int mode, const int32_t* actions, int64_t t, void* state_out, void* rew_out,
                             uint8_t* done_out, void* chobs_out, int out_dtype, const DiralSlotPolicy* pol,
-                            const DiralSlotInfoAge* ia, void* stream) {
+                            const DiralSlotInfoAge* ia, const DiralSlotReplay* rp, void* stream) {
   if (!e || !actions || !pol || pol->struct_bytes != sizeof(DiralSlotPolicy)) return DIRAL_ERR_BAD_ARG;
+  if (rp && replay_block_check(rp) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
   if (ia && ia_block_check(ia, pol->shaped_out) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
   if (!pol->sps_prev_action || !pol->sps_counter || !pol->actions_out) return DIRAL_ERR_BAD_ARG;
   if (mode != DIRAL_STEP_MY_STEP && mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_BAD_ARG;
@@ -1095,11 +1110,14 @@ static int step_policy_impl(DiralEnv* e, int mode, const int32_t* actions, int64
   q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N; q.vel_w = e->vel;
   q.prefill = 0; q.actions_all = nullptr; q.rew_in = nullptr; q.rollout = 0; q.actions_seq = nullptr;
   ia_block_params(ia, q);
+  const bool replay = replay_block_params(rp, q);
   if (slots > 1 && (pol->draw_counter || pol->draw_keep || pol->draw_choice)) return DIRAL_ERR_BAD_ARG;
   // (decided before anything is launched: a caller without a channel-observation buffer can retry with one)
   const StepPlan d = plan_step(e, p, &q);
   if (!d.fused && (!chobs_out || slots > 1)) return DIRAL_ERR_UNSUPPORTED;
   if (ia && d.launch != StepLaunch::Fast64Slots) return DIRAL_ERR_UNSUPPORTED;   // (only that slot loop keeps the stamps)
+  // (... and only its K-slot form takes recorded positions: a one-slot call stays diral_env_set_trace + diral_env_step_policy)
+  if (replay && (d.launch != StepLaunch::Fast64Slots || slots <= 1)) return DIRAL_ERR_UNSUPPORTED;
   HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
   HIP_TRY(e, launch_posdist_if_needed(e, p, (hipStream_t)stream));
   if (d.fused) return DIRAL_OK;
@@ -1117,13 +1135,19 @@ static int step_policy_impl(DiralEnv* e, int mode, const int32_t* actions, int64
 
 int diral_env_step_policy(DiralEnv* e, int mode, const int32_t* actions, int64_t t, void* state_out, void* rew_out,
                           uint8_t* done_out, void* chobs_out, int out_dtype, const DiralSlotPolicy* pol, void* stream) {
-  return step_policy_impl(e, mode, actions, t, state_out, rew_out, done_out, chobs_out, out_dtype, pol, nullptr, stream);
+  return step_policy_impl(e, mode, actions, t, state_out, rew_out, done_out, chobs_out, out_dtype, pol, nullptr, nullptr, stream);
 }
 
 int diral_env_step_policy_ia(DiralEnv* e, int mode, const int32_t* actions, int64_t t, void* state_out, void* rew_out,
                              uint8_t* done_out, void* chobs_out, int out_dtype, const DiralSlotPolicy* pol,
                              const DiralSlotInfoAge* ia, void* stream) {
-  return step_policy_impl(e, mode, actions, t, state_out, rew_out, done_out, chobs_out, out_dtype, pol, ia, stream);
+  return step_policy_impl(e, mode, actions, t, state_out, rew_out, done_out, chobs_out, out_dtype, pol, ia, nullptr, stream);
+}
+
+int diral_env_step_policy_replay(DiralEnv* e, int mode, const int32_t* actions, int64_t t, void* state_out, void* rew_out,
+                                 uint8_t* done_out, void* chobs_out, int out_dtype, const DiralSlotPolicy* pol,
+                                 const DiralSlotInfoAge* ia, const DiralSlotReplay* rp, void* stream) {
+  return step_policy_impl(e, mode, actions, t, state_out, rew_out, done_out, chobs_out, out_dtype, pol, ia, rp, stream);
 }
 
 int diral_env_prefill_mode(DiralEnv* e, int mode, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out,
@@ -1154,8 +1178,9 @@ int diral_env_prefill_mode(DiralEnv* e, int mode, const int32_t* actions, int32_
 
 static int rollout_impl(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
                         int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro,
-                        const DiralSlotInfoAge* ia, void* stream) {
+                        const DiralSlotInfoAge* ia, const DiralSlotReplay* rp, void* stream) {
   if (!e || !actions_seq || !ro || ro->struct_bytes != sizeof(DiralRollout) || slots < 1) return DIRAL_ERR_BAD_ARG;
+  if (rp && replay_block_check(rp) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
   if (ia && ia_block_check(ia, ro->shaped_out) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
   if (mode != DIRAL_STEP_MY_STEP && mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_BAD_ARG;
   if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
@@ -1180,22 +1205,30 @@ static int rollout_impl(DiralEnv* e, int mode, const int32_t* actions_seq, int32
   q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N; q.vel_w = e->vel;
   q.rollout = 1 | ((states_all && p.state_out) ? 2 : 0); q.actions_seq = actions_seq;
   ia_block_params(ia, q);
+  const bool replay = replay_block_params(rp, q);
   const StepPlan d = plan_step(e, p, &q);
   if (!d.fused) return DIRAL_ERR_UNSUPPORTED;                    // (nothing launched: the caller loops step + shape)
   if (ia && d.launch != StepLaunch::Fast64Slots) return DIRAL_ERR_UNSUPPORTED;   // (only that slot loop keeps the stamps)
+  if (replay && d.launch != StepLaunch::Fast64Slots) return DIRAL_ERR_UNSUPPORTED;   // (... and takes recorded positions)
   HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
   return DIRAL_OK;
 }
 
 int diral_env_rollout(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
                       int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro, void* stream) {
-  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, nullptr, stream);
+  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, nullptr, nullptr, stream);
 }
 
 int diral_env_rollout_ia(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
                          int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro,
                          const DiralSlotInfoAge* ia, void* stream) {
-  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, ia, stream);
+  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, ia, nullptr, stream);
+}
+
+int diral_env_rollout_replay(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
+                             int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro,
+                             const DiralSlotInfoAge* ia, const DiralSlotReplay* rp, void* stream) {
+  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, ia, rp, stream);
 }
 
 int diral_env_prefill(DiralEnv* e, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out, int out_dtype,

@@ -48,7 +48,19 @@ hipError_t launch_fast64_policy(const FastParams& f, const RichParams& r, const 
 hipError_t launch_fast64_slots(const FastParams& f, const RichParams& r, const PolParams& q, bool ch, bool out64, int B, hipStream_t s) {
   const bool ia = ch && q.ia_on != 0;       // the information-age block: the IA instantiations (arrival stamps, histogram pass, term)
   const uint32_t lds = fast_lds_layout(f.K, f.A, true, out64, true, ch, true, ia).total;
-  if (ia) {
+  if (q.rp_on != 0) {
+    // the recorded-mobility block: the RP instantiations (positions from the caller's sequence, the position log)
+    if (ia) {
+      if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, true, false, true, true, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
+      else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, true, false, true, true, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
+    } else if (ch) {
+      if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, true, false, true, true, false, true>), dim3(B), dim3(256), lds, s, f, r, q);
+      else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, true, false, true, true, false, true>), dim3(B), dim3(256), lds, s, f, r, q);
+    } else {
+      if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, false, false, true, true, false, true>), dim3(B), dim3(256), lds, s, f, r, q);
+      else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, false, false, true, true, false, true>), dim3(B), dim3(256), lds, s, f, r, q);
+    }
+  } else if (ia) {
     if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, true, false, true, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
     else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, true, false, true, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
   } else if (ch) {

@@ -56,6 +56,13 @@ struct PolParams {
   long long* ia_sum_out;         // [K][B] or null
   int32_t* ia_pen_out;           // [K][B] or null (written with bit 0)
   long long* sum_ia_prev;        // [B] in/out (bit 0)
+  // The recorded-mobility block of a slot loop (diral_env_rollout_replay / diral_env_step_policy_replay, DiralSlotReplay;
+  // step_fast64_slots_kernel only): the position behind slot ks is row (t + ks + clock) mod T of the caller's sequence
+  // (Network.update_positions' replay branch, network.py:194-199) instead of the velocity model's, and / or leaves in the log
+  int rp_on;                     // the call carries the block with at least one of its pointers: the RP instantiations
+  int rp_T, rp_per_env;          // rows of the sequence; != 0: one sequence per env ([B][T][N], the env's index in this handle)
+  const double* rp_x;            // [T][N] / [B][T][N] or null (the velocity model)
+  double* rp_xout;               // [K][B][N] pos_x behind every slot, or null
 };
 
 // counter-based generator (splitmix64 finaliser over seed/stream/index); the

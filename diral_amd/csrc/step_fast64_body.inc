@@ -13,7 +13,10 @@ template <bool FLAT, bool OUT64, bool CH, bool EXTRA, bool RICH, bool POL = fals
 // slot to slot, the histogram pass, the ia_averaging term.  Instantiations of their own: as run-time branches of the two CH
 // slot loops they cost the calls without the block 3 to 5 % (profiles/kslots_ia/)
 #define DIRAL_FAST_STAMPS (EXTRA || IA)
-template <bool FLAT, bool OUT64, bool CH, bool EXTRA, bool RICH, bool POL = false, bool IA = false>
+// RP: the slot loop of a call that carries the recorded-mobility block (PolParams::rp_on, DiralSlotReplay) - the positions
+// behind every slot come from the caller's sequence instead of the velocity model, and / or leave in the position log.
+// Instantiations of their own, as IA's: every other kernel is compiled from the text it had (profiles/kslots_replay/)
+template <bool FLAT, bool OUT64, bool CH, bool EXTRA, bool RICH, bool POL = false, bool IA = false, bool RP = false>
 #endif /* DIRAL_FAST_KSLOTS */
 #ifndef DIRAL_FAST_KSLOTS
 __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES) void DIRAL_FAST_KERNEL(const FastParams p, const RichParams r,
@@ -30,6 +33,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   // (K slots: my_step_ch too - its staged observation is 0 / the constant 1, which the SPS agents read as -200 / -40 dBm)
   static_assert(!POL || (RICH && FLAT && !EXTRA), "the policy epilogue needs the staged channel observation of a my_step / my_step_ch slot");
   static_assert(!IA || (POL && CH), "the information-age block belongs to the my_step_ch slot loop");
+  static_assert(!RP || POL, "the recorded-mobility block belongs to the slot loops");
 #endif /* DIRAL_FAST_KSLOTS */
   extern __shared__ __align__(16) unsigned char smem[];
 #ifndef DIRAL_FAST_KSLOTS
@@ -105,6 +109,9 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   int* const s_ia = reinterpret_cast<int*>(smem + lay.ia + 8);
   // what a slot carries over to the next one (POL, KS > 1)
   double mynpx_prev = 0.0;
+  // the recorded-mobility block (RP): the position BEHIND the coming slot, asked for a slot ahead, and its row of the sequence
+  double rp_next = 0.0;
+  int rp_row = 0;
   unsigned int tkov_prev = 0u, told_next = 0u;
   double ring_s0 = 0.0, ring_s1 = 0.0;                       // the subjects' ring rows in SLOT order (lane l: slot l & 7 of subject l >> 3)
   int pol_action = 0, pol_cnt = 1;          // POL, wave 3: the agents' policy state, loaded in slot 0 and used behind P3
@@ -144,6 +151,9 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   // an open-loop rollout (PolParams::rollout, diral_env_rollout): slot ks + 1 runs actions_seq[ks + 1]; with bit 1 every
   // slot's state vector leaves, as the prefill's
   const bool rollout = rollout_i != 0;
+  // the positions behind this slot come from the caller's sequence (DiralSlotReplay::x_positions)
+  bool rp_src = false;
+  if constexpr (RP) rp_src = ((LatePolArgs)(late_kernarg_base() + kPolArgOffset))->rp_x != nullptr;
   const bool every = prefill || (rollout_i & 2) != 0;
   // (a rollout keeps the velocities on the chip even for one slot: an episode end behind it updates them in this launch)
   const bool kvel_on = KS > 1 || prefill || rollout;
@@ -169,6 +179,18 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   mypx = p.pos_x[vi];
   mypy = FLAT ? 0.0 : p.pos_y[vi];
   myvel = p.vel[vi];
+  if constexpr (RP) {
+    // slot 0's recorded position, with the small loads (ahead of the table words: P1 must not wait for those).  Its row:
+    // (t + clock) mod T with Python's sign, as the one-slot replay branch below; the slots behind it count on from there
+    if (rp_src) {
+      const LatePolArgs lq = (LatePolArgs)(late_kernarg_base() + kPolArgOffset);
+      const long long T = (long long)lq->rp_T;
+      long long tt = (p.t + (p.t_dev ? *p.t_dev : 0ll)) % T;
+      if (tt < 0) tt += T;
+      rp_row = (int)tt;
+      rp_next = lq->rp_x[((lq->rp_per_env ? (size_t)b * (size_t)T : (size_t)0) + (size_t)tt) * N + (live ? lane : 0)];
+    }
+  }
 #endif /* DIRAL_FAST_KSLOTS */
   __builtin_amdgcn_sched_barrier(0);
   if (!live) { myact = -1; mypx = 0.0; mypy = 0.0; myvel = 0.0; }
@@ -252,6 +274,13 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     mynpx = p.trace[(base + (size_t)tt) * N + lane];
   }
   if (EXTRA && p.nomove) mynpx = mypx;                                         // network.py:302-305: no mobility, no move
+#ifdef DIRAL_FAST_KSLOTS
+  // (RP: the recorded position of this slot, Network.update_positions' replay branch - network.py:194-199; whatever the value,
+  // `p1_fast` above and the float32 screening in front of P3b are decided from this slot's positions, every slot)
+  if constexpr (RP) {
+    if (rp_src) mynpx = live ? rp_next : 0.0;
+  }
+#endif /* DIRAL_FAST_KSLOTS */
   if (wave == 1) {
     // the transmitter sets of ALL resources (test_env.py:153-157) for P2 and the RICH tail: every vehicle ORs its bit
     // into the mask of its resource - one 64-bit LDS atomic for the wave, behind the zeroing (a wave's LDS operations
@@ -617,6 +646,11 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     if (live) p.pos_x[bN + lane] = mynpx;
 #else /* DIRAL_FAST_KSLOTS */
     if (live && last) p.pos_x[bN + lane] = mynpx;
+    if constexpr (RP) {
+      // the position log (DiralSlotReplay::xpos_out [K][B][N]): get_x_pos() behind this slot, one float64 store a vehicle
+      double* const xo = ((LatePolArgs)(late_kernarg_base() + kPolArgOffset))->rp_xout;
+      if (xo && live) xo[((size_t)ks * (size_t)p.B) * N + bN + lane] = mynpx;
+    }
 #endif /* DIRAL_FAST_KSLOTS */
   }
   if constexpr (RICH) {
@@ -666,6 +700,16 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     if (wave == 3 && live && rollout && !last) {
       const LatePolArgs lq = (LatePolArgs)(late_kernarg_base() + kPolArgOffset);
       pol_action = lq->actions_seq[((size_t)(ks + 1) * (size_t)p.B) * N + bN + lane];
+    }
+    // (RP: and the next slot's recorded positions, every wave its lanes' - the same 8 N bytes for the four of them, one
+    // round trip under P3; the row counts on modulo T)
+    if constexpr (RP) {
+      if (rp_src && !last) {
+        const LatePolArgs lq = (LatePolArgs)(late_kernarg_base() + kPolArgOffset);
+        const int T = lq->rp_T;
+        rp_row = rp_row + 1 == T ? 0 : rp_row + 1;
+        rp_next = lq->rp_x[((lq->rp_per_env ? (size_t)b * (size_t)T : (size_t)0) + (size_t)rp_row) * N + (live ? lane : 0)];
+      }
     }
 #endif /* DIRAL_FAST_KSLOTS */
   }

@@ -220,7 +220,8 @@ class DriverLoop:
         return out
 
     # K slots of main_test.py:119-236 with the actions given in advance (a replayed log, a fixed schedule)
-    def rollout(self, actions_seq, t: int, states: Optional[str] = "last", vel_seed: int = 0) -> Dict[str, Any]:
+    def rollout(self, actions_seq, t: int, states: Optional[str] = "last", vel_seed: int = 0,
+                positions=None) -> Dict[str, Any]:
         """``for k in range(K): out = slot(actions_seq[k], t + k)`` and, behind a slot that ends an episode,
         ``env.update_velocity(seed=vel_seed + (t + k) // episode_interval)``: returns ``states`` (the last slot's
         [B, N, S]; `states` = ``"all"``: every slot's [K, B, N, S]; None: none), ``reward`` [B, N] (as the env returned it)
@@ -232,11 +233,22 @@ class DriverLoop:
         `enable_channel` on a HIP env with `track_arrival` (the driver reads the information age behind every slot,
         main_test.py:150): the launch carries the information-age block (`diral_env_rollout_ia`) - `ia_averaging` included -
         and the result gains ``ia`` [K, B, 100], ``ia_sum`` [K, B] and, with `ia_averaging`, ``ia_penalty`` [K, B]; the loop
-        behind a refused launch stacks what ``slot(want_ia=True)`` returns."""
+        behind a refused launch stacks what ``slot(want_ia=True)`` returns.
+
+        `positions` ([T, N] or [B, T, N] float64): recorded mobility for these K slots, main_test.py:118's
+        `load_saved_positions` - inside the launch where it is taken (`diral_env_rollout_replay`); behind a refused launch
+        the sequence is set on the handle (`load_saved_positions`), the slots are looped and the trace is removed again.
+        ValueError if the handle already carries a trace: one source of positions per call."""
         env = self.env
         seq = self._t(actions_seq)
         K = int(seq.shape[0])
         hip = hasattr(env, "lib") and hasattr(env, "_stream")
+        if positions is not None:
+            if not hip:
+                raise ValueError("DriverLoop.rollout: positions needs the HIP env")
+            if env.has_trace:
+                raise ValueError("DriverLoop.rollout: the env already replays a trace of its own (load_saved_positions)")
+            positions = env._positions("DriverLoop.rollout", positions)
         with_ia = bool(self.enable_channel and getattr(getattr(env, "cfg", None), "track_arrival", False))
         if hasattr(env, "rollout") and ((with_ia and hip) or not self.ia_averaging):
             pen = None
@@ -250,6 +262,8 @@ class DriverLoop:
                 if self.ia_averaging and self._sum_ia_prev is None:
                     self._sum_ia_prev = torch.zeros((env.B,), dtype=torch.int64, device=env.device)
                 ia_kw = dict(info_age=True, sum_ia_prev=self._sum_ia_prev if self.ia_averaging else None)
+            if positions is not None:
+                ia_kw["positions"] = positions
             try:
                 out = env.rollout(seq, t, mode="my_step_ch" if self.enable_channel else "my_step", states=states,
                                   global_reward_avg=self.global_reward_avg, stuck_penalty=pen, vel_seed=vel_seed, **ia_kw)
@@ -262,6 +276,18 @@ class DriverLoop:
             except DiralError as exc:
                 if exc.status != ERR_UNSUPPORTED:
                     raise
+        if positions is None:
+            return self._rollout_loop(seq, t, states, vel_seed, with_ia)
+        env.load_saved_positions(positions)
+        try:
+            return self._rollout_loop(seq, t, states, vel_seed, with_ia)
+        finally:
+            env.load_saved_positions(None)
+
+    def _rollout_loop(self, seq, t: int, states: Optional[str], vel_seed: int, with_ia: bool) -> Dict[str, Any]:
+        """`rollout` slot by slot: what its launch is equal to."""
+        env = self.env
+        K = int(seq.shape[0])
         kept, shaped, sum_r, coll = [], [], [], []
         ia_keys = ("ia", "ia_sum", "ia_penalty")
         ia_kept: Dict[str, list] = {k: [] for k in ia_keys}

@@ -46,13 +46,15 @@ class CandidateSearch:
         self._K = 0
 
     def evaluate(self, seqs, t: Optional[int] = None, mode="my_step", global_reward_avg: bool = False, vel_seed: int = 0,
-                 info_age: bool = False) -> Dict[str, torch.Tensor]:
+                 info_age: bool = False, positions=None) -> Dict[str, torch.Tensor]:
         """Run every candidate: `seqs` [K, B, C, N] int32, ``seqs[k, b, c]`` the actions of env b's candidate c in slot
         ``t + k`` (`t` defaults to ``env.t``).  Returns ``returns`` [B, C] (the sum of `sum_r` over the K slots, float64),
         ``sum_r`` and ``collision`` [K, B, C] (main_test.py:171, 178) - and leaves `env` as it was.  `info_age` (`mode` =
         ``"my_step_ch"`` on a `track_arrival` handle): the rollout of `work` keeps the arrival stamps (`copy_envs_from`
         carries them) and ``ia_sum`` [K, B, C] int64 - utils/misc.calculate_ia_penalty of every candidate's information-age
-        histogram behind every slot - is returned beside ``returns``: candidates can be scored by information age."""
+        histogram behind every slot - is returned beside ``returns``: candidates can be scored by information age.
+        `positions`: recorded mobility for the K slots (`VecV2VEnv.rollout`'s `positions`) - [T, N] for every env and
+        candidate alike, or [B, T, N], env b's sequence for each of its C candidates (expanded to `work`'s env order here)."""
         env, work, C = self.env, self.work, self.C
         seq = torch.as_tensor(seqs, device=env.device)
         if seq.dim() != 4 or tuple(seq.shape[1:]) != (env.B, C, env.N) or seq.shape[0] < 1:
@@ -61,15 +63,28 @@ class CandidateSearch:
         seq = seq.to(torch.int32).reshape(K, env.B * C, env.N).contiguous()
         if t is None:
             t = env.t
+        pos_kw = {}
+        if positions is not None:
+            pos = env._positions("evaluate", positions)
+            if pos.dim() == 3:                                      # work env b * C + c replays env b's sequence
+                pos = pos.repeat_interleave(C, dim=0)
+            pos_kw = dict(positions=pos)
         work.copy_envs_from(env, src_index=self._gather)
         try:
             out = work.rollout(seq, t, mode=mode, states=None, global_reward_avg=global_reward_avg, vel_seed=vel_seed,
-                               info_age=True if info_age else None)
+                               info_age=True if info_age else None, **pos_kw)
             sum_r, coll, ia_sum = out["sum_r"], out["collision"], out.get("ia_sum")
         except DiralError as exc:
             if exc.status != ERR_UNSUPPORTED:                       # (refused: nothing launched, `work` untouched)
                 raise
-            sum_r, coll, ia_sum = self._loop(seq, int(t), _MODES[mode], global_reward_avg, vel_seed, info_age)
+            if positions is None:
+                sum_r, coll, ia_sum = self._loop(seq, int(t), _MODES[mode], global_reward_avg, vel_seed, info_age)
+            else:                                                   # (the loop replays the sequence from the handle)
+                work.load_saved_positions(pos_kw["positions"])
+                try:
+                    sum_r, coll, ia_sum = self._loop(seq, int(t), _MODES[mode], global_reward_avg, vel_seed, info_age)
+                finally:
+                    work.load_saved_positions(None)
         self._K = K
         res = dict(returns=sum_r.to(torch.float64).sum(0).view(env.B, C), sum_r=sum_r.view(K, env.B, C),
                    collision=coll.view(K, env.B, C))

@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from ._tensors import MSG_OUT, _ptr, check_tensor, dtype_code, policy_seed, seed64
 from .config import (DT_F32, DT_F64, ERR_HIP, ERR_UNSUPPORTED, M_COLUMNS, OK, OPT_ENV_OFFSET, OPT_KERNEL_PATH, PATH_AUTO,
-                     PATH_GENERAL, PATH_LARGE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, ConfigError, DiralRollout, DiralSlotInfoAge,
+                     PATH_GENERAL, PATH_LARGE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, ConfigError, DiralRollout, DiralSlotInfoAge, DiralSlotReplay,
                      DiralSlotPolicy, EnvConfig)
 
 # MA_NeighborTableEntry (envs/ma_messages_pb2.py:195-230) as a host view of DiralNeighborEntry
@@ -181,6 +181,7 @@ class VecV2VEnv:
         self._keep: Dict[str, tuple] = {}       # per call name: what the last launch's raw pointers refer to
         self._last_actions: Optional[torch.Tensor] = None
         self._policy_needs_chobs = False        # step_policy met a configuration that does not run fused
+        self.has_trace = False                  # the handle carries recorded positions of its own (load_saved_positions)
         self._kernel_path = PATH_AUTO           # what force_general_kernel / force_large_path chose (twin() repeats it)
         self._snap_twin: Optional["VecV2VEnv"] = None   # the handle snapshot() copies into, made at its first call
         # section order of obtain_state (test_env.py:527-583): ... velocity, fingerprint last
@@ -270,6 +271,31 @@ class VecV2VEnv:
             blk.flags = 1
             blk.ia_pen_out, blk.sum_ia_prev = _ptr(out["ia_penalty"]), _ptr(sum_ia_prev)
         return blk, out
+
+    def _positions(self, where: str, positions) -> torch.Tensor:
+        """A recorded position sequence as the C-ABI reads it: [T, N] (every env alike) or [B, T, N] float64, contiguous,
+        on the env's device."""
+        tr = torch.as_tensor(positions, dtype=torch.float64, device=self.device).contiguous()
+        shared = tr.dim() == 2 and tr.shape[0] >= 1 and tr.shape[1] == self.N
+        per_env = tr.dim() == 3 and tr.shape[1] >= 1 and tuple(tr.shape[::2]) == (self.B, self.N)
+        if not (shared or per_env):
+            raise ValueError("%s: positions must have shape [T >= 1, N=%d] or [B=%d, T >= 1, N=%d], got %s"
+                             % (where, self.N, self.B, self.N, tuple(tr.shape)))
+        return tr
+
+    def _replay_block(self, where: str, positions, xpos_out, K: int):
+        """The recorded-mobility block of a K-slot call (DiralSlotReplay) and the sequence tensor it points at (kept alive
+        with the call's other buffers); `xpos_out`: [K, B, N] float64 or None."""
+        blk = DiralSlotReplay()
+        blk.struct_bytes = ctypes.sizeof(blk)
+        tr = None
+        if positions is not None:
+            tr = self._positions(where, positions)
+            blk.x_positions, blk.T, blk.per_env = _ptr(tr), int(tr.shape[-2]), 1 if tr.dim() == 3 else 0
+        if xpos_out is not None:
+            check_tensor("%s: xpos_out" % where, xpos_out, torch.float64, (K, self.B, self.N), self.device, MSG_OUT)
+            blk.xpos_out = _ptr(xpos_out)
+        return blk, tr
 
     def _f64(self, a, shape) -> Optional[torch.Tensor]:
         if a is None:
@@ -444,7 +470,8 @@ class VecV2VEnv:
     def step_policy(self, actions: torch.Tensor, t: int, policy, actions_out: torch.Tensor, shaped_out=None, sum_r_out=None,
                     collision_out=None, global_reward_avg: bool = True, want_chobs: bool = False, clock=None,
                     seed_offset: Optional[int] = None, mode: Optional[int] = None, slots: int = 1, vel_seed: int = 0,
-                    want_obs: bool = True, stuck_penalty: Optional[tuple] = None, info_age=None, sum_ia_prev=None):
+                    want_obs: bool = True, stuck_penalty: Optional[tuple] = None, info_age=None, sum_ia_prev=None,
+                    positions=None, xpos_out=None):
         """One slot of a policy-only rollout as ONE launch (`diral_env_step_policy`): env step (state, reward, done,
         optionally the channel observation) + the driver's reward shaping (main_test.py:171-206 without the
         information-age terms) + the SPS agents' decisions for the next slot (algorithms/v2x_sps.py:76-104), the
@@ -475,7 +502,12 @@ class VecV2VEnv:
         ``True`` / ``"hist"`` - the launch keeps the arrival stamps and returns, as a fourth value, a dict with ``ia``
         [K, B, 100] int32 (`info_age(t + k)` behind slot k) and ``ia_sum`` [K, B] int64; ``"stamps"`` - the stamps only
         (an empty dict); `sum_ia_prev` ([B] int64, updated in place) adds the `ia_averaging` term (main_test.py:151-160)
-        to the shaped rewards and ``ia_penalty`` [K, B] int32 to the dict.  ``None``: today's call, three values."""
+        to the shaped rewards and ``ia_penalty`` [K, B] int32 to the dict.  ``None``: today's call, three values.
+
+        `positions` / `xpos_out` (K > 1 slots at 8 <= N <= 64; `diral_env_step_policy_replay`): recorded mobility inside the
+        launch, as `rollout`'s `positions` - [T, N] or [B, T, N] float64, the position behind slot k is row
+        ``(t + k + clock) % T`` - and the position log, a caller's [K, B, N] float64 tensor that receives `get_x_pos()`
+        behind every slot.  The handle must not carry a trace of its own."""
         K = int(slots)
         if K < 1:
             raise ValueError("step_policy: slots must be >= 1")
@@ -513,16 +545,22 @@ class VecV2VEnv:
         self._bind_slot(1, use_chobs)
 
         blk, ia_out = (None, None) if info_age is None else self._info_age_block("step_policy", info_age, sum_ia_prev, K)
+        rblk, rseq = (None, None)
+        if positions is not None or xpos_out is not None:
+            rblk, rseq = self._replay_block("step_policy", positions, xpos_out, K)
 
         def call(chobs):
             args = (self._h, self.step_mode if mode is None else mode, _ptr(actions), int(t),
                     _ptr(self._obs) if (want_obs and self.S > 0) else None, _ptr(self._rew),
                     _ptr(self._done), _ptr(chobs), self._dt, ctypes.byref(q))
+            if rblk is not None:
+                return self.lib.diral_env_step_policy_replay(*args, None if blk is None else ctypes.byref(blk),
+                                                             ctypes.byref(rblk), self._stream())
             if blk is None:
                 return self.lib.diral_env_step_policy(*args, self._stream())
             return self.lib.diral_env_step_policy_ia(*args, ctypes.byref(blk), self._stream())
         st = call(self._chobs if use_chobs else None)
-        if st == ERR_UNSUPPORTED and not use_chobs and K == 1:  # not a fused configuration, nothing launched
+        if st == ERR_UNSUPPORTED and not use_chobs and K == 1 and rblk is None:  # not a fused configuration, nothing launched
             self._policy_needs_chobs = True
             self._bind_slot(0, True)
             st = call(self._chobs)
@@ -531,14 +569,15 @@ class VecV2VEnv:
             policy._t += K        # only once the call is in: slot k drew with seed + k, what K one-slot calls are given; a
                                   # refused call (DIRAL_ERR_UNSUPPORTED: nothing launched) leaves the draw counter alone
         self._keep["step_policy"] = (q, actions, actions_out, shaped_out, sum_r_out, collision_out, clock, stuck_penalty,
-                                     blk, ia_out, sum_ia_prev)
+                                     blk, ia_out, sum_ia_prev, rblk, rseq, xpos_out)
         if blk is not None:
             return self._obs, self._rew, self._done, ia_out
         return self._obs, self._rew, self._done
 
     def rollout(self, actions_seq, t: Optional[int] = None, mode="my_step", states: Optional[str] = "last",
                 global_reward_avg: bool = False, stuck_penalty: Optional[tuple] = None, vel_seed: int = 0,
-                info_age=None, sum_ia_prev=None) -> Dict[str, Optional[torch.Tensor]]:
+                info_age=None, sum_ia_prev=None, positions=None,
+                log_positions: bool = False) -> Dict[str, Optional[torch.Tensor]]:
         """K slots of a GIVEN action sequence as ONE launch (`diral_env_rollout`): slot k runs ``my_step(actions_seq[k],
         t + k)`` (`mode` = ``"my_step_ch"``: ``my_step_ch``, reward_design 2 ... 4), then the driver's reward shaping
         (main_test.py:171-206 without the information-age terms, `diral_driver_shape` with the same flags) and, in configs
@@ -559,7 +598,15 @@ class VecV2VEnv:
         ``"hist"`` - the launch keeps the arrival stamps and the result gains ``ia`` [K, B, 100] int32 (`info_age(t + k)`
         behind slot k) and ``ia_sum`` [K, B] int64; ``"stamps"`` - the stamps only; `sum_ia_prev` ([B] int64, updated in
         place) adds the `ia_averaging` term (main_test.py:151-160, 190-192) to the shaped rewards, in front of the stuck
-        penalty, and ``ia_penalty`` [K, B] int32 to the result.  ``None``: today's call - a tracking handle is refused."""
+        penalty, and ``ia_penalty`` [K, B] int32 to the result.  ``None``: today's call - a tracking handle is refused.
+
+        `positions` (8 <= N <= 64; `diral_env_rollout_replay`): recorded mobility inside the launch, the reference's
+        `load_saved_positions` (network.py:171-178, 194-199) - [T, N] (every env alike) or [B, T, N] float64 on the env's
+        device, read in place; behind slot k the positions are row ``(t + k + clock) % T``, exactly what the loop of one-slot
+        calls does on a handle that had `load_saved_positions(positions)`.  The handle must not carry a trace of its own
+        (refused).  `log_positions`: the result gains ``xpos`` [K, B, N] float64, `get_x_pos()` behind every slot (the
+        driver's position log, main_test.py:140-142), with or without `positions`; the log of a velocity-model launch
+        replays it."""
         step_mode = _MODES.get(mode)
         if step_mode not in (STEP_MY_STEP, STEP_MY_STEP_CH):
             raise ValueError("rollout: mode must be 'my_step' or 'my_step_ch'")
@@ -588,14 +635,23 @@ class VecV2VEnv:
         args = (self._h, step_mode, _ptr(seq), K, int(t), _ptr(st_out), 1 if states == "all" else 0,
                 _ptr(self._rew), _ptr(self._done), self._dt, ctypes.byref(q))
         blk, ia_out = None, {}
-        if info_age is None:
+        if info_age is not None:
+            blk, ia_out = self._info_age_block("rollout", info_age, sum_ia_prev, K)
+        rblk, rseq = None, None
+        if positions is not None or log_positions:
+            xpos = torch.empty((K, self.B, self.N), dtype=torch.float64, device=self.device) if log_positions else None
+            rblk, rseq = self._replay_block("rollout", positions, xpos, K)
+            if log_positions:
+                ia_out = dict(ia_out, xpos=xpos)
+            st = self.lib.diral_env_rollout_replay(*args, None if blk is None else ctypes.byref(blk), ctypes.byref(rblk),
+                                                   self._stream())
+        elif blk is None:
             st = self.lib.diral_env_rollout(*args, self._stream())
         else:
-            blk, ia_out = self._info_age_block("rollout", info_age, sum_ia_prev, K)
             st = self.lib.diral_env_rollout_ia(*args, ctypes.byref(blk), self._stream())
         self._ok(st, "diral_env_rollout", K)            # (a refused call has launched nothing: the ring is back where it was)
         self.t = int(t) + K
-        self._keep["rollout"] = (q, seq, stuck_penalty, blk, sum_ia_prev)
+        self._keep["rollout"] = (q, seq, stuck_penalty, blk, sum_ia_prev, rblk, rseq)
         return dict(states=st_out, reward=self._rew, done=self._done, shaped=shaped, sum_r=sum_r, collision=coll, **ia_out)
 
     def step(self, actions, t: Optional[int] = None, episode: float = 0.0, epsilon: float = 1.0
@@ -712,6 +768,7 @@ class VecV2VEnv:
         self._spec = None
         if x_positions is None:
             self._ok(self.lib.diral_env_set_trace(self._h, None, 0, 0, self._stream()), "diral_env_set_trace")
+            self.has_trace = False
             return
         if isinstance(x_positions, str):
             x_positions = np.load(x_positions)
@@ -724,6 +781,7 @@ class VecV2VEnv:
             raise ValueError("x_positions must be [T, N] or [B, T, N]")
         self._ok(self.lib.diral_env_set_trace(self._h, _ptr(tr), int(T), per_env, self._stream()),
                  "diral_env_set_trace")
+        self.has_trace = True
 
     # ---- env copies: fork, snapshot / restore, the candidates of a search -----------------------
     def twin(self, batch: Optional[int] = None) -> "VecV2VEnv":

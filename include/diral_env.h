@@ -616,6 +616,41 @@ int diral_env_step_policy_ia(DiralEnv* env, int mode, const int32_t* actions, in
                              uint8_t* done_out, void* chobs_out, int out_dtype, const DiralSlotPolicy* policy,
                              const DiralSlotInfoAge* ia, void* stream);
 
+/* Recorded mobility inside the K-slot launches (additive within ABI 8; step_fast64_slots_kernel, 8 <= N <= 64).
+ * The reference's driver replaces the velocity model with a recorded run before its main loop (main_test.py:118,
+ * Network.load_x_positions and the replay branch of update_positions, network.py:171-178, 194-199) and logs the positions of
+ * every slot (main_test.py:140-142, 254-255).  The two entry points below are diral_env_rollout_ia /
+ * diral_env_step_policy_ia with one more argument, the block; slot k of the launch then
+ *   - with x_positions: leaves  pos_x[b][u] = x_positions[(per_env ? b * T : 0) + tt][u],  tt = (t + k + clock) mod T with
+ *     Python's sign (clock: the slot clock, when one is set) - what the one-slot calls do on a handle that had
+ *     diral_env_set_trace(x_positions, T, per_env); `per_env` indexes by the env's index in THIS handle; the positions slot
+ *     0 starts from are the handle's own; velocities are still drawn at episode ends (mobility_vary) and still feed the
+ *     state vector's velocity column, as in the reference;
+ *   - with xpos_out: writes pos_x behind slot k to xpos_out[k] (= get_x_pos() in front of slot k + 1), with or without
+ *     x_positions: the log of a velocity-model launch, handed back as x_positions with T = K, reproduces that launch.
+ * The sequence is the caller's device memory: it is not copied, the call is enqueue-only (capturable), and it may differ
+ * from call to call.  Equal, bit for bit, to the loop of one-slot calls on a handle that carries the trace.
+ *   `replay` NULL, or both pointers NULL: exactly diral_env_rollout_ia / diral_env_step_policy_ia, refusals included.
+ *   DIRAL_ERR_BAD_ARG (checked first, no device needed): struct_bytes, flags != 0, x_positions with T < 1, T != 0 without
+ *     x_positions, and everything the _ia entry point rejects;
+ *   DIRAL_ERR_UNSUPPORTED, nothing launched, env untouched: everything the _ia entry point refuses - a handle with a trace
+ *     of its own among it (one source of positions per call) -, N > 64 (step_wide_slots_kernel does not take the block), and
+ *     a one-slot diral_env_step_policy_replay call (slots <= 1).
+ * The prefill does not take the block: the driver loads the positions behind it (main_test.py:99-118). */
+typedef struct DiralSlotReplay {
+  uint32_t struct_bytes;          /* = sizeof(DiralSlotReplay) */
+  int32_t  flags;                 /* 0 */
+  const double* x_positions;      /* [T][N] (per_env == 0) or [B][T][N] (per_env != 0) float64, device; or NULL: the velocity model */
+  int32_t  T, per_env;
+  double*  xpos_out;              /* [K][B][N] float64: pos_x BEHIND slot k, or NULL */
+} DiralSlotReplay;
+int diral_env_rollout_replay(DiralEnv* env, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
+                             int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* rollout,
+                             const DiralSlotInfoAge* ia, const DiralSlotReplay* replay, void* stream);
+int diral_env_step_policy_replay(DiralEnv* env, int mode, const int32_t* actions, int64_t t, void* state_out, void* rew_out,
+                                 uint8_t* done_out, void* chobs_out, int out_dtype, const DiralSlotPolicy* policy,
+                                 const DiralSlotInfoAge* ia, const DiralSlotReplay* replay, void* stream);
+
 /* ---- slot clock: rollouts captured into a hipGraph ---------------------------------------------
  * A captured sequence of K slots (env step, reward shaping, policy) bakes every by-value argument into its
  * kernel nodes; what has to move on from replay to replay - the slot number behind `done`, arrival stamps and
