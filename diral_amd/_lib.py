@@ -28,7 +28,7 @@ SYMBOLS = [
     "diral_env_set_capture_rotation", "diral_env_align_phase",
     "diral_env_export_prev_obs", "diral_env_import_prev_obs", "diral_env_prefill", "diral_env_prefill_mode",
     "diral_env_rollout", "diral_env_copy_envs", "diral_env_rollout_ia", "diral_env_step_policy_ia",
-    "diral_env_rollout_replay", "diral_env_step_policy_replay",
+    "diral_env_rollout_replay", "diral_env_step_policy_replay", "diral_env_subwave_ok",
 ]
 
 _lib = None
@@ -61,6 +61,7 @@ def load() -> ctypes.CDLL:
         "diral_cfg_defaults": (None, [CFG]),
         "diral_env_state_space": (I, [CFG]),
         "diral_env_validate": (I, [CFG]),
+        "diral_env_subwave_ok": (I, [CFG]),
         "diral_env_strerror": (ctypes.c_char_p, [I]),
         "diral_env_abi_version": (I, []),
         "diral_env_create": (I, [CFG, I, I, ctypes.POINTER(P)]),

@@ -47,7 +47,9 @@ class TestEnv:
 
     __test__ = False   # not a pytest class
 
-    def __init__(self, backend: Any = None, device: str = "cuda:0", **kwargs: Any):
+    def __init__(self, backend: Any = None, device: str = "cuda:0", subwave: bool = False, **kwargs: Any):
+        """`subwave=True`: opt in to the sub-wave step kernel (VecV2VEnv.use_subwave_path: num_users <= 8, num_channels <= 16,
+        num_bins <= 64, no State.piggybacking; raises otherwise) - a build extension, not a key of the reference."""
         if not kwargs:
             raise ConfigError("TestEnv needs the EnvironmentTest keys (test_env.py:12-48)")
         cfg = EnvConfig.from_dict(kwargs, track_arrival=True)
@@ -62,6 +64,8 @@ class TestEnv:
             from .vec_env import VecV2VEnv
             backend = VecV2VEnv(cfg, batch=1, device=device, out_dtype=torch.float64)
         self._env = backend
+        if subwave:
+            self._env.use_subwave_path()
         # the reference constructor draws a random topology (network.py:92-119)
         # or builds the design topology (network.py:69-79)
         if cfg.enable_design_topology:

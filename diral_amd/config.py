@@ -48,12 +48,14 @@ OPT_KERNEL_PATH = 2
 PATH_AUTO = 0
 PATH_GENERAL = 1
 PATH_LARGE = 2
+PATH_SUBWAVE = 3             # opt-in: csrc/step_subwave.hpp, toy-size envs, 4 or 8 lanes per env
 
 KERNEL_GENERAL = 0
 KERNEL_FAST64 = 1
 KERNEL_WIDE = 2
 KERNEL_OBSERVE = 3
 KERNEL_LARGE = 4
+KERNEL_SUBWAVE = 5
 KERNEL_RICH = 16
 KERNEL_EXTRA = 32
 KERNEL_CH = 64
@@ -68,6 +70,8 @@ MAX_SLOTS = 16777214         # DIRAL_MAX_SLOTS: steps between resets, the last s
 SMALL_MAX_USERS = 256        # the one-workgroup kernels; beyond: csrc/step_large.hpp (KERNEL_LARGE)
 SMALL_MAX_CHANNELS = 256
 SMALL_MAX_BINS = 64
+SUBWAVE_MAX_USERS = 8        # PATH_SUBWAVE: num_users, num_channels (and num_bins <= SMALL_MAX_BINS, no State.piggybacking)
+SUBWAVE_MAX_CHANNELS = 16
 
 M_SLOTS, M_SUM_REWARD, M_TX_SOLE, M_TX_COLLIDED, M_PRR_SUM, M_PRR_CNT = range(6)
 M_COLUMNS = 6

@@ -422,7 +422,7 @@ size_t slow_set_words(const DiralEnv* e) { return 16 + (size_t)fast_slow_max(e->
 // What one step call launches: decided in ONE place and without side effects, from the handle, the call's parameters
 // and its policy request (`pol`: diral_env_step_policy / diral_env_prefill / diral_env_rollout, else null) - for the launch itself
 // (launch_step_any) and for everyone who must know the outcome before anything is launched (`fused`).
-enum class StepLaunch { Large, General, Fast64, Wide, Fast64Policy, Fast64Slots, WideSlots };
+enum class StepLaunch { Large, General, Subwave, Fast64, Wide, Fast64Policy, Fast64Slots, WideSlots };
 struct StepPlan {
   StepLaunch launch;
   bool use_fast64, use_wide;   // the kernel family of the five specialised launches
@@ -442,6 +442,11 @@ StepPlan plan_step(const DiralEnv* e, const StepParams& p, const PolParams* pol)
   if (runs_large(e)) {
     // (and diral_env_observe: the search kernel's observe mode + the histogram launch)
     d.launch = StepLaunch::Large; d.last_kernel = DIRAL_KERNEL_LARGE;
+    return d;
+  }
+  if (e->kernel_path == DIRAL_PATH_SUBWAVE && p.mode != kModeObserve) {
+    // toy-size envs, 4 or 8 lanes each (step_subwave.hpp): every step call of a pinned handle, on the planes; never `fused`
+    d.launch = StepLaunch::Subwave; d.last_kernel = DIRAL_KERNEL_SUBWAVE;
     return d;
   }
   // (DIRAL_PATH_GENERAL keeps the general kernel's FAST instantiation: plain_cfg does not ask for the path)
@@ -598,6 +603,7 @@ hipError_t launch_step_any(DiralEnv* e, const StepParams& p, const StepPlan& d, 
   e->last_kernel = d.last_kernel;
   if (d.launch == StepLaunch::Large) return launch_large(p, e->lg, s);
   if (d.launch == StepLaunch::General) return launch_general(e->vpl, d.general_fast, p, e->lds_bytes, s);
+  if (d.launch == StepLaunch::Subwave) return launch_subwave(p, s);
   FastParams f = fast_params(e, p, d);
   if (d.slow_sets) rotate_slow_sets(e, f, s);
   RichParams r = rich_for(e, p);
@@ -794,6 +800,18 @@ int diral_env_validate(const DiralCfg* c) {
   return DIRAL_OK;
 }
 
+// the sizes step_subwave.hpp holds: a viewer's N table entries in its lane's registers, one 4-bit gather source per
+// resource in a 64-bit word, a 4-bit count per bin in four
+int diral_env_subwave_ok(const DiralCfg* c) {
+  const int st = diral_env_validate(c);
+  if (st != DIRAL_OK) return st;
+  if (c->num_users > DIRAL_SUBWAVE_MAX_USERS || c->num_channels > DIRAL_SUBWAVE_MAX_CHANNELS ||
+      c->num_bins > DIRAL_SMALL_MAX_BINS)
+    return DIRAL_ERR_UNSUPPORTED;
+  if (has(c, DIRAL_F_PIGGYBACKING)) return DIRAL_ERR_UNSUPPORTED;   // (the A * A observation: piggyback_kernel.hpp's paths only)
+  return DIRAL_OK;
+}
+
 int diral_env_state_space(const DiralCfg* c) {
   if (!c || c->struct_bytes != sizeof(DiralCfg)) return DIRAL_ERR_BAD_ARG;
   return state_offsets(c).S;
@@ -970,7 +988,14 @@ int diral_env_set_option(DiralEnv* e, int option, int64_t value) {
       e->env_offset = value;
       return DIRAL_OK;
     case DIRAL_OPT_KERNEL_PATH:
-      if (value != DIRAL_PATH_AUTO && value != DIRAL_PATH_GENERAL && value != DIRAL_PATH_LARGE) return DIRAL_ERR_BAD_ARG;
+      if (value != DIRAL_PATH_AUTO && value != DIRAL_PATH_GENERAL && value != DIRAL_PATH_LARGE && value != DIRAL_PATH_SUBWAVE)
+        return DIRAL_ERR_BAD_ARG;
+      if (value == DIRAL_PATH_SUBWAVE) {                          // (opt-in; a refusal leaves the path as it was)
+        const int ok = e->large ? DIRAL_ERR_UNSUPPORTED : diral_env_subwave_ok(&e->cfg);
+        if (ok != DIRAL_OK) return ok;
+        e->kernel_path = DIRAL_PATH_SUBWAVE;
+        return DIRAL_OK;
+      }
       if (e->large) return value == DIRAL_PATH_GENERAL ? DIRAL_ERR_UNSUPPORTED : DIRAL_OK;   // (there is one path for such a handle)
       if (value == DIRAL_PATH_LARGE) {
         if (large_lds_bytes(e->N, e->A, e->K) > 160u * 1024u) return DIRAL_ERR_UNSUPPORTED;

@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from ._tensors import MSG_OUT, _ptr, check_tensor, dtype_code, policy_seed, seed64
 from .config import (DT_F32, DT_F64, ERR_HIP, ERR_UNSUPPORTED, M_COLUMNS, OK, OPT_ENV_OFFSET, OPT_KERNEL_PATH, PATH_AUTO,
-                     PATH_GENERAL, PATH_LARGE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, ConfigError, DiralRollout, DiralSlotInfoAge, DiralSlotReplay,
+                     PATH_GENERAL, PATH_LARGE, PATH_SUBWAVE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, ConfigError, DiralRollout, DiralSlotInfoAge, DiralSlotReplay,
                      DiralSlotPolicy, EnvConfig)
 
 # MA_NeighborTableEntry (envs/ma_messages_pb2.py:195-230) as a host view of DiralNeighborEntry
@@ -333,6 +333,17 @@ class VecV2VEnv:
         self._ok(self.lib.diral_env_set_option(self._h, OPT_KERNEL_PATH, PATH_LARGE if on else PATH_AUTO),
                  "diral_env_set_option")
         self._kernel_path = PATH_LARGE if on else PATH_AUTO
+
+    def use_subwave_path(self, on: bool = True) -> None:
+        """Opt in to the sub-wave step kernel (csrc/step_subwave.hpp): 4 or 8 lanes per env, so 16 or 8 toy-size envs
+        share a wavefront instead of one env per 256-thread workgroup.  Same results, bit for bit.  Limits: num_users
+        <= 8, num_channels <= 16, num_bins <= 64, no State.piggybacking - anything else raises DiralError with
+        ERR_UNSUPPORTED and leaves the handle on the path it had.  Nothing chooses this path by itself.  On a pinned
+        handle `obtain_state` stays the stand-alone observe kernel, a one-slot `step_policy` runs as three launches,
+        and `rollout`, `prefill` and `step_policy(slots > 1)` raise ERR_UNSUPPORTED.  ``on=False``: back to AUTO."""
+        self._ok(self.lib.diral_env_set_option(self._h, OPT_KERNEL_PATH, PATH_SUBWAVE if on else PATH_AUTO),
+                 "diral_env_set_option")
+        self._kernel_path = PATH_SUBWAVE if on else PATH_AUTO
 
     def set_clock(self, clock: Optional[torch.Tensor]) -> None:
         """Install (or, with None, remove) a device slot clock: an int64 tensor of one element on this env's device.
@@ -793,6 +804,8 @@ class VecV2VEnv:
             other.force_general_kernel()
         elif self._kernel_path == PATH_LARGE:
             other.force_large_path()
+        elif self._kernel_path == PATH_SUBWAVE:
+            other.use_subwave_path()
         return other
 
     def _index(self, idx) -> Optional[torch.Tensor]:

@@ -149,6 +149,8 @@ typedef enum DiralDType { DIRAL_F32 = 0, DIRAL_F64 = 1 } DiralDType;
 #define DIRAL_SMALL_MAX_USERS    256   /* the one-workgroup kernels */
 #define DIRAL_SMALL_MAX_CHANNELS 256
 #define DIRAL_SMALL_MAX_BINS     64
+#define DIRAL_SUBWAVE_MAX_USERS    8    /* the sub-wave step kernel (csrc/step_subwave.hpp, DIRAL_PATH_SUBWAVE): 4 or 8 */
+#define DIRAL_SUBWAVE_MAX_CHANNELS 16   /* lanes per env; num_bins <= DIRAL_SMALL_MAX_BINS                              */
 #define DIRAL_MAX_SLOTS    16777214   /* steps between resets (24-bit sequence numbers) */
 
 /* per-env episode metric columns written by diral_env_metrics() */
@@ -176,6 +178,12 @@ int diral_env_state_space(const DiralCfg* cfg);
 
 /* 0 if `cfg` can be run by this build, else the DiralStatus explaining why. */
 int diral_env_validate(const DiralCfg* cfg);
+
+/* Whether a handle of `cfg` can be pinned to the sub-wave step kernel (DIRAL_PATH_SUBWAVE below); needs no device.
+ * DIRAL_OK; DIRAL_ERR_BAD_ARG for a NULL cfg; what diral_env_validate says for a config this build cannot run at all;
+ * DIRAL_ERR_UNSUPPORTED for num_users > DIRAL_SUBWAVE_MAX_USERS, num_channels > DIRAL_SUBWAVE_MAX_CHANNELS,
+ * num_bins > DIRAL_SMALL_MAX_BINS and State.piggybacking (DIRAL_F_PIGGYBACKING). */
+int diral_env_subwave_ok(const DiralCfg* cfg);
 
 const char* diral_env_strerror(int status);
 int diral_env_abi_version(void);
@@ -210,10 +218,16 @@ typedef enum DiralOption {
   /* DIRAL_PATH_AUTO (default): configurations the specialised kernels serve run on
    * them; DIRAL_PATH_GENERAL: always the general kernel (tests compare the two);
    * DIRAL_PATH_LARGE: always the three-launch form of csrc/step_large.hpp (tests run the
-   * reference's fixtures through it; not with State.piggybacking's A * A section). */
+   * reference's fixtures through it; not with State.piggybacking's A * A section);
+   * DIRAL_PATH_SUBWAVE: opt-in, toy-size envs only - every diral_env_step call runs csrc/step_subwave.hpp, 4 or 8 lanes
+   * per env and 16 or 8 envs per wavefront, same results bit for bit.  Returns what diral_env_subwave_ok says for the
+   * handle's config (DIRAL_ERR_UNSUPPORTED on a handle of the three-launch form too) and leaves the path as it was on
+   * refusal.  On such a handle diral_env_observe stays the stand-alone observe kernel, a one-slot diral_env_step_policy
+   * runs its three launches, and diral_env_rollout, diral_env_prefill and slots > 1 return DIRAL_ERR_UNSUPPORTED with
+   * nothing launched (as on a handle pinned to the general kernel).  Any other value: DIRAL_ERR_BAD_ARG. */
   DIRAL_OPT_KERNEL_PATH = 2
 } DiralOption;
-enum { DIRAL_PATH_AUTO = 0, DIRAL_PATH_GENERAL = 1, DIRAL_PATH_LARGE = 2 };
+enum { DIRAL_PATH_AUTO = 0, DIRAL_PATH_GENERAL = 1, DIRAL_PATH_LARGE = 2, DIRAL_PATH_SUBWAVE = 3 };
 int diral_env_set_option(DiralEnv* env, int option, int64_t value);
 
 /* which kernel the last diral_env_step / diral_env_observe call launched:
@@ -225,6 +239,7 @@ enum {
   DIRAL_KERNEL_WIDE    = 2,   /* csrc/step_wide.hpp,  64 < N <= 256  */
   DIRAL_KERNEL_OBSERVE = 3,   /* csrc/observe_kernel.hpp: diral_env_observe (stand-alone obtain_state) */
   DIRAL_KERNEL_LARGE   = 4,   /* csrc/step_large.hpp: N > 256, A > 256 or K > 64 (step and observe) */
+  DIRAL_KERNEL_SUBWAVE = 5,   /* csrc/step_subwave.hpp: N <= 8 on a handle pinned to DIRAL_PATH_SUBWAVE (no instantiation bits) */
   DIRAL_KERNEL_RICH    = 16,  /* channel-obs output / cheap State flags (csrc/rich_out.hpp) */
   DIRAL_KERNEL_EXTRA   = 32,  /* my_step_design / arrival stamps / trace replay */
   DIRAL_KERNEL_CH      = 64,  /* my_step_ch */
