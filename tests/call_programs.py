@@ -24,7 +24,7 @@ from diral_amd.config import (KERNEL_FAST64, KERNEL_GENERAL, KERNEL_LARGE, KERNE
                               STEP_MY_STEP_CH, bench_config)
 from tests import host_closed_loop as H
 # the suite's own bars (importable without a GPU)
-from tests.test_gpu_closed_loop_host import EXP_ATOL, _exp_bounds, uses_exp  # noqa: F401  (re-exported)
+from tests.host_closed_loop import EXP_ATOL, _exp_bounds, uses_exp  # noqa: F401  (re-exported)
 
 RICH_STATE = dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=True, add_position=True)
 MODE_NAME = {STEP_MY_STEP: "my_step", STEP_MY_STEP_CH: "my_step_ch", STEP_DESIGN: "my_step_design"}

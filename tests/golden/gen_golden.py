@@ -797,8 +797,7 @@ def draw_ref_case(i):
 def fuzz_one(i):
     """One sweep case -> its report row (a dict)."""
     import traceback
-    from tests.golden_util import Golden
-    from tests.test_oracle_golden import compare_with_reference
+    from tests.golden_util import Golden, compare_with_reference
     c = draw_ref_case(i)
     cfg, st = c["cfg"], c["cfg"]["State"]
     flags = [k[4:] for k in ("add_reward", "add_index", "add_velocity", "add_position", "add_positional_dist",

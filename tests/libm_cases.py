@@ -25,8 +25,7 @@ import math
 import numpy as np
 
 from diral_amd.config import bench_config
-
-EXP_ATOL = 2e-15                # tests/test_gpu_parity.py: the project's bar for exp()-based rewards; no bound here exceeds it
+from tests.golden_util import EXP_ATOL   # tests/test_gpu_parity.py: the project's bar for exp()-based rewards; no bound here exceeds it
 ORACLE_EXP_ULPS = 1             # the oracle's exp() and the host's log10 against the correctly rounded values, in ulps: the
 HOST_LOG10_ULPS = 1             # conditions tests/test_libm_cases.py asserts, which the device's bounds are derived from
 RC = 250.0

@@ -18,7 +18,7 @@ import torch
 from diral_amd.config import ERR_UNSUPPORTED, KERNEL_POLICY, STEP_MY_STEP_CH
 from tests import call_programs as P
 from tests.call_programs import EXP_ATOL, _exp_bounds, uses_exp
-from tests.test_gpu_parity import make_env
+from tests.gpu_util import make_env
 
 pytestmark = pytest.mark.gpu
 

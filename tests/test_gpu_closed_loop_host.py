@@ -14,70 +14,16 @@ counter, keep, choice) by the index within the handle, i = b * N + lane.
 Ambiguous decisions: device log10 and NumPy's may differ in the last place.  An env one of whose re-selections has a
 host-computed margin below 1e-9 dB is left out from that slot on (the host alone decides); at most 1 % of a test's envs,
 and the seeds here leave out none (`assert_coverage`)."""
-import math
-
 import numpy as np
 import pytest
 import torch
 
-from diral_amd.config import (KERNEL_CH, KERNEL_FAST64, KERNEL_PACKED, KERNEL_POLICY, KERNEL_WIDE, STEP_MY_STEP,
-                              STEP_MY_STEP_CH, bench_config, c2_config)
+from diral_amd.config import (KERNEL_CH, KERNEL_FAST64, KERNEL_PACKED, KERNEL_POLICY, KERNEL_WIDE, STEP_MY_STEP_CH,
+                              bench_config, c2_config)
 from tests import host_closed_loop as H
+from tests.host_closed_loop import EXP_ATOL, RICH, Case, _eq, _exp_bounds, host_run, uses_exp
 
 pytestmark = pytest.mark.gpu
-
-EXP_ATOL = 2e-15            # tests/test_gpu_parity.py: device exp() vs glibc exp()
-RICH = dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=True, add_position=True)
-MODE_NAME = {STEP_MY_STEP: "my_step", STEP_MY_STEP_CH: "my_step_ch"}
-
-
-def _exp_bounds(N):
-    """Rewards built on exp() differ by at most EXP_ATOL each (|reward| <= e).  A sum of N of them in one fixed order
-    then differs by at most N * EXP_ATOL plus the rounding of N - 1 additions of partial sums below N * e on either
-    side, 2 * N * 2**-53 * N * e; a shaped reward (reward + sum / N) by its own EXP_ATOL, that over N, and the rounding
-    of one division and one addition below 8 on either side (4 * 2**-52 * 4)."""
-    sum_atol = N * EXP_ATOL + 2.0 * N * N * math.e * 2.0 ** -53
-    return sum_atol, EXP_ATOL + sum_atol / N + 16 * 2.0 ** -52
-
-
-def uses_exp(cfg, mode):
-    return cfg.reward_design == 3 or (cfg.reward_design == 4 and mode == STEP_MY_STEP_CH)
-
-
-class Case:
-    def __init__(self, cfg, B, dt, plan, *, mode=STEP_MY_STEP, thr=-110.0, keep=0.8, pen=False, vel_seed=0, want_obs=True,
-                 want_chobs=True, clock=False, x0=None, form=None, topo_seed=21, pol_seed=3, env_offset=0, counter_mod=None,
-                 kernel=None, expect=()):
-        self.cfg, self.B, self.dt, self.plan, self.mode = cfg, B, dt, list(plan), mode
-        self.thr, self.keep, self.pen, self.vel_seed = thr, keep, pen, vel_seed
-        self.want_obs, self.want_chobs, self.clock, self.x0, self.form = want_obs, want_chobs, clock, x0, form
-        self.topo_seed, self.pol_seed, self.env_offset, self.counter_mod = topo_seed, pol_seed, env_offset, counter_mod
-        self.kernel, self.expect = kernel, set(expect)
-        self.N, self.A = cfg.num_users, cfg.num_channels
-        self.npdt = np.float32 if dt == torch.float32 else np.float64
-
-
-def host_run(c):
-    """The whole plan of a case on the host: returns (HostClosedLoop, the outputs of every launch)."""
-    B, N, A = c.B, c.N, c.A
-    if c.x0 is not None:
-        x0, v0 = c.x0, np.full(c.x0.shape, 1.7)
-    else:
-        x0, v0 = H.draw_topology(c.topo_seed, B, N, c.cfg.highway_length, c.cfg.mobility_vary, c.env_offset)
-    sps = H.HostSps.from_seed(B * N, A, c.pol_seed, threshold=c.thr, keep_prob=c.keep)
-    if c.counter_mod:
-        sps.counter %= c.counter_mod
-    host = H.HostClosedLoop(c.cfg, B, x0, v0, sps, c.pol_seed, mode=MODE_NAME[c.mode], dtype=c.npdt,
-                            stuck_penalty=(2, -10.0) if c.pen else None, vel_seed=c.vel_seed, env_offset=c.env_offset)
-    a, t, outs = sps.prev_action.reshape(B, N).copy(), 0, []
-    for K in c.plan:
-        o = host.run(a, 0, K, clock=t, offset=0) if c.clock else host.run(a, t, K)
-        o["left_out"] = host.left_out.copy()
-        o["pen"] = (host.pen_counter.copy(), host.pen_prev.copy())
-        o["sps"] = (sps.prev_action.reshape(B, N).copy(), sps.counter.reshape(B, N).copy())
-        outs.append(o)
-        a, t = o["actions"], t + K
-    return host, (x0, v0), outs
 
 
 def assert_coverage(c, host):
@@ -95,16 +41,6 @@ def assert_coverage(c, host):
     if c.cfg.mobility_vary:
         assert rec["vel_changed"] > 0, rec
     return rec
-
-
-def _eq(name, dev, want, keep, baxis=0, atol=None):
-    dev = dev.cpu().numpy() if isinstance(dev, torch.Tensor) else np.asarray(dev)
-    dev, want = np.compress(keep, dev, axis=baxis), np.compress(keep, np.asarray(want), axis=baxis)
-    assert dev.shape == want.shape, (name, dev.shape, want.shape)
-    if atol is None:
-        assert np.array_equal(dev, want), (name, np.argwhere(dev != want)[:4], dev[dev != want][:4], want[dev != want][:4])
-    else:
-        assert np.all(np.abs(dev - want) <= atol), (name, float(np.abs(dev - want).max()), atol)
 
 
 def device_run(c, monkeypatch=None):

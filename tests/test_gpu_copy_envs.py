@@ -23,9 +23,8 @@ import torch
 from diral_amd.config import (ERR_BAD_ARG, ERR_BAD_CONFIG, ERR_CAPTURE, ERR_ENV_INDEX, KERNEL_FAST64, KERNEL_GENERAL,
                               KERNEL_LARGE, KERNEL_RING, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config)
 from diral_amd.vec_env import DiralError
-from tests import call_programs as P
 from tests.call_programs import EXP_ATOL, FAMILIES, uses_exp
-from tests.test_gpu_parity import make_env
+from tests.gpu_util import dev, draw_acts, everything, new_env, run, slot, topo
 
 pytestmark = pytest.mark.gpu
 
@@ -33,56 +32,6 @@ pytestmark = pytest.mark.gpu
 NARROW = dict(cfg=lambda: bench_config(9, 5, 300.0), B=5, B_dst=7, f64=True, mode=STEP_MY_STEP, form=None)
 CASES = dict(FAMILIES, narrow=NARROW)
 SLOTS_SRC, SLOTS_DST = 13, 6
-
-
-def dev(a):
-    return torch.as_tensor(np.ascontiguousarray(a), device="cuda:0")
-
-
-def topo(cfg, B, seed):
-    rng = np.random.default_rng([seed, B, cfg.num_users])
-    return P._positions(rng, B, cfg.num_users, cfg.highway_length), P._speeds(rng, B, cfg.num_users, cfg.mobility_vary)
-
-
-def draw_acts(rng, B, cfg):
-    return rng.integers(0, cfg.num_channels, size=(B, cfg.num_users)).astype(np.int32)
-
-
-def new_env(f, cfg, B, seed, y0=None, f64=None):
-    f64 = f["f64"] if f64 is None else f64
-    env = make_env(cfg, B, mode=f["mode"], dtype=torch.float64 if f64 else torch.float32)
-    x0, v0 = topo(cfg, B, seed)
-    env.reset_topology(x0, y0, v0)
-    return env
-
-
-def run(envs, n, seed, t0=0, sticky=False):
-    """`n` slots of the same random actions on every handle of `envs` (equal batches)."""
-    cfg, B = envs[0].cfg, envs[0].B
-    rng = np.random.default_rng([seed, 77])
-    a = dev(draw_acts(rng, B, cfg))
-    for k in range(n):
-        if not sticky and k:
-            a = dev(draw_acts(rng, B, cfg))
-        for e in envs:
-            e.step(a, t0 + k)
-    return t0 + n
-
-
-def slot(env, a, t):
-    obs, rew, done = env._step(env.step_mode, dev(a), t, want_chobs=True)
-    return dict(state=obs.cpu().numpy().copy(), reward=rew.cpu().numpy().copy(), done=done.cpu().numpy().copy(),
-                chobs=env._chobs.cpu().numpy().copy())
-
-
-def everything(env, t):
-    out = {k: v.cpu().numpy() for k, v in env.export_state().items()}
-    out["metrics"] = env.metrics().cpu().numpy()
-    if env.cfg.track_arrival:
-        out["info_age"] = env.info_age(t).cpu().numpy()
-    if env.cfg.State.piggybacking:
-        out["prev_obs"] = env.prev_obs().cpu().numpy()
-    return out
 
 
 def pick_pairs(Bs, Bd, seed):

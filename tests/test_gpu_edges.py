@@ -15,7 +15,7 @@ import torch
 
 from diral_amd.config import KERNEL_FAST64, KERNEL_GENERAL, KERNEL_RING, KERNEL_WIDE, STEP_MY_STEP, bench_config
 from tests.hist_edge_cases import numpy_hist
-from tests.test_gpu_parity import make_env
+from tests.gpu_util import make_env
 
 pytestmark = pytest.mark.gpu
 

@@ -8,7 +8,7 @@ import pytest
 
 from diral_amd.config import (ConfigError, EnvConfig, KERNEL_FAST64, KERNEL_GENERAL, KERNEL_WIDE, STEP_DESIGN,
                               STEP_MY_STEP, STEP_MY_STEP_CH, bench_config)
-from tests.test_gpu_parity import random_rollout
+from tests.gpu_util import draw_case, random_rollout
 
 pytestmark = pytest.mark.gpu
 
@@ -17,39 +17,13 @@ def exp_reward_close(got, want, f64):
     """Values that pass through exp(): a float64 handle's within EXP_ATOL of the oracle's; a float32 handle's the float32
     cast of the oracle's value or the float32 next to it (two float64 values 2e-15 apart cast to the same or to adjacent
     float32) - and never further from the cast than the 1e-6 this replaces."""
-    from tests.test_gpu_parity import EXP_ATOL
+    from tests.gpu_util import EXP_ATOL
     want = np.asarray(want, dtype=np.float64)
     if f64:
         return bool(np.all(np.abs(got - want) <= EXP_ATOL))
     w = want.astype(np.float32)
     near = (got == w) | (got == np.nextafter(w, np.float32(np.inf))) | (got == np.nextafter(w, np.float32(-np.inf)))
     return got.dtype == np.float32 and bool(np.all(near & (np.abs(got.astype(np.float64) - w.astype(np.float64)) <= 1e-6)))
-
-
-def draw_case(i):
-    rng = np.random.default_rng(9000 + i)
-    N = int(rng.choice([2, 3, 5, 17, 31, 64, 65, 90, 128, 150, 256]))
-    A = int(rng.choice([1, 2, 3, 7, 16, 32, 40, 64]))
-    K = int(rng.choice([1, 3, 10, 20, 21, 40, 64]))
-    mode = int(rng.choice([STEP_MY_STEP, STEP_MY_STEP, STEP_MY_STEP_CH, STEP_DESIGN]))
-    rd = int(rng.choice([2, 3, 4])) if mode == STEP_MY_STEP_CH else int(rng.integers(1, 6))
-    L = float(rng.choice([8.0, 20.0, 40.0]) * N + rng.integers(20, 200))
-    state = dict(type=int(rng.choice([1, 2])), add_reward=bool(rng.random() < 0.3), add_action=bool(rng.random() < 0.8),
-                 add_index=bool(rng.random() < 0.3), add_velocity=bool(rng.random() < 0.3),
-                 action_index=str(rng.choice(["binary", "real"])), add_position=bool(rng.random() < 0.3),
-                 add_positional_dist=bool(rng.random() < 0.2), add_positional_dist_piggy=bool(rng.random() < 0.8),
-                 add_positional_dist_type=int(rng.choice([1, 2, 2])), num_bins=K,
-                 add_channel_obs=bool(rng.random() < 0.4))
-    if state["type"] == 1 and state["add_positional_dist_piggy"]:
-        state["type"] = 2          # SURVEY Q9: the reference crashes on this pair when no tx is in range
-    cfg = bench_config(N, A, L, reward_design=rd, State=state,
-                       mobility=bool(rng.random() < 0.85), mobility_vary=bool(rng.random() < 0.4),
-                       enable_fingerprint=bool(rng.random() < 0.3),
-                       proportional_fair=bool(rng.random() < 0.2 and mode == STEP_MY_STEP),
-                       congestion_test=bool(rng.random() < 0.2),
-                       communication_range=float(rng.choice([30.0, 120.0, 250.0])),
-                       bin_range=float(rng.choice([100.0, 500.0])))
-    return cfg, mode, float(rng.choice([0.0, 0.5, 0.9])), int(rng.choice([0, 7]))
 
 
 @pytest.mark.parametrize("i", range(96))
@@ -98,7 +72,7 @@ def test_random_default_flag_configuration_on_the_specialised_kernels(i):
     so the specialised kernels run) against the oracle, bit for bit."""
     import torch
     from oracle.oracle import Oracle, SQ_IEEE
-    from tests.test_gpu_parity import EXP_ATOL, make_env
+    from tests.gpu_util import EXP_ATOL, make_env
     cfg, mode, sticky, f64 = draw_fast_case(i)
     cfg.validate()
     N, A, L = cfg.num_users, cfg.num_channels, cfg.highway_length
@@ -170,7 +144,7 @@ def test_random_rich_configuration_on_the_specialised_kernels(i):
     bit (exp() rewards within the documented tolerance)."""
     import torch
     from oracle.oracle import Oracle, SQ_IEEE
-    from tests.test_gpu_parity import EXP_ATOL, make_env
+    from tests.gpu_util import EXP_ATOL, make_env
     cfg, mode, sticky, f64, offlane = draw_rich_case(i)
     cfg.validate()
     N, A, L = cfg.num_users, cfg.num_channels, cfg.highway_length

@@ -8,7 +8,7 @@ specialised kernels (step_fast64 / step_wide) or the three-launch form (step_lar
 import numpy as np
 import pytest
 
-import tests.test_gpu_parity as tp
+import tests.gpu_util as gu
 from diral_amd.config import KERNEL_FAST64, KERNEL_LARGE, KERNEL_WIDE
 from tests.golden_util import Golden, golden_names
 
@@ -41,7 +41,7 @@ def test_reference_fixture_as_one_env_of_a_mixed_batch(name):
     y0 = rng.integers(0, 3, size=(B, N)).astype(np.float64) if np.any(g["y0"] != 0) else np.zeros((B, N))
     v0 = np.full((B, N), 1.7) if cfg.mobility_vary else rng.uniform(1.1, 2.7, size=(B, N))
     x0[REF], y0[REF], v0[REF] = g["x0"], g["y0"], g["v0"]
-    env = tp.make_env(cfg, B)
+    env = gu.make_env(cfg, B)
     env.reset_topology(x0, y0, v0)
     orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=5)
     orc.reset(x0, y0, v0)
@@ -51,20 +51,20 @@ def test_reference_fixture_as_one_env_of_a_mixed_batch(name):
     for i, mode, ref_acts, t, (ep, eps) in g.steps():
         acts = np.where(rng.random((B, N)) < 0.5, acts, rng.integers(0, A, size=(B, N))).astype(np.int32)
         acts[REF] = ref_acts
-        obs, rew, chobs, _ = tp.gpu_step(env, mode, acts, t, ep, eps)
+        obs, rew, chobs, _ = gu.gpu_step(env, mode, acts, t, ep, eps)
         assert (env.last_kernel() & 15) == fam, env.last_kernel()
         o_rew, o_chobs = orc.step(mode, acts, t)
         o_state = orc.obtain_state(acts, o_chobs, o_rew, ep, eps)
-        if tp.uses_exp(cfg, mode):
-            assert tp.exp_close(rew, o_rew), (name, i)
+        if gu.uses_exp(cfg, mode):
+            assert gu.exp_close(rew, o_rew), (name, i)
         else:
             assert np.array_equal(rew, o_rew), (name, i, np.argwhere(rew != o_rew)[:5])
         assert np.array_equal(chobs, o_chobs), (name, i)
-        if cfg.State.add_reward and tp.uses_exp(cfg, mode):
-            assert tp.exp_close(obs, o_state), (name, i)
+        if cfg.State.add_reward and gu.uses_exp(cfg, mode):
+            assert gu.exp_close(obs, o_state), (name, i)
         else:
             assert np.array_equal(obs, o_state), (name, i, np.argwhere(obs != o_state)[:5])
-        tp.assert_slot_matches_reference(g, i, mode, rew[REF], chobs[REF], obs[REF])
+        gu.assert_slot_matches_reference(g, i, mode, rew[REF], chobs[REF], obs[REF])
         if i in g.vel_updates:
             draws = rng.integers(1, 4, size=(B, N)).astype(np.uint8)
             draws[REF] = g.vel_updates[i]
@@ -79,7 +79,7 @@ def test_reference_fixture_as_one_env_of_a_mixed_batch(name):
         st = {k: v.cpu().numpy() for k, v in env.export_state(tables=tables).items()}
         oe = orc.export()
         assert np.array_equal(st["pos_x"], oe["pos_x"]) and np.array_equal(st["vel"], oe["vel"]), (name, i)
-        tp.assert_moves_match_reference(g, i, st["pos_x"][REF], st["vel"][REF], ia[REF])
+        gu.assert_moves_match_reference(g, i, st["pos_x"][REF], st["vel"][REF], ia[REF])
         if tables:
             assert np.array_equal(st["seq"], oe["seq"]), (name, i)
             assert np.array_equal(st["age"], np.minimum(oe["age"], 255)), (name, i)

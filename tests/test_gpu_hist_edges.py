@@ -22,8 +22,8 @@ import torch
 from diral_amd.config import (KERNEL_FAST64, KERNEL_GENERAL, KERNEL_LARGE, KERNEL_OBSERVE, KERNEL_PACKED, KERNEL_POLICY,
                               KERNEL_RING, KERNEL_WIDE)
 from tests import hist_edge_cases as H
-from tests.test_gpu_parity import make_env
-from tests.test_gpu_posdist_edges import ran_on, same
+from tests.gpu_util import make_env
+from tests.gpu_util import ran_on, same
 
 pytestmark = pytest.mark.gpu
 

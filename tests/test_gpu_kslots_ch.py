@@ -8,10 +8,9 @@ import torch
 
 from diral_amd.config import (ERR_BAD_CONFIG, ERR_UNSUPPORTED, KERNEL_CH, KERNEL_FAST64, KERNEL_POLICY, STEP_MY_STEP_CH,
                               bench_config, c2_config)
+from tests.kslots_harness import RICH, assert_same_envs, closed_loop_twins, compare_closed_loop
 
 pytestmark = pytest.mark.gpu
-
-RICH = dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=True, add_position=True)
 
 
 def _is_ch_slots_kernel(lk):
@@ -29,89 +28,29 @@ def in_range_counts(x, a, rc):
     return np.where(coll, n_in, -1)
 
 
-def _pair(cfg, B, dt, K, t0, *, want_obs=True, keep=0.8, vel_seed=0, pen=False, x0=None, reps=2):
-    """The same slots on two envs: K one-slot calls (side 0) and one K-slot launch (side 1), `reps` times."""
-    from diral_amd.sps import SpsPolicy
-    from diral_amd.vec_env import VecV2VEnv
-    N, A = cfg.num_users, cfg.num_channels
-    vary = cfg.mobility_vary
-    runs = []
-    for fused_k in (False, True):
-        env = VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=dt)
-        if x0 is not None:
-            env.reset_topology(x0, None, np.full(x0.shape, 1.7))
-        else:
-            env.reset_topology(seed=21)
-        pol = SpsPolicy(B, N, A, device="cuda:0", seed=3)
-        pol.keep_prob = keep
-        pn = None
-        if pen:
-            pn = (2, -10.0, torch.zeros((B, N), dtype=torch.int32, device="cuda:0"),
-                  torch.full((B, N), -1, dtype=torch.int32, device="cuda:0"))
-        a = pol.prev_action.clone()
-        nxt = torch.empty_like(a)
-        t = 0
-
-        def one(sh=None, sr=None, co=None):
-            nonlocal a, nxt, t
-            env.step_policy(a, t, pol, nxt, shaped_out=sh, sum_r_out=sr, collision_out=co, mode=STEP_MY_STEP_CH,
-                            want_chobs=True, want_obs=want_obs, stuck_penalty=pn if sh is not None else None)
-            assert env.last_kernel() & KERNEL_POLICY == 0 and env.last_kernel() & KERNEL_CH      # three launches
-            if vary and t % cfg.episode_interval == cfg.episode_interval - 1:
-                env.update_velocity(seed=vel_seed + t // cfg.episode_interval)
-            a, nxt = nxt, a
-            t += 1
-        sh0 = torch.zeros((B, N), dtype=dt, device="cuda:0")
-        for _ in range(t0):                                       # warm-up, one slot per call on both sides
-            one(sh0 if pen else None)
-        start = (env.export_state()["pos_x"].cpu().numpy(), a.cpu().numpy())
-        outs = []
-        for rep in range(reps):
-            sh = torch.zeros((K, B, N), dtype=dt, device="cuda:0")
-            sr = torch.zeros((K, B), dtype=dt, device="cuda:0")
-            co = torch.zeros((K, B), dtype=dt, device="cuda:0")
-            if fused_k:
-                env.step_policy(a, t, pol, nxt, shaped_out=sh, sum_r_out=sr, collision_out=co, slots=K, vel_seed=vel_seed,
-                                mode=STEP_MY_STEP_CH, want_chobs=True, want_obs=want_obs, stuck_penalty=pn)
-                assert _is_ch_slots_kernel(env.last_kernel()), env.last_kernel()
-                a, nxt = nxt, a
-                t += K
-            else:
-                for k in range(K):
-                    one(sh[k], sr[k], co[k])
-            outs.append(dict(shaped=sh, sum_r=sr, coll=co, obs=env._obs.clone() if want_obs else None, rew=env._rew.clone(),
-                             done=env._done.clone(), actions=a.clone(), chobs=env._chobs.clone()))
-        torch.cuda.synchronize()
-        runs.append((env, pol, outs, pn, start))
-    return runs
+def _one_slot_is_three_launches(lk):
+    return lk & KERNEL_POLICY == 0 and bool(lk & KERNEL_CH)
 
 
-def _compare(runs, want_obs=True):
-    (e1, p1, o1, pn1, _), (e2, p2, o2, pn2, _) = runs
-    for rep in range(len(o1)):
-        for k in ("shaped", "sum_r", "coll", "rew", "done", "chobs", "actions"):
-            assert torch.equal(o1[rep][k], o2[rep][k]), (rep, k, (o1[rep][k] != o2[rep][k]).nonzero()[:4])
-        if want_obs:
-            assert torch.equal(o1[rep]["obs"], o2[rep]["obs"]), (rep, (o1[rep]["obs"] != o2[rep]["obs"]).nonzero()[:4])
-    assert torch.equal(p1.prev_action, p2.prev_action) and torch.equal(p1.counter, p2.counter)
-    sa, sb = e1.export_state(), e2.export_state()
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), k
-    m1, m2 = e1.metrics(), e2.metrics()
-    assert torch.equal(m1, m2), (m1 != m2).nonzero()[:4]        # the PRR sum and count among them
-    assert float(m1[:, 5].min()) > 0.0                           # DIRAL_M_PRR_CNT: the PRR columns were paid
-    if pn1 is not None:
-        assert torch.equal(pn1[2], pn2[2]) and torch.equal(pn1[3], pn2[3])
-    # ... and the envs go on alike: three plain slots
+def _ch_twins(cfg, B, dt, K, t0, *, want_obs=True, keep=0.8, vel_seed=0, pen=False):
+    """tests/kslots_harness.closed_loop_twins in this file's mode, with the start behind the warm-up kept."""
+    return closed_loop_twins(cfg, B, dt, K, t0, topo=21, pol_seed=3, keep=keep, mode=STEP_MY_STEP_CH, want_obs=want_obs,
+                             want_chobs=True, vel_seed=vel_seed, pen=pen, want_start=True,
+                             expect_one=_one_slot_is_three_launches, expect_fused=_is_ch_slots_kernel)
+
+
+def _compare_and_go_on(runs, want_obs=True):
+    """The shared comparison; then what this file adds: the PRR columns were paid, and the envs go on alike - three plain
+    slots, the state and the metrics once more, the sticky flags."""
+    compare_closed_loop(runs, want_obs=want_obs, want_chobs=True, check=False)
+    e1, e2 = runs[0].env, runs[1].env
+    assert float(e1.metrics()[:, 5].min()) > 0.0                 # DIRAL_M_PRR_CNT: the PRR columns were paid
     for t in range(3):
         a = e1.sample(900 + t)
         q1, r1, _ = e1.step(a, t)
         q2, r2, _ = e2.step(a, t)
         assert torch.equal(q1, q2) and torch.equal(r1, r2), t
-    sa, sb = e1.export_state(), e2.export_state()
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), k
-    assert torch.equal(e1.metrics(), e2.metrics())
+    sa = assert_same_envs(e1, e2, entries=False)
     e1.check()
     e2.check()
     return sa
@@ -142,16 +81,16 @@ def test_ch_k_slots_equal_k_one_slot_calls(case):
     kw = dict(CASES[case])
     cfg, dt, K, t0 = kw.pop("cfg"), kw.pop("dt"), kw.pop("K"), kw.pop("t0")
     want_obs = kw.get("want_obs", True)
-    runs = _pair(cfg, 24, dt, K, t0, **kw)
+    runs = _ch_twins(cfg, 24, dt, K, t0, **kw)
     if case == "dense_40_6":
-        n_in = in_range_counts(runs[1][4][0], runs[1][4][1], cfg.communication_range)
+        n_in = in_range_counts(runs[1].start[0], runs[1].start[1], cfg.communication_range)
         assert (n_in == 0).any() and (n_in > 0).any()             # both sides of `R = received / in_range` ran
         assert (n_in >= 0).mean() > 0.5                           # most transmitters collide
-    sa = _compare(runs, want_obs=want_obs)
+    sa = _compare_and_go_on(runs, want_obs=want_obs)
     if cfg.mobility_vary:
         assert not torch.equal(sa["vel"], torch.full_like(sa["vel"], 1.7))      # an episode ended inside the launches
     if case == "stuck_penalty":
-        assert int(runs[1][3][2].max()) > 2
+        assert int(runs[1].pen[2].max()) > 2
     if case == "sparse_64_8":
         seq = sa["seq"]
         own = torch.diagonal(seq, dim1=1, dim2=2).unsqueeze(1)

@@ -13,108 +13,28 @@ import torch
 
 from diral_amd.config import (ERR_BAD_ARG, ERR_BAD_CONFIG, ERR_UNSUPPORTED, KERNEL_CH, KERNEL_EXTRA, KERNEL_FAST64,
                               KERNEL_POLICY, STEP_MY_STEP, STEP_MY_STEP_CH, DiralRollout, DiralSlotInfoAge, DiralSlotPolicy,
-                              EnvConfig, bench_config)
+                              EnvConfig)
 from diral_amd.driver import DriverLoop
 from diral_amd.search import CandidateSearch
 from diral_amd.sps import SpsPolicy
-from diral_amd.vec_env import DiralError, VecV2VEnv, driver_shape
+from diral_amd.vec_env import DiralError, VecV2VEnv
 from oracle.oracle import SQ_IEEE, Oracle
 from tests import host_closed_loop as H
 from tests.golden_util import GOLDEN_DIR, ulp_diff
-from tests.test_gpu_closed_loop_host import EXP_ATOL, _exp_bounds
+from tests.host_closed_loop import EXP_ATOL, _exp_bounds
+from tests.kslots_harness import (DEV, PEN_VAL, VEL_SEED, as_rollout, assert_same, assert_same_envs, chain_cfg, go_on_alike,
+                                   slot_loop, start, stuck_penalty_state, twins)
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-RICH = dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=True, add_position=True)
-VEL_SEED = 4242
-PEN_THR, PEN_VAL = 2, -10.0
-
-
-def _cfg(N, A, rd=2, vary=False, rich=False, track=True):
-    """L = 30 N + 50 with a communication range of 120 (tests/test_driver_loop.py): some pairs are out of range."""
-    kw = dict(reward_design=rd, communication_range=120.0, mobility_vary=vary)
-    if rich:
-        kw["State"] = RICH
-    return bench_config(N, A, 30.0 * N + 50, **kw).replace(track_arrival=track)
-
-
-def _pair(cfg, B, dtype, seed, n=2):
-    rng = np.random.default_rng(seed)
-    x0 = rng.integers(0, int(cfg.highway_length), size=(B, cfg.num_users)).astype(np.float64)
-    v0 = np.full((B, cfg.num_users), 1.7) if cfg.mobility_vary else rng.uniform(1.1, 2.7, size=(B, cfg.num_users))
-    envs = []
-    for _ in range(n):
-        env = VecV2VEnv(cfg, batch=B, device=DEV, out_dtype=dtype)
-        env.reset_topology(x0, 0.0, v0)
-        envs.append(env)
-    return envs
-
-
-def _pen(B, N):
-    return (PEN_THR, PEN_VAL, torch.zeros((B, N), dtype=torch.int32, device=DEV), torch.full((B, N), -1, dtype=torch.int32, device=DEV))
-
-
-def _loop(env, seq, t, states, avg, pen, prev, want_ia=True):
-    """The loop the launch stands for, on `env`: K x [my_step_ch, info_age, diral_driver_shape with the histogram,
-    update_velocity behind an episode end] - the dict VecV2VEnv.rollout(info_age=True, sum_ia_prev=prev) returns."""
-    K, B, N = seq.shape[0], env.B, env.N
-    ei = env.cfg.episode_interval
-    o = dict(dtype=env.out_dtype, device=env.device)
-    shaped, sum_r, coll = torch.empty((K, B, N), **o), torch.empty((K, B), **o), torch.empty((K, B), **o)
-    ia_all = torch.empty((K, B, 100), dtype=torch.int32, device=env.device)
-    ia_sum = torch.empty((K, B), dtype=torch.int64, device=env.device)
-    ia_pen = torch.zeros((K, B), dtype=torch.int32, device=env.device)
-    kept = []
-    thr, val, cnt, pa = pen if pen is not None else (0, 0.0, None, None)
-    for k in range(K):
-        a = seq[k].contiguous()
-        obs, rew, done = env._step(STEP_MY_STEP_CH, a, t + k, want_obs=states is not None)
-        env.t = t + k + 1
-        if want_ia:
-            ia_all[k] = env.info_age(t + k)
-        driver_shape(env, rew, a, shaped=shaped[k], sum_r=sum_r[k], collision=coll[k], global_reward_avg=avg,
-                     ia=ia_all[k] if want_ia else None, sum_ia_prev=prev, ia_sum=ia_sum[k] if want_ia else None,
-                     ia_penalty=ia_pen[k] if prev is not None else None, pen_counter=cnt, prev_actions=pa,
-                     pen_threshold=thr, pen_value=val)
-        if states == "all":
-            kept.append(obs.clone())
-        if (t + k) % ei == ei - 1:
-            env.update_velocity(seed=VEL_SEED + (t + k) // ei)
-    st = None if (states is None or env.S == 0) else (torch.stack(kept) if states == "all" else obs.clone())
-    out = dict(states=st, reward=rew.clone(), done=done.clone(), shaped=shaped, sum_r=sum_r, collision=coll)
-    if want_ia:
-        out.update(ia=ia_all, ia_sum=ia_sum)
-    if prev is not None:
-        out["ia_penalty"] = ia_pen
-    return out
-
-
-def _same(want, got, what):
-    assert set(want) == set(got), (what, sorted(want), sorted(got))
-    for key in want:
-        if want[key] is None:
-            assert got[key] is None, (what, key)
-        else:
-            assert want[key].dtype == got[key].dtype and torch.equal(want[key], got[key]), (what, key, (want[key] != got[key]).nonzero()[:5])
-
-
-def _same_envs(e1, e2):
-    s1, s2 = e1.export_state(), e2.export_state()
-    assert "la" in s1
-    for key in s1:
-        assert torch.equal(s1[key], s2[key]), key
-    assert torch.equal(e1.metrics(), e2.metrics())                  # (the PRR columns among them)
-    return s1
 
 
 def _check(N, A, rd, K, t0, dtype, vary=False, rich=False, pen=False, states="last", reps=2, B=4, seed=31, sticky=0.0,
            hold_from=None, conditions=True):
     """`reps` launches of K slots, each continuing the one before, against the loop on a twin handle.  `sticky`: the
     probability that an agent repeats its action; `hold_from`: from that slot of a launch on every agent repeats it."""
-    cfg = _cfg(N, A, rd, vary, rich)
-    e_loop, e_one = _pair(cfg, B, dtype, seed)
-    pens = [_pen(B, N) if pen else None for _ in range(2)]
+    cfg = chain_cfg(N, A, rd, vary, rich, track=True)
+    e_loop, e_one = twins(cfg, B, dtype, start(cfg, B, seed))
+    pens = [stuck_penalty_state(B, N) if pen else None for _ in range(2)]
     prevs = [torch.zeros((B,), dtype=torch.int64, device=DEV) for _ in range(2)]
     warm = 3 if t0 >= 3 else 0
     for w in range(warm):                                           # stamps older than the launches, from one-slot steps
@@ -134,18 +54,19 @@ def _check(N, A, rd, K, t0, dtype, vary=False, rich=False, pen=False, states="la
             rows.append(acts)
         seq = torch.as_tensor(np.stack(rows), device=DEV)
         la_before = e_loop.export_state()["la"].cpu().numpy()      # the stamps the last launch starts from
-        want = _loop(e_loop, seq, t, states, True, pens[0], prevs[0])
+        want = as_rollout(slot_loop(e_loop, seq, t, "my_step_ch", pen=pens[0], ia_prev=prevs[0], want_ia=True,
+                                    want_obs=states is not None), states)
         got = e_one.rollout(seq, t, mode="my_step_ch", states=states, global_reward_avg=True, stuck_penalty=pens[1],
                             vel_seed=VEL_SEED, info_age=True, sum_ia_prev=prevs[1])
         torch.cuda.synchronize()
         lk = e_one.last_kernel()
         assert (lk & 15) == KERNEL_FAST64 and (lk & KERNEL_POLICY) and (lk & KERNEL_CH) and not (lk & KERNEL_EXTRA), lk
-        _same(want, got, rep)
+        assert_same(want, got, rep)
         assert torch.equal(prevs[0], prevs[1]) and torch.equal(prevs[0], want["ia_sum"][-1])
         assert e_one.t == t + K == e_loop.t
         wants.append(want)
         t_last, t = t, t + K
-    s = _same_envs(e_loop, e_one)
+    s = assert_same_envs(e_loop, e_one)
     if pen:
         assert torch.equal(pens[0][2], pens[1][2]) and torch.equal(pens[0][3], pens[1][3])
     # what the inputs must exercise, from the LOOP's results: entries that never arrived (off the diagonal), stamps of the
@@ -159,13 +80,7 @@ def _check(N, A, rd, K, t0, dtype, vary=False, rich=False, pen=False, states="la
         assert ((la_before != -1) & (la_before < t_last) & off).any()
         assert int(wants[-1]["ia"][0, :, 1:].sum()) > 0
         assert int((wants[-1]["ia"].sum(1) > 0).sum(-1).max()) >= 3
-    for k in range(3):                                              # both handles go on alike
-        a = e_loop.sample(900 + k)
-        o1, r1, d1 = e_loop._step(STEP_MY_STEP_CH, a, t + k)
-        o2, r2, d2 = e_one._step(STEP_MY_STEP_CH, a, t + k)
-        assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2)
-        assert torch.equal(e_loop.info_age(t + k), e_one.info_age(t + k))
-    e_loop.check(); e_one.check()
+    go_on_alike(e_loop, e_one, "my_step_ch", t, info_age=True)
     return wants, pens[0]
 
 
@@ -213,7 +128,7 @@ def test_imported_stamps_at_the_edges_of_the_histogram():
     -1, imported on pairs that stay in range without the transmitter being the receiver's closest one - nothing overwrites
     or clears them: a 3-slot launch against the loop and against the oracle."""
     N, A, B, t0, K = 8, 3, 3, 200, 3
-    cfg = _cfg(N, A, 2)
+    cfg = chain_cfg(N, A, 2, track=True)
     x0 = np.tile(np.arange(N) * 10.0, (B, 1)) + 5.0 * np.arange(B)[:, None]
     v0 = np.full((B, N), 1.7)
     acts = np.array([0, 1, 2, 0, 1, 2, 1, 2], np.int32)              # resource 0: vehicles 0, 3; 1: 1, 4, 6; 2: 2, 5, 7
@@ -238,12 +153,12 @@ def test_imported_stamps_at_the_edges_of_the_histogram():
         orc.step(STEP_MY_STEP_CH, np.broadcast_to(acts, (B, N)).copy(), t0 + k)
         o_ia.append(orc.info_age(t0 + k))
     o_ia = np.stack(o_ia)
-    want = _loop(e_loop, seq, t0, "last", True, None, None)
+    want = as_rollout(slot_loop(e_loop, seq, t0, "my_step_ch", want_ia=True), "last")
     got = e_one.rollout(seq, t0, mode="my_step_ch", states="last", global_reward_avg=True, vel_seed=VEL_SEED, info_age=True)
     torch.cuda.synchronize()
     assert e_one.last_kernel() & KERNEL_POLICY
-    _same(want, got, "edges")
-    s = _same_envs(e_loop, e_one)
+    assert_same(want, got, "edges")
+    s = assert_same_envs(e_loop, e_one)
     assert np.array_equal(got["ia"].cpu().numpy(), o_ia)
     o_la = orc.export()["la"]
     assert np.array_equal(s["la"].cpu().numpy(), o_la)
@@ -266,7 +181,7 @@ def test_closed_loop_with_information_age_against_the_cpu_oracle(N, A, rd, dtype
     (CPU oracle step, shaping, SPS): every slot's histogram and the final stamps exactly, rewards within that file's bars;
     and bit-equal to six one-slot step_policy calls, each followed by info_age."""
     B, K, t0, topo_seed, pol_seed = 4, 6, 3, 21, 3
-    cfg = _cfg(N, A, rd)
+    cfg = chain_cfg(N, A, rd, track=True)
     npdt = np.float32 if dtype == torch.float32 else np.float64
     x0, v0 = H.draw_topology(topo_seed, B, N, cfg.highway_length, cfg.mobility_vary, 0)
     sps = H.HostSps.from_seed(B * N, A, pol_seed, threshold=-110.0, keep_prob=1.0)
@@ -320,7 +235,7 @@ def test_closed_loop_with_information_age_against_the_cpu_oracle(N, A, rd, dtype
         assert torch.equal(s1, sh[k]) and torch.equal(r1, sr[k]) and torch.equal(c1, co[k]), k
         a, nx2 = nx2, a
     assert torch.equal(rew2, rew) and torch.equal(a, nxt)
-    _same_envs(env, env2)
+    assert "la" in assert_same_envs(env, env2)
     assert torch.equal(pol.prev_action, pol2.prev_action) and torch.equal(pol.counter, pol2.counter)
     env.check(); env2.check()
 
@@ -386,14 +301,14 @@ def test_driver_rollout_in_chunks_reproduces_the_reference_recording(name):
 
 def test_stamps_only_keeps_the_stamps_and_builds_no_histogram():
     N, A, B, K, t0 = 33, 9, 4, 7, 5
-    cfg = _cfg(N, A, 3, vary=True)
-    e_loop, e_one = _pair(cfg, B, torch.float32, 77)
+    cfg = chain_cfg(N, A, 3, vary=True, track=True)
+    e_loop, e_one = twins(cfg, B, torch.float32, start(cfg, B, 77))
     seq = torch.stack([e_loop.sample(300 + k) for k in range(K)])
-    want = _loop(e_loop, seq, t0, "last", True, None, None, want_ia=False)
+    want = as_rollout(slot_loop(e_loop, seq, t0, "my_step_ch"), "last")
     got = e_one.rollout(seq, t0, mode="my_step_ch", states="last", global_reward_avg=True, vel_seed=VEL_SEED, info_age="stamps")
     assert e_one.last_kernel() & KERNEL_POLICY
-    _same(want, got, "stamps")                                       # (no ia / ia_sum / ia_penalty in either)
-    _same_envs(e_loop, e_one)
+    assert_same(want, got, "stamps")                                       # (no ia / ia_sum / ia_penalty in either)
+    assert "la" in assert_same_envs(e_loop, e_one)
     assert torch.equal(e_loop.info_age(t0 + K), e_one.info_age(t0 + K))
     assert int(e_one.info_age(t0 + K).sum()) > 0
     e_one.check()
@@ -456,7 +371,7 @@ def test_refusals_and_argument_checks_leave_the_env_untouched(what, N, track, mo
     """One case per row of the header's list, through both entry points: the status, and - nothing was launched - the
     exported state with the stamps, the metrics and the slot counter are what they were."""
     A, B, K, t0 = 6, 3, 4, 3
-    cfg = _cfg(N, A, 2, track=track)
+    cfg = chain_cfg(N, A, 2, track=track)
     env = VecV2VEnv(cfg, batch=B, device=DEV, out_dtype=torch.float32)
     env.reset_topology(seed=5)
     for k in range(t0):
@@ -506,7 +421,7 @@ def test_candidate_search_scores_candidates_by_information_age():
     """CandidateSearch.evaluate(info_age=True): ia_sum[:, b, c] is what a lone handle forked from env b and stepped with
     candidate c's actions reports; `env` is untouched until commit."""
     N, A, B, C, K, t0 = 33, 9, 3, 3, 5, 4
-    cfg = _cfg(N, A, 2)
+    cfg = chain_cfg(N, A, 2, track=True)
     env = VecV2VEnv(cfg, batch=B, device=DEV, out_dtype=torch.float32, step_mode="my_step_ch")
     env.reset_topology(seed=9)
     for k in range(t0):

@@ -15,44 +15,14 @@ from diral_amd.driver import DriverLoop
 from diral_amd.rollout import SlotClock, no_finalizers_during_capture
 from diral_amd.search import CandidateSearch
 from diral_amd.sps import SpsPolicy
-from diral_amd.vec_env import DiralError, VecV2VEnv, driver_shape
+from diral_amd.vec_env import DiralError, VecV2VEnv
 from oracle.oracle import SQ_IEEE, Oracle
 from tests import host_closed_loop as H
 from tests.golden_util import Golden
+from tests.kslots_harness import (DEV, PEN_THR, VEL_SEED, assert_equal, assert_same_envs, chain_cfg, go_on_alike, slot_loop, start,
+                                   stuck_penalty_state, twins)
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
-RICH = dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=True, add_position=True)
-MODES = {"my_step": STEP_MY_STEP, "my_step_ch": STEP_MY_STEP_CH}
-VEL_SEED = 4242
-PEN_THR, PEN_VAL = 2, -10.0
-
-
-def _cfg(N, A, rd=2, vary=False, rich=False, track=False, L=None, Rc=120.0):
-    """L = 30 N + 50 with a communication range of 120 (tests/test_driver_loop.py): some pairs are out of range."""
-    kw = dict(reward_design=rd, communication_range=Rc, mobility_vary=vary)
-    if rich:
-        kw["State"] = RICH
-    cfg = bench_config(N, A, 30.0 * N + 50 if L is None else L, **kw)
-    return cfg.replace(track_arrival=True) if track else cfg
-
-
-def _start(cfg, B, seed):
-    rng = np.random.default_rng(seed)
-    x0 = rng.integers(0, int(cfg.highway_length), size=(B, cfg.num_users)).astype(np.float64)
-    v0 = np.full((B, cfg.num_users), 1.7) if cfg.mobility_vary else rng.uniform(1.1, 2.7, size=(B, cfg.num_users))
-    return x0, v0
-
-
-def _envs(cfg, B, dtype, start, n=2):
-    envs = []
-    for _ in range(n):
-        env = VecV2VEnv(cfg, batch=B, device=DEV, out_dtype=dtype)
-        env.reset_topology(start[0], 0.0, start[1])
-        envs.append(env)
-    return envs
-
 
 def _trace(rng, L, shape):
     """A recorded run [..., T, N]: a row either moves on from the one before (1 ... 3 m, wrapped) or is drawn afresh - a
@@ -62,51 +32,6 @@ def _trace(rng, L, shape):
         smooth = rng.random(shape[:-2] + (1,)) < 0.6
         tr[..., k, :] = np.where(smooth, (tr[..., k - 1, :] + rng.uniform(1, 3, size=shape[:-2] + (shape[-1],))) % L, tr[..., k, :])
     return tr
-
-
-def _pen(B, N):
-    return (PEN_THR, PEN_VAL, torch.zeros((B, N), dtype=torch.int32, device=DEV), torch.full((B, N), -1, dtype=torch.int32, device=DEV))
-
-
-def _loop(env, seq, t, mode, avg=True, pen=None, ia_prev=None, want_ia=False, stop=None):
-    """The loop the launches stand for, on `env` (which carries the trace, if any): K x [step, info_age, diral_driver_shape,
-    update_velocity behind an episode end] - everything of every slot, stacked [K, ...]."""
-    K, B, N = seq.shape[0], env.B, env.N
-    ei = env.cfg.episode_interval
-    o = dict(dtype=env.out_dtype, device=env.device)
-    shaped, sum_r, coll = torch.empty((K, B, N), **o), torch.empty((K, B), **o), torch.empty((K, B), **o)
-    ia_all = torch.empty((K, B, 100), dtype=torch.int32, device=env.device)
-    ia_sum = torch.empty((K, B), dtype=torch.int64, device=env.device)
-    ia_pen = torch.zeros((K, B), dtype=torch.int32, device=env.device)
-    states, rews, dones, xpos = [], [], [], []
-    thr, val, cnt, pa = pen if pen is not None else (0, 0.0, None, None)
-    for k in range(K):
-        a = seq[k].contiguous()
-        obs, rew, done = env._step(MODES[mode], a, t + k)
-        env.t = t + k + 1
-        if want_ia:
-            ia_all[k] = env.info_age(t + k)
-        driver_shape(env, rew, a, shaped=shaped[k], sum_r=sum_r[k], collision=coll[k], global_reward_avg=avg,
-                     ia=ia_all[k] if want_ia else None, sum_ia_prev=ia_prev, ia_sum=ia_sum[k] if want_ia else None,
-                     ia_penalty=ia_pen[k] if ia_prev is not None else None, pen_counter=cnt, prev_actions=pa,
-                     pen_threshold=thr, pen_value=val)
-        states.append(obs.clone()); rews.append(rew.clone()); dones.append(done.clone())
-        xpos.append(env.get_x_pos().clone())
-        if (t + k) % ei == ei - 1:
-            env.update_velocity(seed=VEL_SEED + (t + k) // ei)
-        if stop is not None and k == stop[0]:
-            stop[1](env)
-    out = dict(states=torch.stack(states), reward=torch.stack(rews), done=torch.stack(dones), shaped=shaped, sum_r=sum_r,
-               collision=coll, xpos=torch.stack(xpos))
-    if want_ia:
-        out.update(ia=ia_all, ia_sum=ia_sum)
-    if ia_prev is not None:
-        out["ia_penalty"] = ia_pen
-    return out
-
-
-def _eq(want, got, what):
-    assert want.dtype == got.dtype and torch.equal(want, got), (what, (want != got).nonzero()[:5])
 
 
 def _launches(env, want, seq, t, plan, mode, states="all", avg=True, pen=None, positions=None, log=True, **kw):
@@ -123,74 +48,53 @@ def _launches(env, want, seq, t, plan, mode, states="all", avg=True, pen=None, p
         tag = "slots %d ... %d: " % (k0, k0 + K - 1)
         sl = slice(k0, k0 + K)
         for key in ("shaped", "sum_r", "collision") + (("xpos",) if log else ()) + tuple(k for k in ("ia", "ia_sum", "ia_penalty") if k in want):
-            _eq(want[key][sl], got[key], tag + key)
+            assert_equal(want[key][sl], got[key], tag + key)
         assert log or "xpos" not in got
-        _eq(want["reward"][k0 + K - 1], got["reward"], tag + "reward")
-        _eq(want["done"][k0 + K - 1], got["done"], tag + "done")
+        assert_equal(want["reward"][k0 + K - 1], got["reward"], tag + "reward")
+        assert_equal(want["done"][k0 + K - 1], got["done"], tag + "done")
         if states is None or env.S == 0:
             assert got["states"] is None
         elif states == "all":
-            _eq(want["states"][sl], got["states"], tag + "states")
+            assert_equal(want["states"][sl], got["states"], tag + "states")
         else:
-            _eq(want["states"][k0 + K - 1], got["states"], tag + "states")
+            assert_equal(want["states"][k0 + K - 1], got["states"], tag + "states")
         assert env.t == t + k0 + K
         k0 += K
     assert k0 == seq.shape[0]
 
 
-def _same_envs(e1, e2):
-    """Positions, velocities, the tables in every stored form (planes, packed words, ring as export_entries reads them),
-    arrival stamps where tracked, the metrics with the PRR columns."""
-    s1, s2 = e1.export_state(), e2.export_state()
-    for key in s1:
-        assert torch.equal(s1[key], s2[key]), key
-    assert torch.equal(e1.export_entries(), e2.export_entries())
-    assert torch.equal(e1.metrics(), e2.metrics())
-    return s1
-
-
-def _go_on_alike(e_loop, e_one, mode, t):
-    """Both handles back on the velocity model: three further ordinary steps, then the sticky error flags."""
-    e_loop.load_saved_positions(None)
-    for k in range(3):
-        a = e_loop.sample(900 + k)
-        o1, r1, d1 = e_loop._step(MODES[mode], a, t + k)
-        o2, r2, d2 = e_one._step(MODES[mode], a, t + k)
-        assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2)
-    e_loop.check(); e_one.check()
-
-
 def _check(N, A, rd, mode, K, T, t0, dtype, per_env=False, states="all", vary=False, pen=False, rich=False, reps=2, B=4, seed=31):
     """`reps` launches of K slots, each continuing the one before, against the loop on a twin handle that carries the trace.
     T = 0: no sequence - the position log of the velocity model."""
-    cfg = _cfg(N, A, rd, vary, rich)
-    start = _start(cfg, B, seed)
-    e_loop, e_one = _envs(cfg, B, dtype, start)
+    cfg = chain_cfg(N, A, rd, vary, rich)
+    begin = start(cfg, B, seed)
+    e_loop, e_one = twins(cfg, B, dtype, begin)
     rng = np.random.default_rng(seed + 7)
     tr = None
     if T:
         tr = torch.as_tensor(_trace(rng, cfg.highway_length, ((B,) if per_env else ()) + (T, N)), device=DEV)
         e_loop.load_saved_positions(tr)
-    pens = [_pen(B, N) if pen else None for _ in range(2)]
+    pens = [stuck_penalty_state(B, N) if pen else None for _ in range(2)]
     Kt = K * reps
     if pen:                                                           # agents that repeat their action: the penalty fires
         seq = e_loop.sample(7000).unsqueeze(0).expand(Kt, B, N).contiguous()
     else:
         seq = torch.stack([e_loop.sample(7000 + k) for k in range(Kt)])
-    want = _loop(e_loop, seq, t0, mode, pen=pens[0])
+    want = slot_loop(e_loop, seq, t0, mode, pen=pens[0], want_xpos=True)
     _launches(e_one, want, seq, t0, [K] * reps, mode, states=states, pen=pens[1], positions=tr)
     if T:                                                             # row (t + k) mod T, Python's sign
         rows = torch.as_tensor([(t0 + k) % T for k in range(Kt)], device=DEV)
         exp = tr[:, rows].transpose(0, 1) if per_env else tr[rows].unsqueeze(1).expand(Kt, B, N)
         assert torch.equal(want["xpos"], exp)
     assert e_loop.t == e_one.t == t0 + Kt
-    s = _same_envs(e_loop, e_one)
+    s = assert_same_envs(e_loop, e_one)
     if pen:
         assert torch.equal(pens[0][2], pens[1][2]) and torch.equal(pens[0][3], pens[1][3])
         assert int(pens[1][2].max()) > PEN_THR
     if vary:
         assert not torch.equal(s["vel"], torch.full_like(s["vel"], 1.7))
-    _go_on_alike(e_loop, e_one, mode, t0 + Kt)
+    e_loop.load_saved_positions(None)
+    go_on_alike(e_loop, e_one, mode, t0 + Kt)
 
 
 @pytest.mark.parametrize("N,A,rd,mode,K,T,t0,dtype,per_env,states,vary,pen", [
@@ -244,13 +148,13 @@ def test_closed_loop_with_recorded_positions_equals_the_one_slot_calls(mode, dty
     """`step_policy(slots=K, positions=)` = K three-launch `step_policy` calls on a twin that carries the trace: the per-slot
     outputs, the last slot's state / reward / done, the next actions, the SPS state, the position log, the envs."""
     N, A, B, K, T, t0 = 33, 9, 5, 12, 7, 20
-    cfg = _cfg(N, A, 2, vary, rich=True)
-    start = _start(cfg, B, 17)
-    e_loop, e_one = _envs(cfg, B, dtype, start)
+    cfg = chain_cfg(N, A, 2, vary, rich=True)
+    begin = start(cfg, B, 17)
+    e_loop, e_one = twins(cfg, B, dtype, begin)
     tr = torch.as_tensor(_trace(np.random.default_rng(4), cfg.highway_length, ((B,) if per_env else ()) + (T, N)), device=DEV)
     e_loop.load_saved_positions(tr)
     p1, p2 = _policy(B, N, A), _policy(B, N, A)
-    pn1, pn2 = _pen(B, N), _pen(B, N)
+    pn1, pn2 = stuck_penalty_state(B, N), stuck_penalty_state(B, N)
     o = dict(dtype=dtype, device=DEV)
     EI = cfg.episode_interval
     t = t0
@@ -280,10 +184,10 @@ def test_closed_loop_with_recorded_positions_equals_the_one_slot_calls(mode, dty
                            ("state", obs1, obs2), ("reward", rew1, rew2), ("done", done1, done2), ("actions_out", cur, out2),
                            ("chobs", e_loop._chobs, e_one._chobs), ("prev_action", p1.prev_action, p2.prev_action),
                            ("counter", p1.counter, p2.counter), ("pen_counter", pn1[2], pn2[2]), ("pen_prev", pn1[3], pn2[3])):
-            _eq(x, y, (rep, name))
+            assert_equal(x, y, (rep, name))
         assert p1._t == p2._t
         t += K
-    _same_envs(e_loop, e_one)
+    assert_same_envs(e_loop, e_one)
     e_loop.check(); e_one.check()
 
 
@@ -291,10 +195,10 @@ def test_closed_loop_with_recorded_positions_equals_the_one_slot_calls(mode, dty
 def test_closed_loop_with_recorded_positions_against_the_host_loop(mode):
     """... and against tests/host_closed_loop.HostClosedLoop on an OracleBackend that had load_saved_positions (a shared
     trace): CPU oracle step, the shaping in NumPy's order, the SPS agent on the host."""
-    from tests.test_gpu_closed_loop_host import MODE_NAME, _eq as eq
+    from tests.host_closed_loop import MODE_NAME, _eq as eq
     N, A, B, T = 33, 9, 6, 7
     plan = [12, 9]
-    cfg = _cfg(N, A, 2, vary=True, rich=True)
+    cfg = chain_cfg(N, A, 2, vary=True, rich=True)
     x0, v0 = H.draw_topology(21, B, N, cfg.highway_length, True, 0)
     tr = _trace(np.random.default_rng(9), cfg.highway_length, (T, N))
     sps = H.HostSps.from_seed(B * N, A, 3, threshold=-110.0, keep_prob=0.8)
@@ -304,7 +208,7 @@ def test_closed_loop_with_recorded_positions_against_the_host_loop(mode):
     env = VecV2VEnv(cfg, batch=B, device=DEV, out_dtype=torch.float64)
     env.reset_topology(x0, None, v0)
     pol = _policy(B, N, A)
-    pn = _pen(B, N)
+    pn = stuck_penalty_state(B, N)
     trd = torch.as_tensor(tr, device=DEV)
     a, nxt, t = pol.prev_action.clone(), torch.empty_like(pol.prev_action), 20
     ha = sps.prev_action.reshape(B, N).copy()
@@ -348,28 +252,29 @@ def test_information_age_block_with_recorded_positions(N, A, dtype, K, T, per_en
     """A tracking handle: stamps, histograms, sums, the ia_averaging term and the caller's sum_ia_prev of a launch that
     replays positions = the loop of my_step_ch + info_age + diral_driver_shape on the twin with the trace."""
     B, t0 = 4, 20
-    cfg = _cfg(N, A, 2, vary=True, track=True)
-    start = _start(cfg, B, 5)
-    e_loop, e_one = _envs(cfg, B, dtype, start)
+    cfg = chain_cfg(N, A, 2, vary=True, track=True)
+    begin = start(cfg, B, 5)
+    e_loop, e_one = twins(cfg, B, dtype, begin)
     tr = torch.as_tensor(_trace(np.random.default_rng(6), cfg.highway_length, ((B,) if per_env else ()) + (T, N)), device=DEV)
     e_loop.load_saved_positions(tr)
     prevs = [torch.zeros((B,), dtype=torch.int64, device=DEV) if avg_term else None for _ in range(2)]
-    pens = [_pen(B, N), _pen(B, N)]
+    pens = [stuck_penalty_state(B, N), stuck_penalty_state(B, N)]
     seq = torch.stack([e_loop.sample(7000 + k // 3) for k in range(2 * K)])      # (every action held for three slots)
-    want = _loop(e_loop, seq, t0, "my_step_ch", pen=pens[0], ia_prev=prevs[0], want_ia=True)
+    want = slot_loop(e_loop, seq, t0, "my_step_ch", pen=pens[0], ia_prev=prevs[0], want_ia=True, want_xpos=True)
     _launches(e_one, want, seq, t0, [K, K], "my_step_ch", states="all", pen=pens[1], positions=tr, info_age=True,
               sum_ia_prev=prevs[1])
     if avg_term:
         assert torch.equal(prevs[0], prevs[1]) and torch.equal(prevs[0], want["ia_sum"][-1])
         assert len(set(want["ia_penalty"].unique().tolist())) >= 2
-    s = _same_envs(e_loop, e_one)
+    s = assert_same_envs(e_loop, e_one)
     la = s["la"].cpu().numpy()
     off = ~np.eye(N, dtype=bool)[None]
     assert ((la == -1) & off).any() and ((la >= t0 + K) & off).any()
     assert int((want["ia"].sum(1) > 0).sum(-1).max()) >= 3
     for k in range(2):
         assert torch.equal(e_loop.info_age(t0 + 2 * K + k), e_one.info_age(t0 + 2 * K + k))
-    _go_on_alike(e_loop, e_one, "my_step_ch", t0 + 2 * K)
+    e_loop.load_saved_positions(None)
+    go_on_alike(e_loop, e_one, "my_step_ch", t0 + 2 * K)
 
 
 # ---- 4: the CPU oracle, one per env; the reference's own recording ---------------------------------------------------------
@@ -474,7 +379,7 @@ def test_recorded_positions_outside_what_the_velocity_model_produces(mode, dtype
     in some slots and not in the others, in different slots for different envs, as one launch and split so that a special
     row is slot 0 of a launch: a decision taken once per launch instead of once per slot shows."""
     N, A, B, L, Rc = 16, 4, 4, 500.0, 120.0
-    cfg = _cfg(N, A, 2, L=L, Rc=Rc, rich=True)
+    cfg = chain_cfg(N, A, 2, L=L, Rc=Rc, rich=True)
     rng = np.random.default_rng(77)
     T = 14
     base = np.sort(rng.uniform(0, L, size=(T, N)), axis=1)
@@ -493,19 +398,20 @@ def test_recorded_positions_outside_what_the_velocity_model_produces(mode, dtype
             for u, x in vals.items():
                 tr[b, (r + b) % T, u] = x
     trd = torch.as_tensor(tr, device=DEV)
-    start = (np.broadcast_to(base[0], (B, N)).copy(), np.full((B, N), 1.7))
-    e_loop, e_one, e_split = _envs(cfg, B, dtype, start, n=3)
+    begin = (np.broadcast_to(base[0], (B, N)).copy(), np.full((B, N), 1.7))
+    e_loop, e_one, e_split = twins(cfg, B, dtype, begin, n=3)
     e_loop.load_saved_positions(trd)
     seq = torch.stack([e_loop.sample(7000 + k) for k in range(2 * T)])
-    want = _loop(e_loop, seq, 0, mode)
+    want = slot_loop(e_loop, seq, 0, mode, want_xpos=True)
     assert torch.equal(want["xpos"][:T].transpose(0, 1), trd)       # (bit patterns too: -0.0 == 0.0 for torch.equal ...)
     assert bool((torch.signbit(want["xpos"]) & (want["xpos"] == 0)).any())
     _launches(e_one, want, seq, 0, [2 * T], mode, positions=trd)
     assert torch.equal(torch.signbit(e_one.get_x_pos()), torch.signbit(e_loop.get_x_pos()))
     _launches(e_split, want, seq, 0, [2, 2, 2, 2, 1, 2, 1, 2, 2, 12], mode, positions=trd)
-    _same_envs(e_loop, e_one)
-    _same_envs(e_loop, e_split)
-    _go_on_alike(e_loop, e_one, mode, 2 * T)
+    assert_same_envs(e_loop, e_one)
+    assert_same_envs(e_loop, e_split)
+    e_loop.load_saved_positions(None)
+    go_on_alike(e_loop, e_one, mode, 2 * T)
 
 
 # ---- 6: keyed quads --------------------------------------------------------------------------------------------------------
@@ -524,9 +430,9 @@ def test_a_highway_that_splits_and_merges_again_inside_the_trace():
         else:
             tr[r] = np.sort(rng.uniform(0, 200, N))
     trd = torch.as_tensor(tr, device=DEV)
-    start = (np.broadcast_to(tr[29], (B, N)).copy(), np.full((B, N), 1.7))
+    begin = (np.broadcast_to(tr[29], (B, N)).copy(), np.full((B, N), 1.7))
     for dtype in (torch.float32, torch.float64):
-        e_loop, e_one, e_split = _envs(cfg, B, dtype, start, n=3)
+        e_loop, e_one, e_split = twins(cfg, B, dtype, begin, n=3)
         e_loop.load_saved_positions(trd)
         seq = torch.stack([e_loop.sample(7000 + k) for k in range(30)])
         far = {}
@@ -535,16 +441,17 @@ def test_a_highway_that_splits_and_merges_again_inside_the_trace():
             s = env.export_state()
             own = torch.diagonal(s["seq"], dim1=1, dim2=2).unsqueeze(1)
             far[17] = int(((own - s["seq"] >= 8) & (s["seq"] > 0)).sum())
-        want = _loop(e_loop, seq, 0, "my_step", stop=(17, behind_17))
+        want = slot_loop(e_loop, seq, 0, "my_step", stop=(17, behind_17), want_xpos=True)
         print("entries beyond the codes behind slot 17:", far[17])
         assert far[17] >= 1, "no entry with seq > 0 lags its subject by 8 or more"
         _launches(e_one, want, seq, 0, [30], "my_step", positions=trd)
         _launches(e_split, want, seq, 0, [18, 12], "my_step", positions=trd)
-        s = _same_envs(e_loop, e_one)
-        _same_envs(e_loop, e_split)
+        s = assert_same_envs(e_loop, e_one)
+        assert_same_envs(e_loop, e_split)
         own = torch.diagonal(s["seq"], dim1=1, dim2=2).unsqueeze(1)
         assert not bool(((own - s["seq"] >= 8) & (s["seq"] > 0)).any())        # behind the merge everything is within the codes
-        _go_on_alike(e_loop, e_one, "my_step", 30)
+        e_loop.load_saved_positions(None)
+        go_on_alike(e_loop, e_one, "my_step", 30)
 
 
 # ---- 7: the position log replays its launch ----------------------------------------------------------------------------------
@@ -554,18 +461,18 @@ def test_the_log_of_a_velocity_model_launch_replays_it(mode, dtype):
     with T = K on a fresh env from the same x0 / v0 and the same actions, leaves the same states, rewards, tables,
     velocities and positions."""
     N, A, B, K = 33, 9, 5, 25
-    cfg = _cfg(N, A, 2, vary=True, rich=True)
-    start = _start(cfg, B, 3)
-    e_rec, e_rep = _envs(cfg, B, dtype, start)
+    cfg = chain_cfg(N, A, 2, vary=True, rich=True)
+    begin = start(cfg, B, 3)
+    e_rec, e_rep = twins(cfg, B, dtype, begin)
     seq = torch.stack([e_rec.sample(7000 + k) for k in range(K)])
     rec = e_rec.rollout(seq, 0, mode=mode, states="all", global_reward_avg=True, vel_seed=VEL_SEED, log_positions=True)
     pos = rec["xpos"].transpose(0, 1).contiguous()                  # [B, T = K, N]
     rep = e_rep.rollout(seq, 0, mode=mode, states="all", global_reward_avg=True, vel_seed=VEL_SEED, positions=pos, log_positions=True)
     torch.cuda.synchronize()
     for key in ("states", "reward", "done", "shaped", "sum_r", "collision", "xpos"):
-        _eq(rec[key], rep[key], key)
+        assert_equal(rec[key], rep[key], key)
     assert int(rec["done"].min()) == 1
-    s = _same_envs(e_rec, e_rep)
+    s = assert_same_envs(e_rec, e_rep)
     assert torch.equal(s["pos_x"], rec["xpos"][-1]) and not torch.equal(s["vel"], torch.full_like(s["vel"], 1.7))
     e_rec.check(); e_rep.check()
 
@@ -575,9 +482,9 @@ def test_captured_launch_follows_the_slot_clock():
     """One `rollout(positions=)` with t = 0 on a handle with a slot clock, captured and replayed twice: the row of the
     sequence follows the clock, as in the eager calls on a twin."""
     N, A, B, K, T = 33, 9, 4, 6, 7
-    cfg = _cfg(N, A, 2, vary=True)
-    start = _start(cfg, B, 8)
-    e_cap, e_eag = _envs(cfg, B, torch.float32, start)
+    cfg = chain_cfg(N, A, 2, vary=True)
+    begin = start(cfg, B, 8)
+    e_cap, e_eag = twins(cfg, B, torch.float32, begin)
     tr = torch.as_tensor(_trace(np.random.default_rng(2), cfg.highway_length, (B, T, N)), device=DEV)
     seq = torch.stack([e_cap.sample(7000 + k) for k in range(K)])
     clk = SlotClock(DEV, 0)
@@ -598,12 +505,12 @@ def test_captured_launch_follows_the_slot_clock():
     for rep in range(3):
         wants.append({k: v.clone() for k, v in e_eag.rollout(seq, rep * K, **kw).items()})
     for key in first:
-        _eq(wants[0][key], first[key], ("eager", key))
+        assert_equal(wants[0][key], first[key], ("eager", key))
     for rep in (1, 2):
         g.replay()
         torch.cuda.synchronize()
         for key in out:
-            _eq(wants[rep][key], out[key], (rep, key))
+            assert_equal(wants[rep][key], out[key], (rep, key))
     assert clk.value() == 3 * K
     rows = torch.as_tensor([(2 * K + k) % T for k in range(K)], device=DEV)
     assert torch.equal(out["xpos"], tr[:, rows].transpose(0, 1))
@@ -704,10 +611,10 @@ def test_refusals_leave_the_env_untouched_and_the_driver_loops_with_the_trace(na
 
 
 def test_one_slot_closed_loop_call_is_refused_and_the_driver_takes_the_launch_where_it_can():
-    cfg = _cfg(33, 9, 2, vary=True)
+    cfg = chain_cfg(33, 9, 2, vary=True)
     B, N, A, K, T = 4, 33, 9, 6, 7
-    start = _start(cfg, B, 2)
-    e1, e2 = _envs(cfg, B, torch.float32, start)
+    begin = start(cfg, B, 2)
+    e1, e2 = twins(cfg, B, torch.float32, begin)
     tr = torch.as_tensor(_trace(np.random.default_rng(4), cfg.highway_length, (B, T, N)), device=DEV)
     pol = SpsPolicy(B, N, A, device=DEV, seed=3)
     a = pol.prev_action.clone()
@@ -736,10 +643,10 @@ def test_one_slot_closed_loop_call_is_refused_and_the_driver_takes_the_launch_wh
 
 
 def test_argument_errors_and_the_null_block():
-    cfg = _cfg(33, 9, 2)
+    cfg = chain_cfg(33, 9, 2)
     B, N, K = 2, 33, 3
-    start = _start(cfg, B, 1)
-    env, twin = _envs(cfg, B, torch.float32, start)
+    begin = start(cfg, B, 1)
+    env, twin = twins(cfg, B, torch.float32, begin)
     seq = torch.stack([env.sample(k) for k in range(K)])
     o = dict(dtype=torch.float32, device=DEV)
     out, rew = torch.empty((K, B, N), **o), torch.empty((B, N), **o)
@@ -804,9 +711,9 @@ def test_argument_errors_and_the_null_block():
 @pytest.mark.parametrize("per_env", [False, True])
 def test_candidate_search_with_recorded_positions_equals_the_candidates_one_by_one(per_env):
     C, B, K, N, A, T = 3, 4, 4, 33, 9, 6
-    cfg = _cfg(N, A, 2)
-    start = _start(cfg, B, 12)
-    env, = _envs(cfg, B, torch.float32, start, n=1)
+    cfg = chain_cfg(N, A, 2)
+    begin = start(cfg, B, 12)
+    env, = twins(cfg, B, torch.float32, begin, n=1)
     for w in range(3):
         env.step(env.sample(w), w)
     tr = torch.as_tensor(_trace(np.random.default_rng(4), cfg.highway_length, ((B,) if per_env else ()) + (T, N)), device=DEV)

@@ -7,103 +7,22 @@ import torch
 
 from diral_amd.config import (KERNEL_PACKED, KERNEL_POLICY, KERNEL_RICH, KERNEL_WIDE, STEP_MY_STEP_CH, ERR_UNSUPPORTED,
                               bench_config)
+from tests.kslots_harness import closed_loop_twins, compare_closed_loop
 
 pytestmark = pytest.mark.gpu
 
 
-def _pair(cfg, B, dt, K, t0, *, want_obs=True, want_chobs=False, keep=0.8, vary=False, vel_seed=0, clock=False, pen=False,
-          x0=None, reps=2, prep=None, form=None, monkeypatch=None):
-    """Runs the same slots on two envs: K one-slot calls (side 0) and one K-slot launch (side 1), `reps` times, then one
-    one-slot call on both sides.  Returns the two sides' (env, policy, per-launch outputs, penalty tensors)."""
-    from diral_amd.rollout import SlotClock
-    from diral_amd.sps import SpsPolicy
-    from diral_amd.vec_env import VecV2VEnv
-    if form is not None:
-        monkeypatch.setenv("DIRAL_TABLE_FORM", form)
-    N, A = cfg.num_users, cfg.num_channels
-    runs = []
-    for fused_k in (False, True):
-        env = VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=dt)
-        if x0 is not None:
-            env.reset_topology(x0, None, np.full(x0.shape, 1.7))
-        else:
-            env.reset_topology(seed=21)
-        pol = SpsPolicy(B, N, A, device="cuda:0", seed=3)
-        pol.keep_prob = keep
-        if prep is not None:
-            prep(env, pol)
-        clk = SlotClock("cuda:0", 0) if clock else None
-        if clk is not None:
-            env.set_clock(clk.t)
-        pn = None
-        if pen:
-            pn = (2, -10.0, torch.zeros((B, N), dtype=torch.int32, device="cuda:0"),
-                  torch.full((B, N), -1, dtype=torch.int32, device="cuda:0"))
-        a = pol.prev_action.clone()
-        nxt = torch.empty_like(a)
-        t = 0
-
-        def one(sh=None, sr=None, co=None):
-            nonlocal a, nxt, t
-            env.step_policy(a, 0 if clk is not None else t, pol, nxt, shaped_out=sh, sum_r_out=sr, collision_out=co,
-                            clock=clk, seed_offset=0, want_chobs=want_chobs, want_obs=want_obs,
-                            stuck_penalty=pn if sh is not None else None)
-            assert env.last_kernel() & KERNEL_POLICY == 0
-            if vary and t % cfg.episode_interval == cfg.episode_interval - 1:
-                env.update_velocity(seed=vel_seed + t // cfg.episode_interval)
-            if clk is not None:
-                env.lib.diral_clock_add(clk.ptr(), 1, env._stream())
-            a, nxt = nxt, a
-            t += 1
-        sh0 = torch.zeros((B, N), dtype=dt, device="cuda:0")
-        for _ in range(t0):                                       # warm-up, one slot per call on both sides
-            one(sh0 if pen else None)
-        outs = []
-        for rep in range(reps):
-            sh = torch.zeros((K, B, N), dtype=dt, device="cuda:0")
-            sr = torch.zeros((K, B), dtype=dt, device="cuda:0")
-            co = torch.zeros((K, B), dtype=dt, device="cuda:0")
-            if fused_k:
-                env.step_policy(a, 0 if clk is not None else t, pol, nxt, shaped_out=sh, sum_r_out=sr, collision_out=co,
-                                slots=K, vel_seed=vel_seed, clock=clk, seed_offset=0, want_chobs=want_chobs,
-                                want_obs=want_obs, stuck_penalty=pn)
-                lk = env.last_kernel()
-                assert lk & (15 | KERNEL_POLICY | KERNEL_RICH) == KERNEL_WIDE | KERNEL_POLICY | KERNEL_RICH, lk
-                if clk is not None:
-                    env.lib.diral_clock_add(clk.ptr(), K, env._stream())
-                a, nxt = nxt, a
-                t += K
-            else:
-                for k in range(K):
-                    one(sh[k], sr[k], co[k])
-            outs.append(dict(shaped=sh, sum_r=sr, coll=co, obs=env._obs.clone() if want_obs else None, rew=env._rew.clone(),
-                             done=env._done.clone(), actions=a.clone(), chobs=env._chobs.clone() if want_chobs else None))
-        one()                                                     # a one-slot call behind the K-slot ones
-        torch.cuda.synchronize()
-        runs.append((env, pol, outs, pn, a.clone()))
-    return runs
+def _is_wide_slots_kernel(lk):
+    return lk & (15 | KERNEL_POLICY | KERNEL_RICH) == KERNEL_WIDE | KERNEL_POLICY | KERNEL_RICH
 
 
-def _compare(runs, want_obs=True, want_chobs=False):
-    (e1, p1, o1, pn1, a1), (e2, p2, o2, pn2, a2) = runs
-    for rep in range(len(o1)):
-        for k in ("shaped", "sum_r", "coll", "rew", "done", "actions"):
-            assert torch.equal(o1[rep][k], o2[rep][k]), (rep, k, (o1[rep][k] != o2[rep][k]).nonzero()[:4])
-        if want_obs:
-            assert torch.equal(o1[rep]["obs"], o2[rep]["obs"]), (rep, (o1[rep]["obs"] != o2[rep]["obs"]).nonzero()[:4])
-        if want_chobs:
-            assert torch.equal(o1[rep]["chobs"], o2[rep]["chobs"]), rep
-    assert torch.equal(a1, a2) and torch.equal(e1._rew, e2._rew)
-    assert torch.equal(p1.prev_action, p2.prev_action) and torch.equal(p1.counter, p2.counter)
-    sa, sb = e1.export_state(), e2.export_state()
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), k
-    assert torch.equal(e1.metrics(), e2.metrics())
-    if pn1 is not None:
-        assert torch.equal(pn1[2], pn2[2]) and torch.equal(pn1[3], pn2[3])
-    e1.check()
-    e2.check()
-    return sa
+def _wide_twins(cfg, B, dt, K, t0, *, x0=None, **kw):
+    """tests/kslots_harness.closed_loop_twins as this file runs it: a one-slot call behind the launches, three launches
+    behind every one-slot call."""
+    topo = 21 if x0 is None else (x0, None, np.full(x0.shape, 1.7))
+    kw.setdefault("keep", 0.8)
+    return closed_loop_twins(cfg, B, dt, K, t0, topo=topo, pol_seed=3, tail_slot=True,
+                             expect_one=lambda lk: lk & KERNEL_POLICY == 0, expect_fused=_is_wide_slots_kernel, **kw)
 
 
 @pytest.mark.parametrize("N,A,form,dt,K,want_obs", [
@@ -126,10 +45,11 @@ def test_wide_k_slots_equal_k_one_slot_calls(N, A, form, dt, K, want_obs, monkey
     observation, the next actions, the policy state, the exported tables, positions, velocities and the metrics."""
     cfg = bench_config(N, A, 10.0 * N + 400, reward_design=2)
     B = 24
-    runs = _pair(cfg, B, dt, K, 5, want_obs=want_obs, want_chobs=True, form=form, monkeypatch=monkeypatch)
-    packed = runs[1][0].last_kernel() & KERNEL_PACKED
+    monkeypatch.setenv("DIRAL_TABLE_FORM", form)
+    runs = _wide_twins(cfg, B, dt, K, 5, want_obs=want_obs, want_chobs=True)
+    packed = runs[1].env.last_kernel() & KERNEL_PACKED
     assert bool(packed) == (form == "packed")
-    _compare(runs, want_obs=want_obs, want_chobs=True)
+    compare_closed_loop(runs, want_obs=want_obs, want_chobs=True)
 
 
 @pytest.mark.parametrize("N", [128, 256])
@@ -150,17 +70,17 @@ def test_wide_k_slots_on_the_other_code_paths_of_the_slot_loop(case, N):
     elif case == "sorted_distances":
         kw = dict(State=dict(add_positional_dist=True))
     cfg = bench_config(N, A, 10.0 * N + 400, reward_design=2, mobility_vary=vary, **kw)
-    runs = _pair(cfg, B, dt, K, t0, want_chobs=case == "rich_vel", keep=0.95 if case in ("stuck_penalty", "prop_fair") else 0.8,
-                 vary=vary, vel_seed=4242, clock=case == "slot_clock", pen=case == "stuck_penalty")
-    sa = _compare(runs, want_chobs=case == "rich_vel")
+    runs = _wide_twins(cfg, B, dt, K, t0, want_chobs=case == "rich_vel", keep=0.95 if case in ("stuck_penalty", "prop_fair") else 0.8,
+                       vel_seed=4242, clock=case == "slot_clock", pen=case == "stuck_penalty")
+    sa = compare_closed_loop(runs, want_chobs=case == "rich_vel")
     if vary:
         assert not torch.equal(sa["vel"], torch.full_like(sa["vel"], 1.7))
     if case == "rich_vel":
-        o = runs[1][2]
+        o = runs[1].outs
         vcol = cfg.state_space - 1                                # add_velocity: the last column
         assert not torch.equal(o[0]["obs"][:, :, vcol], torch.full_like(o[0]["obs"][:, :, vcol], 1.7))
     if case == "stuck_penalty":
-        assert int(runs[1][3][2].max()) > 2
+        assert int(runs[1].pen[2].max()) > 2
 
 
 def test_wide_k_slots_when_every_agent_reselects():
@@ -171,8 +91,8 @@ def test_wide_k_slots_when_every_agent_reselects():
 
     def prep(env, pol):
         pol.counter.zero_()
-    runs = _pair(cfg, 8, torch.float64, 6, 0, keep=0.0, want_chobs=True, prep=prep)
-    _compare(runs, want_chobs=True)
+    runs = _wide_twins(cfg, 8, torch.float64, 6, 0, keep=0.0, want_chobs=True, prep=prep)
+    compare_closed_loop(runs, want_chobs=True)
 
 
 def test_wide_k_slots_on_a_highway_that_breaks_apart(monkeypatch):
@@ -183,9 +103,9 @@ def test_wide_k_slots_on_a_highway_that_breaks_apart(monkeypatch):
     rng = np.random.default_rng(N + A)
     x0 = rng.integers(0, int(L), size=(B, N)).astype(np.float64)
     x0[0] = np.concatenate([rng.integers(0, 1200, size=N // 2), rng.integers(2400, 3600, size=N - N // 2)])
-    runs = _pair(cfg, B, torch.float64, 25, 100, keep=0.9, vary=True, vel_seed=99, x0=x0, reps=8, form="packed",
-                 monkeypatch=monkeypatch)
-    sa = _compare(runs)
+    monkeypatch.setenv("DIRAL_TABLE_FORM", "packed")
+    runs = _wide_twins(cfg, B, torch.float64, 25, 100, keep=0.9, vel_seed=99, x0=x0, reps=8)
+    sa = compare_closed_loop(runs)
     seq = sa["seq"]
     own = torch.diagonal(seq, dim1=1, dim2=2).unsqueeze(1)
     assert bool(((own - seq >= 8) & (seq > 0)).any()), "no entry fell beyond the codes"

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-import tests.test_gpu_parity as tp
+import tests.gpu_util as gu
 from diral_amd.config import (KERNEL_LARGE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config, c2_config)
 from tests.golden_util import golden_names, horizon_tables
 
@@ -21,18 +21,18 @@ pytestmark = pytest.mark.gpu
 @pytest.fixture
 def large_path(monkeypatch):
     """make_env of the parity tests hands out handles pinned to the large path."""
-    plain = tp.make_env
+    plain = gu.make_env
 
     def make(cfg, B, mode=STEP_MY_STEP, dtype=torch.float64):
         env = plain(cfg, B, mode, dtype)
         env.force_large_path()
         return env
-    monkeypatch.setattr(tp, "make_env", make)
+    monkeypatch.setattr(gu, "make_env", make)
 
 
 @pytest.mark.parametrize("name", golden_names())
 def test_golden_replay_on_the_large_path(name, large_path):
-    tp.test_golden_replay_on_gpu(name)
+    gu.golden_replay_on_gpu(name)
 
 
 @pytest.mark.parametrize("mode,rd", [(STEP_MY_STEP, 1), (STEP_MY_STEP, 2), (STEP_MY_STEP, 3), (STEP_MY_STEP, 5),
@@ -41,12 +41,12 @@ def test_c2_shapes_on_the_large_path(mode, rd):
     """64 vehicles / 32 resources, rich State flags, sticky actions, PRR tracking: against the oracle."""
     cfg = c2_config(reward_design=rd, State=dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=True,
                                                   add_position=True))
-    tp.random_rollout(cfg, B=12, T=30, seed=900 + rd + 10 * mode, mode=mode, sticky=0.7, track_prr=(mode == STEP_MY_STEP),
+    gu.random_rollout(cfg, B=12, T=30, seed=900 + rd + 10 * mode, mode=mode, sticky=0.7, track_prr=(mode == STEP_MY_STEP),
                       path="large", expect_kernel=KERNEL_LARGE)
 
 
 def test_c5_shapes_with_velocity_updates_on_the_large_path():
-    tp.random_rollout(bench_config(128, 64, 4000.0, mobility_vary=True, proportional_fair=True), B=6, T=55, seed=907,
+    gu.random_rollout(bench_config(128, 64, 4000.0, mobility_vary=True, proportional_fair=True), B=6, T=55, seed=907,
                       vel_every=25, sticky=0.9, path="large", expect_kernel=KERNEL_LARGE)
 
 
@@ -69,28 +69,28 @@ def test_sizes_only_the_large_path_runs(N, A, K, L, rc, mode, kw):
     cfg = bench_config(N, A, L, communication_range=rc,
                        State=dict(num_bins=K, add_channel_obs=True, add_reward=True, add_index=True, add_position=True), **kw)
     T = 8 if N >= 700 else 14
-    tp.random_rollout(cfg, B=2 if N >= 700 else 3, T=T, seed=1000 + N + A, mode=mode, sticky=0.5,
+    gu.random_rollout(cfg, B=2 if N >= 700 else 3, T=T, seed=1000 + N + A, mode=mode, sticky=0.5,
                       track_prr=(mode == STEP_MY_STEP), expect_kernel=KERNEL_LARGE)
 
 
 def test_lanes_off_the_line_and_velocity_updates_at_400_vehicles():
     cfg = bench_config(400, 50, 6000.0, mobility_vary=True, State=dict(add_velocity=True, add_position=True))
-    tp.random_rollout(cfg, B=2, T=30, seed=1400, vel_every=25, y0=_lanes, expect_kernel=KERNEL_LARGE)
+    gu.random_rollout(cfg, B=2, T=30, seed=1400, vel_every=25, y0=_lanes, expect_kernel=KERNEL_LARGE)
 
 
 def test_secondary_observation_modes_at_300_vehicles():
     """add_positional_dist (sorted true distances) and the type-1 histogram beyond 256 vehicles: posdist_kernel.hpp's
     flat ranking and its literal statement."""
     cfg = bench_config(300, 16, 5000.0, State=dict(add_positional_dist=True, add_positional_dist_type=1, num_bins=12))
-    tp.random_rollout(cfg, B=2, T=8, seed=1500, expect_kernel=KERNEL_LARGE)
+    gu.random_rollout(cfg, B=2, T=8, seed=1500, expect_kernel=KERNEL_LARGE)
     cfg = bench_config(300, 16, 5000.0, State=dict(add_positional_dist=True))
-    tp.random_rollout(cfg, B=2, T=8, seed=1501, y0=_lanes, expect_kernel=KERNEL_LARGE)
+    gu.random_rollout(cfg, B=2, T=8, seed=1501, y0=_lanes, expect_kernel=KERNEL_LARGE)
 
 
 def test_2048_vehicles_two_slots():
     """The table column of 2048 viewers in one wave's LDS (two columns per workgroup)."""
     cfg = bench_config(2048, 128, 30000.0)
-    tp.random_rollout(cfg, B=1, T=3, seed=1600, expect_kernel=KERNEL_LARGE)
+    gu.random_rollout(cfg, B=1, T=3, seed=1600, expect_kernel=KERNEL_LARGE)
 
 
 def test_limits_of_the_large_path():
@@ -126,7 +126,7 @@ def test_entries_a_million_stamps_old_take_the_64_bit_merge(N, A, L):
     tab = horizon_tables(rng, B, N, L, T0)
     pos_x, vel, seq, age, x = (tab[k] for k in ("pos_x", "vel", "seq", "age", "x"))
     assert ((seq > 0) & (T0 - seq >= 1 << 20)).any(axis=1).mean() > 0.5     # most columns hold entries beyond the 20-bit rank
-    env = tp.make_env(cfg, B)
+    env = gu.make_env(cfg, B)
     env.force_large_path()
     env.reset_topology(pos_x, 0.0, vel)
     env.import_state(pos_x, np.zeros((B, N)), vel, seq=seq, age=age, x=x)
@@ -135,7 +135,7 @@ def test_entries_a_million_stamps_old_take_the_64_bit_merge(N, A, L):
     orc.import_state(seq=seq, age=age, x=x, y=np.zeros((B, N, N)))
     for t in range(6):
         acts = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        obs, rew, chobs, _ = tp.gpu_step(env, STEP_MY_STEP, acts, t)
+        obs, rew, chobs, _ = gu.gpu_step(env, STEP_MY_STEP, acts, t)
         assert env.last_kernel() == KERNEL_LARGE
         o_rew, o_chobs = orc.step(STEP_MY_STEP, acts, t)
         assert np.array_equal(rew, o_rew) and np.array_equal(chobs, o_chobs)
@@ -193,12 +193,12 @@ def test_random_configuration_on_the_large_path(i):
     State blocks without piggybacked tables, both secondary observation modes, proportional fairness - with the handle
     pinned to the three-launch form: against the oracle, PRR metrics tracked on odd draws."""
     from diral_amd.config import ConfigError
-    from tests.test_gpu_fuzz import draw_case
+    from tests.gpu_util import draw_case
     cfg, mode, sticky, vel_every = draw_case(i)
     if not (cfg.mobility or cfg.enable_design_topology):
         cfg = cfg.replace(enable_design_topology=True)
     cfg.validate()
-    tp.random_rollout(cfg, B=3 if cfg.num_users > 64 else 8, T=20, seed=300 + i, mode=mode, sticky=sticky,
+    gu.random_rollout(cfg, B=3 if cfg.num_users > 64 else 8, T=20, seed=300 + i, mode=mode, sticky=sticky,
                       vel_every=vel_every or None, threads=8, track_prr=bool(i & 1), path="large", expect_kernel=KERNEL_LARGE)
 
 
@@ -228,7 +228,7 @@ def draw_large_case(i):
 def test_random_configuration_beyond_256_vehicles(i):
     cfg, mode, sticky, vel_every = draw_large_case(i)
     cfg.validate()
-    tp.random_rollout(cfg, B=2, T=11, seed=700 + i, mode=mode, sticky=sticky, vel_every=vel_every or None, threads=8,
+    gu.random_rollout(cfg, B=2, T=11, seed=700 + i, mode=mode, sticky=sticky, vel_every=vel_every or None, threads=8,
                       track_prr=bool(i & 1), expect_kernel=KERNEL_LARGE)
 
 
@@ -239,4 +239,4 @@ def test_piggybacking_beyond_256_vehicles(N, A, L):
     three-launch step, against the oracle (which replays np.insert on real arrays)."""
     cfg = bench_config(N, A, L, communication_range=L + 1.0, State=dict(piggybacking=True, add_channel_obs=True, add_reward=True))
     assert cfg.chobs_width == A * A
-    tp.random_rollout(cfg, B=2, T=6, seed=2000 + N, sticky=0.3, expect_kernel=KERNEL_LARGE)
+    gu.random_rollout(cfg, B=2, T=6, seed=2000 + N, sticky=0.3, expect_kernel=KERNEL_LARGE)

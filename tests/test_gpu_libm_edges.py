@@ -33,7 +33,7 @@ import torch
 from diral_amd.config import (KERNEL_CH, KERNEL_FAST64, KERNEL_GENERAL, KERNEL_LARGE, KERNEL_PACKED, KERNEL_POLICY, KERNEL_RICH,
                               KERNEL_WIDE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config)
 from tests import libm_cases as C
-from tests.test_gpu_parity import make_env
+from tests.gpu_util import make_env
 
 ORACLE_EXP_ULPS, HOST_LOG10_ULPS = C.ORACLE_EXP_ULPS, C.HOST_LOG10_ULPS
 

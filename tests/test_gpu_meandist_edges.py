@@ -22,7 +22,7 @@ import torch
 from diral_amd.config import (KERNEL_CH, KERNEL_FAST64, KERNEL_GENERAL, KERNEL_LARGE, KERNEL_PACKED, KERNEL_POLICY, KERNEL_RICH,
                               KERNEL_WIDE, STEP_DESIGN)
 from tests import meandist_cases as C
-from tests.test_gpu_parity import make_env
+from tests.gpu_util import make_env
 
 pytestmark = pytest.mark.gpu
 

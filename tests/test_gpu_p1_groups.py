@@ -22,7 +22,8 @@ import pytest
 import torch
 
 from diral_amd.config import KERNEL_FAST64, KERNEL_POLICY, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config
-from tests.test_gpu_parity import make_env
+from tests.gpu_util import make_env
+from tests.kslots_harness import check_rollout, closed_loop_twins, compare_closed_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -157,63 +158,20 @@ def test_rich_state_with_per_resource_rewards_vs_oracle(A):
 @pytest.mark.parametrize("A", A_VALUES)
 def test_step_policy_of_five_slots_equals_five_one_slot_calls(A):
     """The K-slot compilation of the same text (step_fast64_slots_kernel), the SPS agents reading the staged rows."""
-    from diral_amd.sps import SpsPolicy
-    from diral_amd.vec_env import VecV2VEnv
     N, K = _n_for(A), 5
-    cfg = _cfg(N, A, "my_step")
     x0, v0 = _topology(np.random.default_rng(77 + A), N)
-    runs = []
-    for fused_k in (False, True):
-        env = VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=torch.float32)
-        env.reset_topology(x0, 0.0, v0)
-        pol = SpsPolicy(B, N, A, device="cuda:0", seed=5)
-        pol.keep_prob = 0.7
-        a = pol.prev_action.clone()
-        nxt = torch.empty_like(a)
-        t, outs = 0, []
-        for _ in range(3):                                                   # one slot per launch on both sides first
-            env.step_policy(a, t, pol, nxt)
-            a, nxt = nxt, a
-            t += 1
-        for rep in range(2):
-            sh = torch.zeros((K, B, N), dtype=torch.float32, device="cuda:0")
-            sr = torch.zeros((K, B), dtype=torch.float32, device="cuda:0")
-            co = torch.zeros((K, B), dtype=torch.float32, device="cuda:0")
-            if fused_k:
-                env.step_policy(a, t, pol, nxt, shaped_out=sh, sum_r_out=sr, collision_out=co, slots=K)
-                lk = env.last_kernel()
-                assert (lk & 15) == KERNEL_FAST64 and (lk & KERNEL_POLICY), lk
-                a, nxt = nxt, a
-                t += K
-            else:
-                for k in range(K):
-                    env.step_policy(a, t, pol, nxt, shaped_out=sh[k], sum_r_out=sr[k], collision_out=co[k])
-                    a, nxt = nxt, a
-                    t += 1
-            outs.append((sh, sr, co, env._obs.clone(), env._rew.clone(), env._done.clone(), a.clone()))
-        torch.cuda.synchronize()
-        runs.append((env, pol, outs))
-    (e1, p1, o1), (e2, p2, o2) = runs
-    for rep in range(2):
-        for i, name in enumerate(("shaped", "sum_r", "collisions", "state", "reward", "done", "actions")):
-            assert torch.equal(o1[rep][i], o2[rep][i]), (N, A, rep, name)
-    assert torch.equal(p1.prev_action, p2.prev_action) and torch.equal(p1.counter, p2.counter)
-    sa, sb = e1.export_state(), e2.export_state()
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), (N, A, k)
-    assert torch.equal(e1.metrics(), e2.metrics())
-    e1.check()
-    e2.check()
+    runs = closed_loop_twins(_cfg(N, A, "my_step"), B, torch.float32, K, 3, topo=(x0, 0.0, v0), pol_seed=5, keep=0.7,
+                             expect_fused=lambda lk: (lk & 15) == KERNEL_FAST64 and bool(lk & KERNEL_POLICY))
+    compare_closed_loop(runs)
 
 
 @pytest.mark.parametrize("A", A_VALUES)
 def test_rollout_of_five_slots_equals_five_one_slot_calls(A):
     """`rollout(K = 5)` with every slot's state against the loop of step + shaping calls on a twin env."""
-    from tests.test_gpu_rollout import _check
     N = _n_for(A)
     x0, _ = _topology(np.random.default_rng(99 + A), N)
-    _, _, env = _check(_cfg(N, A, "my_step"), B, torch.float32 if A % 2 else torch.float64, 5, states="all", warm=3, x0=x0)
-    # (`_check` asserts the family and the policy bit behind each of its launches; once more here, on a launch of this
+    _, _, env = check_rollout(_cfg(N, A, "my_step"), B, torch.float32 if A % 2 else torch.float64, 5, states="all", warm=3, x0=x0)
+    # (`check_rollout` asserts the family and the policy bit behind each of its launches; once more here, on a launch of this
     # file's own, so that a fallback to one-slot launches cannot pass unseen)
     seq = torch.stack([env.sample(300 + k) for k in range(5)])
     got = env.rollout(seq, env.t, states="all")

@@ -15,223 +15,20 @@ import torch
 
 from diral_amd.config import (EnvConfig, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config,
                               c2_config)
-from tests.golden_util import Golden, golden_names, out_sha, ulp_diff
+from tests.golden_util import EXP_ATOL, Golden, golden_names, out_sha, ulp_diff
+from tests.gpu_util import (DIST_ULP, assert_moves_match_reference, exp_close, golden_replay_on_gpu,
+                            gpu_step, make_env, random_rollout, uses_exp)
+from tests.kslots_harness import closed_loop_twins, compare_closed_loop
 
 pytestmark = pytest.mark.gpu
 
-EXP_ATOL = 2e-15   # device exp() vs glibc exp(): <= 1-2 ulp of exp(x) <= e; the rewards built
-                   # from it (1-exp(1-R), test_env.py:414) cancel, so the bound is absolute
-DIST_ULP = 1       # sqrt(x*x+y*y) vs sqrt(pow(x,2)+pow(y,2))
-
 UNBUILT = set()
-
-
-def make_env(cfg, B, mode=STEP_MY_STEP, dtype=torch.float64):
-    from diral_amd.vec_env import VecV2VEnv
-    return VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=dtype, step_mode=mode)
-
-
-def gpu_step(env, mode, acts, t, ep=0.0, eps=1.0):
-    a = env._actions(np.asarray(acts))
-    obs, rew, done = env._step(mode, a, t, ep, eps, want_chobs=True)
-    torch.cuda.synchronize()
-    return obs.cpu().numpy().copy(), rew.cpu().numpy().copy(), env._chobs.cpu().numpy().copy(), \
-        done.cpu().numpy().copy()
-
-
-def uses_exp(cfg, mode):
-    return cfg.reward_design in (3, 4)
-
-
-def exp_close(a, b):
-    return bool(np.all(np.abs(np.asarray(a) - np.asarray(b)) <= EXP_ATOL))
-
-
-def assert_slot_matches_reference(g, i, mode, rew, chobs, obs):
-    """One env's outputs of slot i against what the reference recorded (tests/golden/*.npz): rewards exact (exp()
-    designs within EXP_ATOL), distances within DIST_ULP, the type-2 histogram bins exact.  A thinned fixture
-    (gen_golden.py `record_every`) holds the arrays at some slots and a hash at every slot: the hash is compared
-    wherever this bar is "exact", so a slot without arrays still pins its rewards."""
-    cfg, name = g.cfg, g.name
-    ref_rew, ref_chobs, ref_state = g.out("rews", i), g.out("chobs", i), g.out("state", i)
-    if not uses_exp(cfg, mode) and g.kept is not None:
-        assert out_sha(rew) == g.out_sha("rews", i), (name, i)
-    if ref_rew is None:
-        return
-    assert exp_close(rew, ref_rew) if uses_exp(cfg, mode) else np.array_equal(rew, ref_rew), (name, i)
-    assert ulp_diff(chobs, ref_chobs) <= DIST_ULP, (name, i)
-    assert ulp_diff(obs, ref_state) <= DIST_ULP or (cfg.State.add_reward and exp_close(obs, ref_state)), (name, i)
-    if cfg.State.add_positional_dist_piggy:
-        K = cfg.State.num_bins
-        off = (cfg.num_channels if cfg.State.action_index == "binary" else 1) if cfg.State.add_action else 0
-        off += cfg.chobs_width if cfg.State.add_channel_obs else 0
-        off += cfg.num_users - 1 if cfg.State.add_positional_dist else 0
-        if cfg.State.add_positional_dist_type == 2:
-            assert np.array_equal(obs[:, off:off + K], ref_state[:, off:off + K]), "histogram bins"
-
-
-def assert_moves_match_reference(g, i, pos_x, vel, ia):
-    """Positions, speeds and the information-age histogram after slot i: exact (by hash where a thinned fixture
-    dropped the arrays)."""
-    for key, got in (("pos_x", pos_x), ("vel", vel), ("ia", ia)):
-        ref = g.out(key, i)
-        if ref is None:
-            assert out_sha(got) == g.out_sha(key, i), (g.name, key, i)
-        else:
-            assert np.array_equal(got, ref), (g.name, key, i)
 
 
 @pytest.mark.parametrize("name", [n for n in golden_names() if n not in UNBUILT])
 def test_golden_replay_on_gpu(name):
     """Every reference fixture replayed through libdiral_env.so (B=3 replicas)."""
-    from oracle.oracle import Oracle, SQ_IEEE
-    g = Golden(name)
-    B = 3
-    env = make_env(g.cfg, B)
-    env.reset_topology(g["x0"], g["y0"], g["v0"])
-    orc = Oracle(g.cfg, batch=1, sq_mode=SQ_IEEE)
-    orc.reset(g["x0"], g["y0"], g["v0"])
-    ck = g.table_checkpoints()
-    S = env.S
-    cfg = g.cfg
-    for i, mode, acts, t, (ep, eps) in g.steps():
-        obs, rew, chobs, done = gpu_step(env, mode, acts, t, ep, eps)
-        o_rew, o_chobs = orc.step(mode, acts, t)
-        o_state = orc.obtain_state(acts, o_chobs, o_rew, ep, eps)
-        for b in range(B):
-            # --- vs the oracle (IEEE squares): bit-exact except exp() rewards
-            if uses_exp(cfg, mode):
-                assert exp_close(rew[b], o_rew[0]), (name, i)
-            else:
-                assert np.array_equal(rew[b], o_rew[0]), (name, i, rew[b], o_rew[0])
-            assert np.array_equal(chobs[b], o_chobs[0]), (name, i)
-            if cfg.State.add_reward and uses_exp(cfg, mode):
-                assert exp_close(obs[b], o_state[0])
-            else:
-                assert np.array_equal(obs[b], o_state[0]), (name, i, np.argwhere(obs[b] != o_state[0])[:5])
-            # --- vs the reference fixture
-            assert_slot_matches_reference(g, i, mode, rew[b], chobs[b], obs[b])
-            assert done[b] == ((t % cfg.episode_interval) == cfg.episode_interval - 1)
-        if i in g.vel_updates:
-            env.update_velocity(g.vel_updates[i])
-            orc.update_velocity(g.vel_updates[i])
-        if g.trace is not None and i == g.trace_after:
-            env.load_saved_positions(g.trace)
-            orc.set_trace(g.trace)
-        ia = env.info_age(t).cpu().numpy()
-        st = {k: v.cpu().numpy() for k, v in env.export_state().items()}
-        oe = orc.export()
-        for b in range(B):
-            assert_moves_match_reference(g, i, st["pos_x"][b], st["vel"][b], ia[b])
-            assert np.array_equal(st["seq"][b], oe["seq"][0]), (name, i)
-            assert np.array_equal(st["age"][b], np.minimum(oe["age"][0], 255)), (name, i)
-            assert np.array_equal(st["x"][b], oe["x"][0]), (name, i)
-            assert np.array_equal(st["y"][b], oe["y"][0]), (name, i)
-            assert np.array_equal(st["la"][b].astype(np.int64), oe["la"][0]), (name, i)
-            if i in ck:
-                j = ck[i]
-                assert np.array_equal(st["seq"][b], g["tab_seq"][j])
-                assert np.array_equal(st["age"][b], np.minimum(g["tab_age"][j], 255))
-                assert np.array_equal(st["x"][b], g["tab_x"][j])
-                assert np.array_equal(st["y"][b], g["tab_y"][j])
-                assert np.array_equal(st["la"][b], g["tab_la"][j])
-    env.check()
-    if cfg.State.piggybacking:
-        # TestEnv.prev_obs after the last slot (test_env.py:260-261): distances, within 1 ulp of the reference's pow()
-        po = env.prev_obs().cpu().numpy()
-        for b in range(B):
-            assert np.array_equal(po[b], orc.prev_obs()[0]) and ulp_diff(po[b], g["prev_obs"]) <= DIST_ULP
-        if "keyerror_actions" in g.d.files:
-            # the slot the reference left with KeyError (`self.prev_obs[None]`, test_env.py:243): the sticky device flag
-            from diral_amd.config import ERR_PIGGY_NO_TX
-            from diral_amd.vec_env import DiralError
-            gpu_step(env, STEP_MY_STEP, g["keyerror_actions"], int(g["keyerror_t"]))
-            with pytest.raises(DiralError) as ei:
-                env.check()
-            assert ei.value.status == ERR_PIGGY_NO_TX
-            env.check()                                             # reported once, then cleared
-
-
-def random_rollout(cfg, B, T, seed, mode=STEP_MY_STEP, sticky=0.0, vel_every=None, threads=8, track_prr=False,
-                   expect_kernel=None, force_general=False, path=None, y0=None):
-    """GPU vs oracle (IEEE squares) on B different random envs, T slots; returns
-    the number of compared slots.  Everything must match bit for bit (exp()
-    rewards within EXP_ATOL).  The specialised kernels serve every configuration they can
-    (`expect_kernel`: assert which family ran); `force_general` pins the run to the general
-    kernel (DIRAL_OPT_KERNEL_PATH), `path="large"` to the three launches of csrc/step_large.hpp (the only path beyond
-    256 vehicles / 256 resources / 64 bins); track_prr: PRR metrics also in my_step (a build extension); `y0`: a
-    function (rng, B, N) -> lanes (default: the one-lane highway the reference draws)."""
-    from oracle.oracle import Oracle, SQ_IEEE
-    rng = np.random.default_rng(seed)
-    N, A, L = cfg.num_users, cfg.num_channels, cfg.highway_length
-    cfg = cfg.replace(track_arrival=True, track_prr=track_prr)
-    x0 = rng.integers(0, int(L), size=(B, N)).astype(np.float64)
-    y0 = np.zeros((B, N)) if y0 is None else y0(rng, B, N)
-    v0 = np.full((B, N), 1.7) if cfg.mobility_vary else rng.uniform(1.1, 2.7, size=(B, N))
-    env = make_env(cfg, B)
-    env.force_general_kernel(force_general)
-    if path == "large":
-        env.force_large_path()
-    env.reset_topology(x0, y0, v0)
-    orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=threads)
-    orc.reset(x0, y0, v0)
-    acts = rng.integers(0, A, size=(B, N))
-    for t in range(T):
-        new = rng.integers(0, A, size=(B, N))
-        acts = np.where(rng.random((B, N)) < sticky, acts, new).astype(np.int32)
-        obs, rew, chobs, _ = gpu_step(env, mode, acts, t)
-        if expect_kernel is not None:
-            assert (env.last_kernel() & 15) == expect_kernel, env.last_kernel()
-        o_rew, o_chobs = orc.step(mode, acts, t)
-        o_state = orc.obtain_state(acts, o_chobs, o_rew)
-        if uses_exp(cfg, mode):
-            assert exp_close(rew, o_rew)
-        else:
-            assert np.array_equal(rew, o_rew), t
-        assert np.array_equal(chobs, o_chobs), t
-        if uses_exp(cfg, mode) and cfg.State.add_reward:       # the state carries the exp() reward
-            assert exp_close(obs, o_state), t
-        else:
-            assert np.array_equal(obs, o_state), (t, np.argwhere(obs != o_state)[:5])
-        if t % 6 == 4 and env.S > 0:
-            # a stand-alone obtain_state with FOREIGN arguments (test_env.py:527-583 on the current tables):
-            # diral_env_observe -> observe_kernel.hpp (the general kernel's observe mode when forced)
-            from diral_amd.config import KERNEL_GENERAL, KERNEL_LARGE, KERNEL_OBSERVE
-            fa = rng.integers(0, A, size=(B, N)).astype(np.int32)
-            fc = rng.uniform(0.0, 300.0, size=(B, N, cfg.chobs_width))
-            fr = rng.uniform(-3.0, 1.0, size=(B, N))
-            s1 = env.obtain_state(fc, fa, fr, 3.0, 0.25).cpu().numpy()
-            assert (env.last_kernel() & 15) == (KERNEL_LARGE if (path == "large" or expect_kernel == KERNEL_LARGE) else (KERNEL_GENERAL if force_general else KERNEL_OBSERVE))
-            s2 = orc.obtain_state(fa, fc, fr, 3.0, 0.25)
-            assert np.array_equal(s1, s2), (t, np.argwhere(s1 != s2)[:5])
-        if vel_every and t % vel_every == vel_every - 1:
-            draws = rng.integers(1, 4, size=(B, N)).astype(np.uint8)
-            env.update_velocity(draws)
-            orc.update_velocity(draws)
-    st = {k: v.cpu().numpy() for k, v in env.export_state().items()}
-    oe = orc.export()
-    assert np.array_equal(st["pos_x"], oe["pos_x"])
-    assert np.array_equal(st["vel"], oe["vel"])
-    assert np.array_equal(st["seq"], oe["seq"])
-    assert np.array_equal(st["age"], np.minimum(oe["age"], 255))
-    assert np.array_equal(st["x"], oe["x"])
-    assert np.array_equal(st["y"], oe["y"])
-    assert np.array_equal(st["la"].astype(np.int64), oe["la"])
-    assert np.array_equal(env.info_age(T - 1).cpu().numpy(), orc.info_age(T - 1))
-    if cfg.proportional_fair and mode == STEP_MY_STEP and sticky >= 0.9 and T >= 40:
-        assert oe["pf"].max() > 10                    # the threshold was crossed: the penalty branch ran
-    m, om = env.metrics().cpu().numpy(), orc.metrics()
-    assert np.array_equal(m[:, [0, 2, 3]], om[:, [0, 2, 3]])                # counts: exact
-    assert np.allclose(m[:, 1], om[:, 1], rtol=1e-12, atol=1e-9)            # float sums: order differs
-    if track_prr or mode == STEP_MY_STEP_CH:
-        assert np.array_equal(m[:, 5], om[:, 5])
-        assert np.allclose(m[:, 4], om[:, 4], rtol=1e-12, atol=1e-9)
-        # PRR parity (north_star: within 1e-6)
-        prr = m[:, 4] / np.maximum(m[:, 5], 1)
-        oprr = om[:, 4] / np.maximum(om[:, 5], 1)
-        assert np.max(np.abs(prr - oprr)) < 1e-6
-    env.check()
-    return T
+    golden_replay_on_gpu(name)
 
 
 def _fam(N):
@@ -2062,65 +1859,14 @@ def test_k_slots_in_one_launch_equal_k_one_slot_launches(vary, K, t0, want_obs):
     warm-up puts entries beyond the codes (keyed quads) into the tables first; two K-slot launches back to back, then a
     one-slot launch on both sides."""
     from diral_amd.config import KERNEL_POLICY
-    from diral_amd.sps import SpsPolicy
-    from diral_amd.vec_env import VecV2VEnv
     N, A, B = 64, 32, 96
     cfg = bench_config(N, A, 30.0 * N + 100, reward_design=2, mobility_vary=vary)
-    vel_seed = 777
-    runs = []
-    for fused_k in (False, True):
-        env = VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=torch.float32)
-        env.reset_topology(seed=11)
-        pol = SpsPolicy(B, N, A, device="cuda:0", seed=5)
-        pol.keep_prob = 0.9
-        a = pol.prev_action.clone()
-        nxt = torch.empty_like(a)
-        t = 0
-        for _ in range(t0):                                   # warm-up, one slot per launch on both sides
-            env.step_policy(a, t, pol, nxt)
-            if vary and t % cfg.episode_interval == cfg.episode_interval - 1:
-                env.update_velocity(seed=vel_seed + t // cfg.episode_interval)
-            a, nxt = nxt, a
-            t += 1
-        outs = []
-        for rep in range(2):
-            sh = torch.zeros((K, B, N), dtype=torch.float32, device="cuda:0")
-            sr = torch.zeros((K, B), dtype=torch.float32, device="cuda:0")
-            co = torch.zeros((K, B), dtype=torch.float32, device="cuda:0")
-            if fused_k:
-                env.step_policy(a, t, pol, nxt, shaped_out=sh, sum_r_out=sr, collision_out=co, slots=K, vel_seed=vel_seed,
-                                want_obs=want_obs)
-                assert env.last_kernel() & KERNEL_POLICY
-                a, nxt = nxt, a
-                t += K
-            else:
-                for k in range(K):
-                    env.step_policy(a, t, pol, nxt, shaped_out=sh[k], sum_r_out=sr[k], collision_out=co[k])
-                    if vary and t % cfg.episode_interval == cfg.episode_interval - 1:
-                        env.update_velocity(seed=vel_seed + t // cfg.episode_interval)
-                    a, nxt = nxt, a
-                    t += 1
-            outs.append((sh, sr, co, env._obs.clone(), env._rew.clone(), env._done.clone(), a.clone()))
-        env.step_policy(a, t, pol, nxt)                        # a one-slot launch behind the K-slot ones
-        torch.cuda.synchronize()
-        runs.append((env, pol, outs, nxt.clone()))
-    (e1, p1, o1, n1), (e2, p2, o2, n2) = runs
-    for rep in range(2):
-        for i, name in enumerate(("shaped", "sum_r", "collisions")):
-            assert torch.equal(o1[rep][i], o2[rep][i]), (rep, name)
-        if want_obs:
-            assert torch.equal(o1[rep][3], o2[rep][3]), rep
-        assert torch.equal(o1[rep][4], o2[rep][4]) and torch.equal(o1[rep][5], o2[rep][5]) and torch.equal(o1[rep][6], o2[rep][6]), rep
-    assert torch.equal(n1, n2) and torch.equal(e1._obs, e2._obs) and torch.equal(e1._rew, e2._rew)
-    assert torch.equal(p1.prev_action, p2.prev_action) and torch.equal(p1.counter, p2.counter)
-    sa, sb = e1.export_state(), e2.export_state()
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), k
-    assert torch.equal(e1.metrics(), e2.metrics())
+    runs = closed_loop_twins(cfg, B, torch.float32, K, t0, topo=11, pol_seed=5, keep=0.9, want_obs=want_obs, one_slot_obs=True,
+                             vel_seed=777, tail_slot=True, expect_fused=lambda lk: bool(lk & KERNEL_POLICY))
+    sa = compare_closed_loop(runs, want_obs=want_obs)
+    assert torch.equal(runs[0].env._obs, runs[1].env._obs)           # the one-slot launch behind them wrote its state
     if vary:
         assert not torch.equal(sa["vel"], torch.full_like(sa["vel"], 1.7))      # an episode ended inside the launches
-    e1.check()
-    e2.check()
 
 
 @pytest.mark.parametrize("case", ["rich_vel", "rich_vel_last_ends", "f64_chobs", "stuck_penalty", "prop_fair", "slot_clock",
@@ -2133,9 +1879,6 @@ def test_k_slots_in_one_launch_on_the_other_code_paths_of_the_slot_loop(case):
     proportional-fair counters, the device slot clock, and the secondary observation launch behind a K-slot step - each
     against K one-slot calls, bit for bit."""
     from diral_amd.config import KERNEL_POLICY
-    from diral_amd.rollout import SlotClock
-    from diral_amd.sps import SpsPolicy
-    from diral_amd.vec_env import VecV2VEnv
     N, A, B = 64, 32, 48
     kw, dt, K, t0, vary = {}, torch.float32, 6, 21, False
     if case in ("rich_vel", "rich_vel_last_ends"):
@@ -2149,79 +1892,19 @@ def test_k_slots_in_one_launch_on_the_other_code_paths_of_the_slot_loop(case):
     elif case == "sorted_distances":
         kw = dict(State=dict(add_positional_dist=True))
     cfg = bench_config(N, A, 30.0 * N + 100, reward_design=2, mobility_vary=vary, **kw)
-    vel_seed = 4242
     want_chobs = case in ("f64_chobs", "rich_vel")
-    runs = []
-    for fused_k in (False, True):
-        env = VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=dt)
-        env.reset_topology(seed=13)
-        pol = SpsPolicy(B, N, A, device="cuda:0", seed=9)
-        pol.keep_prob = 0.95 if case in ("stuck_penalty", "prop_fair") else 0.8
-        clock = SlotClock("cuda:0", 0) if case == "slot_clock" else None
-        if clock is not None:
-            env.set_clock(clock.t)
-        pen = None
-        if case == "stuck_penalty":
-            pen = (2, -10.0, torch.zeros((B, N), dtype=torch.int32, device="cuda:0"),
-                   torch.full((B, N), -1, dtype=torch.int32, device="cuda:0"))
-        a = pol.prev_action.clone()
-        nxt = torch.empty_like(a)
-        t = 0
-
-        def one(sh=None, sr=None, co=None):
-            nonlocal a, nxt, t
-            # (with a device clock the by-value slot number is an offset: 0)
-            env.step_policy(a, 0 if clock is not None else t, pol, nxt, shaped_out=sh, sum_r_out=sr, collision_out=co,
-                            clock=clock, seed_offset=0, want_chobs=want_chobs, stuck_penalty=pen if sh is not None else None)
-            if vary and t % cfg.episode_interval == cfg.episode_interval - 1:
-                env.update_velocity(seed=vel_seed + t // cfg.episode_interval)
-            if clock is not None:
-                env.lib.diral_clock_add(clock.ptr(), 1, env._stream())
-            a, nxt = nxt, a
-            t += 1
-        sh0 = torch.zeros((B, N), dtype=dt, device="cuda:0")
-        for _ in range(t0):
-            one(sh0 if pen else None)
-        outs = []
-        for rep in range(2):
-            sh = torch.zeros((K, B, N), dtype=dt, device="cuda:0")
-            sr = torch.zeros((K, B), dtype=dt, device="cuda:0")
-            co = torch.zeros((K, B), dtype=dt, device="cuda:0")
-            if fused_k:
-                env.step_policy(a, 0 if clock is not None else t, pol, nxt, shaped_out=sh, sum_r_out=sr, collision_out=co, slots=K,
-                                vel_seed=vel_seed, clock=clock, seed_offset=0, want_chobs=want_chobs, stuck_penalty=pen)
-                assert env.last_kernel() & KERNEL_POLICY
-                if clock is not None:
-                    env.lib.diral_clock_add(clock.ptr(), K, env._stream())
-                a, nxt = nxt, a
-                t += K
-            else:
-                for k in range(K):
-                    one(sh[k], sr[k], co[k])
-            outs.append((sh, sr, co, env._obs.clone(), env._rew.clone(), env._done.clone(), a.clone(),
-                         env._chobs.clone() if want_chobs else None))
-        torch.cuda.synchronize()
-        runs.append((env, pol, outs, pen))
-    (e1, p1, o1, pen1), (e2, p2, o2, pen2) = runs
-    for rep in range(2):
-        for i, name in enumerate(("shaped", "sum_r", "collisions", "state", "reward", "done", "actions")):
-            assert torch.equal(o1[rep][i], o2[rep][i]), (rep, name, (o1[rep][i] != o2[rep][i]).nonzero()[:4])
-        if want_chobs:
-            assert torch.equal(o1[rep][7], o2[rep][7]), rep
-    assert torch.equal(p1.prev_action, p2.prev_action) and torch.equal(p1.counter, p2.counter)
-    sa, sb = e1.export_state(), e2.export_state()
-    for k in sa:
-        assert torch.equal(sa[k], sb[k]), k
-    assert torch.equal(e1.metrics(), e2.metrics())
-    if pen1 is not None:
-        assert torch.equal(pen1[2], pen2[2]) and torch.equal(pen1[3], pen2[3]) and int(pen1[2].max()) > 2
-        assert float((o1[1][0] == -10.0 + o1[1][1][:, :, None] / N).sum()) > 0           # the penalty branch ran
+    runs = closed_loop_twins(cfg, B, dt, K, t0, topo=13, pol_seed=9, keep=0.95 if case in ("stuck_penalty", "prop_fair") else 0.8,
+                             want_chobs=want_chobs, vel_seed=4242, clock=case == "slot_clock", pen=case == "stuck_penalty",
+                             expect_fused=lambda lk: bool(lk & KERNEL_POLICY))
+    sa = compare_closed_loop(runs, want_chobs=want_chobs)
+    last = runs[0].outs[1]
+    if case == "stuck_penalty":
+        assert int(runs[0].pen[2].max()) > 2
+        assert float((last["shaped"] == -10.0 + last["sum_r"][:, :, None] / N).sum()) > 0           # the penalty branch ran
     if vary:
         vcol = cfg.state_space - 1                                                   # add_velocity: the last column
-        assert torch.equal(o1[1][3][:, :, vcol].double(), sa["vel"].to(o1[1][3].dtype).double()) or case == "rich_vel_last_ends"
+        assert torch.equal(last["obs"][:, :, vcol].double(), sa["vel"].to(last["obs"].dtype).double()) or case == "rich_vel_last_ends"
         assert not torch.equal(sa["vel"], torch.full_like(sa["vel"], 1.7))
-    e1.check()
-    e2.check()
 
 
 @pytest.mark.parametrize("N,A", [(128, 64), (100, 16)])

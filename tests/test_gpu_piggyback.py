@@ -15,7 +15,7 @@ import torch
 from diral_amd.config import (ERR_BAD_CONFIG, ERR_PIGGY_NO_TX, ERR_UNSUPPORTED, KERNEL_FAST64, KERNEL_GENERAL, KERNEL_WIDE,
                               STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config)
 from tests.golden_util import Golden
-from tests.test_gpu_parity import gpu_step, make_env, random_rollout
+from tests.gpu_util import gpu_step, make_env, random_rollout
 
 pytestmark = pytest.mark.gpu
 

@@ -18,11 +18,9 @@ import torch
 from diral_amd.config import (KERNEL_FAST64, KERNEL_GENERAL, KERNEL_LARGE, KERNEL_OBSERVE, KERNEL_PACKED, KERNEL_RING,
                               KERNEL_WIDE)
 from tests import posdist_cases as P
-from tests.test_gpu_parity import make_env
+from tests.gpu_util import make_env, ran_on, same
 
 pytestmark = pytest.mark.gpu
-
-FAMILY = {KERNEL_FAST64: "FAST64", KERNEL_WIDE: "WIDE", KERNEL_GENERAL: "GENERAL", KERNEL_LARGE: "LARGE", KERNEL_OBSERVE: "OBSERVE"}
 
 
 def step_family(N, K, off_lane):
@@ -33,16 +31,6 @@ def step_family(N, K, off_lane):
     if N <= 64:
         return KERNEL_FAST64
     return KERNEL_GENERAL if off_lane else KERNEL_WIDE
-
-
-def ran_on(env, family):
-    assert (env.last_kernel() & 15) == family, (FAMILY.get(env.last_kernel() & 15), FAMILY[family], env.last_kernel())
-
-
-def same(got, want, what, equal_nan=False):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    ok = (got == want) | (np.isnan(got) & np.isnan(want)) if equal_nan else got == want
-    assert np.array_equal(got, want, equal_nan=equal_nan), (what, int((~ok).sum()), np.argwhere(~ok)[:5], got[~ok][:5], want[~ok][:5])
 
 
 @pytest.mark.parametrize("case", P.A15_CASES, ids=P.a15_id)

@@ -1,29 +1,15 @@
 """The driver's random prefill (main_test.py:99-114: sample -> my_step_design -> obtain_state, every state kept) as ONE
 launch of K slots (`diral_env_prefill`, step_fast64_slots_kernel with PolParams::prefill) against the loop of one-slot
 calls it replaces: states, actions, tables, positions, metrics - bit for bit."""
-import numpy as np
 import pytest
 import torch
 
 from diral_amd.config import (ERR_UNSUPPORTED, KERNEL_FAST64, KERNEL_POLICY, bench_config, c2_config)
 from diral_amd.driver import DriverLoop
-from diral_amd.vec_env import DiralError, VecV2VEnv
+from diral_amd.vec_env import DiralError
+from tests.kslots_harness import RICH, assert_same_envs, start, twins
 
 pytestmark = pytest.mark.gpu
-
-RICH = dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=True, add_position=True)
-
-
-def _pair(cfg, B, dtype, seed):
-    envs = []
-    rng = np.random.default_rng(seed)
-    x0 = rng.integers(0, int(cfg.highway_length), size=(B, cfg.num_users)).astype(np.float64)
-    v0 = np.full((B, cfg.num_users), 1.7) if cfg.mobility_vary else rng.uniform(1.1, 2.7, size=(B, cfg.num_users))
-    for _ in range(2):
-        env = VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=dtype)
-        env.reset_topology(x0, 0.0, v0)
-        envs.append(env)
-    return envs
 
 
 @pytest.mark.parametrize("cfg,K,dtype", [
@@ -36,7 +22,7 @@ def _pair(cfg, B, dtype, seed):
 ])
 def test_prefill_in_one_launch_equals_the_loop_of_one_slot_calls(cfg, K, dtype):
     B, seed = 24, 77001
-    e_loop, e_one = _pair(cfg, B, dtype, 5)
+    e_loop, e_one = twins(cfg, B, dtype, start(cfg, B, 5))
     loops = [DriverLoop(e) for e in (e_loop, e_one)]
     a0 = e_loop.sample(123)
     for lp in loops:
@@ -52,10 +38,7 @@ def test_prefill_in_one_launch_equals_the_loop_of_one_slot_calls(cfg, K, dtype):
     assert torch.equal(acts, torch.stack(want_a)) and torch.equal(nxt, e_loop.sample(seed + K))
     for k in range(K):
         assert torch.equal(states[k], want_s[k]), (k, (states[k] != want_s[k]).nonzero()[:5])
-    s1, s2 = e_loop.export_state(), e_one.export_state()
-    for key in s1:
-        assert torch.equal(s1[key], s2[key]), key
-    assert torch.equal(e_loop.metrics(), e_one.metrics())
+    assert_same_envs(e_loop, e_one, entries=False)
     # ... and the envs go on alike (what the launch wrote back: tables, ring, positions)
     for t in range(3):
         a = e_loop.sample(900 + t)
@@ -68,7 +51,7 @@ def test_prefill_in_one_launch_equals_the_loop_of_one_slot_calls(cfg, K, dtype):
 def test_driver_loop_prefill_takes_the_launch_where_it_can_and_loops_elsewhere():
     for cfg, fused in ((c2_config(), True), (bench_config(128, 16, 4000.0), False),
                        (c2_config(track_arrival=True), False)):
-        e1, e2 = _pair(cfg, 6, torch.float64, 9)
+        e1, e2 = twins(cfg, 6, torch.float64, start(cfg, 6, 9))
         l1, l2 = DriverLoop(e1), DriverLoop(e2)
         a0 = e1.sample(1)
         l1.bootstrap(a0); l2.bootstrap(a0)

@@ -4,30 +4,16 @@ with PolParams::prefill) against the loop of one-slot calls it replaces: states,
 bit for bit."""
 import ctypes
 
-import numpy as np
 import pytest
 import torch
 
 from diral_amd.config import (ERR_UNSUPPORTED, KERNEL_CH, KERNEL_FAST64, KERNEL_POLICY, STEP_MY_STEP_CH, bench_config,
                               c2_config)
 from diral_amd.driver import DriverLoop
-from diral_amd.vec_env import DiralError, VecV2VEnv
+from diral_amd.vec_env import DiralError
+from tests.kslots_harness import RICH, assert_same_envs, start, twins
 
 pytestmark = pytest.mark.gpu
-
-RICH = dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=True, add_position=True)
-
-
-def _pair(cfg, B, dtype, seed):
-    envs = []
-    rng = np.random.default_rng(seed)
-    x0 = rng.integers(0, int(cfg.highway_length), size=(B, cfg.num_users)).astype(np.float64)
-    v0 = np.full((B, cfg.num_users), 1.7) if cfg.mobility_vary else rng.uniform(1.1, 2.7, size=(B, cfg.num_users))
-    for _ in range(2):
-        env = VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=dtype)
-        env.reset_topology(x0, 0.0, v0)
-        envs.append(env)
-    return envs
 
 
 @pytest.mark.parametrize("cfg,K,dtype", [
@@ -39,7 +25,7 @@ def _pair(cfg, B, dtype, seed):
 ])
 def test_ch_prefill_in_one_launch_equals_the_loop_of_one_slot_calls(cfg, K, dtype):
     B, seed = 24, 77001
-    e_loop, e_one = _pair(cfg, B, dtype, 5)
+    e_loop, e_one = twins(cfg, B, dtype, start(cfg, B, 5))
     loops = [DriverLoop(e, enable_channel=True) for e in (e_loop, e_one)]
     a0 = e_loop.sample(123)
     for lp in loops:
@@ -75,7 +61,7 @@ def test_ch_prefill_in_one_launch_equals_the_loop_of_one_slot_calls(cfg, K, dtyp
 def test_ch_driver_loop_prefill_takes_the_launch_where_it_can_and_loops_elsewhere():
     for cfg, fused in ((c2_config(), True), (bench_config(128, 16, 4000.0), False),
                        (c2_config(track_arrival=True), False)):
-        e1, e2 = _pair(cfg, 6, torch.float64, 9)
+        e1, e2 = twins(cfg, 6, torch.float64, start(cfg, 6, 9))
         l1, l2 = DriverLoop(e1, enable_channel=True), DriverLoop(e2, enable_channel=True)
         a0 = e1.sample(1)
         l1.bootstrap(a0); l2.bootstrap(a0)
@@ -95,7 +81,7 @@ def test_design_prefill_through_the_new_entry_point_equals_diral_env_prefill():
     """`prefill(mode="my_step_design")` (diral_env_prefill_mode) against `diral_env_prefill` called directly, on a rich
     case: the older symbol is a call of the new one."""
     cfg, K, B, seed = c2_config(State=RICH, enable_fingerprint=True), 12, 24, 31007
-    e_new, e_old = _pair(cfg, B, torch.float64, 5)
+    e_new, e_old = twins(cfg, B, torch.float64, start(cfg, B, 5))
     rews = []
     for e in (e_new, e_old):
         lp = DriverLoop(e)
@@ -114,8 +100,5 @@ def test_design_prefill_through_the_new_entry_point_equals_diral_env_prefill():
     assert st == 0
     torch.cuda.synchronize()
     assert torch.equal(s_new, s_old) and torch.equal(a_new, a_old) and torch.equal(n_new, n_old)
-    s1, s2 = e_new.export_state(), e_old.export_state()
-    for key in s1:
-        assert torch.equal(s1[key], s2[key]), key
-    assert torch.equal(e_new.metrics(), e_old.metrics())
+    assert_same_envs(e_new, e_old, entries=False)
     e_new.check(); e_old.check()

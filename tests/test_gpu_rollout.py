@@ -7,115 +7,13 @@ import numpy as np
 import pytest
 import torch
 
-from diral_amd.config import (ERR_BAD_ARG, ERR_BAD_CONFIG, ERR_UNSUPPORTED, KERNEL_CH, KERNEL_FAST64, KERNEL_PACKED,
-                              KERNEL_POLICY, KERNEL_WIDE, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config, c2_config)
+from diral_amd.config import (ERR_BAD_ARG, ERR_BAD_CONFIG, ERR_UNSUPPORTED, KERNEL_PACKED, KERNEL_POLICY, KERNEL_WIDE,
+                              STEP_MY_STEP, STEP_MY_STEP_CH, bench_config, c2_config)
 from diral_amd.driver import DriverLoop
 from diral_amd.vec_env import DiralError, VecV2VEnv
+from tests.kslots_harness import RICH, VEL_SEED, check_rollout, start, twins
 
 pytestmark = pytest.mark.gpu
-
-RICH = dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=True, add_position=True)
-MODES = {"my_step": STEP_MY_STEP, "my_step_ch": STEP_MY_STEP_CH}
-VEL_SEED = 4242
-
-
-def _pair(cfg, B, dtype, seed, x0=None):
-    envs = []
-    rng = np.random.default_rng(seed)
-    if x0 is None:
-        x0 = rng.integers(0, int(cfg.highway_length), size=(B, cfg.num_users)).astype(np.float64)
-    v0 = np.full((B, cfg.num_users), 1.7) if cfg.mobility_vary else rng.uniform(1.1, 2.7, size=(B, cfg.num_users))
-    for _ in range(2):
-        env = VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=dtype)
-        env.reset_topology(x0, 0.0, v0)
-        envs.append(env)
-    return envs
-
-
-def _shape(env, rew, a, flags, pen):
-    """diral_driver_shape behind one step: (shaped [B, N], sum_r [B], collision [B])."""
-    o = dict(dtype=rew.dtype, device=rew.device)
-    shaped, sum_r, coll = torch.empty((env.B, env.N), **o), torch.empty((env.B,), **o), torch.empty((env.B,), **o)
-    thr, val, cnt, prev = pen if pen is not None else (0, 0.0, None, None)
-    st = env.lib.diral_driver_shape(env.B, env.N, env.A, rew.data_ptr(), 1 if rew.dtype == torch.float64 else 0, a.data_ptr(),
-                                    None, None, None if cnt is None else cnt.data_ptr(), None if prev is None else prev.data_ptr(),
-                                    flags, int(thr), float(val), shaped.data_ptr(), sum_r.data_ptr(), coll.data_ptr(), None, None,
-                                    env._stream())
-    assert st == 0
-    return shaped, sum_r, coll
-
-
-def _loop(env, seq, t, mode, states, avg, pen):
-    """The loop the launch stands for, on `env`: the same dict VecV2VEnv.rollout returns."""
-    K = seq.shape[0]
-    ei = env.cfg.episode_interval
-    kept, shaped, sum_r, coll = [], [], [], []
-    for k in range(K):
-        a = seq[k].contiguous()
-        obs, rew, done = env._step(MODES[mode], a, t + k, want_obs=states is not None)
-        env.t = t + k + 1
-        s, sr, co = _shape(env, rew, a, (1 if avg else 0) | (4 if pen is not None else 0), pen)
-        shaped.append(s); sum_r.append(sr); coll.append(co)
-        if states == "all":
-            kept.append(obs.clone())
-        if (t + k) % ei == ei - 1:
-            env.update_velocity(seed=VEL_SEED + (t + k) // ei)
-    st = None if (states is None or env.S == 0) else (torch.stack(kept) if states == "all" else obs.clone())
-    return dict(states=st, reward=rew.clone(), done=done.clone(), shaped=torch.stack(shaped), sum_r=torch.stack(sum_r),
-                collision=torch.stack(coll))
-
-
-def _pen(B, N):
-    return (2, -10.0, torch.zeros((B, N), dtype=torch.int32, device="cuda:0"), torch.full((B, N), -1, dtype=torch.int32, device="cuda:0"))
-
-
-def _same(want, got, what):
-    for key in want:
-        if want[key] is None:
-            assert got[key] is None, (what, key)
-        else:
-            assert torch.equal(want[key], got[key]), (what, key, (want[key] != got[key]).nonzero()[:5])
-
-
-def _check(cfg, B, dtype, K, mode="my_step", states="last", t0=0, warm=0, avg=True, pen=False, constant=False, reps=2,
-           x0=None, family=KERNEL_FAST64, seed=31):
-    """`reps` launches of K slots, the second continuing the first, against the loop on a twin env; then the exported
-    state, the metrics, three further ordinary steps and env.check()."""
-    e_loop, e_one = _pair(cfg, B, dtype, seed, x0)
-    N = cfg.num_users
-    pens = [_pen(B, N) if pen else None for _ in range(2)]
-    for w in range(warm):                                            # ordinary steps on both sides first
-        a = e_loop.sample(500 + w)
-        for env in (e_loop, e_one):
-            env._step(MODES[mode], a, w)
-    t = t0
-    for rep in range(reps):
-        if constant:
-            seq = e_loop.sample(9000 + rep).unsqueeze(0).expand(K, B, N).contiguous()
-        else:
-            seq = torch.stack([e_loop.sample(7000 + 100 * rep + k) for k in range(K)])
-        want = _loop(e_loop, seq, t, mode, states, avg, pens[0])
-        got = e_one.rollout(seq, t, mode=mode, states=states, global_reward_avg=avg, stuck_penalty=pens[1], vel_seed=VEL_SEED)
-        torch.cuda.synchronize()
-        lk = e_one.last_kernel()
-        assert (lk & 15) == family and (lk & KERNEL_POLICY), lk
-        assert bool(lk & KERNEL_CH) == (mode == "my_step_ch")
-        _same(want, got, rep)
-        assert e_one.t == t + K == e_loop.t
-        t += K
-    s1, s2 = e_loop.export_state(), e_one.export_state()
-    for key in s1:
-        assert torch.equal(s1[key], s2[key]), key
-    assert torch.equal(e_loop.metrics(), e_one.metrics())
-    if pen:
-        assert torch.equal(pens[0][2], pens[1][2]) and torch.equal(pens[0][3], pens[1][3])
-    for k in range(3):
-        a = e_loop.sample(900 + k)
-        o1, r1, d1 = e_loop._step(MODES[mode], a, t + k)
-        o2, r2, d2 = e_one._step(MODES[mode], a, t + k)
-        assert torch.equal(o1, o2) and torch.equal(r1, r2) and torch.equal(d1, d2)
-    e_loop.check(); e_one.check()
-    return s2, pens[1], e_one
 
 
 @pytest.mark.parametrize("dtype,K,mode,rd,states", [
@@ -136,14 +34,14 @@ def _check(cfg, B, dtype, K, mode="my_step", states="last", t0=0, warm=0, avg=Tr
 def test_rollout_in_one_launch_equals_the_loop_of_one_slot_calls(dtype, K, mode, rd, states):
     """C2 in both dtypes, K = 1 ... 30, my_step and my_step_ch (reward_design 2, 3, 4), states last / all / none, from t = 3,
     a second launch continuing the first."""
-    _check(c2_config(reward_design=rd), 24, dtype, K, mode=mode, states=states, t0=3)
+    check_rollout(c2_config(reward_design=rd), 24, dtype, K, mode=mode, states=states, t0=3)
 
 
 @pytest.mark.parametrize("mode", ["my_step", "my_step_ch"])
 @pytest.mark.parametrize("states", ["last", "all"])
 def test_rollout_with_the_rich_state_columns_and_the_fingerprint(mode, states):
-    _check(c2_config(State=RICH, enable_fingerprint=True), 16, torch.float64, 6, mode=mode, states=states)
-    _check(c2_config(State=RICH, enable_fingerprint=True), 16, torch.float32, 5, mode=mode, states=states, avg=False)
+    check_rollout(c2_config(State=RICH, enable_fingerprint=True), 16, torch.float64, 6, mode=mode, states=states)
+    check_rollout(c2_config(State=RICH, enable_fingerprint=True), 16, torch.float32, 5, mode=mode, states=states, avg=False)
 
 
 @pytest.mark.parametrize("mode", ["my_step", "my_step_ch"])
@@ -154,14 +52,14 @@ def test_rollout_updates_the_velocities_at_episode_ends_inside_the_launch(mode, 
     every slot's state vector shows the velocities that slot started with."""
     cfg = bench_config(40, 12, 900.0, State=RICH, mobility_vary=True)
     assert cfg.episode_interval == 25
-    s, _, _ = _check(cfg, 16, torch.float32, K, mode=mode, states="all", t0=t0)
+    s, _, _ = check_rollout(cfg, 16, torch.float32, K, mode=mode, states="all", t0=t0)
     assert not torch.equal(s["vel"], torch.full_like(s["vel"], 1.7))
 
 
 @pytest.mark.parametrize("mode", ["my_step", "my_step_ch"])
 def test_rollout_on_a_sparse_highway_takes_the_keyed_quads(mode):
     cfg = bench_config(64, 8, 9000.0, communication_range=100.0)
-    s, _, _ = _check(cfg, 24, torch.float32, 25, mode=mode, states="all", warm=12)
+    s, _, _ = check_rollout(cfg, 24, torch.float32, 25, mode=mode, states="all", warm=12)
     own = torch.diagonal(s["seq"], dim1=1, dim2=2).unsqueeze(1)
     assert bool(((own - s["seq"] >= 8) & (s["seq"] > 0)).any()), "no entry fell beyond the codes"
 
@@ -169,20 +67,20 @@ def test_rollout_on_a_sparse_highway_takes_the_keyed_quads(mode):
 @pytest.mark.parametrize("N,A", [(8, 3), (33, 7)])
 @pytest.mark.parametrize("mode", ["my_step", "my_step_ch"])
 def test_rollout_with_few_vehicles(N, A, mode):
-    _check(bench_config(N, A, 30.0 * N + 200), 24, torch.float64, 6, mode=mode, states="all")
-    _check(bench_config(N, A, 30.0 * N + 200, State=RICH), 24, torch.float32, 25, mode=mode, states="last")
+    check_rollout(bench_config(N, A, 30.0 * N + 200), 24, torch.float64, 6, mode=mode, states="all")
+    check_rollout(bench_config(N, A, 30.0 * N + 200, State=RICH), 24, torch.float32, 25, mode=mode, states="last")
 
 
 @pytest.mark.parametrize("mode,avg", [("my_step", True), ("my_step", False), ("my_step_ch", True)])
 def test_rollout_stuck_action_penalty_fires_on_a_constant_sequence(mode, avg):
-    _, pen, _ = _check(c2_config(), 24, torch.float64, 6, mode=mode, states="last", avg=avg, pen=True, constant=True)
+    _, pen, _ = check_rollout(c2_config(), 24, torch.float64, 6, mode=mode, states="last", avg=avg, pen=True, constant=True)
     assert int(pen[2].max()) > 2                                      # beyond the threshold: the penalty was paid
 
 
 def test_rollout_without_shaping_flags_returns_the_reward_of_every_slot():
     """shape_flags = 0: shaped[k] is the reward as step k returns it, and a [K, N] sequence is every env's."""
     cfg = c2_config()
-    e_loop, e_one = _pair(cfg, 8, torch.float32, 3)
+    e_loop, e_one = twins(cfg, 8, torch.float32, start(cfg, 8, 3))
     seq = torch.stack([e_loop.sample(40 + k)[0] for k in range(5)])           # [K, N]
     got = e_one.rollout(seq, 0)
     for k in range(5):
@@ -203,7 +101,7 @@ def test_wide_rollout_equals_the_loop(N, A, form, dtype, K, states, monkeypatch)
     """64 < N <= 256, my_step, both table forms: step_wide_slots_kernel with the actions of every slot from the sequence."""
     monkeypatch.setenv("DIRAL_TABLE_FORM", form)
     cfg = bench_config(N, A, 10.0 * N + 400, reward_design=2, State=dict(add_reward=True, add_velocity=True), mobility_vary=True)
-    _, _, env = _check(cfg, 12, dtype, K, states=states, t0=20, family=KERNEL_WIDE, pen=(K == 6))
+    _, _, env = check_rollout(cfg, 12, dtype, K, states=states, t0=20, family=KERNEL_WIDE, pen=(K == 6))
     assert bool(env.last_kernel() & KERNEL_PACKED) == (form == "packed")
 
 
@@ -215,7 +113,7 @@ def test_wide_rollout_on_a_highway_that_breaks_apart(monkeypatch):
     rng = np.random.default_rng(N + A)
     x0 = rng.integers(0, int(L), size=(B, N)).astype(np.float64)
     x0[0] = np.concatenate([rng.integers(0, 1200, size=N // 2), rng.integers(2400, 3600, size=N - N // 2)])
-    s, _, _ = _check(cfg, B, torch.float64, 25, states="last", warm=100, x0=x0, reps=8, family=KERNEL_WIDE)
+    s, _, _ = check_rollout(cfg, B, torch.float64, 25, states="last", warm=100, x0=x0, reps=8, family=KERNEL_WIDE)
     own = torch.diagonal(s["seq"], dim1=1, dim2=2).unsqueeze(1)
     assert bool(((own - s["seq"] >= 8) & (s["seq"] > 0)).any()), "no entry fell beyond the codes"
 
@@ -303,7 +201,7 @@ def test_driver_loop_rollout_takes_the_launch_where_it_can():
     the episode ends - shaped rewards with the stuck-action penalty and the global average, every slot's state vector with
     the loop's fingerprint columns."""
     cfg = c2_config(State=RICH, enable_fingerprint=True, mobility_vary=True)
-    e1, e2 = _pair(cfg, 8, torch.float64, 11)
+    e1, e2 = twins(cfg, 8, torch.float64, start(cfg, 8, 11))
     kw = dict(global_reward_avg=True, ia_penalty_enable=True, ia_penalty_threshold=1, ia_penalty_value=-7.0)
     l1, l2 = DriverLoop(e1, **kw), DriverLoop(e2, **kw)
     K, t0 = 8, 20

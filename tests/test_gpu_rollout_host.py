@@ -14,7 +14,7 @@ import torch
 from diral_amd.config import (KERNEL_CH, KERNEL_FAST64, KERNEL_PACKED, KERNEL_POLICY, KERNEL_WIDE, STEP_MY_STEP,
                               STEP_MY_STEP_CH, bench_config, c2_config)
 from tests import host_closed_loop as H
-from tests.test_gpu_closed_loop_host import EXP_ATOL, MODE_NAME, RICH, Case, _eq, _exp_bounds, host_run, uses_exp
+from tests.host_closed_loop import EXP_ATOL, MODE_NAME, RICH, Case, _eq, _exp_bounds, host_run, uses_exp
 
 pytestmark = pytest.mark.gpu
 

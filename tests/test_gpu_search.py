@@ -12,7 +12,7 @@ from diral_amd.config import ERR_UNSUPPORTED, KERNEL_POLICY, STEP_MY_STEP, bench
 from diral_amd.search import CandidateSearch
 from diral_amd.vec_env import DiralError, driver_shape
 from tests.call_programs import FAMILIES, MODE_NAME
-from tests.test_gpu_copy_envs import dev, everything, new_env, run, slot
+from tests.gpu_util import dev, everything, new_env, run, slot
 
 pytestmark = pytest.mark.gpu
 

@@ -20,12 +20,14 @@ import numpy as np
 import pytest
 import torch
 
-import tests.test_gpu_parity as tp
-from diral_amd.config import (ERR_SEQ_OVERFLOW, KERNEL_CH, KERNEL_FAST64, KERNEL_GENERAL, KERNEL_LARGE, KERNEL_PACKED,
+import tests.gpu_util as gu
+from diral_amd.config import (KERNEL_CH, KERNEL_FAST64, KERNEL_GENERAL, KERNEL_LARGE, KERNEL_PACKED,
                               KERNEL_POLICY, KERNEL_RING, KERNEL_WIDE, MAX_SLOTS, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH,
                               bench_config)
-from diral_amd.vec_env import DiralError, VecV2VEnv
+from diral_amd.vec_env import VecV2VEnv
 from tests.golden_util import HORIZON_LAGS, horizon_tables
+from tests.gpu_util import _expect_overflow, assert_slot, assert_tables, exported, load, make_oracle
+from tests.kslots_harness import VEL_SEED, as_rollout, assert_same, assert_same_envs, slot_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -109,52 +111,10 @@ LARGE = [Case("large-forced-40-6", 40, 6, 1500.0, KERNEL_LARGE, path="large", ri
 BY_NAME = {c.name: c for c in FAST64 + WIDE + GENERAL + LARGE}
 
 
-def make_oracle(cfg, tab, threads=8):
-    from oracle.oracle import Oracle, SQ_IEEE
-    B, N = tab["pos_x"].shape
-    orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=threads)
-    orc.reset(tab["pos_x"], np.zeros((B, N)), tab["vel"])
-    orc.import_state(seq=tab["seq"], age=tab["age"], x=tab["x"], y=np.zeros((B, N, N)))
-    return orc
-
-
-def load(env, tab):
-    env.reset_topology(tab["pos_x"], 0.0, tab["vel"])
-    env.import_state(tab["pos_x"], np.zeros(tab["pos_x"].shape), tab["vel"], seq=tab["seq"], age=tab["age"], x=tab["x"])
-
-
 def shifted(tab, delta):
     out = dict(tab)
     out["seq"] = np.where(tab["seq"] > 0, tab["seq"].astype(np.int64) + delta, 0).astype(np.int32)
     return out
-
-
-def exported(env):
-    return {k: v.cpu().numpy() for k, v in env.export_state().items()}
-
-
-def assert_tables(st, oe, what):
-    for k in ("seq", "x", "y", "pos_x", "vel"):
-        assert np.array_equal(st[k], oe[k]), (k, what, np.argwhere(st[k] != oe[k])[:4])
-    assert np.array_equal(st["age"], np.minimum(oe["age"], 255)), what
-    if "la" in st:
-        assert np.array_equal(st["la"].astype(np.int64), oe["la"]), what
-
-
-def assert_slot(cfg, mode, got, orc, acts, t, what):
-    """rewards, channel observation and state of one slot against the oracle (exp() rewards within EXP_ATOL)."""
-    obs, rew, chobs = got
-    o_rew, o_chobs = orc.step(mode, acts, t)
-    o_state = orc.obtain_state(acts, o_chobs, o_rew)
-    if tp.uses_exp(cfg, mode):
-        assert tp.exp_close(rew, o_rew), what
-    else:
-        assert np.array_equal(rew, o_rew), what
-    assert np.array_equal(chobs, o_chobs), what
-    if tp.uses_exp(cfg, mode) and cfg.State.add_reward:
-        assert tp.exp_close(obs, o_state), what
-    else:
-        assert np.array_equal(obs, o_state), (what, np.argwhere(obs != o_state)[:4])
 
 
 def run_from(case, monkeypatch, tab, acts):
@@ -165,7 +125,7 @@ def run_from(case, monkeypatch, tab, acts):
     orc = make_oracle(cfg, tab)
     out = []
     for t in range(len(acts)):
-        obs, rew, chobs, _ = tp.gpu_step(env, case.mode, acts[t], t)
+        obs, rew, chobs, _ = gu.gpu_step(env, case.mode, acts[t], t)
         case.assert_kernel(env)
         assert_slot(cfg, case.mode, (obs, rew, chobs), orc, acts[t], t, (case.name, t))
         st = exported(env)
@@ -223,18 +183,11 @@ def _fresh_slots(case, env, cfg, rng, n):
     orc.reset(x0, np.zeros((case.B, case.N)), v0)
     for t in range(n):
         a = rng.integers(0, case.A, size=(case.B, case.N)).astype(np.int32)
-        obs, rew, chobs, _ = tp.gpu_step(env, case.mode, a, t)
+        obs, rew, chobs, _ = gu.gpu_step(env, case.mode, a, t)
         case.assert_kernel(env)
         assert_slot(cfg, case.mode, (obs, rew, chobs), orc, a, t, (case.name, "after reset", t))
     assert_tables(exported(env), orc.export(), (case.name, "after reset"))
     env.check()
-
-
-def _expect_overflow(env):
-    with pytest.raises(DiralError) as ei:
-        env.check()
-    assert ei.value.status == ERR_SEQ_OVERFLOW, ei.value
-    env.check()                                                                  # reported once, then cleared
 
 
 @pytest.mark.parametrize("name", HORIZON)
@@ -251,14 +204,14 @@ def test_the_slot_past_the_last_number_is_reported_once(name, monkeypatch):
     orc = make_oracle(cfg, tab)
     for t in range(3):
         a = rng.integers(0, case.A, size=(case.B, case.N)).astype(np.int32)
-        obs, rew, chobs, _ = tp.gpu_step(env, case.mode, a, t)
+        obs, rew, chobs, _ = gu.gpu_step(env, case.mode, a, t)
         case.assert_kernel(env)
         assert_slot(cfg, case.mode, (obs, rew, chobs), orc, a, t, (name, t))
         env.check()
     st = exported(env)
     assert_tables(st, orc.export(), name)
     assert st["seq"].max() == MAX_SLOTS
-    tp.gpu_step(env, case.mode, rng.integers(0, case.A, size=(case.B, case.N)).astype(np.int32), 3)
+    gu.gpu_step(env, case.mode, rng.integers(0, case.A, size=(case.B, case.N)).astype(np.int32), 3)
     case.assert_kernel(env)
     _expect_overflow(env)
     _fresh_slots(case, env, cfg, rng, 3)
@@ -281,14 +234,14 @@ def test_one_vehicle_at_the_horizon_among_young_ones(name, monkeypatch):
     load(env, tab)
     orc = make_oracle(cfg, tab)
     a = rng.integers(0, case.A, size=(case.B, case.N)).astype(np.int32)
-    obs, rew, chobs, _ = tp.gpu_step(env, case.mode, a, 0)
+    obs, rew, chobs, _ = gu.gpu_step(env, case.mode, a, 0)
     case.assert_kernel(env)
     assert_slot(cfg, case.mode, (obs, rew, chobs), orc, a, 0, name)
     st = exported(env)
     assert_tables(st, orc.export(), name)
     assert st["seq"][0, case.N - 3, case.N - 3] == MAX_SLOTS
     env.check()
-    tp.gpu_step(env, case.mode, a, 1)
+    gu.gpu_step(env, case.mode, a, 1)
     case.assert_kernel(env)
     _expect_overflow(env)
 
@@ -362,10 +315,7 @@ def test_k_policy_slots_in_one_launch_across_the_range(case, own, monkeypatch):
     for k in one:
         assert torch.equal(one[k], got[k]), (k, (one[k] != got[k]).nonzero()[:4])
     assert torch.equal(p1.prev_action, p2.prev_action) and torch.equal(p1.counter, p2.counter)
-    s1, s2 = e1.export_state(), e2.export_state()
-    for k in s1:
-        assert torch.equal(s1[k], s2[k]), k
-    assert torch.equal(e1.metrics(), e2.metrics())
+    s2 = assert_same_envs(e1, e2, entries=False)
     for t, a in enumerate(given):
         a = a.cpu().numpy()
         o_rew, o_chobs = orc.step(case.mode, a, t)
@@ -394,26 +344,22 @@ def test_rollout_in_one_launch_across_the_range(case, own, monkeypatch):
     """rollout (five slots of a given action sequence) against the loop of one-slot steps on a twin handle (every slot's
     shaped rewards, sums and collisions, the last slot's outputs, tables, metrics) and against the oracle (the LAST slot's
     reward and state, the exported tables); six slots from DIRAL_MAX_SLOTS - 5 raise the flag."""
-    from tests.test_gpu_rollout import VEL_SEED, _loop, _same
     cfg, tab, (e1, e2), orc = _twins(case, monkeypatch, own, 800 + case.N)
     mode = "my_step_ch" if case.mode == STEP_MY_STEP_CH else "my_step"
     seq = torch.stack([e1.sample(7000 + k) for k in range(K + 1)])
-    want = _loop(e1, seq[:K], 0, mode, "last", True, None)
+    want = as_rollout(slot_loop(e1, seq[:K], 0, mode), "last")
     got = e2.rollout(seq[:K], 0, mode=mode, states="last", global_reward_avg=True, vel_seed=VEL_SEED)
     torch.cuda.synchronize()
     lk = e2.last_kernel()
     assert (lk & 15) == case.family and lk & KERNEL_POLICY, lk
     assert case.family != KERNEL_WIDE or bool(lk & KERNEL_PACKED) == (case.form == "packed"), lk
-    _same(want, got, (case.name, own))
-    s1, s2 = e1.export_state(), e2.export_state()
-    for k in s1:
-        assert torch.equal(s1[k], s2[k]), k
-    assert torch.equal(e1.metrics(), e2.metrics())
+    assert_same(want, got, (case.name, own))
+    assert_same_envs(e1, e2, entries=False)
     for t in range(K):
         a = seq[t].cpu().numpy()
         o_rew, o_chobs = orc.step(case.mode, a, t)
     rew = got["reward"].cpu().numpy()
-    assert tp.exp_close(rew, o_rew) if tp.uses_exp(cfg, case.mode) else np.array_equal(rew, o_rew)
+    assert gu.exp_close(rew, o_rew) if gu.uses_exp(cfg, case.mode) else np.array_equal(rew, o_rew)
     assert np.array_equal(got["states"].cpu().numpy(), orc.obtain_state(a, o_chobs, o_rew))
     assert_tables(exported(e2), orc.export(), (case.name, own))
     e1.check(); e2.check()
@@ -459,10 +405,7 @@ def test_prefill_in_one_launch_across_the_range(mode, rd, own, monkeypatch):
     assert torch.equal(acts, torch.stack(want_a))
     for k in range(K):
         assert torch.equal(states[k], want_s[k]), (k, (states[k] != want_s[k]).nonzero()[:5])
-    s1, s2 = e_loop.export_state(), e_one.export_state()
-    for key in s1:
-        assert torch.equal(s1[key], s2[key]), key
-    assert torch.equal(e_loop.metrics(), e_one.metrics())
+    assert_same_envs(e_loop, e_one, entries=False)
     assert_tables(exported(e_one), orc.export(), (mode, own))
     e_loop.check(); e_one.check()
     if own == MAX_SLOTS - K:
@@ -502,7 +445,7 @@ def test_a_captured_slot_replayed_across_bit_31(name, monkeypatch):
         torch.cuda.synchronize()
         case.assert_kernel(graphed)
         got = (obs_g.cpu().numpy(), rew_g.cpu().numpy(), chobs_g.cpu().numpy())
-        obs_e, rew_e, chobs_e, _ = tp.gpu_step(eager, case.mode, acts[i], 1)
+        obs_e, rew_e, chobs_e, _ = gu.gpu_step(eager, case.mode, acts[i], 1)
         assert all(np.array_equal(x, y) for x, y in zip(got, (obs_e, rew_e, chobs_e))), i
         assert_slot(cfg, case.mode, got, orc, acts[i], 1, (name, i))
     sg = exported(graphed)
@@ -533,7 +476,7 @@ def test_an_imported_number_outside_the_range_is_reported(bad, where, N, A, L):
     rng = np.random.default_rng(N + 5)
     tab = horizon_tables(rng, B, N, L, 5000, lags=NO_ANCIENT)
     u, k = (N - 2, N - 2) if where == "own" else (3, N - 2)
-    env = tp.make_env(cfg, B)
+    env = gu.make_env(cfg, B)
     load(env, tab)
     env.check()
     env.import_entries(_entries(tab))
@@ -554,7 +497,7 @@ def test_the_last_legal_number_round_trips_through_both_imports(N, A, L):
     cfg = bench_config(N, A, L)
     tab = horizon_tables(np.random.default_rng(N + 6), B, N, L, MAX_SLOTS)
     assert tab["seq"].max() == MAX_SLOTS == (1 << 24) - 2
-    env = tp.make_env(cfg, B)
+    env = gu.make_env(cfg, B)
     load(env, tab)
     for again in range(2):
         st = exported(env)

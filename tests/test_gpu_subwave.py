@@ -15,12 +15,12 @@ import numpy as np
 import pytest
 import torch
 
-import tests.test_gpu_parity as tp
+import tests.gpu_util as gu
 from diral_amd.config import (ERR_ACTION_RANGE, ERR_BAD_ARG, ERR_UNSUPPORTED, KERNEL_FAST64, KERNEL_GENERAL, KERNEL_OBSERVE,
                               KERNEL_SUBWAVE, MAX_SLOTS, OPT_KERNEL_PATH, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config)
 from tests import hist_edge_cases as H
 from tests.golden_util import Golden, golden_names, horizon_tables
-from tests.test_gpu_seq_horizon import _expect_overflow, assert_slot, assert_tables, exported, load, make_oracle
+from tests.gpu_util import _expect_overflow, assert_slot, assert_tables, exported, load, make_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -30,7 +30,7 @@ def subwave_path(monkeypatch):
     """make_env of the parity tests hands out handles pinned to the sub-wave path; yields the handles it made.
     (random_rollout calls `force_general_kernel(False)` right behind make_env, which would put the handle back on AUTO:
     the method is shadowed on the instance.)"""
-    plain = tp.make_env
+    plain = gu.make_env
     made = []
 
     def make(cfg, B, mode=STEP_MY_STEP, dtype=torch.float64):
@@ -39,7 +39,7 @@ def subwave_path(monkeypatch):
         env.force_general_kernel = lambda on=True: None
         made.append(env)
         return env
-    monkeypatch.setattr(tp, "make_env", make)
+    monkeypatch.setattr(gu, "make_env", make)
     yield made
 
 
@@ -50,7 +50,7 @@ def ran_subwave(made):
 
 
 def pinned(cfg, B, dtype=torch.float64, mode=STEP_MY_STEP):
-    env = tp.make_env(cfg, B, mode, dtype)
+    env = gu.make_env(cfg, B, mode, dtype)
     env.use_subwave_path()
     return env
 
@@ -78,7 +78,7 @@ def test_the_fixture_filter_selects_the_small_fixtures():
 @pytest.mark.parametrize("name", SMALL_GOLDENS)
 def test_golden_replay_on_the_subwave_path(name, subwave_path):
     """B = 3 replicas: a wave whose last groups hold no env."""
-    tp.test_golden_replay_on_gpu(name)
+    gu.golden_replay_on_gpu(name)
     ran_subwave(subwave_path)
 
 
@@ -96,7 +96,7 @@ def test_testenv_shim_forwards_the_opt_in(name):
         assert (env._env.last_kernel() & 15) == KERNEL_SUBWAVE
         state = env.obtain_state(obs, acts, list(rews), ep, eps)
         assert np.array_equal(rews, g["rews"][i])
-        assert ulp_diff(np.array(state), g["state"][i]) <= tp.DIST_ULP
+        assert ulp_diff(np.array(state), g["state"][i]) <= gu.DIST_ULP
         assert env.get_x_pos() == list(g["pos_x"][i])
 
 
@@ -117,7 +117,7 @@ SIZES = [
 @pytest.mark.parametrize("N,A,K,B,L,Rc", SIZES)
 def test_sizes_around_the_lane_groups_vs_oracle(N, A, K, B, L, Rc, subwave_path):
     cfg = toy(N, A, K, L, Rc, State=dict(add_channel_obs=True, add_reward=True))
-    tp.random_rollout(cfg, B=B, T=30, seed=5000 + 17 * N + A + K + B, sticky=0.5, track_prr=bool(B & 1),
+    gu.random_rollout(cfg, B=B, T=30, seed=5000 + 17 * N + A + K + B, sticky=0.5, track_prr=bool(B & 1),
                       expect_kernel=KERNEL_SUBWAVE)
     ran_subwave(subwave_path)
 
@@ -133,7 +133,7 @@ RICH = dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=
 def test_step_kinds_and_reward_designs_vs_oracle(N, A, B, mode, rd, toyw, subwave_path):
     """All three step kinds, reward_design 1-5 with toy and non-toy weights, the rich State flags, the fingerprint."""
     cfg = toy(N, A, 20, 300.0, 120.0, reward_design=rd, congestion_test=toyw, enable_fingerprint=True, State=RICH)
-    tp.random_rollout(cfg, B=B, T=30, seed=6000 + 100 * mode + 10 * rd + N + int(toyw), mode=mode, sticky=0.6,
+    gu.random_rollout(cfg, B=B, T=30, seed=6000 + 100 * mode + 10 * rd + N + int(toyw), mode=mode, sticky=0.6,
                       track_prr=(mode == STEP_MY_STEP and rd % 2 == 0), expect_kernel=KERNEL_SUBWAVE)
     ran_subwave(subwave_path)
 
@@ -141,7 +141,7 @@ def test_step_kinds_and_reward_designs_vs_oracle(N, A, B, mode, rd, toyw, subwav
 @pytest.mark.parametrize("N,A,B", [(4, 3, 16), (8, 16, 15), (5, 3, 9)])
 def test_state_type_1_with_the_real_action_index(N, A, B, subwave_path):
     cfg = toy(N, A, 10, 300.0, 120.0, State=dict(type=1, action_index="real", add_channel_obs=True, add_reward=True))
-    tp.random_rollout(cfg, B=B, T=30, seed=6500 + N, expect_kernel=KERNEL_SUBWAVE)
+    gu.random_rollout(cfg, B=B, T=30, seed=6500 + N, expect_kernel=KERNEL_SUBWAVE)
     ran_subwave(subwave_path)
 
 
@@ -150,7 +150,7 @@ def test_proportional_fairness_with_sticky_actions(N, A, mode, subwave_path):
     """Sticky actions take the pf counters over the threshold (random_rollout asserts that they did)."""
     cfg = toy(N, A, 20, 100.0, 250.0, reward_design=2 if mode != STEP_MY_STEP else 1, proportional_fair=True,
               State=dict(add_reward=True))
-    tp.random_rollout(cfg, B=17, T=45, seed=6600 + N + mode, mode=mode, sticky=0.9, expect_kernel=KERNEL_SUBWAVE)
+    gu.random_rollout(cfg, B=17, T=45, seed=6600 + N + mode, mode=mode, sticky=0.9, expect_kernel=KERNEL_SUBWAVE)
     ran_subwave(subwave_path)
 
 
@@ -161,7 +161,7 @@ def _lanes(rng, B, N):
 @pytest.mark.parametrize("N,A,B", [(4, 3, 17), (8, 5, 9), (3, 16, 33)])
 def test_velocity_updates_and_lanes_off_the_line(N, A, B, subwave_path):
     cfg = toy(N, A, 20, 300.0, 120.0, mobility_vary=True, reward_design=1, State=dict(add_velocity=True, add_position=True))
-    tp.random_rollout(cfg, B=B, T=30, seed=6700 + N, vel_every=25, y0=_lanes, sticky=0.4, track_prr=True,
+    gu.random_rollout(cfg, B=B, T=30, seed=6700 + N, vel_every=25, y0=_lanes, sticky=0.4, track_prr=True,
                       expect_kernel=KERNEL_SUBWAVE)
     ran_subwave(subwave_path)
 
@@ -169,7 +169,7 @@ def test_velocity_updates_and_lanes_off_the_line(N, A, B, subwave_path):
 @pytest.mark.parametrize("N,A,mode", [(4, 3, STEP_DESIGN), (6, 3, STEP_MY_STEP), (8, 4, STEP_MY_STEP_CH)])
 def test_static_design_topology(N, A, mode, subwave_path):
     cfg = toy(N, A, 20, 300.0, 120.0, mobility=False, enable_design_topology=True, State=dict(add_position=True))
-    tp.random_rollout(cfg, B=9, T=30, seed=6800 + N, mode=mode, sticky=0.5, expect_kernel=KERNEL_SUBWAVE)
+    gu.random_rollout(cfg, B=9, T=30, seed=6800 + N, mode=mode, sticky=0.5, expect_kernel=KERNEL_SUBWAVE)
     ran_subwave(subwave_path)
 
 
@@ -181,7 +181,7 @@ def test_static_design_topology(N, A, mode, subwave_path):
 def test_handles_without_tables_and_the_secondary_observation_launches(N, A, state, subwave_path):
     """No piggybacked tables at all; the sorted distances and the type-1 histogram, launches of their own behind this step."""
     cfg = toy(N, A, 20, 300.0, 120.0, State=state)
-    tp.random_rollout(cfg, B=17, T=30, seed=6900 + N + len(state), sticky=0.3, y0=_lanes if N == 8 else None,
+    gu.random_rollout(cfg, B=17, T=30, seed=6900 + N + len(state), sticky=0.3, y0=_lanes if N == 8 else None,
                       expect_kernel=KERNEL_SUBWAVE)
     ran_subwave(subwave_path)
 
@@ -206,7 +206,7 @@ def test_trace_replay_vs_oracle(N, A, per_env):
         o.set_trace(traces[b] if per_env else traces)
     for t in list(range(14)) + [40, 41, 5]:
         a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        obs, rew, chobs, _ = tp.gpu_step(env, STEP_MY_STEP, a, t)
+        obs, rew, chobs, _ = gu.gpu_step(env, STEP_MY_STEP, a, t)
         assert (env.last_kernel() & 15) == KERNEL_SUBWAVE
         for b, o in enumerate(orcs):
             o_rew, o_chobs = o.step(STEP_MY_STEP, a[b:b + 1], t)
@@ -237,7 +237,7 @@ def test_path_switches_on_one_handle(N, A):
     B = 17
     rng = np.random.default_rng(7100 + N)
     tab = dict(pos_x=rng.integers(0, 300, size=(B, N)).astype(np.float64), vel=rng.uniform(1.1, 2.7, size=(B, N)))
-    env = tp.make_env(cfg, B)
+    env = gu.make_env(cfg, B)
     env.reset_topology(tab["pos_x"], 0.0, tab["vel"])
     from oracle.oracle import Oracle, SQ_IEEE
     orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=4)
@@ -252,7 +252,7 @@ def test_path_switches_on_one_handle(N, A):
             _set_path(env, path)
         acts = rng.integers(0, A, size=(B, N)).astype(np.int32)
         mode = STEP_MY_STEP_CH if t % 3 == 2 else STEP_MY_STEP
-        obs, rew, chobs, _ = tp.gpu_step(env, mode, acts, t)
+        obs, rew, chobs, _ = gu.gpu_step(env, mode, acts, t)
         assert (env.last_kernel() & 15) == family[path], (t, path, env.last_kernel())
         seen.add(env.last_kernel() & 15)
         assert_slot(cfg, mode, (obs, rew, chobs), orc, acts, t, (path, t))
@@ -275,7 +275,7 @@ def test_env_copies_between_a_pinned_and_an_auto_handle_and_snapshot_restore(N, 
     rng = np.random.default_rng(7200 + N)
     x0, v0 = rng.integers(0, 300, size=(B, N)).astype(np.float64), rng.uniform(1.1, 2.7, size=(B, N))
     tab = dict(pos_x=x0, vel=v0)
-    sub, auto = pinned(cfg, B), tp.make_env(cfg, B)
+    sub, auto = pinned(cfg, B), gu.make_env(cfg, B)
     sub.reset_topology(x0, 0.0, v0)
     auto.reset_topology(seed=5)
     from oracle.oracle import Oracle, SQ_IEEE
@@ -289,7 +289,7 @@ def test_env_copies_between_a_pinned_and_an_auto_handle_and_snapshot_restore(N, 
             acts = rng.integers(0, A, size=(B, N)).astype(np.int32)
             got = []
             for env, kind in zip(envs, kinds):
-                obs, rew, chobs, _ = tp.gpu_step(env, STEP_MY_STEP, acts, t)
+                obs, rew, chobs, _ = gu.gpu_step(env, STEP_MY_STEP, acts, t)
                 assert (env.last_kernel() & 15) == kind
                 got.append((obs, rew, chobs))
             assert_slot(cfg, STEP_MY_STEP, got[0], orc, acts, t, t)
@@ -310,13 +310,13 @@ def test_env_copies_between_a_pinned_and_an_auto_handle_and_snapshot_restore(N, 
     snap = sub.snapshot()
     before = exported(sub)
     acts = rng.integers(0, A, size=(3, B, N)).astype(np.int32)
-    first = [tp.gpu_step(sub, STEP_MY_STEP, acts[i], t + i) for i in range(3)]
+    first = [gu.gpu_step(sub, STEP_MY_STEP, acts[i], t + i) for i in range(3)]
     after = exported(sub)
     sub.restore(snap)
     again = exported(sub)
     for k in before:
         assert np.array_equal(before[k], again[k]), k
-    second = [tp.gpu_step(sub, STEP_MY_STEP, acts[i], t + i) for i in range(3)]
+    second = [gu.gpu_step(sub, STEP_MY_STEP, acts[i], t + i) for i in range(3)]
     assert (sub.last_kernel() & 15) == KERNEL_SUBWAVE
     for f, s in zip(first, second):
         assert all(np.array_equal(x, y) for x, y in zip(f, s))
@@ -348,7 +348,7 @@ def test_entries_of_every_lag_class_a_million_stamps_old(A):
     orc = make_oracle(cfg, tab)
     for t in range(6):
         acts = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        obs, rew, chobs, _ = tp.gpu_step(env, STEP_MY_STEP, acts, t)
+        obs, rew, chobs, _ = gu.gpu_step(env, STEP_MY_STEP, acts, t)
         assert (env.last_kernel() & 15) == KERNEL_SUBWAVE
         assert_slot(cfg, STEP_MY_STEP, (obs, rew, chobs), orc, acts, t, t)
         assert_tables(exported(env), orc.export(), t)
@@ -368,14 +368,14 @@ def test_the_slot_past_the_last_number_is_reported_once(N, mode):
     orc = make_oracle(cfg, tab)
     for t in range(3):
         acts = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        obs, rew, chobs, _ = tp.gpu_step(env, mode, acts, t)
+        obs, rew, chobs, _ = gu.gpu_step(env, mode, acts, t)
         assert (env.last_kernel() & 15) == KERNEL_SUBWAVE
         assert_slot(cfg, mode, (obs, rew, chobs), orc, acts, t, t)
         env.check()
     st = exported(env)
     assert_tables(st, orc.export(), "horizon")
     assert st["seq"].max() == MAX_SLOTS
-    tp.gpu_step(env, mode, rng.integers(0, A, size=(B, N)).astype(np.int32), 3)
+    gu.gpu_step(env, mode, rng.integers(0, A, size=(B, N)).astype(np.int32), 3)
     assert (env.last_kernel() & 15) == KERNEL_SUBWAVE
     _expect_overflow(env)
 
@@ -496,7 +496,7 @@ def test_histogram_bin_edges_vs_oracle_and_numpy(K):
 def test_handles_the_path_does_not_take_keep_their_kernel(cfg):
     from diral_amd.vec_env import DiralError
     B = 3
-    env = tp.make_env(cfg, B)
+    env = gu.make_env(cfg, B)
     env.reset_topology(seed=3)
     acts = np.broadcast_to(np.arange(cfg.num_users) % cfg.num_channels, (B, cfg.num_users)).astype(np.int32)
     env.step(acts, 0)
@@ -511,7 +511,7 @@ def test_handles_the_path_does_not_take_keep_their_kernel(cfg):
 
 
 def test_option_values_beyond_the_paths_are_bad_arguments():
-    env = tp.make_env(toy(), 3)
+    env = gu.make_env(toy(), 3)
     assert env.lib.diral_env_set_option(env._h, OPT_KERNEL_PATH, 4) == ERR_BAD_ARG
     assert env.lib.diral_env_set_option(env._h, OPT_KERNEL_PATH, -1) == ERR_BAD_ARG
     assert env.lib.diral_env_set_option(env._h, OPT_KERNEL_PATH, 3) == 0
@@ -529,7 +529,7 @@ def test_k_slot_calls_are_refused_with_the_env_untouched_and_one_policy_slot_equ
     B = 17
     rng = np.random.default_rng(7600 + N)
     x0, v0 = rng.integers(0, 300, size=(B, N)).astype(np.float64), rng.uniform(1.1, 2.7, size=(B, N))
-    sub, auto = pinned(cfg, B), tp.make_env(cfg, B)
+    sub, auto = pinned(cfg, B), gu.make_env(cfg, B)
     pols = []
     for env in (sub, auto):
         env.reset_topology(x0, 0.0, v0)
@@ -613,8 +613,8 @@ def test_f32_outputs_are_the_cast_of_the_f64_ones(N, A, mode, rd):
         e.reset_topology(x0, 0.0, v0)
     for t in range(25):
         a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        o64, r64, c64, d64 = tp.gpu_step(e64, mode, a, t, 2.0, 0.5)
-        o32, r32, c32, d32 = tp.gpu_step(e32, mode, a, t, 2.0, 0.5)
+        o64, r64, c64, d64 = gu.gpu_step(e64, mode, a, t, 2.0, 0.5)
+        o32, r32, c32, d32 = gu.gpu_step(e32, mode, a, t, 2.0, 0.5)
         assert (e32.last_kernel() & 15) == (e64.last_kernel() & 15) == KERNEL_SUBWAVE
         assert o32.dtype == np.float32 and np.array_equal(o64.astype(np.float32), o32), t
         assert np.array_equal(r64.astype(np.float32), r32) and np.array_equal(c64.astype(np.float32), c32), t

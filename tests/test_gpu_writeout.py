@@ -29,7 +29,7 @@ import pytest
 import torch
 
 from diral_amd.config import KERNEL_FAST64, KERNEL_POLICY, STEP_DESIGN, STEP_MY_STEP, bench_config
-from tests.test_gpu_parity import make_env
+from tests.gpu_util import make_env
 
 gpu = pytest.mark.gpu
 

@@ -6,74 +6,11 @@ Every fixture under tests/golden/ was recorded from the real reference
 channel observations, state vectors, positions, velocities, neighbour-table
 planes, arrival stamps and the information-age histogram.
 """
-import hashlib
-
 import numpy as np
 import pytest
 
 from oracle.oracle import Oracle, SQ_IEEE, SQ_POW
-from tests.golden_util import Golden, golden_names, out_sha, ulp_diff
-
-
-def sha(a):
-    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
-def replay(g, sq_mode, batch=1):
-    o = Oracle(g.cfg, batch=batch, sq_mode=sq_mode)
-    o.reset(g["x0"], g["y0"], g["v0"])
-    out = dict(rews=[], chobs=[], state=[], pos_x=[], vel=[], ia=[], exp=[])
-    for i, mode, acts, t, (ep, eps) in g.steps():
-        rews, chobs = o.step(mode, acts, t)
-        st = o.obtain_state(acts, chobs, rews, ep, eps)
-        out["rews"].append(rews)
-        out["chobs"].append(chobs)
-        out["state"].append(st)
-        out["ia"].append(o.info_age(t))
-        if i in g.vel_updates:
-            o.update_velocity(g.vel_updates[i])
-        if g.trace is not None and i == g.trace_after:
-            o.set_trace(g.trace)
-        e = o.export()
-        out["pos_x"].append(e["pos_x"])
-        out["vel"].append(e["vel"])
-        out["exp"].append(e)
-    return o, out
-
-
-def compare_with_reference(g):
-    """The oracle in its reference-faithful mode against one recorded fixture: every output of every slot bit for
-    bit (a thinned fixture: by its per-slot hashes where it dropped the arrays), the table planes by hash at every
-    slot and in full at the checkpoints.  AssertionError((key, slot)) on the first difference; also what
-    tests/golden/gen_golden.py `fuzz` runs on every drawn case."""
-    o, out = replay(g, SQ_POW)
-    assert o.S == int(g["state_space"]), ("state_space", -1)
-    ck = g.table_checkpoints()
-    for i in range(g.T):
-        for key in ("rews", "chobs", "state", "pos_x", "vel"):
-            got = out[key][i][0]
-            ref = g.out(key, i)
-            if ref is None:
-                assert out_sha(got) == g.out_sha(key, i), (key, i)
-                continue
-            assert got.shape == ref.shape, (key, i)
-            assert np.array_equal(got.view(np.int64), ref.view(np.int64)) or \
-                np.array_equal(got, ref), (key, i, "max ulp %d" % ulp_diff(got, ref))
-        if g.kept is not None:                  # the hashes cover the kept slots as well
-            for key in ("rews", "chobs", "state", "pos_x", "vel"):
-                assert out_sha(out[key][i][0]) == g.out_sha(key, i), (key, i)
-            assert out_sha(out["ia"][i][0]) == g.out_sha("ia", i), ("ia", i)
-        if g.out("ia", i) is not None:
-            assert np.array_equal(out["ia"][i][0], g.out("ia", i)), ("ia", i)
-        e = out["exp"][i]
-        shas = [sha(e["seq"][0].astype(np.int64)), sha(e["age"][0].astype(np.int64)),
-                sha(e["x"][0]), sha(e["y"][0]), sha(e["la"][0])]
-        assert shas == list(g["table_sha"][i]), ("table_sha", i)
-        if i in ck:
-            j = ck[i]
-            for k in ("seq", "age", "x", "y", "la"):
-                assert np.array_equal(e[k][0], g["tab_" + k][j]), ("tab_" + k, i)
-    return o
+from tests.golden_util import Golden, compare_with_reference, golden_names, replay, ulp_diff
 
 
 @pytest.mark.parametrize("name", golden_names())
