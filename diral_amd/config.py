@@ -45,6 +45,7 @@ DT_F64 = 1
 
 OPT_ENV_OFFSET = 1
 OPT_KERNEL_PATH = 2
+OPT_SUBWAVE_SLOTS = 3        # 0 / 1 on a PATH_SUBWAVE handle: rollout and prefill as one launch (csrc/step_subwave_slots.hpp)
 PATH_AUTO = 0
 PATH_GENERAL = 1
 PATH_LARGE = 2

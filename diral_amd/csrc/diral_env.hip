@@ -57,6 +57,7 @@ struct DiralEnv {
   uint32_t lds_bytes = 0;
   int64_t env_offset = 0;  // global index of env 0 (DIRAL_OPT_ENV_OFFSET): device RNG draws are indexed globally
   int kernel_path = DIRAL_PATH_AUTO;   // DIRAL_OPT_KERNEL_PATH
+  bool subwave_slots = false;          // DIRAL_OPT_SUBWAVE_SLOTS (only while kernel_path == DIRAL_PATH_SUBWAVE)
   int last_kernel = -1;    // DIRAL_KERNEL_* of the last step / observe launch
   double* pos_x = nullptr;
   double* pos_y = nullptr;
@@ -422,13 +423,13 @@ size_t slow_set_words(const DiralEnv* e) { return 16 + (size_t)fast_slow_max(e->
 // What one step call launches: decided in ONE place and without side effects, from the handle, the call's parameters
 // and its policy request (`pol`: diral_env_step_policy / diral_env_prefill / diral_env_rollout, else null) - for the launch itself
 // (launch_step_any) and for everyone who must know the outcome before anything is launched (`fused`).
-enum class StepLaunch { Large, General, Subwave, Fast64, Wide, Fast64Policy, Fast64Slots, WideSlots };
+enum class StepLaunch { Large, General, Subwave, SubwaveSlots, Fast64, Wide, Fast64Policy, Fast64Slots, WideSlots };
 struct StepPlan {
   StepLaunch launch;
   bool use_fast64, use_wide;   // the kernel family of the five specialised launches
   bool use_ring;               // xpos ring (step_fast64.hpp): the kernel keeps the plane only for entries older than the ring reaches
   bool slow_sets;              // the launch reads the slow-env sets (and rotates them: rotate_slow_sets); its grid has their blocks
-  bool fused;                  // the policy request is part of the launch (Fast64Policy, Fast64Slots, WideSlots)
+  bool fused;                  // the policy request is part of the launch (Fast64Policy, Fast64Slots, WideSlots, SubwaveSlots)
   // the run-time switches of the EXTRA instantiations, host-folded (FastParams::design ... nomove)
   bool design, prr, notab, nomove;
   int32_t* la;
@@ -447,6 +448,18 @@ StepPlan plan_step(const DiralEnv* e, const StepParams& p, const PolParams* pol)
   if (e->kernel_path == DIRAL_PATH_SUBWAVE && p.mode != kModeObserve) {
     // toy-size envs, 4 or 8 lanes each (step_subwave.hpp): every step call of a pinned handle, on the planes; never `fused`
     d.launch = StepLaunch::Subwave; d.last_kernel = DIRAL_KERNEL_SUBWAVE;
+    // ... unless the handle opted in to the slot loop (DIRAL_OPT_SUBWAVE_SLOTS, step_subwave_slots.hpp): an open-loop rollout of
+    // any K >= 1 and the random prefill, without the information-age and replay / position-log blocks.  The secondary
+    // observation modes are launches of their own behind ONE state vector (posdist_kernel.hpp); the prefill refuses a handle
+    // with a trace or arrival stamps, as the fast64 prefill does.  diral_env_step_policy stays where it was: the SPS agents
+    // are wave-cooperative code.
+    if (e->subwave_slots && pol && (pol->prefill || pol->rollout) && !pol->ia_on && !pol->rp_on) {
+      const bool secondary = p.state_out && ((p.flags & DIRAL_F_ADD_POSDIST) || ((p.flags & DIRAL_F_ADD_POSDIST_PIGGY) && p.posdist_type == 1));
+      const bool tracking = ((p.flags & DIRAL_F_TRACK_ARRIVAL) && p.la != nullptr) || p.trace != nullptr;
+      if (!secondary && !e->prev_obs && !(pol->prefill && tracking)) {
+        d.launch = StepLaunch::SubwaveSlots; d.fused = true; d.last_kernel = DIRAL_KERNEL_SUBWAVE | DIRAL_KERNEL_POLICY;
+      }
+    }
     return d;
   }
   // (DIRAL_PATH_GENERAL keeps the general kernel's FAST instantiation: plain_cfg does not ask for the path)
@@ -604,6 +617,7 @@ hipError_t launch_step_any(DiralEnv* e, const StepParams& p, const StepPlan& d, 
   if (d.launch == StepLaunch::Large) return launch_large(p, e->lg, s);
   if (d.launch == StepLaunch::General) return launch_general(e->vpl, d.general_fast, p, e->lds_bytes, s);
   if (d.launch == StepLaunch::Subwave) return launch_subwave(p, s);
+  if (d.launch == StepLaunch::SubwaveSlots) return launch_subwave_slots(p, *pol, s);
   FastParams f = fast_params(e, p, d);
   if (d.slow_sets) rotate_slow_sets(e, f, s);
   RichParams r = rich_for(e, p);
@@ -1003,6 +1017,12 @@ int diral_env_set_option(DiralEnv* e, int option, int64_t value) {
         HIP_TRY(e, alloc_large_scratch(e));
       }
       e->kernel_path = (int)value;
+      e->subwave_slots = false;                                    // (leaving DIRAL_PATH_SUBWAVE clears DIRAL_OPT_SUBWAVE_SLOTS)
+      return DIRAL_OK;
+    case DIRAL_OPT_SUBWAVE_SLOTS:
+      if (value != 0 && value != 1) return DIRAL_ERR_BAD_ARG;
+      if (value == 1 && e->kernel_path != DIRAL_PATH_SUBWAVE) return DIRAL_ERR_UNSUPPORTED;
+      e->subwave_slots = value == 1;
       return DIRAL_OK;
     default:
       return DIRAL_ERR_BAD_ARG;

@@ -43,6 +43,8 @@ hipError_t launch_general(int vpl, bool fast, const StepParams& p, uint32_t lds,
 hipError_t set_attr_general(int vpl, uint32_t lds);
 // num_users <= 8 with 4 or 8 lanes per env (step_subwave.hpp): one launch, no dynamic LDS, handles pinned to DIRAL_PATH_SUBWAVE
 hipError_t launch_subwave(const StepParams& p, hipStream_t s);
+// ... and K slots of it per launch (step_subwave_slots.hpp): diral_env_rollout and the prefill with DIRAL_OPT_SUBWAVE_SLOTS
+hipError_t launch_subwave_slots(const StepParams& p, const PolParams& q, hipStream_t s);
 // num_users > 256 / num_channels > 256 / num_bins > 64 (step_large.hpp): search + merge + histogram launches
 hipError_t launch_large(const StepParams& p, const LargeScratch& g, hipStream_t s);
 hipError_t set_attr_large(int N, int A, int K);

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from ._tensors import MSG_OUT, _ptr, check_tensor, dtype_code, policy_seed, seed64
-from .config import (DT_F32, DT_F64, ERR_HIP, ERR_UNSUPPORTED, M_COLUMNS, OK, OPT_ENV_OFFSET, OPT_KERNEL_PATH, PATH_AUTO,
+from .config import (DT_F32, DT_F64, ERR_HIP, ERR_UNSUPPORTED, M_COLUMNS, OK, OPT_ENV_OFFSET, OPT_KERNEL_PATH, OPT_SUBWAVE_SLOTS, PATH_AUTO,
                      PATH_GENERAL, PATH_LARGE, PATH_SUBWAVE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, ConfigError, DiralRollout, DiralSlotInfoAge, DiralSlotReplay,
                      DiralSlotPolicy, EnvConfig)
 
@@ -183,6 +183,7 @@ class VecV2VEnv:
         self._policy_needs_chobs = False        # step_policy met a configuration that does not run fused
         self.has_trace = False                  # the handle carries recorded positions of its own (load_saved_positions)
         self._kernel_path = PATH_AUTO           # what force_general_kernel / force_large_path chose (twin() repeats it)
+        self._subwave_slots = False             # use_subwave_path(slots=True)
         self._snap_twin: Optional["VecV2VEnv"] = None   # the handle snapshot() copies into, made at its first call
         # section order of obtain_state (test_env.py:527-583): ... velocity, fingerprint last
         self._fp_offset = self.S - 2
@@ -326,6 +327,7 @@ class VecV2VEnv:
         self._ok(self.lib.diral_env_set_option(self._h, OPT_KERNEL_PATH, PATH_GENERAL if on else PATH_AUTO),
                  "diral_env_set_option")
         self._kernel_path = PATH_GENERAL if on else PATH_AUTO
+        self._subwave_slots = False
 
     def force_large_path(self, on: bool = True) -> None:
         """Tests: run every step / observe on the three launches of csrc/step_large.hpp, the form that serves
@@ -333,17 +335,28 @@ class VecV2VEnv:
         self._ok(self.lib.diral_env_set_option(self._h, OPT_KERNEL_PATH, PATH_LARGE if on else PATH_AUTO),
                  "diral_env_set_option")
         self._kernel_path = PATH_LARGE if on else PATH_AUTO
+        self._subwave_slots = False
 
-    def use_subwave_path(self, on: bool = True) -> None:
+    def use_subwave_path(self, on: bool = True, slots: bool = False) -> None:
         """Opt in to the sub-wave step kernel (csrc/step_subwave.hpp): 4 or 8 lanes per env, so 16 or 8 toy-size envs
         share a wavefront instead of one env per 256-thread workgroup.  Same results, bit for bit.  Limits: num_users
         <= 8, num_channels <= 16, num_bins <= 64, no State.piggybacking - anything else raises DiralError with
         ERR_UNSUPPORTED and leaves the handle on the path it had.  Nothing chooses this path by itself.  On a pinned
-        handle `obtain_state` stays the stand-alone observe kernel, a one-slot `step_policy` runs as three launches,
-        and `rollout`, `prefill` and `step_policy(slots > 1)` raise ERR_UNSUPPORTED.  ``on=False``: back to AUTO."""
+        handle `obtain_state` stays the stand-alone observe kernel and a one-slot `step_policy` runs as three launches.
+
+        `slots` (DIRAL_OPT_SUBWAVE_SLOTS): ``False`` - `rollout`, `prefill` and `step_policy(slots > 1)` raise
+        ERR_UNSUPPORTED on the pinned handle; ``True`` - `rollout` (any K >= 1) and `prefill` run as ONE launch of
+        csrc/step_subwave_slots.hpp, the env in registers from slot to slot, bit-equal to the loop of one-slot calls.
+        Still refused then: `step_policy(slots > 1)`, `rollout(info_age=...)`, `rollout(positions=... / log_positions=True)`,
+        a state vector with a secondary observation mode, and `prefill` on a handle with a trace or arrival stamps.
+        ``on=False``: back to AUTO, which clears `slots`."""
         self._ok(self.lib.diral_env_set_option(self._h, OPT_KERNEL_PATH, PATH_SUBWAVE if on else PATH_AUTO),
                  "diral_env_set_option")
         self._kernel_path = PATH_SUBWAVE if on else PATH_AUTO
+        want = bool(on and slots)
+        if want or (on and self._subwave_slots):                     # (leaving the path clears the option by itself)
+            self._ok(self.lib.diral_env_set_option(self._h, OPT_SUBWAVE_SLOTS, 1 if want else 0), "diral_env_set_option")
+        self._subwave_slots = want
 
     def set_clock(self, clock: Optional[torch.Tensor]) -> None:
         """Install (or, with None, remove) a device slot clock: an int64 tensor of one element on this env's device.
@@ -448,7 +461,9 @@ class VecV2VEnv:
         Returns ``(states [K, B, N, S] or None, actions_all [K, B, N], next_actions [B, N])``; `next_actions` is
         the draw of ``seed + slots`` (pass it, with that seed, to continue).  Bit-equal to the loop of
         sample + my_step_design / my_step_ch + obtain_state calls.  Raises DiralError(ERR_UNSUPPORTED) with nothing launched
-        for configurations the fused kernel does not take (diral_amd.driver.DriverLoop.prefill loops then)."""
+        for configurations the fused kernels do not take (diral_amd.driver.DriverLoop.prefill loops then): on an AUTO
+        handle below 8 vehicles, and on a handle pinned with `use_subwave_path()` unless it was pinned with ``slots=True``
+        (toy-size envs: csrc/step_subwave_slots.hpp; not on a handle with a trace or arrival stamps)."""
         step_mode = _MODES.get(mode)
         if step_mode not in (STEP_DESIGN, STEP_MY_STEP_CH):
             raise ValueError("prefill: mode must be 'my_step_design' or 'my_step_ch'")
@@ -603,7 +618,10 @@ class VecV2VEnv:
         ``shaped`` [K, B, N], ``sum_r`` [K, B], ``collision`` [K, B] of every slot (fresh tensors).  Bit-equal to the loop of
         K `step` + `diral_driver_shape` (+ `update_velocity`) calls; the env's slot counter moves on by K.  Raises
         DiralError(ERR_UNSUPPORTED) with nothing launched and the env untouched where the slot loops do not apply
-        (include/diral_env.h lists them; diral_amd.driver.DriverLoop.rollout loops then).
+        (include/diral_env.h lists them; diral_amd.driver.DriverLoop.rollout loops then).  Toy-size envs (N <= 8) have their
+        slot loop on a handle pinned with ``use_subwave_path(slots=True)`` (csrc/step_subwave_slots.hpp: every `states` form,
+        every run-time switch of the one-slot kernel, the handle's own trace and arrival stamps; not `info_age`, `positions`
+        or `log_positions`); an AUTO handle below 8 vehicles and a handle pinned without `slots` refuse.
 
         `info_age` (`mode` = ``"my_step_ch"`` on a `track_arrival` handle, 8 <= N <= 64; `diral_env_rollout_ia`): ``True`` /
         ``"hist"`` - the launch keeps the arrival stamps and the result gains ``ia`` [K, B, 100] int32 (`info_age(t + k)`
@@ -805,7 +823,7 @@ class VecV2VEnv:
         elif self._kernel_path == PATH_LARGE:
             other.force_large_path()
         elif self._kernel_path == PATH_SUBWAVE:
-            other.use_subwave_path()
+            other.use_subwave_path(slots=self._subwave_slots)
         return other
 
     def _index(self, idx) -> Optional[torch.Tensor]:

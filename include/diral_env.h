@@ -224,8 +224,22 @@ typedef enum DiralOption {
    * handle's config (DIRAL_ERR_UNSUPPORTED on a handle of the three-launch form too) and leaves the path as it was on
    * refusal.  On such a handle diral_env_observe stays the stand-alone observe kernel, a one-slot diral_env_step_policy
    * runs its three launches, and diral_env_rollout, diral_env_prefill and slots > 1 return DIRAL_ERR_UNSUPPORTED with
-   * nothing launched (as on a handle pinned to the general kernel).  Any other value: DIRAL_ERR_BAD_ARG. */
-  DIRAL_OPT_KERNEL_PATH = 2
+   * nothing launched (as on a handle pinned to the general kernel) - unless DIRAL_OPT_SUBWAVE_SLOTS is set, below.
+   * Any other value: DIRAL_ERR_BAD_ARG. */
+  DIRAL_OPT_KERNEL_PATH = 2,
+  /* 0 (default) / 1; 1 only on a handle pinned to DIRAL_PATH_SUBWAVE (else DIRAL_ERR_UNSUPPORTED), cleared by setting
+   * any other kernel path; any other value: DIRAL_ERR_BAD_ARG.  While it is set, diral_env_rollout (any slots >= 1,
+   * my_step and my_step_ch, states last / all / none) and diral_env_prefill / diral_env_prefill_mode (my_step_design and
+   * my_step_ch) run as ONE launch of csrc/step_subwave_slots.hpp: the env's tables, positions, velocities and counters
+   * stay in registers from slot to slot; same results as the loop of one-slot calls, bit for bit;
+   * diral_env_last_kernel says DIRAL_KERNEL_SUBWAVE | DIRAL_KERNEL_POLICY.  The rollout takes every run-time switch of
+   * the one-slot kernel (reward_design 1-5, proportional fairness, PRR metrics, static topology, no tables, off-lane
+   * vehicles, the handle's trace, arrival stamps, the slot clock).  Still DIRAL_ERR_UNSUPPORTED, with nothing launched
+   * and the env untouched: diral_env_step_policy with slots > 1 (a one-slot call keeps its three launches), the
+   * information-age block (diral_env_rollout_ia), the replay / position-log block (diral_env_rollout_replay with a
+   * non-empty block), a state vector with a secondary observation mode (sorted distances, type-1 histogram), and the
+   * prefill on a handle with a trace or arrival stamps. */
+  DIRAL_OPT_SUBWAVE_SLOTS = 3
 } DiralOption;
 enum { DIRAL_PATH_AUTO = 0, DIRAL_PATH_GENERAL = 1, DIRAL_PATH_LARGE = 2, DIRAL_PATH_SUBWAVE = 3 };
 int diral_env_set_option(DiralEnv* env, int option, int64_t value);
@@ -246,7 +260,8 @@ enum {
   DIRAL_KERNEL_RING    = 128, /* the xpos ring (the per-entry xpos plane only for old entries) */
   DIRAL_KERNEL_PACKED  = 256, /* the packed table form: thermometer codes + ages + own sequence numbers (N <= 64 always;
                                  128 < N <= 256 on dense topologies), else the (seq, age) plane */
-  DIRAL_KERNEL_POLICY  = 512  /* diral_env_step_policy ran as ONE launch (reward shaping + SPS decision in the step) */
+  DIRAL_KERNEL_POLICY  = 512  /* diral_env_step_policy ran as ONE launch (reward shaping + SPS decision in the step);
+                                 DIRAL_KERNEL_SUBWAVE | DIRAL_KERNEL_POLICY: csrc/step_subwave_slots.hpp (DIRAL_OPT_SUBWAVE_SLOTS) */
 };
 int diral_env_last_kernel(const DiralEnv* env);
 
@@ -541,7 +556,8 @@ int diral_env_step_policy(DiralEnv* env, int mode, const int32_t* actions, int64
  *   rew_in [B][N] float64     the reward column of the state vectors (State.add_reward), or NULL: each slot's own reward
  * Configurations the fused kernel takes - N <= 64 (>= 8), A <= 64, the one-lane highway, piggybacked tables, no arrival /
  * PRR tracking, no trace replay, no secondary observation mode; otherwise DIRAL_ERR_UNSUPPORTED with nothing launched
- * (loop over the three calls instead: diral_amd.driver.DriverLoop.prefill does). */
+ * (loop over the three calls instead: diral_amd.driver.DriverLoop.prefill does).  Toy-size envs (N <= 8): on a handle pinned
+ * to DIRAL_PATH_SUBWAVE with DIRAL_OPT_SUBWAVE_SLOTS, in both modes below; not on a handle with a trace or arrival stamps. */
 int diral_env_prefill(DiralEnv* env, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out, int out_dtype,
                       int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in, double episode,
                       double epsilon, void* stream);
@@ -576,7 +592,10 @@ int diral_env_prefill_mode(DiralEnv* env, int mode, const int32_t* actions, int3
  * see diral_env_rollout_ia) / PRR tracking, no trace replay, no static topology, no State.piggybacking, no secondary observation mode behind a state
  * vector; my_step_ch and states_all = 1 at N <= 64 only.  Otherwise DIRAL_ERR_UNSUPPORTED with nothing launched and the env
  * untouched (loop over the calls instead: diral_amd.driver.DriverLoop.rollout does).  my_step_ch with reward_design
- * outside 2 ... 4: DIRAL_ERR_BAD_CONFIG (as diral_env_step). */
+ * outside 2 ... 4: DIRAL_ERR_BAD_CONFIG (as diral_env_step).  Toy-size envs (N <= 8, A <= 16): on a handle pinned to
+ * DIRAL_PATH_SUBWAVE with DIRAL_OPT_SUBWAVE_SLOTS (csrc/step_subwave_slots.hpp), with every run-time switch of the one-slot
+ * kernel - arrival and PRR tracking, the handle's trace, static topologies, off-lane vehicles, no tables -, both modes and
+ * states_all = 1; diral_env_rollout_ia and a non-empty diral_env_rollout_replay block stay DIRAL_ERR_UNSUPPORTED there. */
 typedef struct DiralRollout {
   uint32_t struct_bytes;          /* = sizeof(DiralRollout) */
   int32_t  shape_flags;
