@@ -13,21 +13,29 @@ namespace diral {
 // Device draws are indexed by the GLOBAL vehicle index idx0 + i (idx0 = env offset of this
 // handle x N, DIRAL_OPT_ENV_OFFSET): a batch sharded over several handles / GPUs draws
 // exactly what one handle holding the whole batch draws.
+// One vehicle: `g` its global index (the draws), `i` its place in this handle's [B][N] arrays (the given values).
+// reset_kernel and reset_envs_kernel (reset_envs_kernel.hpp) both state a fresh vehicle through here.
+template <typename Index>
+__device__ __forceinline__ void reset_draw(double L, int vary, uint64_t seed, uint64_t g, Index i, const double* x0,
+                                           const double* y0, const double* v0, double& x, double& y, double& v) {
+  if (x0) x = x0[i];
+  else {
+    const double Lf = floor(L);
+    x = floor(rng_unit(rng_u64(seed, 1, g)) * Lf);
+    if (x >= Lf) x = Lf - 1.0;
+  }
+  y = y0 ? y0[i] : 0.0;
+  if (v0) v = v0[i];
+  else v = vary ? 1.7 : 1.1 + rng_unit(rng_u64(seed, 2, g)) * (2.7 - 1.1);
+}
+
 __global__ void reset_kernel(int total, double L, int vary, uint64_t seed, uint64_t idx0, const double* x0,
                              const double* y0, const double* v0, double* pos_x, double* pos_y,
                              double* vel) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= total) return;
   double x, y, v;
-  if (x0) x = x0[i];
-  else {
-    const double Lf = floor(L);
-    x = floor(rng_unit(rng_u64(seed, 1, idx0 + (uint64_t)i)) * Lf);
-    if (x >= Lf) x = Lf - 1.0;
-  }
-  y = y0 ? y0[i] : 0.0;
-  if (v0) v = v0[i];
-  else v = vary ? 1.7 : 1.1 + rng_unit(rng_u64(seed, 2, idx0 + (uint64_t)i)) * (2.7 - 1.1);
+  reset_draw(L, vary, seed, idx0 + (uint64_t)i, i, x0, y0, v0, x, y, v);
   pos_x[i] = x; pos_y[i] = y; vel[i] = v;
 }
 

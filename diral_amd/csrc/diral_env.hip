@@ -19,6 +19,7 @@
 #include "observe_kernel.hpp"
 #include "piggyback_kernel.hpp"
 #include "posdist_kernel.hpp"
+#include "reset_envs_kernel.hpp"
 #include "step_params.hpp"
 
 using namespace diral;
@@ -751,7 +752,7 @@ const char* diral_env_strerror(int status) {
     case DIRAL_ERR_CAPTURE: return "call needs a ring <-> plane conversion and the stream is being captured into a hipGraph";
     case DIRAL_ERR_TABLE_CONFLICT: return "imported tables hold entries about one subject with equal sequence numbers but different xpos";
     case DIRAL_ERR_PIGGY_NO_TX: return "State.piggybacking: a receiver heard no transmitter on a used resource (the reference's prev_obs[None] KeyError)";
-    case DIRAL_ERR_ENV_INDEX: return "diral_env_copy_envs: an env index outside its handle (that pair was skipped)";
+    case DIRAL_ERR_ENV_INDEX: return "diral_env_copy_envs / diral_env_reset_envs: an env index outside its handle (that entry was skipped)";
     default: return "unknown status";
   }
 }
@@ -1411,6 +1412,41 @@ int diral_env_copy_envs(DiralEnv* dst, const int32_t* dst_index, DiralEnv* src, 
   dst->plane_valid = dst->plane_valid && src->plane_valid;
   dst->ring_valid = dst->ring_valid && src->ring_valid;
   dst->flat_y = dst->flat_y && src->flat_y;                       // (the non-flat instantiations are correct for flat data)
+  return DIRAL_OK;
+}
+
+int diral_env_reset_envs(DiralEnv* e, const int32_t* index, int32_t count, const uint8_t* mask, const double* x0,
+                         const double* y0, const double* v0, uint64_t seed, void* stream) {
+  if (!e || (index && mask)) return DIRAL_ERR_BAD_ARG;
+  if (!mask && count < 1) return DIRAL_ERR_BAD_ARG;
+  if (!mask && !index && count > e->B) return DIRAL_ERR_BAD_ARG;
+  // the slabs of copy_slabs other than the positions, each with the fill byte of its `own`
+  ResetPlan plan;
+  std::memset(&plan, 0, sizeof(plan));
+  for (const DevBuf& b : e->bufs) {
+    if (!b.reset_bytes || b.p == e->slow) continue;
+    if (plan.slabs == kCopyMaxSlabs) return DIRAL_ERR_UNSUPPORTED;   // (a bug in this file, as in copy_slabs)
+    const uint32_t bytes = (uint32_t)(b.reset_bytes / (size_t)e->B);
+    plan.slab[plan.slabs++] = {(char*)b.p, bytes, plan.units, 0x01010101u * (uint32_t)(b.fill & 0xFF)};
+    plan.units += copy_units(bytes);
+  }
+  DEVICE_ENTER(e->device);
+  hipStream_t s = (hipStream_t)stream;
+  // y0: `flat_y` is recomputed on the host behind the launch, which a capture cannot hold - refused with nothing enqueued
+  if (y0 && stream_is_capturing(s)) {
+    e->last_hip_error = "diral_env_reset_envs: y0 needs a host read-back of the lanes, which cannot be part of a stream capture";
+    return DIRAL_ERR_CAPTURE;
+  }
+  // Host flags stay as they are: an all-fill env is valid in the ring form and in the plane form alike (a fresh handle
+  // has both), so whichever form is current for the other envs is current for the listed ones too.
+  const int n = mask ? e->B : (int)count;
+  const uint32_t chunks = std::max(1u, (plan.units + kCopyChunk - 1) / kCopyChunk);
+  HIP_TRY(e, launch_k<reset_envs_kernel>(dim3(chunks, (uint32_t)std::min(n, 65535)), dim3(kCopyThreads), 0, s, plan, index, mask, n,
+                                         e->B, e->N, e->cfg.highway_length, has(&e->cfg, DIRAL_F_MOBILITY_VARY) ? 1 : 0, seed,
+                                         (uint64_t)e->env_offset * (uint64_t)e->N, x0, y0, v0, e->pos_x, e->pos_y, e->vel, e->err));
+  // without y0 the listed envs are on the lane: the flag stays true where it was, and where it was false the non-flat
+  // instantiations are correct for flat data (as in diral_env_copy_envs)
+  if (y0 && refresh_flat_y(e, s) != DIRAL_OK) return DIRAL_ERR_HIP;
   return DIRAL_OK;
 }
 

@@ -418,6 +418,48 @@ class VecV2VEnv:
         self._spec = None
         self._vel_calls = 0                     # default-seed velocity draws after a reset == those of a fresh env
 
+    def reset_envs(self, index=None, mask=None, count: Optional[int] = None, x0=None, y0=None, v0=None, seed: int = 0) -> None:
+        """Put SOME envs back to a fresh topology while the others go on (`diral_env_reset_envs`, include/diral_env.h):
+        every listed env b ends with exactly what ``reset_topology(x0, y0, v0, seed)`` leaves in env b of this handle -
+        zeroed tables in every stored form, arrival stamps, proportional-fair counters, metric sums, `prev_obs`, and row b
+        of `x0` / `y0` / `v0` or, where one is None, the device draws of the env's global index - as ONE launch.
+
+        `index`: a list, ndarray or int32 tensor of env indices (an int32 device tensor is passed straight through);
+        `mask`: a bool / uint8 device tensor [B], non-zero = reset this env (no `nonzero()`, no host round trip: the call
+        can follow a device-side criterion and sit in a captured graph, each replay reading the mask again); neither:
+        envs ``0 ... count - 1``.  `count` defaults to the length of `index`, else to B.  `x0` / `y0` / `v0` are shaped
+        [B, N] as in `reset_topology`; only the listed rows are read.  With `y0` the handle's flat-lane flag is recomputed
+        on the host: DiralError(ERR_CAPTURE) inside a stream capture.  An index outside [0, B) skips that env and makes the
+        next `check()` raise ERR_ENV_INDEX; duplicates are harmless.
+
+        Handle-wide and therefore left alone: the slot counter `t`, the default-seed counter of `update_velocity`, the
+        replay trace, the clock, the env offset.  The speculative state of the last `my_step*` describes tables that no
+        longer exist and is dropped, as in `copy_envs_from`.  State a caller keeps per env OUTSIDE the handle (an
+        `SpsPolicy`'s counters) is the caller's to re-initialise."""
+        if index is not None and mask is not None:
+            raise ValueError("reset_envs: give index or mask, not both")
+        shape = (self.B, self.N)
+        x0, y0, v0 = self._f64(x0, shape), self._f64(y0, shape), self._f64(v0, shape)
+        idx = self._index(index)
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask, device=self.device)
+            if m.dtype not in (torch.bool, torch.uint8) or tuple(m.shape) != (self.B,):
+                raise ValueError("reset_envs: mask must be a bool / uint8 tensor of shape [B=%d], got %s %s"
+                                 % (self.B, m.dtype, tuple(m.shape)))
+            m = m.contiguous()                                       # (bool is one byte, 0 / 1: read in place)
+        if count is None:
+            count = int(idx.numel()) if idx is not None else self.B
+        count = int(count)
+        if idx is not None and idx.numel() < count:
+            raise ValueError("reset_envs: the index array is shorter than count = %d" % count)
+        self._spec = None
+        self._last_actions = None
+        self._keep["reset_envs"] = (idx, m, x0, y0, v0)
+        st = self.lib.diral_env_reset_envs(self._h, _ptr(idx), count, _ptr(m), _ptr(x0), _ptr(y0), _ptr(v0), seed64(seed),
+                                           self._stream())
+        self._ok(st, "diral_env_reset_envs")
+
     def reset(self, x0=None, y0=None, v0=None, seed: int = 0, actions=None) -> torch.Tensor:
         """``reset() -> obs``.  The reference has no reset(); its driver
         bootstraps with ``action = env.sample(); obs, rews = env.my_step(action, 0);

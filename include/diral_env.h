@@ -420,6 +420,29 @@ int diral_env_import_entries(DiralEnv* env, const DiralNeighborEntry* entries, v
 int diral_env_copy_envs(DiralEnv* dst, const int32_t* dst_index, DiralEnv* src, const int32_t* src_index,
                         int32_t count, void* stream);
 
+/* ---- reset of a chosen subset of envs: index list or device mask --------------------------------------
+ * (additive within ABI 8; csrc/reset_envs_kernel.hpp)
+ * Every listed env b ends with exactly what diral_env_reset(env, x0, y0, v0, seed) leaves in env b of this handle; every
+ * other env is untouched.  ONE fill-and-draw launch over the listed envs' slabs in their stored form.
+ *   Which envs: `index` - a device array of `count` >= 1 env indices; or `mask` - a device array [B] of bytes, non-zero =
+ *     reset this env (`count` is ignored); or neither: envs 0 ... count - 1 (count <= B), as diral_env_copy_envs reads a
+ *     NULL index.
+ *   What a listed env gets: every slab diral_env_copy_envs moves, other than the positions, filled as at create (zero; the
+ *     arrival stamps -1) - tables in every stored form, arrival stamps, proportional-fair counters, metric sums, prev_obs;
+ *     pos_x / pos_y / vel from ROW b of x0 / y0 / v0 ([B][N] float64 device arrays indexed by env as in diral_env_reset;
+ *     only the listed rows are read), a NULL one from the device draws of diral_env_reset at the env's global index.
+ *   What it leaves alone: the slow-first sets (a dispatch-order hint), the validity of ring and plane (an all-fill env is
+ *     valid in both forms), the error flags, trace, clock, env offset, options.  The "every y == 0" flag is recomputed as
+ *     in diral_env_reset when y0 is given - that reads back to the host, so inside a stream capture the call returns
+ *     DIRAL_ERR_CAPTURE with nothing enqueued; without y0 the listed envs get y = 0, the flag stays as it was, and the
+ *     call only ENQUEUES: no host synchronisation, no allocation, capturable (a replay reads index / mask again).
+ *   DIRAL_ERR_BAD_ARG, checked first and without touching a device: a NULL handle; `index` and `mask` both given;
+ *     count < 1 without a mask; a NULL index with count larger than B.
+ *   An index outside [0, B): that env is skipped, the others are reset, and the sticky flag behind DIRAL_ERR_ENV_INDEX
+ *     is raised (diral_env_check).  Duplicate indices are allowed: every writer stores the same values. */
+int diral_env_reset_envs(DiralEnv* env, const int32_t* index, int32_t count, const uint8_t* mask,
+                         const double* x0, const double* y0, const double* v0, uint64_t seed, void* stream);
+
 /* ---- metrics ------------------------------------------------------------------ */
 
 /* out [B][DIRAL_M_COLUMNS] float64 device array; clear != 0 zeroes the
@@ -427,7 +450,7 @@ int diral_env_copy_envs(DiralEnv* dst, const int32_t* dst_index, DiralEnv* src, 
 int diral_env_metrics(DiralEnv* env, double* out, int clear, void* stream);
 
 /* Sticky device-side error flags (action range, sequence overflow, piggybacking without a transmitter, an env index
- * outside its handle in diral_env_copy_envs) raised by
+ * outside its handle in diral_env_copy_envs / diral_env_reset_envs) raised by
  * kernels since the last call.  SYNCHRONISES `stream`.  Returns DIRAL_OK or the
  * first error. */
 int diral_env_check(DiralEnv* env, void* stream);
