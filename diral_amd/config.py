@@ -42,6 +42,13 @@ STEP_DESIGN = 2
 
 DT_F32 = 0
 DT_F64 = 1
+DT_F16 = 2                   # the 16-bit kinds: DiralSelect.q_dtype only
+DT_BF16 = 3
+
+SELECT_GREEDY = 0            # DiralSelectKind (diral_policy_select)
+SELECT_EPS_GREEDY = 1
+SELECT_SOFTMAX = 2
+SELECT_BOLTZMANN = 3
 
 OPT_ENV_OFFSET = 1
 OPT_KERNEL_PATH = 2
@@ -191,6 +198,36 @@ class DiralSlotReplay(ctypes.Structure):
         ("T", ctypes.c_int32),
         ("per_env", ctypes.c_int32),
         ("xpos_out", ctypes.c_void_p),
+    ]
+
+
+class DiralSelect(ctypes.Structure):
+    """ctypes image of ``struct DiralSelect`` (include/diral_env.h): the one argument of ``diral_policy_select``."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("kind", ctypes.c_int32),
+        ("agents", ctypes.c_int32),
+        ("num_users", ctypes.c_int32),
+        ("num_channels", ctypes.c_int32),
+        ("q", ctypes.c_void_p),
+        ("q_dtype", ctypes.c_int32),
+        ("eps", ctypes.c_double),
+        ("tmp", ctypes.c_double),
+        ("beta", ctypes.c_double),
+        ("alpha", ctypes.c_double),
+        ("explore_p", ctypes.c_double),
+        ("param_dev", ctypes.c_void_p),
+        ("param_per_env", ctypes.c_int32),
+        ("draw_u", ctypes.c_void_p),
+        ("draw_a", ctypes.c_void_p),
+        ("seed", ctypes.c_uint64),
+        ("idx0", ctypes.c_uint64),
+        ("clock", ctypes.c_void_p),
+        ("clock_offset", ctypes.c_int64),
+        ("actions_out", ctypes.c_void_p),
+        ("explored_out", ctypes.c_void_p),
+        ("bad_rows", ctypes.c_void_p),
     ]
 
 

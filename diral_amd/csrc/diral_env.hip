@@ -20,6 +20,7 @@
 #include "piggyback_kernel.hpp"
 #include "posdist_kernel.hpp"
 #include "reset_envs_kernel.hpp"
+#include "select_kernel.hpp"
 #include "step_params.hpp"
 
 using namespace diral;
@@ -1655,6 +1656,52 @@ int diral_sps_init(int agents, int selection_window, int32_t* prev_action, int32
   if (agents < 1 || selection_window < 0 || !prev_action || !counter) return DIRAL_ERR_BAD_ARG;
   DEVICE_ENTER(prev_action);
   return hip_status(launch_1d<sps_init_kernel>((size_t)agents, (hipStream_t)stream, agents, selection_window, seed, prev_action, counter));
+}
+
+int diral_policy_select(const DiralSelect* s, void* stream) {
+  if (!s || s->struct_bytes != sizeof(DiralSelect) || !s->q || !s->actions_out) return DIRAL_ERR_BAD_ARG;
+  if (s->agents < 1 || s->num_channels < 1 || s->num_users < 1 || s->agents % s->num_users != 0) return DIRAL_ERR_BAD_ARG;
+  if (s->kind < DIRAL_SELECT_GREEDY || s->kind > DIRAL_SELECT_BOLTZMANN) return DIRAL_ERR_BAD_ARG;
+  if (s->q_dtype < DIRAL_F32 || s->q_dtype > DIRAL_BF16) return DIRAL_ERR_BAD_ARG;
+  if (s->kind == DIRAL_SELECT_SOFTMAX && !s->param_dev && !(s->tmp > 0.0 && std::isfinite(s->tmp))) return DIRAL_ERR_BAD_ARG;
+  if (s->param_per_env && !s->param_dev) return DIRAL_ERR_BAD_ARG;
+  if (s->num_channels > kSelMaxA) return DIRAL_ERR_UNSUPPORTED;
+  DEVICE_ENTER(s->q);
+  const int A = s->num_channels;
+  SelParams p{};
+  p.q = s->q; p.agents = s->agents; p.N = s->num_users; p.A = A;
+  while ((1 << p.gshift) < A || p.gshift < 2) ++p.gshift;          // lanes per row (A <= 64): the power of two >= A, at least 4
+  p.param = s->kind == DIRAL_SELECT_EPS_GREEDY ? s->eps : s->kind == DIRAL_SELECT_SOFTMAX ? s->tmp : s->explore_p;
+  p.beta = s->beta; p.alpha = s->alpha;
+  p.param_dev = s->kind == DIRAL_SELECT_GREEDY ? nullptr : s->param_dev; p.param_per_env = s->param_per_env;
+  p.draw_u = s->draw_u; p.draw_a = s->draw_a; p.seed = s->seed; p.idx0 = s->idx0;
+  p.clock = (const long long*)s->clock; p.clock_offset = (long long)s->clock_offset;
+  p.actions_out = s->actions_out; p.explored_out = s->explored_out; p.bad_rows = s->bad_rows;
+  const hipStream_t st = (hipStream_t)stream;
+  auto launch = [&](auto tag, auto kind) {
+    using QT = decltype(tag);
+    constexpr int KIND = decltype(kind)::value;
+    if (A > 64) {
+      const uint32_t lds = (KIND == kSelSoftmax || KIND == kSelBoltzmann) ? (uint32_t)A * 8u : 0u;
+      return launch_k<select_actions_wide_kernel<QT, KIND>>(dim3((uint32_t)p.agents), dim3(64), lds, st, p);
+    }
+    const size_t waves = ((size_t)p.agents + (64u >> p.gshift) - 1) >> (6 - p.gshift);
+    return launch_k<select_actions_kernel<QT, KIND>>(dim3(blocks(waves * 64, kSelBlock)), dim3(kSelBlock), 0, st, p);
+  };
+  auto by_q = [&](auto kind) {
+    switch (s->q_dtype) {
+      case DIRAL_F64: return launch(double{}, kind);
+      case DIRAL_F32: return launch(float{}, kind);
+      case DIRAL_F16: return launch(_Float16{}, kind);
+      default: return launch(bf16_bits{}, kind);
+    }
+  };
+  switch (s->kind) {
+    case DIRAL_SELECT_GREEDY: return hip_status(by_q(std::integral_constant<int, kSelGreedy>{}));
+    case DIRAL_SELECT_EPS_GREEDY: return hip_status(by_q(std::integral_constant<int, kSelEpsGreedy>{}));
+    case DIRAL_SELECT_SOFTMAX: return hip_status(by_q(std::integral_constant<int, kSelSoftmax>{}));
+    default: return hip_status(by_q(std::integral_constant<int, kSelBoltzmann>{}));
+  }
 }
 
 int diral_env_check(DiralEnv* e, void* stream) {

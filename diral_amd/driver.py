@@ -147,6 +147,17 @@ class DriverLoop:
             states.append(self.prefill_step(a))
         return torch.stack(states), torch.stack(acts)
 
+    # main_test.py:127-136: where a slot's actions come from
+    def act(self, q, time_step: int, episode: int, policy: Any, explore_step: int, greedy_step: int) -> torch.Tensor:
+        """The three-way choice of the reference's slot loop: uniform draws (``policy="explore"``, `env.sample`) while
+        `time_step` < `explore_step`, the exploration policy over the Q-values `q` [B, N, A] (`policy.act`, a
+        :class:`QPolicy`) while `time_step` < `greedy_step`, ``np.argmax`` (``policy="greedy"``) behind it."""
+        if time_step < explore_step:
+            return self.env.sample()
+        if time_step < greedy_step:
+            return policy.act(q, episode=episode, time_slot=time_step)
+        return policy.greedy(q)
+
     # main_test.py:119-236, everything between the agent's action and memory.add
     def slot(self, action, time_step: int, want_ia: Optional[bool] = None) -> Dict[str, Any]:
         env = self.env

@@ -132,7 +132,7 @@ typedef enum DiralStepMode {
 
 /* element type of the floating-point OUTPUT buffers (state, reward, chobs).
  * The arithmetic is always float64, like the reference; F32 is a final cast. */
-typedef enum DiralDType { DIRAL_F32 = 0, DIRAL_F64 = 1 } DiralDType;
+typedef enum DiralDType { DIRAL_F32 = 0, DIRAL_F64 = 1, DIRAL_F16 = 2, DIRAL_BF16 = 3 } DiralDType;   /* the 16-bit kinds: DiralSelect::q_dtype only */
 
 /* limits of this build (the reference has none: TestEnv takes any N, A and State.num_bins, test_env.py:12-13, 40).
  * The specialised kernels (csrc/step_fast64.hpp, step_wide.hpp: every number bench.py reports) serve num_users <= 256
@@ -736,6 +736,54 @@ int diral_sps_step_chobs_clocked(int agents, int num_channels, const void* chobs
                                  const int32_t* actions, int32_t* prev_action, int32_t* counter,
                                  double rssi_threshold, double inc_db, double keep_prob, uint64_t seed,
                                  const int64_t* clock, int32_t* actions_out, void* stream);
+
+/* ---- actions from Q-values: the exploration policies of algorithms/policies.py ---------------------
+ * diral_policy_select: actions_out[i] for agents = B * N rows of num_channels Q-values, ONE launch, handle-free like
+ * diral_sps_*.  Every Q-value (q_dtype: DIRAL_F64 / F32 / F16 / BF16) is converted exactly to float64; all arithmetic
+ * is float64 in NumPy's order.
+ *   DIRAL_SELECT_GREEDY (policies.py:24-35): np.argmax - the first index of the maximum (-0.0 == +0.0), the first NaN
+ *     of a row that holds one, 0 for a row of -inf.
+ *   DIRAL_SELECT_EPS_GREEDY (:45-54): draw_u > eps -> greedy, else draw_a % A.
+ *   DIRAL_SELECT_SOFTMAX (:92-112, np.random.choice(p=)): x = q / tmp; x -= max(x); y = exp(x); p = y / np.sum(y);
+ *     cdf = cumsum(p) sequentially; cdf /= cdf[A - 1]; the action is the number of cdf[j] <= draw_u, at most A - 1.  A row
+ *     the reference raises on (a NaN, a +inf, nothing but -inf) is answered by the GREEDY rule and counted in *bad_rows.
+ *   DIRAL_SELECT_BOLTZMANN (:144-178): explore_p > draw_u -> draw_a % A, else
+ *     argmax((1 - alpha) * exp(beta * q) / np.sum(exp(beta * q)) + alpha / A) as written (inf / inf is NaN: the first one).
+ * draw_u [agents] float64 in [0, 1) / draw_a [agents] int32 >= 0: injected draws; NULL: the device generator at
+ * (seed, stream 10 / 11, idx0 + i), idx0 = the caller's DIRAL_OPT_ENV_OFFSET * num_users - shards of a batch draw what
+ * the whole batch draws.  clock != NULL: the launch draws with seed + clock_offset + *clock (a device counter, see
+ * diral_clock_add), so a replayed graph draws afresh.  param_dev != NULL: the kind's parameter (eps / tmp / explore_p)
+ * is read from device memory instead - one float64, or one per env ([agents / num_users], param_per_env != 0); a tmp
+ * read there is not checked.  explored_out (uint8 [agents], 1 where the exploring branch chose) and bad_rows (int32,
+ * added to) may be NULL.
+ * DIRAL_ERR_BAD_ARG, before any device is touched: a NULL struct / q / actions_out, a wrong struct_bytes, agents < 1,
+ * num_channels < 1, agents no multiple of num_users, an unknown kind or dtype, a by-value tmp that is not finite and
+ * > 0 (SOFTMAX), param_per_env without param_dev.  DIRAL_ERR_UNSUPPORTED: num_channels > 4096. */
+typedef enum DiralSelectKind {
+  DIRAL_SELECT_GREEDY = 0, DIRAL_SELECT_EPS_GREEDY = 1, DIRAL_SELECT_SOFTMAX = 2, DIRAL_SELECT_BOLTZMANN = 3
+} DiralSelectKind;
+typedef struct DiralSelect {
+  uint32_t struct_bytes;       /* sizeof(DiralSelect) */
+  int32_t kind;                /* DiralSelectKind */
+  int32_t agents;              /* B * N */
+  int32_t num_users;
+  int32_t num_channels;
+  const void* q;               /* [agents][num_channels], contiguous */
+  int32_t q_dtype;             /* DiralDType */
+  double eps, tmp, beta, alpha, explore_p;
+  const double* param_dev;
+  int32_t param_per_env;
+  const double* draw_u;
+  const int32_t* draw_a;
+  uint64_t seed;
+  uint64_t idx0;
+  const int64_t* clock;
+  int64_t clock_offset;
+  int32_t* actions_out;
+  uint8_t* explored_out;
+  int32_t* bad_rows;
+} DiralSelect;
+int diral_policy_select(const DiralSelect* s, void* stream);
 
 /* Replaces SemiPersistentScheduling.__init__ (v2x_sps.py:8-22): prev_action =
  * randint(0, selection_window) (inclusive, as in the reference), counter =
