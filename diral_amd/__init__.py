@@ -8,8 +8,8 @@ interface.  See DESIGN.md.
 from .config import (ConfigError, EnvConfig, StateConfig, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH,
                      bench_config, c2_config)
 
-__all__ = ["EnvConfig", "StateConfig", "ConfigError", "VecV2VEnv", "StreamedVecEnv", "TestEnv", "QPolicy", "bench_config", "c2_config",
-           "STEP_MY_STEP", "STEP_MY_STEP_CH", "STEP_DESIGN"]
+__all__ = ["EnvConfig", "StateConfig", "ConfigError", "VecV2VEnv", "StreamedVecEnv", "TestEnv", "QPolicy", "ReplayMemory",
+           "bench_config", "c2_config", "STEP_MY_STEP", "STEP_MY_STEP_CH", "STEP_DESIGN"]
 
 
 def __getattr__(name):
@@ -24,6 +24,9 @@ def __getattr__(name):
     if name == "QPolicy":
         from .qpolicy import QPolicy
         return QPolicy
+    if name == "ReplayMemory":
+        from .memory import ReplayMemory
+        return ReplayMemory
     if name == "TestEnv":
         from .compat import TestEnv
         return TestEnv

@@ -29,7 +29,7 @@ SYMBOLS = [
     "diral_env_export_prev_obs", "diral_env_import_prev_obs", "diral_env_prefill", "diral_env_prefill_mode",
     "diral_env_rollout", "diral_env_copy_envs", "diral_env_rollout_ia", "diral_env_step_policy_ia",
     "diral_env_rollout_replay", "diral_env_step_policy_replay", "diral_env_subwave_ok", "diral_env_reset_envs",
-    "diral_policy_select",
+    "diral_policy_select", "diral_memory_add", "diral_memory_sample",
 ]
 
 _lib = None
@@ -107,6 +107,8 @@ def load() -> ctypes.CDLL:
         "diral_env_rollout_replay": (I, [P, I, P, I, I64, P, I, P, P, I, P, P, P, P]),
         "diral_env_step_policy_replay": (I, [P, I, P, I64, P, P, P, P, I, P, P, P, P]),
         "diral_policy_select": (I, [P, P]),
+        "diral_memory_add": (I, [P, P, P]),
+        "diral_memory_sample": (I, [P, P, P]),
     }
     for name in SYMBOLS:
         try:

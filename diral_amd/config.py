@@ -231,6 +231,64 @@ class DiralSelect(ctypes.Structure):
     ]
 
 
+class DiralMemory(ctypes.Structure):
+    """ctypes image of ``struct DiralMemory`` (include/diral_env.h): the rings of a replay memory."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("capacity", ctypes.c_int32),
+        ("batch", ctypes.c_int32),
+        ("num_users", ctypes.c_int32),
+        ("state_space", ctypes.c_int32),
+        ("dtype", ctypes.c_int32),
+        ("states", ctypes.c_void_p),
+        ("actions", ctypes.c_void_p),
+        ("rewards", ctypes.c_void_p),
+        ("count", ctypes.c_int64),
+        ("count_dev", ctypes.c_void_p),
+    ]
+
+
+class DiralMemoryAdd(ctypes.Structure):
+    """ctypes image of ``struct DiralMemoryAdd``: the second argument of ``diral_memory_add``."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("slots", ctypes.c_int32),
+        ("next_states", ctypes.c_void_p),
+        ("state0", ctypes.c_void_p),
+        ("src_dtype", ctypes.c_int32),
+        ("rewards_dtype", ctypes.c_int32),
+        ("actions", ctypes.c_void_p),
+        ("rewards", ctypes.c_void_p),
+        ("rewards_broadcast", ctypes.c_int32),
+    ]
+
+
+class DiralMemorySample(ctypes.Structure):
+    """ctypes image of ``struct DiralMemorySample``: the second argument of ``diral_memory_sample``."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("windows", ctypes.c_int32),
+        ("step", ctypes.c_int32),
+        ("out_dtype", ctypes.c_int32),
+        ("last_only", ctypes.c_int32),
+        ("idx", ctypes.c_void_p),
+        ("env", ctypes.c_void_p),
+        ("seed", ctypes.c_uint64),
+        ("clock", ctypes.c_void_p),
+        ("clock_offset", ctypes.c_int64),
+        ("states_out", ctypes.c_void_p),
+        ("next_states_out", ctypes.c_void_p),
+        ("actions_out", ctypes.c_void_p),
+        ("rewards_out", ctypes.c_void_p),
+        ("idx_out", ctypes.c_void_p),
+        ("env_out", ctypes.c_void_p),
+        ("bad_samples", ctypes.c_void_p),
+    ]
+
+
 class ConfigError(ValueError):
     """A config the reference itself cannot run, or one this build rejects."""
 

@@ -16,6 +16,7 @@
 #include "common.hpp"
 #include "copy_envs_kernel.hpp"
 #include "launch.hpp"
+#include "memory_kernel.hpp"
 #include "observe_kernel.hpp"
 #include "piggyback_kernel.hpp"
 #include "posdist_kernel.hpp"
@@ -258,6 +259,23 @@ hipError_t launch_1d(size_t total, hipStream_t s, Args... args) {
 // run-time DIRAL_F32 / DIRAL_F64 -> the element type, handed to `f` as a value of it
 template <typename F>
 hipError_t by_dtype(int dtype, F&& f) { return dtype == DIRAL_F64 ? f(double{}) : f(float{}); }
+// VEC of the memory kernels: the widest of 4 / 2 / 1 elements per lane that `values` per block and the addresses allow
+int mem_vec(long long values, size_t elem, std::initializer_list<const void*> ptrs) {
+  for (int v = 4; v > 1; v >>= 1) {
+    bool ok = values % v == 0;
+    for (const void* q : ptrs) ok = ok && (q == nullptr || (uintptr_t)q % (elem * v) == 0);
+    if (ok) return v;
+  }
+  return 1;
+}
+template <typename F>
+hipError_t by_vec(int vec, F&& f) {
+  return vec == 4 ? f(std::integral_constant<int, 4>{}) : vec == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 1>{});
+}
+bool memory_ok(const DiralMemory* m) {
+  return m && m->struct_bytes == sizeof(DiralMemory) && m->states && m->actions && m->rewards && m->capacity >= 1 && m->batch >= 1 &&
+         m->num_users >= 1 && m->state_space >= 1 && (m->dtype == DIRAL_F32 || m->dtype == DIRAL_F64) && (m->count_dev || m->count >= 0);
+}
 
 // State flags that only add OUTPUT columns to the state vector (test_env.py:527-583): served
 // by the RICH instantiations of the specialised kernels (rich_out.hpp)
@@ -1702,6 +1720,72 @@ int diral_policy_select(const DiralSelect* s, void* stream) {
     case DIRAL_SELECT_SOFTMAX: return hip_status(by_q(std::integral_constant<int, kSelSoftmax>{}));
     default: return hip_status(by_q(std::integral_constant<int, kSelBoltzmann>{}));
   }
+}
+
+int diral_memory_add(const DiralMemory* m, const DiralMemoryAdd* a, void* stream) {
+  if (!memory_ok(m) || !a || a->struct_bytes != sizeof(DiralMemoryAdd)) return DIRAL_ERR_BAD_ARG;
+  if (a->slots < 1 || a->slots > m->capacity || !a->next_states || !a->actions || !a->rewards) return DIRAL_ERR_BAD_ARG;
+  if ((a->src_dtype != DIRAL_F32 && a->src_dtype != DIRAL_F64) || (a->rewards_dtype != DIRAL_F32 && a->rewards_dtype != DIRAL_F64))
+    return DIRAL_ERR_BAD_ARG;
+  DEVICE_ENTER(m->states);
+  MemAddParams p{};
+  p.states = m->states; p.actions = m->actions; p.rewards = m->rewards;
+  p.C = m->capacity; p.K = a->slots;
+  p.BN = (long long)m->batch * m->num_users; p.BNS = p.BN * m->state_space;
+  p.count = (long long)m->count; p.count_dev = (const long long*)m->count_dev;
+  p.next_states = a->next_states; p.state0 = a->state0; p.a_in = a->actions; p.r_in = a->rewards;
+  p.r_f64 = a->rewards_dtype == DIRAL_F64; p.r_bcast = a->rewards_broadcast != 0;
+  const size_t es = a->src_dtype == DIRAL_F64 ? 8 : 4, er = m->dtype == DIRAL_F64 ? 8 : 4;
+  const int vec = std::min(mem_vec(p.BNS, es, {a->next_states, a->state0}), mem_vec(p.BNS, er, {m->states}));
+  const int ny = p.K + (p.state0 ? 1 : 0);
+  const dim3 grid((uint32_t)std::min<size_t>(blocks((size_t)p.BNS / vec, kMemBlock), 4096), (uint32_t)std::min(ny, 65535));
+  const hipStream_t st = (hipStream_t)stream;
+  return hip_status(by_dtype(a->src_dtype, [&](auto src) {
+    return by_dtype(m->dtype, [&](auto ring) {
+      return by_vec(vec, [&](auto v) {
+        return launch_k<memory_add_kernel<decltype(src), decltype(ring), decltype(v)::value>>(grid, dim3(kMemBlock), 0, st, p);
+      });
+    });
+  }));
+}
+
+int diral_memory_sample(const DiralMemory* m, const DiralMemorySample* s, void* stream) {
+  if (!memory_ok(m) || !s || s->struct_bytes != sizeof(DiralMemorySample)) return DIRAL_ERR_BAD_ARG;
+  if (s->step < 1 || s->windows < 1 || (s->idx == nullptr) != (s->env == nullptr)) return DIRAL_ERR_BAD_ARG;
+  if (!m->count_dev) {
+    const long long len = std::min<long long>(m->count, m->capacity);
+    if (len <= s->step) return DIRAL_ERR_BAD_ARG;
+    if (!s->idx && (long long)s->windows > (len - s->step) * m->batch) return DIRAL_ERR_BAD_ARG;
+  }
+  const bool f64 = m->dtype == DIRAL_F64;
+  const int od = s->out_dtype;
+  if (f64 ? (od != DIRAL_F64 && od != DIRAL_F32) : (od != DIRAL_F32 && od != DIRAL_F16 && od != DIRAL_BF16)) return DIRAL_ERR_UNSUPPORTED;
+  const long long NS = (long long)m->num_users * m->state_space;
+  if (NS > 0x7fffffffLL || ((long long)s->windows + 8) * (s->step + 1LL) > 0x7fffffffLL) return DIRAL_ERR_UNSUPPORTED;
+  DEVICE_ENTER(m->states);
+  MemSampleParams p{};
+  p.states = m->states; p.actions = m->actions; p.rewards = m->rewards;
+  p.C = m->capacity; p.B = m->batch; p.N = m->num_users; p.S = m->state_space;
+  p.count = (long long)m->count; p.count_dev = (const long long*)m->count_dev;
+  p.M = s->windows; p.step = s->step; p.last_only = s->last_only != 0;
+  p.idx = s->idx; p.env = s->env; p.seed = s->seed; p.clock = (const long long*)s->clock; p.clock_offset = (long long)s->clock_offset;
+  p.states_out = s->states_out; p.next_out = s->next_states_out; p.actions_out = s->actions_out; p.rewards_out = s->rewards_out;
+  p.idx_out = s->idx_out; p.env_out = s->env_out; p.bad = s->bad_samples;
+  const size_t er = f64 ? 8 : 4, eo = od == DIRAL_F64 ? 8 : od == DIRAL_F32 ? 4 : 2;
+  const int vec = mem_vec(NS, er, {m->states});
+  p.vst = vec > 1 && mem_vec(m->state_space, eo, {s->states_out, s->next_states_out}) >= vec;
+  p.ushift = NS / vec <= 256 ? 6 : 8;                               // a wave per item up to four loads per lane
+  // per XCD: the items of ceil(M / 8) windows, kMemBlock >> ushift of them to a workgroup (memory_kernel.hpp)
+  const size_t per_xcd = ((size_t)s->windows + 7) / 8 * ((size_t)s->step + 1), ipb = (size_t)(kMemBlock >> p.ushift);
+  const dim3 grid((uint32_t)(8 * ((per_xcd + ipb - 1) / ipb)));
+  const hipStream_t st = (hipStream_t)stream;
+  auto launch = [&](auto ring, auto out) {
+    return by_vec(vec, [&](auto v) {
+      return launch_k<memory_sample_kernel<decltype(ring), decltype(out), decltype(v)::value>>(grid, dim3(kMemBlock), 0, st, p);
+    });
+  };
+  if (f64) return hip_status(od == DIRAL_F64 ? launch(double{}, double{}) : launch(double{}, float{}));
+  return hip_status(od == DIRAL_F32 ? launch(float{}, float{}) : od == DIRAL_F16 ? launch(float{}, _Float16{}) : launch(float{}, bf16_bits{}));
 }
 
 int diral_env_check(DiralEnv* e, void* stream) {

@@ -785,6 +785,89 @@ typedef struct DiralSelect {
 } DiralSelect;
 int diral_policy_select(const DiralSelect* s, void* stream);
 
+/* ---- replay memory: Memory of utils/memory.py:162-194 for B envs, and the regrouping of drl_drqn.py:294-377 --------
+ * Handle-free like diral_policy_select: the caller owns three rings of capacity + 1 rows and describes them here.
+ *   states  [capacity + 1][batch][num_users][state_space]   dtype (DIRAL_F32 / DIRAL_F64)
+ *   actions [capacity + 1][batch][num_users]                int32
+ *   rewards [capacity + 1][batch][num_users]                dtype
+ * The driver always has state = next_state (main_test.py:113, 217), so a state is stored once: logical state j lives in
+ * row j mod (capacity + 1), transition j (state j -> j + 1) keeps its action and reward in row j mod (capacity + 1).
+ * With `count` transitions added so far the live ones are j in [count - len, count), len = min(count, capacity) - the
+ * deque's maxlen.  count is the host value below, or *count_dev (device memory, read by the kernels) when that is given;
+ * the caller moves it on behind an add (diral_clock_add(count_dev, slots)). */
+typedef struct DiralMemory {
+  uint32_t struct_bytes;       /* sizeof(DiralMemory) */
+  int32_t capacity;            /* C >= 1 */
+  int32_t batch, num_users, state_space;
+  int32_t dtype;               /* DiralDType of states and rewards: DIRAL_F32 / DIRAL_F64 */
+  void* states;
+  int32_t* actions;
+  void* rewards;
+  int64_t count;               /* transitions added so far (>= 0); not read when count_dev != NULL */
+  const int64_t* count_dev;
+} DiralMemory;
+
+/* diral_memory_add: ONE launch writes `slots` = K transitions: next_states[k] into state row (count + 1 + k), actions[k]
+ * and rewards[k] into row (count + k), all mod (capacity + 1) - across the wrap.  state0 != NULL (the first call after a
+ * begin): written to state row count.  src_dtype / rewards_dtype: DIRAL_F32 / DIRAL_F64 of next_states + state0 / of
+ * rewards; float64 into a float32 ring is rounded to nearest, float32 into a float64 ring is exact.  rewards_broadcast
+ * != 0: rewards is ONE [batch][num_users] row stored for every slot (the prefill's stale bootstrap rewards,
+ * main_test.py:110-112).  The count itself is the caller's to move on.
+ * DIRAL_ERR_BAD_ARG, before any device is touched: a NULL struct / ring / source, a wrong struct_bytes, capacity, batch,
+ * num_users or state_space < 1, count < 0, slots < 1, slots > capacity, an unknown dtype. */
+typedef struct DiralMemoryAdd {
+  uint32_t struct_bytes;       /* sizeof(DiralMemoryAdd) */
+  int32_t slots;               /* K */
+  const void* next_states;     /* [K][batch][num_users][state_space] */
+  const void* state0;          /* [batch][num_users][state_space] or NULL */
+  int32_t src_dtype;
+  int32_t rewards_dtype;
+  const int32_t* actions;      /* [K][batch][num_users] */
+  const void* rewards;         /* [K][batch][num_users], or [batch][num_users] (rewards_broadcast) */
+  int32_t rewards_broadcast;
+} DiralMemoryAdd;
+int diral_memory_add(const DiralMemory* m, const DiralMemoryAdd* a, void* stream);
+
+/* diral_memory_sample: `windows` = M windows of `step` consecutive transitions as ONE launch, regrouped user-major as
+ * DRQN.get_states_user and the three like it leave them (row n * M + m):
+ *   states_out, next_states_out [num_users * M][step][state_space]  out_dtype
+ *   actions_out [num_users * M][step] int32, rewards_out [num_users * M][step] ring dtype
+ *   last_only != 0: actions_out / rewards_out [num_users * M], the last step only (drl_drqn.py:255, 288)
+ * Any output may be NULL.  out_dtype: F32 ring -> DIRAL_F32 / F16 / BF16 (one round-to-nearest-even from float32), F64
+ * ring -> DIRAL_F64 / F32; any other pair is DIRAL_ERR_UNSUPPORTED.  Each of a window's step + 1 state rows is read once.
+ * Window m is (env b, start i), i in [0, L), L = len - step (np.arange(len(buffer) - step_size): the last start is
+ * excluded as there); it covers the logical transitions count - len + i + s, s < step.
+ *   Injected: idx [M] and env [M] (int32, device).  A start outside [0, L) or an env outside [0, batch) makes that
+ *   window's outputs zeros and adds one to *bad_samples; nothing out of bounds is read.
+ *   Drawn (idx == env == NULL): distinct by construction over the R = batch * L pairs: v = P(m), b = v mod batch,
+ *   i = v div batch, P a cycle-walking 4-round Feistel permutation of [0, R) on 2 w bits, w = max(1, ceil(ceil_log2(R)
+ *   / 2)): (l, r) -> (r, l ^ (rng(seed', round, r) & (2^w - 1))), applied again while the value is >= R; rng is the
+ *   generator of diral_env_sample, seed' = seed (+ clock_offset + *clock when clock != NULL: a replayed graph draws
+ *   afresh).  idx_out / env_out [M] (may be NULL) receive the windows, so that a run can be replayed by injection.
+ * DIRAL_ERR_BAD_ARG, before any device is touched: a NULL struct, a wrong struct_bytes, step < 1, windows < 1, a host
+ * count with len <= step, drawn windows > R, idx without env or env without idx.  With count_dev the kernel applies the
+ * last two itself: every window is zeros and counted in *bad_samples. */
+typedef struct DiralMemorySample {
+  uint32_t struct_bytes;       /* sizeof(DiralMemorySample) */
+  int32_t windows;             /* M */
+  int32_t step;
+  int32_t out_dtype;           /* DiralDType of states_out / next_states_out */
+  int32_t last_only;
+  const int32_t* idx;
+  const int32_t* env;
+  uint64_t seed;
+  const int64_t* clock;
+  int64_t clock_offset;
+  void* states_out;
+  void* next_states_out;
+  int32_t* actions_out;
+  void* rewards_out;
+  int32_t* idx_out;
+  int32_t* env_out;
+  int32_t* bad_samples;
+} DiralMemorySample;
+int diral_memory_sample(const DiralMemory* m, const DiralMemorySample* s, void* stream);
+
 /* Replaces SemiPersistentScheduling.__init__ (v2x_sps.py:8-22): prev_action =
  * randint(0, selection_window) (inclusive, as in the reference), counter =
  * randint(5, 15); device RNG from `seed`. */
