@@ -1,4 +1,5 @@
-// k_subwave.hip - the sub-wave step kernel (step_subwave.hpp): N <= 8, 4 or 8 lanes per env, DIRAL_PATH_SUBWAVE only.
+// k_subwave.hip - the sub-wave step kernel (step_subwave.hpp): N <= 8, 4 or 8 lanes per env, DIRAL_PATH_SUBWAVE only.  That
+// header also holds the slot's phases for the K-slot kernel of k_subwave_slots.hip.
 #include "launch.hpp"
 #include "step_subwave.hpp"
 

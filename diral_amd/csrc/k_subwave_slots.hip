@@ -1,6 +1,6 @@
 // k_subwave_slots.hip - K slots per launch of the sub-wave step (step_subwave_slots.hpp): N <= 8, 4 or 8 lanes per env,
-// handles pinned to DIRAL_PATH_SUBWAVE with DIRAL_OPT_SUBWAVE_SLOTS.  A translation unit of its own: k_subwave.hip is
-// compiled from the text it had.
+// handles pinned to DIRAL_PATH_SUBWAVE with DIRAL_OPT_SUBWAVE_SLOTS.  The slot's phases are the one-slot kernel's
+// (step_subwave.hpp); a translation unit of its own, so that the two kernels compile in parallel.
 #include "launch.hpp"
 #include "step_subwave_slots.hpp"
 

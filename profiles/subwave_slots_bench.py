@@ -11,8 +11,10 @@ add_action + the type-2 piggybacked histogram), float32 outputs, K = 25, global_
 of sample + step + observe.  Every launch must leave what the parent's loop leaves (`equal_to_parent_loop`: exported state,
 metrics, shaped rewards, sums, states).
 
-The guard for what exists: the one-slot sub-wave step at B = 65 536, the parent's library against this one, interleaved
-(`slower_than_parent`; the 2 % band of item 16).
+The guards for what exists, the parent's library against this one, interleaved, at B = 65 536 (`slower_than_parent`; the
+2 % band of item 16; `equal_to_parent`: exported state, metrics and every output): the one-slot sub-wave step, and the
+K-slot launch itself - `rollout` of K = 25 `my_step` slots with states last, and `prefill` - on two handles pinned with
+`use_subwave_path(slots=True)`.
 
   python profiles/subwave_slots_bench.py --parent-lib /path/to/parent/libdiral_env.so [--rounds 7] [--warm 2] [--out FILE]
 """
@@ -181,6 +183,44 @@ def run_guard(B, parent, rounds, warm, slots=50):
     return out
 
 
+def run_guard_slots(B, parent, rounds, warm, what):
+    """The K-slot launch (`what`: "rollout" of my_step with states last, or "prefill"), the parent's library against this one."""
+    envs = [("launch (parent)", make_env(B, parent, True)), ("launch", make_env(B, None, True))]
+    if what == "rollout":
+        seq = torch.stack([envs[1][1].sample(4000 + k) for k in range(K)])
+
+        def body(f):
+            out = f["env"].rollout(seq, f["t"], mode="my_step", states="last", global_reward_avg=True)
+            f["t"] += K
+            f["out"] = [out[k] for k in ("shaped", "sum_r", "collision", "states", "reward", "done") if out[k] is not None]
+    else:
+        a0 = envs[1][1].sample(123)
+        for _, env in envs:
+            _, rew, _ = env._step(STEP_MY_STEP, a0, 0)
+            rews0 = rew.to(torch.float64).clone()
+
+        def body(f):
+            env = f["env"]
+            f["out"] = list(env.prefill(env.sample(f["t"]), K, f["t"], rew_in=rews0))   # states, actions of every slot, next draw
+            f["t"] += K
+
+    forms = [dict(form=name, env=env, t=0 if what == "rollout" else 77001, ms=[], body=body) for name, env in envs]
+    timed(forms, rounds, warm)
+    for f in forms:
+        assert f["env"].last_kernel() == (KERNEL_SUBWAVE | KERNEL_POLICY), f["env"].last_kernel()
+        f["env"].check()
+    us, rnd = medians(forms)
+    p, x = forms
+    equal = same_env(p["env"], x["env"]) and all(torch.equal(a, b) for a, b in zip(p["out"], x["out"]))
+    name = "my_step states=last rollout" if what == "rollout" else "prefill my_step_design"
+    out = {"config": "4ue_3r_toy %s, K slots per launch (guard)" % name, "B": B, "slots_per_round": K, "rounds": rounds,
+           "us_per_slot": us, "us_per_slot_rounds": rnd, "equal_to_parent": bool(equal),
+           "slower_than_parent": round(us["launch"] / us["launch (parent)"] - 1.0, 4)}
+    del forms, envs
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent-lib", required=True)
@@ -205,6 +245,8 @@ def main():
             show(run_rollout(int(b), mode, states, parent, args.rounds, args.warm), "launch_vs_loop")
         show(run_prefill(int(b), parent, args.rounds, args.warm), "launch_vs_loop")
     show(run_guard(65536, parent, args.rounds, args.warm), "slower_than_parent")
+    for what in ("rollout", "prefill"):
+        show(run_guard_slots(65536, parent, args.rounds, args.warm, what), "slower_than_parent")
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:
