@@ -570,6 +570,13 @@ int f32_margin16(double L, double Rb, int K, int hook) {
   // (the kernel computes t = fma(float(xpos), float(inv_w 2^16), float((Rb - npx) inv_w 2^16)): the conversion of the
   // stamp and of the factor lose 2 |xpos| 2^-24 / w bin widths, the addend's |Rb - npx| 2^-24 / w <= (xmax + Rb) 2^-24 / w,
   // the fma's own rounding K 2^-24)
+  // The margin itself rides in the addend: the kernel forms float((Rb - npx) inv_w 2^16 + m) and
+  // the fma yields t + m.  m / 65536 is at most 1 / 4 bin width (the hook stops at 16384), so the addend's conversion loses
+  // at most 2^-26 bin widths more and the fma rounds a sum of at most K + 1 / 4: (K + 1 / 2) 2^-24 in all where the term
+  // below allows 4 K 2^-24 before its factor of two - for every K >= 1 the larger addend is covered with the bound as it
+  // was, and the bands (and the lists derived from them in tests/hist_edge_cases.py) stay what they are.  Truncation: for
+  // t >= 0 trunc(t + m) == trunc(t) + m; for t in (-m - 1, 0) the two differ by at most one and both lie in [0, m] - in
+  // range and inside the band, left to float64 either way.
   const double lost = 2.0 * (((3.0 * xmax + Rb) * 0x1p-24) / w + 2.0 * (double)K * 0x1p-23);
   const double m = std::ceil(lost * 65536.0) + 1.0;
   const bool on = m <= 64.0 && xmax < 1e6 && hook != 0;

@@ -62,8 +62,9 @@ __host__ __device__ constexpr int fast_hist_stride(int K) { return (K + 1) | 1; 
 // merge reads the sources of FOUR consecutive resources with one ds_read_b32; the row stride of a32 + 4 bytes = 9 / 17
 // words puts the 64 lanes' words - read by the merge, written by P1 a group at a time, lane = row - on distinct banks
 __host__ __device__ constexpr int fast_mtab_stride(int A) { return (A <= 32 ? 32 : 64) + 4; }
-__host__ __device__ inline FastLds fast_lds_layout(int K, int A, bool rich, bool out64, bool flat, bool ratios = true, bool pol = false,
-                                                     bool ia = false) {
+// The order the slot loops (step_fast64_slots_kernel, `pol`) keep, K- and A-sized arrays in front: their text is the parent's
+// (step_fast64_body.inc), and so is what they are compiled to.
+__host__ __device__ inline FastLds fast_lds_layout_slots(int K, int A, bool rich, bool out64, bool flat, bool ratios, bool ia) {
   FastLds l;
   uint32_t o = 0;
   const uint32_t a32 = A <= 32 ? 32u : 64u;
@@ -73,9 +74,43 @@ __host__ __device__ inline FastLds fast_lds_layout(int K, int A, bool rich, bool
   l.act = o;   o += 4u * 64;
   l.hist = o;  o += 4u * fast_hist_stride(K) * 64;
   l.cnt = o;   o += 4u * 64;
+  l.slow = o;  o += 16u;
+  l.inv = o;   o += out64 ? 0u : 8u * 64;
+  l.mtab = o;  o += 64u * fast_mtab_stride(A);
+  l.rtx = o;   o += ratios ? 8u * 64 : 0u;
+  l.inr = o;   o += ratios ? 4u * 64 : 0u;
+  l.px = l.py = l.npx = l.rew = l.stage = o;
+  if (!rich) { l.px = o; o += 8u * 64; }
+  if (rich) {
+    l.px = o;  o += 8u * 64;
+    l.py = o;  o += flat ? 0u : 8u * 64;
+    l.npx = o; o += 8u * 64;
+    l.rew = o; o += 8u * 64;
+    o = align_up(o, 16);
+    l.stage = o; o += (out64 ? 8u : 4u) * 64 * fast_stage_stride(A);
+  }
+  l.nact = o;  o += 4u * 64;
+  o = align_up(o, 8);
+  l.kvel = o;  o += 8u * 64;
+  l.ia = o;    o += ia ? 8u + 4u * 100 : 0u;
+  l.total = align_up(o, 16);
+  return l;
+}
+__host__ __device__ inline FastLds fast_lds_layout(int K, int A, bool rich, bool out64, bool flat, bool ratios = true, bool pol = false,
+                                                     bool ia = false) {
+  // The arrays whose size depends on neither K nor A come FIRST: their offsets are compile-time constants of an
+  // instantiation (every flag below is a template parameter there) and ride in the DS instructions' immediate offsets.
+  // Behind them the arrays sized by A (32 or 64 columns), whose offsets are constants plus multiples of one value, and
+  // last the two sized by K.  With the K- and A-sized arrays in front, as they were, every offset was a run-time sum that
+  // the kernel kept in an SGPR from P0 to P4 - ten of the one-slot kernel's sixteen spilled SGPRs.
+  if (pol) return fast_lds_layout_slots(K, A, rich, out64, flat, ratios, ia);
+  FastLds l;
+  uint32_t o = 0;
+  const uint32_t a32 = A <= 32 ? 32u : 64u;
+  l.act = o;   o += 4u * 64;
+  l.cnt = o;   o += 4u * 64;
   l.slow = o;  o += 16u;                     // the workgroup holds a quad flagged for the keyed path of the next slot
   l.inv = o;   o += out64 ? 0u : 8u * 64;   // float32 outputs: 1.0 / n for the 64 possible neighbour counts (P4), staged in P0
-  l.mtab = o;  o += 64u * fast_mtab_stride(A);      // [vehicle][resource] gather source lane * 4 (bpermute address), bytes
   // (CH and EXTRA instantiations only - `ratios`: without them the RICH workgroup of A <= 32 stays at 20 KB, eight per CU)
   l.rtx = o;   o += ratios ? 8u * 64 : 0u;  // my_step_ch: reception ratio R per transmitter
   l.inr = o;   o += ratios ? 4u * 64 : 0u;  // my_step_ch: receivers in range per transmitter
@@ -86,15 +121,20 @@ __host__ __device__ inline FastLds fast_lds_layout(int K, int A, bool rich, bool
     l.py = o;  o += flat ? 0u : 8u * 64;    // every pos_y == 0: not staged (keeps 8 workgroups per CU at A <= 32)
     l.npx = o; o += 8u * 64;
     l.rew = o; o += 8u * 64;
-    o = align_up(o, 16);
+  }
+  l.nact = l.kvel = l.ia = o;               // (the slot loops' arrays: above)
+  o = align_up(o, 16);
+  // -- sized by A
+  l.mask = o;  o += 8u * a32;
+  l.rv = o;    o += 8u * a32;
+  l.mtab = o;  o += 64u * fast_mtab_stride(A);      // [vehicle][resource] gather source lane * 4 (bpermute address), bytes
+  if (rich) {                               // (16-byte aligned: everything above is a multiple of 16)
     l.stage = o; o += (out64 ? 8u : 4u) * 64 * fast_stage_stride(A);   // channel observation [vehicle][resource]
   }
-  l.nact = o;  o += pol ? 4u * 64 : 0u;     // POL: the agents' actions of the next slot (K slots per launch)
-  o = align_up(o, 8);
-  l.kvel = o;  o += pol ? 8u * 64 : 0u;     // K slots per launch: the velocities the last slot's state vector reports (they live in registers)
-  // the information-age block of a my_step_ch slot loop (PolParams::ia_on), and only then: the caller's sum_ia_prev (8 bytes)
-  // and the 100 bins of Network.get_information_age
-  l.ia = o;    o += ia ? 8u + 4u * 100 : 0u;
+  // -- sized by K
+  l.edges = o; o += 8u * (K + 2);
+  o = align_up(o, 16);                      // (the histogram is zeroed with 16-byte stores: P0)
+  l.hist = o;  o += 4u * fast_hist_stride(K) * 64;
   l.total = align_up(o, 16);
   return l;
 }

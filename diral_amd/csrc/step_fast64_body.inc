@@ -306,7 +306,8 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     }
   }
 #ifndef DIRAL_FAST_KSLOTS
-  for (int j = tid; j < KP * 64; j += 256) s_hist[j] = 0u;
+  // (16 bytes a store: fast_lds_layout aligns the histogram, and KP * 64 words are KP * 16 such pieces)
+  for (int j = tid; j < KP * 16; j += 256) reinterpret_cast<uint4*>(s_hist)[j] = make_uint4(0u, 0u, 0u, 0u);
 #else /* DIRAL_FAST_KSLOTS */
   if (tally_on) {
     for (int j = tid; j < KP * 64; j += 256) s_hist[j] = 0u;
@@ -891,7 +892,16 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   const float invw16f = (float)(inv_w * 65536.0);
   // (the own position folded into the addend: t16 = xpos * (inv_w 2^16) + (Rb - npx) * inv_w 2^16 - one v_fma_f32 per entry
   // instead of a subtraction and the fma; the host's bound FastParams::f32_m16 covers this form: csrc/diral_env.hip)
+  // ... and the margin m16 with it, formed in float64 and rounded once: the fma yields t16 + m16, the ONE sum column32 tests
+  // and takes the bin from (one v_add_u32 per entry less).  For y = t16 >= 0 trunc(y + m) == trunc(y) + m; for y in
+  // (-m - 1, 0) the two may differ by one, and both lie in [0, m]: in range and inside the band, so float64 decides such an
+  // entry either way (tests/test_fast64_diet_identities.py); the larger addend in the host's bound: csrc/diral_env.hip
+  // (the slot loop keeps the parent's form, t16 from the fma and the margin added behind it: DESIGN.md 3.2 item 23)
+#ifndef DIRAL_FAST_KSLOTS
+  const float cfix16f = (float)((p.Rb - mynpx) * inv_w * 65536.0 + (double)m16);
+#else /* DIRAL_FAST_KSLOTS */
   const float cfix16f = (float)((p.Rb - mynpx) * inv_w * 65536.0);
+#endif /* DIRAL_FAST_KSLOTS */
   const unsigned int m16x2 = 2u * (unsigned int)m16;
   const unsigned int k16m = ((unsigned int)K << 16) + m16x2;                    // -m16 <= t16 < K * 2^16 + m16
   unsigned int* const hrow = s_hist + lane * KP;
@@ -993,9 +1003,13 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
             if (!f32_ok) return true;
             const int src = ((int)((__builtin_ctz((cnq >> (8 * cc)) | 0x100u)) & 7) << 2) + (((4 * q + cc) & 7) << 5);
             const float xf = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(q >= 2 ? ringf1 : ringf0)));
+#ifndef DIRAL_FAST_KSLOTS
+            const unsigned int s = (unsigned int)cvt_i32_f32_sat(__builtin_fmaf(xf, invw16f, cfix16f));   // t16 + m16
+#else /* DIRAL_FAST_KSLOTS */
             const int t16 = cvt_i32_f32_sat(__builtin_fmaf(xf, invw16f, cfix16f));
-            const unsigned int s = (unsigned int)t16 + (unsigned int)m16;     // (the same two tests on the same sum as column32)
-            return s < k16m && (s & 0xffffu) < m16x2;
+            const unsigned int s = (unsigned int)t16 + (unsigned int)m16;
+#endif /* DIRAL_FAST_KSLOTS */
+            return s < k16m && (s & 0xffffu) < m16x2;                         // (the same two tests on the same sum as column32)
           };
           auto column = [&](auto cc_tag) {
             constexpr int cc = decltype(cc_tag)::value;
@@ -1043,9 +1057,13 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
             const int c = 4 * q + cc;
             const int src = (ffbl_byte<cc>(cnq) << 2) + ((c & 7) << 5);
             const float xf = __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(q >= 2 ? ringf1 : ringf0)));
+#ifndef DIRAL_FAST_KSLOTS
+            const unsigned int s = (unsigned int)cvt_i32_f32_sat(__builtin_fmaf(xf, invw16f, cfix16f));
+#else /* DIRAL_FAST_KSLOTS */
             const int t16 = cvt_i32_f32_sat(__builtin_fmaf(xf, invw16f, cfix16f));
+#endif /* DIRAL_FAST_KSLOTS */
             const bool agev = ((agt >> (8 * cc)) & 255u) < (unsigned int)p.age_limit;
-            // ONE sum serves both tests and the bin.  s = t16 + m16: the range test is s < K 2^16 + 2 m16 as before; the
+            // ONE sum serves both tests and the bin.  s = t16 + m16 (the margin rides in the fma's addend): the range test is s < K 2^16 + 2 m16 as before; the
             // fraction of t16 lies within m16 of an integer iff (t16 - m16) mod 2^16 >= 2^16 - 2 m16, and since
             // t16 - m16 = s - 2 m16 (mod 2^16) that is (s mod 2^16) < 2 m16 - one compare of the low half, its complement
             // taken on the mask.  A counted entry has m16 <= frac(t16) < 2^16 - m16, so adding m16 carries nothing into the
@@ -1053,12 +1071,19 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
             // The results stay lane masks (every lane is active here): counted = in range and not in the band, left for
             // float64 = in range and in the band - scalar instructions - and the select and the count take the mask as it is
             // (select_lane_mask / add_lane_mask read the masks of ALL lanes: this must stay outside any lane-divergent branch)
+            // (the bin s >> 16 is the high half of s: the select's source selector, select_lane_mask_hi16)
+#ifdef DIRAL_FAST_KSLOTS
             const unsigned int s = (unsigned int)t16 + (unsigned int)m16;
+#endif /* DIRAL_FAST_KSLOTS */
             const unsigned long long mm = __builtin_amdgcn_ballot_w64(agev) & __builtin_amdgcn_ballot_w64(s < k16m);
             const unsigned long long band = __builtin_amdgcn_ballot_w64((s & 0xffffu) < m16x2);
             const unsigned long long cnt = mm & ~band;
             redo_m |= mm & band;
+#ifndef DIRAL_FAST_KSLOTS
+            atomicAdd(&hrow[select_lane_mask_hi16(cnt, s, K)], 1u);
+#else /* DIRAL_FAST_KSLOTS */
             atomicAdd(&hrow[select_lane_mask(cnt, (int)(s >> 16), K)], 1u);
+#endif /* DIRAL_FAST_KSLOTS */
             mycnt = add_lane_mask(mycnt, cnt);
           };
           if (f32_ok) {                                             // (uniform)

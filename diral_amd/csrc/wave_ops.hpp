@@ -80,6 +80,16 @@ __device__ inline int select_lane_mask(unsigned long long m, int a, int b) {
   return r;
 }
 
+// the HIGH half of a (a >> 16) in the lanes of `m`, b elsewhere: the shift is the SDWA source selector of the select.  The
+// SDWA form takes its mask from VCC (a scalar move: an asm operand cannot be bound to VCC); ONE vector instruction where the
+// shift and v_cndmask_b32_e64 are two
+__device__ inline int select_lane_mask_hi16(unsigned long long m, unsigned int a, int b) {
+  int r;
+  asm("s_mov_b64 vcc, %3\n\tv_cndmask_b32_sdwa %0, %1, %2, vcc dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1"
+      : "=v"(r) : "v"(b), "v"(a), "s"(m) : "vcc");
+  return r;
+}
+
 // An LDS object by its absolute byte address (register + compile-time constant: the constant goes
 // into the DS instruction's immediate offset; going through the `extern __shared__` symbol instead
 // leaves a relocated `+ 0` add in front of every access)
