@@ -30,6 +30,7 @@ SYMBOLS = [
     "diral_env_rollout", "diral_env_copy_envs", "diral_env_rollout_ia", "diral_env_step_policy_ia",
     "diral_env_rollout_replay", "diral_env_step_policy_replay", "diral_env_subwave_ok", "diral_env_reset_envs",
     "diral_policy_select", "diral_memory_add", "diral_memory_sample",
+    "diral_env_rollout_memory", "diral_env_prefill_memory",
 ]
 
 _lib = None
@@ -109,6 +110,8 @@ def load() -> ctypes.CDLL:
         "diral_policy_select": (I, [P, P]),
         "diral_memory_add": (I, [P, P, P]),
         "diral_memory_sample": (I, [P, P, P]),
+        "diral_env_rollout_memory": (I, [P, I, P, I, I64, P, I, P, P, I, P, P, P, P, P]),
+        "diral_env_prefill_memory": (I, [P, I, P, I, U64, P, I, P, P, P, D, D, P, P]),
     }
     for name in SYMBOLS:
         try:

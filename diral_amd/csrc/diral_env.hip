@@ -1145,6 +1145,25 @@ static bool replay_block_params(const DiralSlotReplay* rp, PolParams& q) {
   return true;
 }
 
+// The memory block of a rollout / prefill (DiralMemory: diral_env_rollout_memory / diral_env_prefill_memory): its own
+// argument checks - no device is needed for any of them ...
+static int memory_block_check(const DiralEnv* e, const DiralMemory* m, int32_t slots, int out_dtype) {
+  if (!memory_ok(m) || slots > m->capacity) return DIRAL_ERR_BAD_ARG;
+  if (m->batch != e->B || m->num_users != e->N || m->state_space != e->S) return DIRAL_ERR_BAD_ARG;
+  if (m->dtype != out_dtype) return DIRAL_ERR_BAD_ARG;           // (the stored bits are the scratch path's: no conversion)
+  return DIRAL_OK;
+}
+// ... and what the slot loops are handed (a host count: its row; a device count is read by the kernel)
+static void memory_block_params(const DiralMemory* m, PolParams& q) {
+  q.mem_on = 0; q.mem_rows = 0; q.mem_head = 0; q.mem_count_dev = nullptr;
+  q.mem_states = nullptr; q.mem_actions = nullptr; q.mem_rewards = nullptr;
+  if (!m) return;
+  q.mem_on = 1; q.mem_rows = m->capacity + 1;
+  q.mem_head = m->count_dev ? 0 : (int)(m->count % (int64_t)q.mem_rows);
+  q.mem_count_dev = (const long long*)m->count_dev;
+  q.mem_states = m->states; q.mem_actions = m->actions; q.mem_rewards = m->rewards;
+}
+
 static int step_policy_impl(DiralEnv* e, int mode, const int32_t* actions, int64_t t, void* state_out, void* rew_out,
                             uint8_t* done_out, void* chobs_out, int out_dtype, const DiralSlotPolicy* pol,
                             const DiralSlotInfoAge* ia, const DiralSlotReplay* rp, void* stream) {
@@ -1181,6 +1200,7 @@ static int step_policy_impl(DiralEnv* e, int mode, const int32_t* actions, int64
   q.K = slots; q.vel_vary = has(&e->cfg, DIRAL_F_MOBILITY_VARY) ? 1 : 0; q.vel_seed = pol->vel_seed;
   q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N; q.vel_w = e->vel;
   q.prefill = 0; q.actions_all = nullptr; q.rew_in = nullptr; q.rollout = 0; q.actions_seq = nullptr;
+  memory_block_params(nullptr, q);                               // (the closed loop writes the last state only)
   ia_block_params(ia, q);
   const bool replay = replay_block_params(rp, q);
   if (slots > 1 && (pol->draw_counter || pol->draw_keep || pol->draw_choice)) return DIRAL_ERR_BAD_ARG;
@@ -1222,12 +1242,17 @@ int diral_env_step_policy_replay(DiralEnv* e, int mode, const int32_t* actions, 
   return step_policy_impl(e, mode, actions, t, state_out, rew_out, done_out, chobs_out, out_dtype, pol, ia, rp, stream);
 }
 
-int diral_env_prefill_mode(DiralEnv* e, int mode, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out,
-                           int out_dtype, int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in,
-                           double episode, double epsilon, void* stream) {
+static int prefill_impl(DiralEnv* e, int mode, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out,
+                        int out_dtype, int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in,
+                        double episode, double epsilon, const DiralMemory* mem, void* stream) {
   if (!e || !actions || !actions_next_out || slots < 1) return DIRAL_ERR_BAD_ARG;
   if (mode != DIRAL_STEP_DESIGN && mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_BAD_ARG;
   if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
+  if (mem) {
+    // the rings take the place of the scratch outputs; the reward they store is the stale bootstrap one
+    if (memory_block_check(e, mem, slots, out_dtype) != DIRAL_OK || states_out || actions_all_out || !rew_in) return DIRAL_ERR_BAD_ARG;
+    states_out = mem->states;
+  }
   const bool ch = mode == DIRAL_STEP_MY_STEP_CH;
   // my_step_ch defines rewards only for reward_design 2,3,4 (test_env.py:413-429)
   if (ch && (e->cfg.reward_design < 2 || e->cfg.reward_design > 4)) return DIRAL_ERR_BAD_CONFIG;
@@ -1242,23 +1267,44 @@ int diral_env_prefill_mode(DiralEnv* e, int mode, const int32_t* actions, int32_
   std::memset(&q, 0, sizeof(q));
   q.K = slots; q.prefill = 1; q.seed = seed; q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N;
   q.actions_out = actions_next_out; q.actions_all = actions_all_out; q.rew_in = rew_in; q.vel_w = e->vel;
+  memory_block_params(mem, q);
   const StepPlan d = plan_step(e, p, &q);
   if (!d.fused) return DIRAL_ERR_UNSUPPORTED;                    // (nothing launched: the caller loops sample + step + observe)
   HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
   return DIRAL_OK;
 }
 
+int diral_env_prefill_mode(DiralEnv* e, int mode, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out,
+                           int out_dtype, int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in,
+                           double episode, double epsilon, void* stream) {
+  return prefill_impl(e, mode, actions, slots, seed, states_out, out_dtype, actions_all_out, actions_next_out, rew_in, episode,
+                      epsilon, nullptr, stream);
+}
+
+int diral_env_prefill_memory(DiralEnv* e, int mode, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out,
+                             int out_dtype, int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in,
+                             double episode, double epsilon, const DiralMemory* memory, void* stream) {
+  return prefill_impl(e, mode, actions, slots, seed, states_out, out_dtype, actions_all_out, actions_next_out, rew_in, episode,
+                      epsilon, memory, stream);
+}
+
 static int rollout_impl(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
                         int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro,
-                        const DiralSlotInfoAge* ia, const DiralSlotReplay* rp, void* stream) {
+                        const DiralSlotInfoAge* ia, const DiralSlotReplay* rp, const DiralMemory* mem, void* stream) {
   if (!e || !actions_seq || !ro || ro->struct_bytes != sizeof(DiralRollout) || slots < 1) return DIRAL_ERR_BAD_ARG;
   if (rp && replay_block_check(rp) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
-  if (ia && ia_block_check(ia, ro->shaped_out) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
-  if (mode != DIRAL_STEP_MY_STEP && mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_BAD_ARG;
   if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
+  void* shaped_out = ro->shaped_out;
+  if (mem) {
+    // the rings take the place of the scratch outputs: every slot's state vector and shaped reward leave, into ring rows
+    if (memory_block_check(e, mem, slots, out_dtype) != DIRAL_OK || states_out || ro->shaped_out) return DIRAL_ERR_BAD_ARG;
+    states_out = mem->states; states_all = 1; shaped_out = mem->rewards;
+  }
+  if (ia && ia_block_check(ia, shaped_out) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
+  if (mode != DIRAL_STEP_MY_STEP && mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_BAD_ARG;
   if ((ro->shape_flags & ~5) != 0) return DIRAL_ERR_BAD_ARG;                  // global_reward_avg | stuck-action penalty
   if (ro->shaped_out && !rew_out) return DIRAL_ERR_BAD_ARG;                   // (the wide slot loop shapes what rew_out holds)
-  if (ro->shaped_out && (ro->shape_flags & 4) && (!ro->pen_counter || !ro->pen_prev_actions)) return DIRAL_ERR_BAD_ARG;
+  if (shaped_out && (ro->shape_flags & 4) && (!ro->pen_counter || !ro->pen_prev_actions)) return DIRAL_ERR_BAD_ARG;
   // my_step_ch defines rewards only for reward_design 2,3,4 (test_env.py:413-429)
   if (mode == DIRAL_STEP_MY_STEP_CH && (e->cfg.reward_design < 2 || e->cfg.reward_design > 4)) return DIRAL_ERR_BAD_CONFIG;
   if (ia) {
@@ -1271,36 +1317,45 @@ static int rollout_impl(DiralEnv* e, int mode, const int32_t* actions_seq, int32
   PolParams q;
   std::memset(&q, 0, sizeof(q));
   q.shape_flags = ro->shape_flags; q.pen_threshold = ro->pen_threshold; q.pen_value = ro->pen_value;
-  q.shaped_out = ro->shaped_out; q.sum_r_out = ro->sum_r_out; q.coll_out = ro->collision_out;
+  q.shaped_out = shaped_out; q.sum_r_out = ro->sum_r_out; q.coll_out = ro->collision_out;
   q.pen_counter = ro->pen_counter; q.pen_prev = ro->pen_prev_actions;
   q.K = slots; q.vel_vary = has(&e->cfg, DIRAL_F_MOBILITY_VARY) ? 1 : 0; q.vel_seed = ro->vel_seed;
   q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N; q.vel_w = e->vel;
   q.rollout = 1 | ((states_all && p.state_out) ? 2 : 0); q.actions_seq = actions_seq;
   ia_block_params(ia, q);
   const bool replay = replay_block_params(rp, q);
+  memory_block_params(mem, q);
   const StepPlan d = plan_step(e, p, &q);
   if (!d.fused) return DIRAL_ERR_UNSUPPORTED;                    // (nothing launched: the caller loops step + shape)
   if (ia && d.launch != StepLaunch::Fast64Slots) return DIRAL_ERR_UNSUPPORTED;   // (only that slot loop keeps the stamps)
   if (replay && d.launch != StepLaunch::Fast64Slots) return DIRAL_ERR_UNSUPPORTED;   // (... and takes recorded positions)
+  // (the memory block: the two slot loops that keep the env on the chip - the wide one has no states_all)
+  if (mem && d.launch != StepLaunch::Fast64Slots && d.launch != StepLaunch::SubwaveSlots) return DIRAL_ERR_UNSUPPORTED;
   HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
   return DIRAL_OK;
 }
 
 int diral_env_rollout(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
                       int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro, void* stream) {
-  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, nullptr, nullptr, stream);
+  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, nullptr, nullptr, nullptr, stream);
 }
 
 int diral_env_rollout_ia(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
                          int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro,
                          const DiralSlotInfoAge* ia, void* stream) {
-  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, ia, nullptr, stream);
+  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, ia, nullptr, nullptr, stream);
 }
 
 int diral_env_rollout_replay(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
                              int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro,
                              const DiralSlotInfoAge* ia, const DiralSlotReplay* rp, void* stream) {
-  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, ia, rp, stream);
+  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, ia, rp, nullptr, stream);
+}
+
+int diral_env_rollout_memory(DiralEnv* e, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
+                             int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* ro,
+                             const DiralSlotInfoAge* ia, const DiralSlotReplay* rp, const DiralMemory* memory, void* stream) {
+  return rollout_impl(e, mode, actions_seq, slots, t, states_out, states_all, rew_out, done_out, out_dtype, ro, ia, rp, memory, stream);
 }
 
 int diral_env_prefill(DiralEnv* e, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out, int out_dtype,

@@ -43,33 +43,34 @@ hipError_t launch_fast64_policy(const FastParams& f, const RichParams& r, const 
   return hipGetLastError();
 }
 
+namespace {
+// one of the slot loop's instantiations (FLAT, RICH, POL; no EXTRA switches), in the launch's out dtype
+template <bool CH, bool IA, bool RP, bool MEM>
+void launch_slots_as(const FastParams& f, const RichParams& r, const PolParams& q, bool out64, int B, uint32_t lds, hipStream_t s) {
+  if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, CH, false, true, true, IA, RP, MEM>), dim3(B), dim3(256), lds, s, f, r, q);
+  else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, CH, false, true, true, IA, RP, MEM>), dim3(B), dim3(256), lds, s, f, r, q);
+}
+template <bool RP, bool MEM>
+void launch_slots_blocks(const FastParams& f, const RichParams& r, const PolParams& q, bool ch, bool ia, bool out64, int B, uint32_t lds,
+                         hipStream_t s) {
+  if (ia) launch_slots_as<true, true, RP, MEM>(f, r, q, out64, B, lds, s);
+  else if (ch) launch_slots_as<true, false, RP, MEM>(f, r, q, out64, B, lds, s);
+  else launch_slots_as<false, false, RP, MEM>(f, r, q, out64, B, lds, s);
+}
+}  // namespace
+
 // ... K slots per launch (PolParams::K > 1): step_fast64_slots_kernel, the same body with the env kept on the chip; `ch`:
 // my_step_ch slots (the reception ratios of P1 in LDS next to the policy's arrays)
 hipError_t launch_fast64_slots(const FastParams& f, const RichParams& r, const PolParams& q, bool ch, bool out64, int B, hipStream_t s) {
   const bool ia = ch && q.ia_on != 0;       // the information-age block: the IA instantiations (arrival stamps, histogram pass, term)
   const uint32_t lds = fast_lds_layout(f.K, f.A, true, out64, true, ch, true, ia).total;
-  if (q.rp_on != 0) {
-    // the recorded-mobility block: the RP instantiations (positions from the caller's sequence, the position log)
-    if (ia) {
-      if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, true, false, true, true, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
-      else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, true, false, true, true, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
-    } else if (ch) {
-      if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, true, false, true, true, false, true>), dim3(B), dim3(256), lds, s, f, r, q);
-      else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, true, false, true, true, false, true>), dim3(B), dim3(256), lds, s, f, r, q);
-    } else {
-      if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, false, false, true, true, false, true>), dim3(B), dim3(256), lds, s, f, r, q);
-      else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, false, false, true, true, false, true>), dim3(B), dim3(256), lds, s, f, r, q);
-    }
-  } else if (ia) {
-    if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, true, false, true, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
-    else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, true, false, true, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
-  } else if (ch) {
-    if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, true, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
-    else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, true, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
-  } else {
-    if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, false, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
-    else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, false, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
-  }
+  // the recorded-mobility block: the RP instantiations (positions from the caller's sequence, the position log); the memory
+  // block: the MEM instantiations (the slots write rows of the caller's replay rings)
+  const bool rp = q.rp_on != 0, mem = q.mem_on != 0;
+  if (rp && mem) launch_slots_blocks<true, true>(f, r, q, ch, ia, out64, B, lds, s);
+  else if (rp) launch_slots_blocks<true, false>(f, r, q, ch, ia, out64, B, lds, s);
+  else if (mem) launch_slots_blocks<false, true>(f, r, q, ch, ia, out64, B, lds, s);
+  else launch_slots_blocks<false, false>(f, r, q, ch, ia, out64, B, lds, s);
   return hipGetLastError();
 }
 }  // namespace diral

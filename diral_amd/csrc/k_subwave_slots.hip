@@ -10,7 +10,9 @@ template <int G, bool OUT64>
 hipError_t launch_sub_slots(const StepParams& p, const PolParams& q, hipStream_t s) {
   constexpr int kEnvsPerBlock = kSubwaveThreads / G;
   const unsigned int grid = (unsigned int)((p.B + kEnvsPerBlock - 1) / kEnvsPerBlock);
-  hipLaunchKernelGGL((step_subwave_slots_kernel<G, OUT64>), dim3(grid), dim3(kSubwaveThreads), 0, s, p, q);
+  // (the memory block, PolParams::mem_on: the MEM instantiations - the slots write rows of the caller's replay rings)
+  if (q.mem_on) hipLaunchKernelGGL((step_subwave_slots_kernel<G, OUT64, true>), dim3(grid), dim3(kSubwaveThreads), 0, s, p, q);
+  else hipLaunchKernelGGL((step_subwave_slots_kernel<G, OUT64, false>), dim3(grid), dim3(kSubwaveThreads), 0, s, p, q);
   return hipGetLastError();
 }
 }  // namespace

@@ -63,7 +63,31 @@ struct PolParams {
   int rp_T, rp_per_env;          // rows of the sequence; != 0: one sequence per env ([B][T][N], the env's index in this handle)
   const double* rp_x;            // [T][N] / [B][T][N] or null (the velocity model)
   double* rp_xout;               // [K][B][N] pos_x behind every slot, or null
+  // The memory block of a rollout / prefill (diral_env_rollout_memory / diral_env_prefill_memory, DiralMemory; the slot loops
+  // of step_fast64_slots_kernel and step_subwave_slots_kernel): slot ks writes the caller's replay rings instead of [K]-major
+  // scratch - its state vector to state row (count + 1 + ks), the actions it ran with and its reward to row (count + ks), all
+  // mod mem_rows.  A ring row has the shape of a scratch row, so the slot index of three stores is all that changes: the host
+  // hands the ring bases over as StepParams::state_out, shaped_out (rollout) and actions_all, and the bases below.
+  int mem_on;                    // the call carries the block
+  int mem_rows;                  // capacity + 1
+  int mem_head;                  // count mod mem_rows of a host count
+  const long long* mem_count_dev;   // null, or the device count (read once per workgroup)
+  void* mem_states;              // [mem_rows][B][N][S] out dtype
+  int32_t* mem_actions;          // [mem_rows][B][N]
+  void* mem_rewards;             // [mem_rows][B][N] out dtype
 };
+
+// The memory block's row of slot 0, (count mod mem_rows), once per workgroup (launch-uniform: a scalar), and the step from
+// one slot's row to the next one's - slots <= capacity < mem_rows, so one conditional subtract wraps it.
+__device__ inline int mem_row_head(const PolParams& q) {
+  if (!q.mem_on) return 0;
+  if (!q.mem_count_dev) return q.mem_head;
+  return (int)((unsigned long long)*q.mem_count_dev % (unsigned long long)(unsigned int)q.mem_rows);
+}
+__device__ inline int mem_row_next(int row, int rows) {
+  row += 1;
+  return row >= rows ? row - rows : row;
+}
 
 // counter-based generator (splitmix64 finaliser over seed/stream/index); the
 // reference uses unseeded global RNGs, so only the distribution matters.

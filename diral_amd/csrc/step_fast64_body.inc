@@ -16,7 +16,10 @@ template <bool FLAT, bool OUT64, bool CH, bool EXTRA, bool RICH, bool POL = fals
 // RP: the slot loop of a call that carries the recorded-mobility block (PolParams::rp_on, DiralSlotReplay) - the positions
 // behind every slot come from the caller's sequence instead of the velocity model, and / or leave in the position log.
 // Instantiations of their own, as IA's: every other kernel is compiled from the text it had (profiles/kslots_replay/)
-template <bool FLAT, bool OUT64, bool CH, bool EXTRA, bool RICH, bool POL = false, bool IA = false, bool RP = false>
+// MEM: the slot loop of a call that carries the memory block (PolParams::mem_on, DiralMemory) - every slot's state vector,
+// actions and reward go to rows of the caller's replay rings.  Instantiations of their own once more: as a run-time switch
+// the block cost the float32 my_step slot loop 20 more spilled VGPRs and 16 bytes of scratch (profiles/rollout_memory/)
+template <bool FLAT, bool OUT64, bool CH, bool EXTRA, bool RICH, bool POL = false, bool IA = false, bool RP = false, bool MEM = false>
 #endif /* DIRAL_FAST_KSLOTS */
 #ifndef DIRAL_FAST_KSLOTS
 __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES) void DIRAL_FAST_KERNEL(const FastParams p, const RichParams r,
@@ -34,6 +37,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   static_assert(!POL || (RICH && FLAT && !EXTRA), "the policy epilogue needs the staged channel observation of a my_step / my_step_ch slot");
   static_assert(!IA || (POL && CH), "the information-age block belongs to the my_step_ch slot loop");
   static_assert(!RP || POL, "the recorded-mobility block belongs to the slot loops");
+  static_assert(!MEM || POL, "the memory block belongs to the slot loops");
 #endif /* DIRAL_FAST_KSLOTS */
   extern __shared__ __align__(16) unsigned char smem[];
 #ifndef DIRAL_FAST_KSLOTS
@@ -120,6 +124,10 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   unsigned int cw[4], ag[4];
   unsigned int ts_own = 0u, told_l = 0u;
   const int tid_k = tid, wave_k = wave, b_k = b;
+  // the memory block (MEM, PolParams::mem_on): the ring row of this slot's actions and reward - the row in front of the one its
+  // state vector goes to -, launch-uniform and kept scalar from slot to slot
+  int mem_row = 0;
+  if constexpr (MEM) mem_row = __builtin_amdgcn_readfirstlane(mem_row_head(q));
 #pragma unroll 1
   for (int ks = 0; ks < KS; ++ks) {
   // (the lane / wave indices as fresh values every slot: everything derived from them - table rows, LDS rows, byte masks,
@@ -130,6 +138,7 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   const int lane = tid & 63;
   int wave = wave_k, b = b_k;
   asm volatile("" : "+s"(wave), "+s"(b));
+  if constexpr (MEM) asm volatile("" : "+s"(mem_row));
   const size_t bN = (size_t)b * N;
   const bool live = lane < N;
   // ... and the kernel arguments through the kernarg segment, loaded where a slot uses them (late_kernarg_base, above): as
@@ -294,9 +303,12 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     s_px[lane] = mypx;
 #ifdef DIRAL_FAST_KSLOTS
     if constexpr (POL) {
-      if (prefill && live) {                                          // the actions this slot runs with (the replay buffer's)
-        int32_t* const aa = ((LatePolArgs)(late_kernarg_base() + kPolArgOffset))->actions_all;
-        if (aa) aa[((size_t)ks * (size_t)p.B) * N + bN + lane] = myact;
+      // the actions this slot runs with (the replay buffer's): the prefill's [K][B][N] output - or, with the memory block
+      // (prefill and rollout alike), row `mem_row` of the action ring
+      if ((prefill || MEM) && live) {
+        const LatePolArgs lqa = (LatePolArgs)(late_kernarg_base() + kPolArgOffset);
+        int32_t* const aa = MEM ? lqa->mem_actions : lqa->actions_all;
+        if (aa) aa[((size_t)(MEM ? mem_row : ks) * (size_t)p.B) * N + bN + lane] = myact;
       }
     }
 #endif /* DIRAL_FAST_KSLOTS */
@@ -1284,8 +1296,14 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     // terms) of this env: wave 1, lane = vehicle, from the rewards P2 left in LDS - np.sum in NumPy's order
     if (wave == 1) {
       const LatePolArgs lq = (LatePolArgs)(late_kernarg_base() + kPolArgOffset);
+#ifndef DIRAL_FAST_KSLOTS
       void* const shaped_out = lq->shaped_out;
-#ifdef DIRAL_FAST_KSLOTS
+#else /* DIRAL_FAST_KSLOTS */
+      // (the memory block: a rollout's shaped rewards go to row `mem_row` of the reward ring; a prefill stores the stale
+      // bootstrap rewards `rew_in` there, cast to the ring dtype, for every slot - what add_prefill's copy stores)
+      void* const shaped_out = (MEM && !prefill) ? lq->mem_rewards : lq->shaped_out;
+      if (MEM && prefill && live)
+        static_cast<out_t*>(lq->mem_rewards)[((size_t)mem_row * (size_t)p.B) * N + bN + lane] = (out_t)lq->rew_in[bN + lane];
       // the information-age block: this slot's histogram leaves, utils/misc.calculate_ia_penalty of it, and the
       // ia_averaging term (main_test.py:151-160) against the sum of the slot before
       int ia_term = 0;
@@ -1359,7 +1377,8 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
 #ifndef DIRAL_FAST_KSLOTS
           static_cast<out_t*>(shaped_out)[bN + lane] = rr;
 #else /* DIRAL_FAST_KSLOTS */
-          static_cast<out_t*>(shaped_out)[sB * N + bN + lane] = rr;
+          // (sum_r_out / coll_out stay [K][B] with the block; the shaped rewards take the ring's row)
+          static_cast<out_t*>(shaped_out)[(MEM ? (size_t)mem_row * (size_t)p.B : sB) * N + bN + lane] = rr;
 #endif /* DIRAL_FAST_KSLOTS */
         }
       }
@@ -1383,7 +1402,11 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
   void* state_out = (last || every) ? ((LateFastArgs)late)->state_out : nullptr;   // (K slots: the last slot's state vector)
   if (every && state_out) {                                          // (prefill, rollout with states_all: every slot's, [K][B][N][S])
     const size_t S_row = RICH ? (size_t)((LateRichArgs)(late + kRichArgOffset))->S : (size_t)(A + K);
-    state_out = static_cast<out_t*>(state_out) + (size_t)ks * (size_t)p.B * (size_t)N * S_row;
+    // (the memory block: `state_out` is the state ring, the slot's state vector is the NEXT state of its transition - the
+    // row behind `mem_row`)
+    int srow = ks;
+    if constexpr (MEM) srow = mem_row_next(mem_row, ((LatePolArgs)(late + kPolArgOffset))->mem_rows);
+    state_out = static_cast<out_t*>(state_out) + (size_t)srow * (size_t)p.B * (size_t)N * S_row;
   }
   bool plain_out = true;
 #endif /* DIRAL_FAST_KSLOTS */
@@ -1547,6 +1570,8 @@ __global__ __launch_bounds__(256, DIRAL_FAST_MINWAVES_KS) void DIRAL_FAST_KERNEL
     // (CH: `s_inr` / `s_rtx` need no barrier of their own.  Wave 0 reads this slot's ratios in P2, in front of its P3 and so
     //  in front of the barrier behind P3; every wave's P1 of the next slot - the next writer - lies behind that barrier and
     //  the one below.  Nothing else of my_step_ch crosses a slot: the ratios are rebuilt from the positions every slot.)
+    // (the memory block: the next slot's ring row - an add and a conditional subtract on the scalar unit)
+    if constexpr (MEM) mem_row = mem_row_next(mem_row, ((LatePolArgs)(late_kernarg_base() + kPolArgOffset))->mem_rows);
     if (KS > 1 || rollout) {
       mynpx_prev = mynpx;
       tkov_prev = tkov;

@@ -29,7 +29,9 @@
 
 namespace diral {
 
-template <int G, bool OUT64>
+// MEM: the launch carries the memory block (PolParams::mem_on).  An instantiation of its own: as a run-time switch the block
+// cost every launch without it 3 to 7 % (profiles/rollout_memory/).
+template <int G, bool OUT64, bool MEM = false>
 __global__ __launch_bounds__(kSubwaveThreads) void step_subwave_slots_kernel(const StepParams p, const PolParams q) {
   using out_t = typename std::conditional<OUT64, double, float>::type;
   __shared__ double s_px[kSubwaveThreads];
@@ -49,6 +51,11 @@ __global__ __launch_bounds__(kSubwaveThreads) void step_subwave_slots_kernel(con
   const bool pen_on = shaping && (q.shape_flags & 4) != 0;
   const size_t BN = (size_t)p.B * (size_t)N;
   const long long clock = p.t_dev ? *p.t_dev : 0ll;
+  // the memory block (MEM): slot ks writes ring rows instead of [K]-major scratch - p.state_out is the state ring, `mem_row`
+  // the row of the slot's actions and reward, the row behind it the one of its state vector; launch-uniform
+  constexpr bool mem = MEM;
+  int mem_row = 0;
+  if constexpr (MEM) mem_row = mem_row_head(q);
 
   // ---- in front of slot 0: everything the slots keep in registers -----------
   unsigned int w1[G];
@@ -77,13 +84,18 @@ __global__ __launch_bounds__(kSubwaveThreads) void step_subwave_slots_kernel(con
     const long long slot = p.t + (prefill ? 0 : ks) + clock;
     // where this slot's state vector goes, if it leaves
     void* const state_out = (p.state_out && (last || every)) ? p.state_out : nullptr;
-    const size_t srow0 = every ? (size_t)ks * BN : 0;
+    const size_t srow0 = mem ? (size_t)mem_row_next(mem_row, q.mem_rows) * BN : (every ? (size_t)ks * BN : 0);
     const bool want_hist = hist_cfg && state_out != nullptr;
 
     // ---- P0: the action, the post-move position --------------------------------
     const int myact = subwave_action(p, L, a);
     const double mynpx = valid ? subwave_move(p, L, slot, mypx, myvel) : 0.0;
     if (valid && prefill && q.actions_all) q.actions_all[(size_t)ks * BN + bN + u] = a;   // the actions this slot runs with
+    if constexpr (MEM) if (valid) {
+      // ... into the action ring, and a prefill's stale bootstrap rewards into the reward ring (add_prefill's rows)
+      q.mem_actions[(size_t)mem_row * BN + bN + u] = a;
+      if (prefill) static_cast<out_t*>(q.mem_rewards)[(size_t)mem_row * BN + bN + u] = (out_t)q.rew_in[bN + u];
+    }
     wave_lds_order();                              // (behind the last read of the slot before)
     L.gx[u] = mypx; L.gy[u] = mypy;
     wave_lds_order();
@@ -146,12 +158,13 @@ __global__ __launch_bounds__(kSubwaveThreads) void step_subwave_slots_kernel(con
           penp = a;
         }
         if (q.shape_flags & 1) rr = rr + sr / (out_t)N;
-        static_cast<out_t*>(q.shaped_out)[sB * N + bN + u] = rr;
+        static_cast<out_t*>(q.shaped_out)[(mem ? (size_t)mem_row * (size_t)p.B : sB) * N + bN + u] = rr;   // (the block: the reward ring's row)
       }
     }
 
     // ---- what the next slot takes over ------------------------------------------
     if (valid) mypx = mynpx;
+    if constexpr (MEM) mem_row = mem_row_next(mem_row, q.mem_rows);
     if (q.vel_vary) {
       // Network.update_velocity (network.py:208-223) behind a slot that ends an episode, as velocity_kernel draws it:
       // diral_env_update_velocity(env, NULL, vel_seed + episode)

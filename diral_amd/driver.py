@@ -124,12 +124,31 @@ class DriverLoop:
         return self._t(self.env.obtain_state(obs, action, self._rews0)).clone()
 
     # main_test.py:99-114 as a whole: K random slots, every state kept (what the loop hands to memory.add)
-    def prefill(self, slots: int, seed: int):
+    def prefill(self, slots: int, seed: int, memory=None):
         """``for k in range(slots): a = env.sample(seed + k); states[k] = prefill_step(a)``: returns
         ``(states [K, B, N, S], actions [K, B, N])``.  On the HIP env this is ONE launch (`VecV2VEnv.prefill` ->
         `diral_env_prefill_mode`, my_step_design or - `enable_channel` - my_step_ch: the env stays on the chip for the K
-        slots); configurations that launch does not take - and any other env - run the loop."""
+        slots); configurations that launch does not take - and any other env - run the loop.
+
+        `memory` (a :class:`diral_amd.ReplayMemory`): the K transitions are stored in it with the bootstrap's stale
+        rewards (main_test.py:110-112) - by the launch itself where the env takes that (`VecV2VEnv.prefill(memory=)`),
+        otherwise by this call's usual form followed by ``memory.add_prefill``: the same rings either way.  Returns
+        ``(None, None)`` then."""
         env = self.env
+        if memory is not None:
+            if hasattr(env, "prefill") and hasattr(env, "lib"):
+                try:
+                    env.prefill(env.sample(seed), slots, seed, rew_in=self._rews0, memory=memory,
+                                mode="my_step_ch" if self.enable_channel else "my_step_design")
+                    return None, None
+                except DiralError as exc:
+                    if exc.status != ERR_UNSUPPORTED:
+                        raise
+            states, acts = self.prefill(slots, seed)
+            dev = memory.device
+            memory.add_prefill(self._t(states).to(dev).contiguous(), self._t(acts).to(device=dev, dtype=torch.int32).contiguous(),
+                               self._t(self._rews0).to(dev).contiguous())
+            return None, None
         if hasattr(env, "prefill"):
             try:
                 if self.enable_channel:
@@ -232,7 +251,7 @@ class DriverLoop:
 
     # K slots of main_test.py:119-236 with the actions given in advance (a replayed log, a fixed schedule)
     def rollout(self, actions_seq, t: int, states: Optional[str] = "last", vel_seed: int = 0,
-                positions=None) -> Dict[str, Any]:
+                positions=None, memory=None) -> Dict[str, Any]:
         """``for k in range(K): out = slot(actions_seq[k], t + k)`` and, behind a slot that ends an episode,
         ``env.update_velocity(seed=vel_seed + (t + k) // episode_interval)``: returns ``states`` (the last slot's
         [B, N, S]; `states` = ``"all"``: every slot's [K, B, N, S]; None: none), ``reward`` [B, N] (as the env returned it)
@@ -249,11 +268,21 @@ class DriverLoop:
         `positions` ([T, N] or [B, T, N] float64): recorded mobility for these K slots, main_test.py:118's
         `load_saved_positions` - inside the launch where it is taken (`diral_env_rollout_replay`); behind a refused launch
         the sequence is set on the handle (`load_saved_positions`), the slots are looped and the trace is removed again.
-        ValueError if the handle already carries a trace: one source of positions per call."""
+        ValueError if the handle already carries a trace: one source of positions per call.
+
+        `memory` (a :class:`diral_amd.ReplayMemory`): the K transitions - every slot's state, actions and shaped reward -
+        are stored in it, by the launch itself where the env takes that (`VecV2VEnv.rollout(memory=)`: no [K]-major
+        scratch, no second launch); where it does not (N > 64, an unpinned toy handle, fingerprint columns, any other
+        env) this call runs with ``states="all"`` and ``memory.add_rollout`` follows: the same rings either way.
+        `states` is not read; ``shaped`` is None in the result and ``states`` the memory's last state row (None when
+        it counts on the device)."""
         env = self.env
         seq = self._t(actions_seq)
         K = int(seq.shape[0])
         hip = hasattr(env, "lib") and hasattr(env, "_stream")
+        direct = memory is not None and hip and not env.cfg.enable_fingerprint
+        if memory is not None and not direct:
+            return self._rollout_then_add(seq, t, vel_seed, positions, memory)
         if positions is not None:
             if not hip:
                 raise ValueError("DriverLoop.rollout: positions needs the HIP env")
@@ -275,11 +304,13 @@ class DriverLoop:
                 ia_kw = dict(info_age=True, sum_ia_prev=self._sum_ia_prev if self.ia_averaging else None)
             if positions is not None:
                 ia_kw["positions"] = positions
+            if direct:
+                ia_kw["memory"] = memory
             try:
                 out = env.rollout(seq, t, mode="my_step_ch" if self.enable_channel else "my_step", states=states,
                                   global_reward_avg=self.global_reward_avg, stuck_penalty=pen, vel_seed=vel_seed, **ia_kw)
                 if "ia_penalty" in out:                                          # (as slot() reports it)
-                    out["ia_penalty"] = out["ia_penalty"].to(out["shaped"].dtype)
+                    out["ia_penalty"] = out["ia_penalty"].to(out["sum_r"].dtype)
                 if out["states"] is not None and env.cfg.enable_fingerprint:     # test_env.py:577-579
                     out["states"][..., env._fp_offset] = self.episode
                     out["states"][..., env._fp_offset + 1] = self.eps
@@ -287,6 +318,8 @@ class DriverLoop:
             except DiralError as exc:
                 if exc.status != ERR_UNSUPPORTED:
                     raise
+        if memory is not None:                   # (the launch was refused, or this driver's terms keep it from being tried)
+            return self._rollout_then_add(seq, t, vel_seed, positions, memory)
         if positions is None:
             return self._rollout_loop(seq, t, states, vel_seed, with_ia)
         env.load_saved_positions(positions)
@@ -294,6 +327,17 @@ class DriverLoop:
             return self._rollout_loop(seq, t, states, vel_seed, with_ia)
         finally:
             env.load_saved_positions(None)
+
+    def _rollout_then_add(self, seq, t: int, vel_seed: int, positions, memory) -> Dict[str, Any]:
+        """`rollout(memory=)` in two calls: every slot's state kept, then ``memory.add_rollout``."""
+        out = self.rollout(seq, t, states="all", vel_seed=vel_seed, positions=positions)
+        dev = memory.device
+        if seq.dim() == 2:                                               # ([K, N]: every env alike)
+            seq = seq.unsqueeze(1).expand(seq.shape[0], memory.B, memory.N)
+        memory.add_rollout(seq.to(device=dev, dtype=torch.int32).contiguous(),
+                           dict(states=self._t(out["states"]).to(dev).contiguous(), shaped=self._t(out["shaped"]).to(dev).contiguous()))
+        last = None if memory.count_dev is not None else memory.states[memory.count % (memory.C + 1)]
+        return dict(out, states=last, shaped=None)
 
     def _rollout_loop(self, seq, t: int, states: Optional[str], vel_seed: int, with_ia: bool) -> Dict[str, Any]:
         """`rollout` slot by slot: what its launch is equal to."""

@@ -132,6 +132,42 @@ class ReplayMemory:
         (main_test.py:110-112)."""
         self.add_many(actions, rews0, states)
 
+    # ---- a launch that writes the ring rows itself (VecV2VEnv.rollout / prefill with memory=) ----
+    def ring_block(self, K: int, batch: int, num_users: int, state_space: int, dtype: torch.dtype, device,
+                   where: str = "memory") -> DiralMemory:
+        """The descriptor a K-slot launch writes its transitions through (`diral_env_rollout_memory` /
+        `diral_env_prefill_memory`): slot k's state vector goes to state row ``count + 1 + k``, its actions and reward
+        to row ``count + k``, mod ``capacity + 1`` - `add_many`'s rows, without the scratch and without its launch.
+        Checks K and the launch's shapes, dtype and device against the rings; nothing is written or moved on here -
+        `commit` does that behind a launch that was taken."""
+        K = int(K)
+        if K < 1 or K > self.C:
+            raise ValueError("%s: 1 <= K <= capacity (%d), got %d" % (where, self.C, K))
+        if (int(batch), int(num_users), int(state_space)) != (self.B, self.N, self.S):
+            raise ValueError("%s: the memory holds [B=%d, N=%d, S=%d] rows, the launch writes [%d, %d, %d]"
+                             % (where, self.B, self.N, self.S, batch, num_users, state_space))
+        if dtype != self.dtype:
+            raise ValueError("%s: the rings are %s, the launch writes %s (no conversion: use add_rollout / add_prefill)"
+                             % (where, self.dtype, dtype))
+        if torch.device(device) != self.device:
+            raise ValueError("%s: the memory lives on %s, the env on %s" % (where, self.device, device))
+        if self.count == 0 and self.count_dev is None and self._state0 is None:
+            raise ValueError("add before begin(state)")
+        return self._desc()
+
+    def commit(self, K: int) -> Optional[torch.Tensor]:
+        """Behind a launch that wrote K transitions through `ring_block`: the pending `begin` state goes to state row
+        `count` (a stream-ordered copy, cast to the rings' dtype - the launch neither reads nor writes that row), the
+        count moves on by K.  Returns a view of the last state row written, or None when the count lives on the device."""
+        if self._state0 is not None:
+            self.states[self.count % (self.C + 1)].copy_(self._state0)   # (a begin has zeroed both counts: row 0)
+            self._state0 = None
+        if self.count_dev is None:
+            self.count += int(K)
+            return self.states[self.count % (self.C + 1)]
+        check_status(self.lib.diral_clock_add(ctypes.c_void_p(_ptr(self.count_dev)), int(K), self._stream()), "diral_clock_add")
+        return None
+
     # ---- reading ----
     def _sample(self, M: int, step: int, out_dtype, idx, env, last_only, out, seed, clock, offset):
         M, step = int(M), int(step)

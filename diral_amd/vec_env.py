@@ -234,15 +234,16 @@ class VecV2VEnv:
         self._spec = None
 
     def _shaping(self, q, where: str, global_reward_avg: bool, stuck_penalty: Optional[tuple], shaped, sum_r, collision,
-                 vel_seed: int):
-        """The fields DiralSlotPolicy and DiralRollout share: flags, the stuck penalty (its tensors checked), outputs."""
+                 vel_seed: int, ring_shaped: bool = False):
+        """The fields DiralSlotPolicy and DiralRollout share: flags, the stuck penalty (its tensors checked), outputs.
+        `ring_shaped`: the shaped rewards go to a replay memory's reward ring (`rollout(memory=)`), `shaped` is None."""
         q.struct_bytes = ctypes.sizeof(q)
         q.shape_flags = 1 if global_reward_avg else 0
         if stuck_penalty is not None:
             thr, val, cnt, prev = stuck_penalty
             for name, a in (("counter", cnt), ("prev_actions", prev)):
                 check_tensor("%s: stuck_penalty %s" % (where, name), a, torch.int32, (self.B, self.N), self.device)
-            if shaped is None:
+            if shaped is None and not ring_shaped:
                 raise ValueError("%s: stuck_penalty needs shaped_out" % where)
             q.shape_flags |= 4
             q.pen_threshold, q.pen_value = int(thr), float(val)
@@ -494,7 +495,7 @@ class VecV2VEnv:
         return out
 
     def prefill(self, actions: torch.Tensor, slots: int, seed: int, rew_in=None, want_states: bool = True,
-                episode: float = 0.0, eps: float = 1.0, mode="my_step_design"):
+                episode: float = 0.0, eps: float = 1.0, mode="my_step_design", memory=None):
         """The driver's random prefill (main_test.py:99-114) as ONE launch of `slots` slots (`diral_env_prefill_mode`):
         slot 0 runs `actions` ([B, N] int32, e.g. ``env.sample(seed)``), slot k the draw ``env.sample(seed + k)``
         would make; every slot is ``my_step_design(a_k, 0)`` - or, with `mode` = ``"my_step_ch"`` / STEP_MY_STEP_CH, the
@@ -505,12 +506,33 @@ class VecV2VEnv:
         sample + my_step_design / my_step_ch + obtain_state calls.  Raises DiralError(ERR_UNSUPPORTED) with nothing launched
         for configurations the fused kernels do not take (diral_amd.driver.DriverLoop.prefill loops then): on an AUTO
         handle below 8 vehicles, and on a handle pinned with `use_subwave_path()` unless it was pinned with ``slots=True``
-        (toy-size envs: csrc/step_subwave_slots.hpp; not on a handle with a trace or arrival stamps)."""
+        (toy-size envs: csrc/step_subwave_slots.hpp; not on a handle with a trace or arrival stamps).
+
+        `memory` (a :class:`diral_amd.ReplayMemory` of this env's B, N, S and out dtype; `rew_in` is mandatory then): the
+        launch writes the K transitions into the memory's rings itself (`diral_env_prefill_memory`) - what
+        ``memory.add_prefill(states, actions_all, rew_in)`` would store, bit for bit, without the [K]-major scratch and
+        without that launch - and the memory moves on by K.  Returns ``(last, None, next_actions)``: `last` is a view of
+        the last state row written ([B, N, S]), None when the memory counts on the device.  A refused launch leaves the
+        env and the memory as they were (N > 64 among the refusals; `DriverLoop.prefill(memory=)` loops then)."""
         step_mode = _MODES.get(mode)
         if step_mode not in (STEP_DESIGN, STEP_MY_STEP_CH):
             raise ValueError("prefill: mode must be 'my_step_design' or 'my_step_ch'")
         K = int(slots)
         a = self._actions(actions)
+        if memory is not None:
+            if rew_in is None:
+                raise ValueError("prefill: memory= stores rew_in as every slot's reward: it is mandatory")
+            blk = memory.ring_block(K, self.B, self.N, self.S, self.out_dtype, self.device, "prefill")
+            a_next = torch.empty((self.B, self.N), dtype=torch.int32, device=self.device)
+            rin = self._f64(rew_in, (self.B, self.N))
+            self._spec = None
+            st = self.lib.diral_env_prefill_memory(self._h, step_mode, _ptr(a), K, seed64(seed), None, self._dt, None,
+                                                   _ptr(a_next), _ptr(rin), float(episode), float(eps), ctypes.byref(blk),
+                                                   self._stream())
+            self._ok(st, "diral_env_prefill_memory")
+            last = memory.commit(K)
+            torch.cuda.current_stream(self.device).synchronize()   # `rin` may be a temporary
+            return last, None, a_next
         states = torch.empty((K, self.B, self.N, self.S), dtype=self.out_dtype, device=self.device) if (want_states and self.S > 0) else None
         a_all = torch.empty((K, self.B, self.N), dtype=torch.int32, device=self.device)
         a_next = torch.empty((self.B, self.N), dtype=torch.int32, device=self.device)
@@ -645,7 +667,7 @@ class VecV2VEnv:
     def rollout(self, actions_seq, t: Optional[int] = None, mode="my_step", states: Optional[str] = "last",
                 global_reward_avg: bool = False, stuck_penalty: Optional[tuple] = None, vel_seed: int = 0,
                 info_age=None, sum_ia_prev=None, positions=None,
-                log_positions: bool = False) -> Dict[str, Optional[torch.Tensor]]:
+                log_positions: bool = False, memory=None) -> Dict[str, Optional[torch.Tensor]]:
         """K slots of a GIVEN action sequence as ONE launch (`diral_env_rollout`): slot k runs ``my_step(actions_seq[k],
         t + k)`` (`mode` = ``"my_step_ch"``: ``my_step_ch``, reward_design 2 ... 4), then the driver's reward shaping
         (main_test.py:171-206 without the information-age terms, `diral_driver_shape` with the same flags) and, in configs
@@ -677,7 +699,16 @@ class VecV2VEnv:
         calls does on a handle that had `load_saved_positions(positions)`.  The handle must not carry a trace of its own
         (refused).  `log_positions`: the result gains ``xpos`` [K, B, N] float64, `get_x_pos()` behind every slot (the
         driver's position log, main_test.py:140-142), with or without `positions`; the log of a velocity-model launch
-        replays it."""
+        replays it.
+
+        `memory` (a :class:`diral_amd.ReplayMemory` of this env's B, N, S and out dtype; N <= 64;
+        `diral_env_rollout_memory`): the launch writes the K transitions into the memory's rings itself - every slot's state
+        vector, ``actions_seq[k]`` and shaped reward, what ``memory.add_rollout(actions_seq, rollout(..., states="all"))``
+        would store, bit for bit, without the [K]-major scratch and without that launch - and the memory moves on by K
+        (a pending `begin` state is stored in front).  `states` is not read; in the result ``shaped`` is None and ``states``
+        a view of the last state row written ([B, N, S]; None when the memory counts on the device); everything else is as
+        above, `info_age`, `positions` and `log_positions` included.  A refused launch leaves the env and the memory as
+        they were (`DriverLoop.rollout(memory=)` loops and adds then)."""
         step_mode = _MODES.get(mode)
         if step_mode not in (STEP_MY_STEP, STEP_MY_STEP_CH):
             raise ValueError("rollout: mode must be 'my_step' or 'my_step_ch'")
@@ -695,15 +726,22 @@ class VecV2VEnv:
         if t is None:
             t = self.t
         o = dict(dtype=self.out_dtype, device=self.device)
-        shaped, sum_r, coll = torch.empty((K, self.B, self.N), **o), torch.empty((K, self.B), **o), torch.empty((K, self.B), **o)
-        q = self._shaping(DiralRollout(), "rollout", global_reward_avg, stuck_penalty, shaped, sum_r, coll, vel_seed)
+        mblk = None
+        if memory is not None:
+            mblk = memory.ring_block(K, self.B, self.N, self.S, self.out_dtype, self.device, "rollout")
+        shaped = None if mblk is not None else torch.empty((K, self.B, self.N), **o)
+        sum_r, coll = torch.empty((K, self.B), **o), torch.empty((K, self.B), **o)
+        q = self._shaping(DiralRollout(), "rollout", global_reward_avg, stuck_penalty, shaped, sum_r, coll, vel_seed,
+                          ring_shaped=mblk is not None)
         self._bind_slot(K, False)
         want_states = states is not None and self.S > 0
-        if states == "all" and want_states:
+        if mblk is not None:
+            st_out = None                                # (the state ring takes every slot's state vector)
+        elif states == "all" and want_states:
             st_out = torch.empty((K, self.B, self.N, self.S), dtype=self.out_dtype, device=self.device)
         else:
             st_out = self._obs if want_states else None
-        args = (self._h, step_mode, _ptr(seq), K, int(t), _ptr(st_out), 1 if states == "all" else 0,
+        args = (self._h, step_mode, _ptr(seq), K, int(t), _ptr(st_out), 1 if (states == "all" and mblk is None) else 0,
                 _ptr(self._rew), _ptr(self._done), self._dt, ctypes.byref(q))
         blk, ia_out = None, {}
         if info_age is not None:
@@ -714,6 +752,11 @@ class VecV2VEnv:
             rblk, rseq = self._replay_block("rollout", positions, xpos, K)
             if log_positions:
                 ia_out = dict(ia_out, xpos=xpos)
+        if mblk is not None:
+            st = self.lib.diral_env_rollout_memory(*args, None if blk is None else ctypes.byref(blk),
+                                                   None if rblk is None else ctypes.byref(rblk), ctypes.byref(mblk),
+                                                   self._stream())
+        elif rblk is not None:
             st = self.lib.diral_env_rollout_replay(*args, None if blk is None else ctypes.byref(blk), ctypes.byref(rblk),
                                                    self._stream())
         elif blk is None:
@@ -723,6 +766,8 @@ class VecV2VEnv:
         self._ok(st, "diral_env_rollout", K)            # (a refused call has launched nothing: the ring is back where it was)
         self.t = int(t) + K
         self._keep["rollout"] = (q, seq, stuck_penalty, blk, sum_ia_prev, rblk, rseq)
+        if mblk is not None:
+            st_out = memory.commit(K)
         return dict(states=st_out, reward=self._rew, done=self._done, shaped=shaped, sum_r=sum_r, collision=coll, **ia_out)
 
     def step(self, actions, t: Optional[int] = None, episode: float = 0.0, epsilon: float = 1.0

@@ -868,6 +868,37 @@ typedef struct DiralMemorySample {
 } DiralMemorySample;
 int diral_memory_sample(const DiralMemory* m, const DiralMemorySample* s, void* stream);
 
+/* The K-slot rollout and prefill write the ring rows themselves (additive within ABI 8; step_fast64_slots_kernel at
+ * 8 <= N <= 64 and step_subwave_slots_kernel at N <= 8).  diral_env_rollout_memory is diral_env_rollout_replay with one
+ * more argument, the caller's DiralMemory; diral_env_prefill_memory is diral_env_prefill_mode with the same.  A ring row is
+ * a [batch][num_users][state_space] block like a row of states_out, so with the block slot k of the launch writes
+ *   its state vector (what states_out[k] would get)                       to state row  (count + 1 + k)
+ *   the actions it ran with (actions_seq[k]; prefill: actions_all_out[k]) to action row (count + k)
+ *   rollout: its shaped reward (what shaped_out[k] would get)             to reward row (count + k)
+ *   prefill: rew_in[b][n] cast to the ring dtype, for every slot          to reward row (count + k)
+ * all mod (capacity + 1), across the wrap: the rows and values diral_memory_add writes from the launch's scratch outputs
+ * (above; rewards_broadcast for the prefill), without that launch and without the scratch.  count is the host value, or
+ * *count_dev read once per workgroup.  State row `count` must already be valid - the last state of the previous add, or
+ * state0 written there by the caller after a begin -: the launch does not write it.  The count is the caller's to move on
+ * (diral_clock_add(count_dev, slots)), as for diral_memory_add.  sum_r_out and collision_out stay [K][B] caller outputs,
+ * rew_out and done_out the last slot's; ia and replay blocks are taken as by diral_env_rollout_replay.  Enqueue-only.
+ *   `memory` NULL: exactly diral_env_rollout_replay / diral_env_prefill_mode, refusals included.
+ *   DIRAL_ERR_BAD_ARG (checked first, no device needed): a wrong struct_bytes, a NULL ring, capacity < 1, slots > capacity,
+ *     count < 0 (host count), batch / num_users / state_space that differ from the handle's B, N and state size, the ring
+ *     dtype != out_dtype (no conversion is added: the stored bits are the scratch path's), states_out or shaped_out
+ *     (rollout) / states_out or actions_all_out (prefill) given together with the block - the rings take their place -,
+ *     a prefill without rew_in, and everything the base entry point rejects;
+ *   DIRAL_ERR_UNSUPPORTED, nothing launched, env and rings untouched: N > 64 (step_wide_slots_kernel has no states_all),
+ *     a handle pinned to DIRAL_PATH_SUBWAVE without DIRAL_OPT_SUBWAVE_SLOTS, and everything the base entry point refuses
+ *     (loop and diral_memory_add instead: diral_amd.driver.DriverLoop.rollout / prefill with memory= do). */
+int diral_env_rollout_memory(DiralEnv* env, int mode, const int32_t* actions_seq, int32_t slots, int64_t t, void* states_out,
+                             int states_all, void* rew_out, uint8_t* done_out, int out_dtype, const DiralRollout* rollout,
+                             const DiralSlotInfoAge* ia, const DiralSlotReplay* replay, const DiralMemory* memory,
+                             void* stream);
+int diral_env_prefill_memory(DiralEnv* env, int mode, const int32_t* actions, int32_t slots, uint64_t seed, void* states_out,
+                             int out_dtype, int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in,
+                             double episode, double epsilon, const DiralMemory* memory, void* stream);
+
 /* Replaces SemiPersistentScheduling.__init__ (v2x_sps.py:8-22): prev_action =
  * randint(0, selection_window) (inclusive, as in the reference), counter =
  * randint(5, 15); device RNG from `seed`. */
