@@ -440,11 +440,21 @@ hipError_t alloc_large_scratch(DiralEnv* e) {
 
 size_t slow_set_words(const DiralEnv* e) { return 16 + (size_t)fast_slow_max(e->B) + (size_t)e->B; }
 
-// What one step call launches: decided in ONE place and without side effects, from the handle, the call's parameters
-// and its policy request (`pol`: diral_env_step_policy / diral_env_prefill / diral_env_rollout, else null) - for the launch itself
-// (launch_step_any) and for everyone who must know the outcome before anything is launched (`fused`).
+// A slot call (diral_env_step_policy - the closed loop -, diral_env_prefill, diral_env_rollout), described once: what the
+// slot loops are handed, zero until the call or a block sets it (`prefill` / `rollout`: which call; ia_on / rp_on / mem_on:
+// which blocks), and whether the closed loop got a channel-observation buffer (it can run a slot as three launches then)
+struct SlotRequest { PolParams q{}; bool chobs = false; };
+// a state vector with a secondary observation mode (a15 / a16): launches of their own behind ONE vector (posdist_kernel.hpp)
+bool secondary_obs(const StepParams& p) {
+  return p.state_out && ((p.flags & DIRAL_F_ADD_POSDIST) || ((p.flags & DIRAL_F_ADD_POSDIST_PIGGY) && p.posdist_type == 1));
+}
+
+// What one step call launches, or the status that refuses it: decided by plan_step - which refuses, and has choose_launch
+// pick the kernel - without side effects or HIP calls, from the handle, the call's parameters and its slot request (null: diral_env_step / diral_env_observe) -
+// for the launch itself (launch_step_any) and for everyone who must know the outcome before anything is launched.
 enum class StepLaunch { Large, General, Subwave, SubwaveSlots, Fast64, Wide, Fast64Policy, Fast64Slots, WideSlots };
 struct StepPlan {
+  int status;                  // DIRAL_OK, or why the slot call is refused: nothing is launched then
   StepLaunch launch;
   bool use_fast64, use_wide;   // the kernel family of the five specialised launches
   bool use_ring;               // xpos ring (step_fast64.hpp): the kernel keeps the plane only for entries older than the ring reaches
@@ -458,7 +468,8 @@ struct StepPlan {
   KernelSel k;
   int last_kernel;             // DIRAL_KERNEL_*
 };
-StepPlan plan_step(const DiralEnv* e, const StepParams& p, const PolParams* pol) {
+// the kernel family and instantiation of a call that plan_step has not refused by then
+StepPlan choose_launch(const DiralEnv* e, const StepParams& p, const PolParams* pol) {
   StepPlan d = {};
   if (runs_large(e)) {
     // (and diral_env_observe: the search kernel's observe mode + the histogram launch)
@@ -469,16 +480,12 @@ StepPlan plan_step(const DiralEnv* e, const StepParams& p, const PolParams* pol)
     // toy-size envs, 4 or 8 lanes each (step_subwave.hpp): every step call of a pinned handle, on the planes; never `fused`
     d.launch = StepLaunch::Subwave; d.last_kernel = DIRAL_KERNEL_SUBWAVE;
     // ... unless the handle opted in to the slot loop (DIRAL_OPT_SUBWAVE_SLOTS, step_subwave_slots.hpp): an open-loop rollout of
-    // any K >= 1 and the random prefill, without the information-age and replay / position-log blocks.  The secondary
-    // observation modes are launches of their own behind ONE state vector (posdist_kernel.hpp); the prefill refuses a handle
-    // with a trace or arrival stamps, as the fast64 prefill does.  diral_env_step_policy stays where it was: the SPS agents
-    // are wave-cooperative code.
-    if (e->subwave_slots && pol && (pol->prefill || pol->rollout) && !pol->ia_on && !pol->rp_on) {
-      const bool secondary = p.state_out && ((p.flags & DIRAL_F_ADD_POSDIST) || ((p.flags & DIRAL_F_ADD_POSDIST_PIGGY) && p.posdist_type == 1));
-      const bool tracking = ((p.flags & DIRAL_F_TRACK_ARRIVAL) && p.la != nullptr) || p.trace != nullptr;
-      if (!secondary && !e->prev_obs && !(pol->prefill && tracking)) {
-        d.launch = StepLaunch::SubwaveSlots; d.fused = true; d.last_kernel = DIRAL_KERNEL_SUBWAVE | DIRAL_KERNEL_POLICY;
-      }
+    // any K >= 1 and the random prefill, without the information-age and replay / position-log blocks; the prefill refuses a
+    // handle with a trace or arrival stamps, as the fast64 prefill does.  diral_env_step_policy stays where it was: the SPS
+    // agents are wave-cooperative code.
+    const bool tracking = ((p.flags & DIRAL_F_TRACK_ARRIVAL) && p.la != nullptr) || p.trace != nullptr;
+    if (e->subwave_slots && pol && (pol->prefill || pol->rollout) && !pol->ia_on && !pol->rp_on && !(pol->prefill && tracking)) {
+      d.launch = StepLaunch::SubwaveSlots; d.fused = true; d.last_kernel = DIRAL_KERNEL_SUBWAVE | DIRAL_KERNEL_POLICY;
     }
     return d;
   }
@@ -526,13 +533,9 @@ StepPlan plan_step(const DiralEnv* e, const StepParams& p, const PolParams* pol)
   if (pol && pol->prefill) { if (prefill_ok || pol_ch_ok) d.launch = StepLaunch::Fast64Slots; }
   else if (pol && pol->rollout) {
     // an open-loop rollout (diral_env_rollout): any K >= 1 on the two slot loops - every slot's state vector only where
-    // the env stays on the chip (N <= 64); the secondary observation modes are launches of their own behind ONE state
-    // vector (posdist_kernel.hpp), State.piggybacking's A * A observation is piggy_emit_kernel's
-    const bool secondary = p.state_out && ((p.flags & DIRAL_F_ADD_POSDIST) || ((p.flags & DIRAL_F_ADD_POSDIST_PIGGY) && p.posdist_type == 1));
-    if (!secondary && !e->prev_obs) {
-      if (pol_ok || pol_ch_ok) d.launch = StepLaunch::Fast64Slots;
-      else if (wide_kslots_ok && !(pol->rollout & 2)) d.launch = StepLaunch::WideSlots;
-    }
+    // the env stays on the chip (N <= 64)
+    if (pol_ok || pol_ch_ok) d.launch = StepLaunch::Fast64Slots;
+    else if (wide_kslots_ok && !(pol->rollout & 2)) d.launch = StepLaunch::WideSlots;
   }
   else if (pol && pol->K > 1) { if (pol_ok || pol_ch_ok) d.launch = StepLaunch::Fast64Slots; else if (wide_kslots_ok) d.launch = StepLaunch::WideSlots; }
   else if (pol && pol_ok) d.launch = StepLaunch::Fast64Policy;
@@ -557,6 +560,36 @@ StepPlan plan_step(const DiralEnv* e, const StepParams& p, const PolParams* pol)
   d.last_kernel = (d.use_wide ? DIRAL_KERNEL_WIDE : DIRAL_KERNEL_FAST64) | ((k.rich || d.fused) ? DIRAL_KERNEL_RICH : 0) |
                   ((k.packed || d.use_fast64) ? DIRAL_KERNEL_PACKED : 0) | (k.extra ? DIRAL_KERNEL_EXTRA : 0) |
                   (k.ch ? DIRAL_KERNEL_CH : 0) | (d.use_ring ? DIRAL_KERNEL_RING : 0) | (d.fused ? DIRAL_KERNEL_POLICY : 0);
+  return d;
+}
+
+// The verdict of a call (DESIGN.md section 6 tabulates it): a slot call is refused here by what the handle is, or by which
+// launch choose_launch picks for it.  The first reason below wins - the order is behaviour (tests/test_gpu_slot_refusals.py).
+StepPlan plan_step(const DiralEnv* e, const StepParams& p, const SlotRequest* req) {
+  if (!req) return choose_launch(e, p, nullptr);
+  const PolParams& q = req->q;
+  const bool closed = !q.prefill && !q.rollout, ch = p.mode == DIRAL_STEP_MY_STEP_CH, ia = q.ia_on != 0;
+  const bool bad_draws = closed && q.K > 1 && (q.draw_counter || q.draw_keep || q.draw_choice);   // (they draw on the device)
+  auto refuse = [](int status) { StepPlan d = {}; d.status = status; return d; };
+  if (ia && bad_draws) return refuse(DIRAL_ERR_BAD_ARG);
+  if (ia && !e->la) return refuse(DIRAL_ERR_BAD_CONFIG);        // (as diral_env_info_age)
+  // my_step's only stamp effect is the -1 of network.py:394; there is no fused one-slot my_step_ch launch
+  if (ia && (!ch || (closed && q.K <= 1))) return refuse(DIRAL_ERR_UNSUPPORTED);
+  if (closed && e->A > kSpsWaveMaxA) return refuse(DIRAL_ERR_UNSUPPORTED);
+  // State.piggybacking: the SPS agents sense A values, not A * A, the A * A observation is piggy_emit_kernel's, and the steps
+  // are my_step only (diral_env_step): the loop a my_step_design prefill stands for fails there too
+  if (e->prev_obs) return refuse(q.prefill && !ch ? DIRAL_ERR_BAD_CONFIG : DIRAL_ERR_UNSUPPORTED);
+  if (bad_draws) return refuse(DIRAL_ERR_BAD_ARG);
+  if (!closed && secondary_obs(p)) return refuse(DIRAL_ERR_UNSUPPORTED);   // (the closed loop's last state vector gets its launches)
+  StepPlan d = choose_launch(e, p, &q);
+  const bool fast_slots = d.launch == StepLaunch::Fast64Slots;
+  // not fused: one slot of the closed loop runs as three launches around the caller's channel observation (a caller without
+  // the buffer can retry with one); a prefill or rollout launches nothing, the caller loops
+  if (!d.fused && (!closed || !req->chobs || q.K > 1)) d.status = DIRAL_ERR_UNSUPPORTED;
+  // only step_fast64's slot loop keeps the stamps and takes recorded positions (one closed-loop slot: diral_env_set_trace)
+  if ((ia && !fast_slots) || (q.rp_on && (!fast_slots || (closed && q.K <= 1)))) d.status = DIRAL_ERR_UNSUPPORTED;
+  // the memory block: the two slot loops that keep the env on the chip - the wide one has no states_all
+  if (q.mem_on && !fast_slots && d.launch != StepLaunch::SubwaveSlots) d.status = DIRAL_ERR_UNSUPPORTED;
   return d;
 }
 
@@ -667,7 +700,7 @@ hipError_t launch_step_any(DiralEnv* e, const StepParams& p, const StepPlan& d, 
 hipError_t launch_posdist_if_needed(DiralEnv* e, const StepParams& p, hipStream_t s) {
   const bool full = (p.flags & DIRAL_F_ADD_POSDIST) != 0;
   const bool type1 = (p.flags & DIRAL_F_ADD_POSDIST_PIGGY) && p.posdist_type == 1;
-  if (!p.state_out || !(full || type1)) return hipSuccess;
+  if (!secondary_obs(p)) return hipSuccess;
   PosdistParams q;
   q.N = p.N; q.A = p.A; q.K = p.K; q.S = p.S; q.NV = p.NV; q.NR = p.NR; q.flags = p.flags;
   q.posdist_type = p.posdist_type; q.age_limit = p.age_limit; q.out_f64 = p.out_f64;
@@ -757,6 +790,32 @@ hipError_t launch_sps_wave(int agents, int num_channels, const void* src, hipStr
   if (num_channels <= 64) return launch_1d<sps_step_wave_kernel<1, T, CHOBS>>((size_t)agents, s, agents, num_channels, in, rest...);
   if (num_channels <= 128) return launch_1d<sps_step_wave_kernel<2, T, CHOBS>>((size_t)agents, s, agents, num_channels, in, rest...);
   return launch_1d<sps_step_wave_kernel<4, T, CHOBS>>((size_t)agents, s, agents, num_channels, in, rest...);
+}
+
+// The argument checks every step entry point shares: the step mode (`not_taken`: the one DIRAL_STEP_* the entry does not
+// take, -1: it takes all three), the out dtype, my_step_ch's reward_design - rewards only for 2, 3, 4 (test_env.py:413-429)
+int call_check(const DiralEnv* e, int mode, int not_taken, int out_dtype) {
+  if ((mode != DIRAL_STEP_MY_STEP && mode != DIRAL_STEP_MY_STEP_CH && mode != DIRAL_STEP_DESIGN) || mode == not_taken) return DIRAL_ERR_BAD_ARG;
+  if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
+  if (mode == DIRAL_STEP_MY_STEP_CH && (e->cfg.reward_design < 2 || e->cfg.reward_design > 4)) return DIRAL_ERR_BAD_CONFIG;
+  return DIRAL_OK;
+}
+// The shaping fields DiralSlotPolicy and DiralRollout share by name (`S`: either), checked and handed to the slot loops;
+// `shaped_out`: the struct's own buffer or a memory block's reward ring
+template <typename S>
+int shaping_params(const S& s, void* shaped_out, const void* rew_out, PolParams& q) {
+  if ((s.shape_flags & ~5) != 0) return DIRAL_ERR_BAD_ARG;       // global_reward_avg | stuck-action penalty
+  if (s.shaped_out && !rew_out) return DIRAL_ERR_BAD_ARG;        // (the three-launch form and the wide slot loop shape rew_out)
+  if (shaped_out && (s.shape_flags & 4) && (!s.pen_counter || !s.pen_prev_actions)) return DIRAL_ERR_BAD_ARG;
+  q.shape_flags = s.shape_flags; q.pen_threshold = s.pen_threshold; q.pen_value = s.pen_value;
+  q.shaped_out = shaped_out; q.sum_r_out = s.sum_r_out; q.coll_out = s.collision_out;
+  q.pen_counter = s.pen_counter; q.pen_prev = s.pen_prev_actions;
+  return DIRAL_OK;
+}
+// The launch-wide fields; `vel_updates`: mobility_vary's draws behind episode ends (the prefill's slots all run at t = 0)
+void launch_params(const DiralEnv* e, int slots, bool vel_updates, uint64_t vel_seed, PolParams& q) {
+  q.K = slots; q.vel_vary = (vel_updates && has(&e->cfg, DIRAL_F_MOBILITY_VARY)) ? 1 : 0; q.vel_seed = vel_seed;
+  q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N; q.vel_w = e->vel;
 }
 
 }  // namespace
@@ -1082,12 +1141,7 @@ int diral_env_step(DiralEnv* e, int mode, const int32_t* actions, int64_t t, voi
                    uint8_t* done_out, void* chobs_out, int out_dtype, double episode, double epsilon,
                    void* stream) {
   if (!e || !actions) return DIRAL_ERR_BAD_ARG;
-  if (mode != DIRAL_STEP_MY_STEP && mode != DIRAL_STEP_MY_STEP_CH && mode != DIRAL_STEP_DESIGN)
-    return DIRAL_ERR_BAD_ARG;
-  if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
-  // my_step_ch defines rewards only for reward_design 2,3,4 (test_env.py:413-429)
-  if (mode == DIRAL_STEP_MY_STEP_CH && (e->cfg.reward_design < 2 || e->cfg.reward_design > 4))
-    return DIRAL_ERR_BAD_CONFIG;
+  if (const int bad = call_check(e, mode, -1, out_dtype)) return bad;
   DEVICE_ENTER(e->device);
   hipStream_t s = (hipStream_t)stream;
   StepParams p = call_params(e, mode, t, actions, state_out, out_dtype, episode, epsilon);
@@ -1123,7 +1177,6 @@ static int ia_block_check(const DiralSlotInfoAge* ia, const void* shaped_out) {
 }
 // ... and what the slot loop is handed (PolParams::ia_on: bit 0 the block, bit 1 a histogram pass every slot)
 static void ia_block_params(const DiralSlotInfoAge* ia, PolParams& q) {
-  q.ia_on = 0; q.ia_flags = 0; q.ia_out = nullptr; q.ia_sum_out = nullptr; q.ia_pen_out = nullptr; q.sum_ia_prev = nullptr;
   if (!ia) return;
   const bool hist = ia->ia_out || ia->ia_sum_out || (ia->flags & 1);
   q.ia_on = 1 | (hist ? 2 : 0); q.ia_flags = ia->flags;
@@ -1137,12 +1190,10 @@ static int replay_block_check(const DiralSlotReplay* rp) {
   if (rp->x_positions ? rp->T < 1 : rp->T != 0) return DIRAL_ERR_BAD_ARG;
   return DIRAL_OK;
 }
-// ... and what the slot loop is handed; false: the block is absent or empty - the call is its _ia entry point's
-static bool replay_block_params(const DiralSlotReplay* rp, PolParams& q) {
-  q.rp_on = 0; q.rp_T = 0; q.rp_per_env = 0; q.rp_x = nullptr; q.rp_xout = nullptr;
-  if (!rp || (!rp->x_positions && !rp->xpos_out)) return false;
+// ... and what the slot loop is handed (nothing where the block is absent or empty: the call is its _ia entry point's)
+static void replay_block_params(const DiralSlotReplay* rp, PolParams& q) {
+  if (!rp || (!rp->x_positions && !rp->xpos_out)) return;
   q.rp_on = 1; q.rp_T = rp->T; q.rp_per_env = rp->per_env ? 1 : 0; q.rp_x = rp->x_positions; q.rp_xout = rp->xpos_out;
-  return true;
 }
 
 // The memory block of a rollout / prefill (DiralMemory: diral_env_rollout_memory / diral_env_prefill_memory): its own
@@ -1155,8 +1206,6 @@ static int memory_block_check(const DiralEnv* e, const DiralMemory* m, int32_t s
 }
 // ... and what the slot loops are handed (a host count: its row; a device count is read by the kernel)
 static void memory_block_params(const DiralMemory* m, PolParams& q) {
-  q.mem_on = 0; q.mem_rows = 0; q.mem_head = 0; q.mem_count_dev = nullptr;
-  q.mem_states = nullptr; q.mem_actions = nullptr; q.mem_rewards = nullptr;
   if (!m) return;
   q.mem_on = 1; q.mem_rows = m->capacity + 1;
   q.mem_head = m->count_dev ? 0 : (int)(m->count % (int64_t)q.mem_rows);
@@ -1171,45 +1220,21 @@ static int step_policy_impl(DiralEnv* e, int mode, const int32_t* actions, int64
   if (rp && replay_block_check(rp) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
   if (ia && ia_block_check(ia, pol->shaped_out) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
   if (!pol->sps_prev_action || !pol->sps_counter || !pol->actions_out) return DIRAL_ERR_BAD_ARG;
-  if (mode != DIRAL_STEP_MY_STEP && mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_BAD_ARG;
-  if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
-  if (mode == DIRAL_STEP_MY_STEP_CH && (e->cfg.reward_design < 2 || e->cfg.reward_design > 4)) return DIRAL_ERR_BAD_CONFIG;
-  if (pol->shaped_out && !rew_out) return DIRAL_ERR_BAD_ARG;                 // (the three-launch form shapes rew_out)
-  if ((pol->shape_flags & ~5) != 0) return DIRAL_ERR_BAD_ARG;                // global_reward_avg | stuck-action penalty
-  if (pol->shaped_out && (pol->shape_flags & 4) && (!pol->pen_counter || !pol->pen_prev_actions)) return DIRAL_ERR_BAD_ARG;
-  if (ia) {
-    if (pol->slots > 1 && (pol->draw_counter || pol->draw_keep || pol->draw_choice)) return DIRAL_ERR_BAD_ARG;
-    if (!e->la) return DIRAL_ERR_BAD_CONFIG;                     // (as diral_env_info_age)
-    // my_step's only stamp effect is the -1 of network.py:394; there is no fused one-slot my_step_ch launch
-    if (mode != DIRAL_STEP_MY_STEP_CH || pol->slots <= 1) return DIRAL_ERR_UNSUPPORTED;
-  }
-  if (e->A > kSpsWaveMaxA) return DIRAL_ERR_UNSUPPORTED;
-  if (e->prev_obs) return DIRAL_ERR_UNSUPPORTED;                // State.piggybacking: the SPS agents sense A values, not A * A
-  DEVICE_ENTER(e->device);
+  if (const int bad = call_check(e, mode, DIRAL_STEP_DESIGN, out_dtype)) return bad;
+  SlotRequest req{{}, chobs_out != nullptr};
+  PolParams& q = req.q;                                          // (no memory block: the closed loop writes the last state only)
+  if (const int bad = shaping_params(*pol, pol->shaped_out, rew_out, q)) return bad;
   StepParams p = call_params(e, mode, t, actions, state_out, out_dtype, 0.0, 1.0);
   p.rew_out = rew_out; p.done_out = done_out; p.chobs_out = chobs_out;
-  PolParams q;
-  q.shape_flags = pol->shape_flags; q.pen_threshold = pol->pen_threshold; q.pen_value = pol->pen_value;
-  q.shaped_out = pol->shaped_out; q.sum_r_out = pol->sum_r_out; q.coll_out = pol->collision_out;
-  q.pen_counter = pol->pen_counter; q.pen_prev = pol->pen_prev_actions;
   q.sps_prev = pol->sps_prev_action; q.sps_counter = pol->sps_counter;
   q.threshold = pol->rssi_threshold; q.inc_db = pol->inc_db; q.keep_prob = pol->keep_prob;
   q.draw_counter = pol->draw_counter; q.draw_keep = pol->draw_keep; q.draw_choice = pol->draw_choice;
   q.seed = pol->seed; q.clock = (const long long*)pol->seed_clock; q.actions_out = pol->actions_out;
-  const int slots = pol->slots > 1 ? pol->slots : 1;
-  q.K = slots; q.vel_vary = has(&e->cfg, DIRAL_F_MOBILITY_VARY) ? 1 : 0; q.vel_seed = pol->vel_seed;
-  q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N; q.vel_w = e->vel;
-  q.prefill = 0; q.actions_all = nullptr; q.rew_in = nullptr; q.rollout = 0; q.actions_seq = nullptr;
-  memory_block_params(nullptr, q);                               // (the closed loop writes the last state only)
-  ia_block_params(ia, q);
-  const bool replay = replay_block_params(rp, q);
-  if (slots > 1 && (pol->draw_counter || pol->draw_keep || pol->draw_choice)) return DIRAL_ERR_BAD_ARG;
-  // (decided before anything is launched: a caller without a channel-observation buffer can retry with one)
-  const StepPlan d = plan_step(e, p, &q);
-  if (!d.fused && (!chobs_out || slots > 1)) return DIRAL_ERR_UNSUPPORTED;
-  if (ia && d.launch != StepLaunch::Fast64Slots) return DIRAL_ERR_UNSUPPORTED;   // (only that slot loop keeps the stamps)
-  // (... and only its K-slot form takes recorded positions: a one-slot call stays diral_env_set_trace + diral_env_step_policy)
-  if (replay && (d.launch != StepLaunch::Fast64Slots || slots <= 1)) return DIRAL_ERR_UNSUPPORTED;
+  launch_params(e, pol->slots > 1 ? pol->slots : 1, true, pol->vel_seed, q);
+  ia_block_params(ia, q); replay_block_params(rp, q);
+  const StepPlan d = plan_step(e, p, &req);
+  if (d.status != DIRAL_OK) return d.status;                     // (nothing launched, no device entered)
+  DEVICE_ENTER(e->device);
   HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
   HIP_TRY(e, launch_posdist_if_needed(e, p, (hipStream_t)stream));
   if (d.fused) return DIRAL_OK;
@@ -1246,30 +1271,21 @@ static int prefill_impl(DiralEnv* e, int mode, const int32_t* actions, int32_t s
                         int out_dtype, int32_t* actions_all_out, int32_t* actions_next_out, const double* rew_in,
                         double episode, double epsilon, const DiralMemory* mem, void* stream) {
   if (!e || !actions || !actions_next_out || slots < 1) return DIRAL_ERR_BAD_ARG;
-  if (mode != DIRAL_STEP_DESIGN && mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_BAD_ARG;
-  if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
   if (mem) {
     // the rings take the place of the scratch outputs; the reward they store is the stale bootstrap one
     if (memory_block_check(e, mem, slots, out_dtype) != DIRAL_OK || states_out || actions_all_out || !rew_in) return DIRAL_ERR_BAD_ARG;
     states_out = mem->states;
   }
-  const bool ch = mode == DIRAL_STEP_MY_STEP_CH;
-  // my_step_ch defines rewards only for reward_design 2,3,4 (test_env.py:413-429)
-  if (ch && (e->cfg.reward_design < 2 || e->cfg.reward_design > 4)) return DIRAL_ERR_BAD_CONFIG;
-  // State.piggybacking: my_step only (diral_env_step) - the loop this launch stands for fails there too
-  if (e->prev_obs) return ch ? DIRAL_ERR_UNSUPPORTED : DIRAL_ERR_BAD_CONFIG;
-  // the secondary observation modes are launches of their own behind ONE state vector (posdist_kernel.hpp)
-  if (states_out && (has(&e->cfg, DIRAL_F_ADD_POSDIST) || (has(&e->cfg, DIRAL_F_ADD_POSDIST_PIGGY) && e->cfg.posdist_type == 1)))
-    return DIRAL_ERR_UNSUPPORTED;
-  DEVICE_ENTER(e->device);
+  if (const int bad = call_check(e, mode, DIRAL_STEP_MY_STEP, out_dtype)) return bad;
   const StepParams p = call_params(e, mode, 0, actions, states_out, out_dtype, episode, epsilon);
-  PolParams q;
-  std::memset(&q, 0, sizeof(q));
-  q.K = slots; q.prefill = 1; q.seed = seed; q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N;
-  q.actions_out = actions_next_out; q.actions_all = actions_all_out; q.rew_in = rew_in; q.vel_w = e->vel;
+  SlotRequest req; PolParams& q = req.q;
+  launch_params(e, slots, false, 0, q);
+  q.prefill = 1; q.seed = seed;
+  q.actions_out = actions_next_out; q.actions_all = actions_all_out; q.rew_in = rew_in;
   memory_block_params(mem, q);
-  const StepPlan d = plan_step(e, p, &q);
-  if (!d.fused) return DIRAL_ERR_UNSUPPORTED;                    // (nothing launched: the caller loops sample + step + observe)
+  const StepPlan d = plan_step(e, p, &req);
+  if (d.status != DIRAL_OK) return d.status;                     // (nothing launched, no device entered: the caller loops sample + step + observe)
+  DEVICE_ENTER(e->device);
   HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
   return DIRAL_OK;
 }
@@ -1293,7 +1309,6 @@ static int rollout_impl(DiralEnv* e, int mode, const int32_t* actions_seq, int32
                         const DiralSlotInfoAge* ia, const DiralSlotReplay* rp, const DiralMemory* mem, void* stream) {
   if (!e || !actions_seq || !ro || ro->struct_bytes != sizeof(DiralRollout) || slots < 1) return DIRAL_ERR_BAD_ARG;
   if (rp && replay_block_check(rp) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
-  if (out_dtype != DIRAL_F32 && out_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
   void* shaped_out = ro->shaped_out;
   if (mem) {
     // the rings take the place of the scratch outputs: every slot's state vector and shaped reward leave, into ring rows
@@ -1301,36 +1316,17 @@ static int rollout_impl(DiralEnv* e, int mode, const int32_t* actions_seq, int32
     states_out = mem->states; states_all = 1; shaped_out = mem->rewards;
   }
   if (ia && ia_block_check(ia, shaped_out) != DIRAL_OK) return DIRAL_ERR_BAD_ARG;
-  if (mode != DIRAL_STEP_MY_STEP && mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_BAD_ARG;
-  if ((ro->shape_flags & ~5) != 0) return DIRAL_ERR_BAD_ARG;                  // global_reward_avg | stuck-action penalty
-  if (ro->shaped_out && !rew_out) return DIRAL_ERR_BAD_ARG;                   // (the wide slot loop shapes what rew_out holds)
-  if (shaped_out && (ro->shape_flags & 4) && (!ro->pen_counter || !ro->pen_prev_actions)) return DIRAL_ERR_BAD_ARG;
-  // my_step_ch defines rewards only for reward_design 2,3,4 (test_env.py:413-429)
-  if (mode == DIRAL_STEP_MY_STEP_CH && (e->cfg.reward_design < 2 || e->cfg.reward_design > 4)) return DIRAL_ERR_BAD_CONFIG;
-  if (ia) {
-    if (!e->la) return DIRAL_ERR_BAD_CONFIG;                     // (as diral_env_info_age)
-    if (mode != DIRAL_STEP_MY_STEP_CH) return DIRAL_ERR_UNSUPPORTED;   // my_step's only stamp effect is the -1 of network.py:394
-  }
-  DEVICE_ENTER(e->device);
+  SlotRequest req; PolParams& q = req.q;
+  if (const int bad = shaping_params(*ro, shaped_out, rew_out, q)) return bad;
+  if (const int bad = call_check(e, mode, DIRAL_STEP_DESIGN, out_dtype)) return bad;
   StepParams p = call_params(e, mode, t, actions_seq, states_out, out_dtype, 0.0, 1.0);
   p.rew_out = rew_out; p.done_out = done_out;
-  PolParams q;
-  std::memset(&q, 0, sizeof(q));
-  q.shape_flags = ro->shape_flags; q.pen_threshold = ro->pen_threshold; q.pen_value = ro->pen_value;
-  q.shaped_out = shaped_out; q.sum_r_out = ro->sum_r_out; q.coll_out = ro->collision_out;
-  q.pen_counter = ro->pen_counter; q.pen_prev = ro->pen_prev_actions;
-  q.K = slots; q.vel_vary = has(&e->cfg, DIRAL_F_MOBILITY_VARY) ? 1 : 0; q.vel_seed = ro->vel_seed;
-  q.idx0 = (uint64_t)e->env_offset * (uint64_t)e->N; q.vel_w = e->vel;
+  launch_params(e, slots, true, ro->vel_seed, q);
   q.rollout = 1 | ((states_all && p.state_out) ? 2 : 0); q.actions_seq = actions_seq;
-  ia_block_params(ia, q);
-  const bool replay = replay_block_params(rp, q);
-  memory_block_params(mem, q);
-  const StepPlan d = plan_step(e, p, &q);
-  if (!d.fused) return DIRAL_ERR_UNSUPPORTED;                    // (nothing launched: the caller loops step + shape)
-  if (ia && d.launch != StepLaunch::Fast64Slots) return DIRAL_ERR_UNSUPPORTED;   // (only that slot loop keeps the stamps)
-  if (replay && d.launch != StepLaunch::Fast64Slots) return DIRAL_ERR_UNSUPPORTED;   // (... and takes recorded positions)
-  // (the memory block: the two slot loops that keep the env on the chip - the wide one has no states_all)
-  if (mem && d.launch != StepLaunch::Fast64Slots && d.launch != StepLaunch::SubwaveSlots) return DIRAL_ERR_UNSUPPORTED;
+  ia_block_params(ia, q); replay_block_params(rp, q); memory_block_params(mem, q);
+  const StepPlan d = plan_step(e, p, &req);
+  if (d.status != DIRAL_OK) return d.status;                     // (nothing launched, no device entered: the caller loops step + shape)
+  DEVICE_ENTER(e->device);
   HIP_TRY(e, launch_step_any(e, p, d, (hipStream_t)stream, &q));
   return DIRAL_OK;
 }

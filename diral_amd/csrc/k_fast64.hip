@@ -13,18 +13,36 @@ namespace diral {
 #undef DIRAL_FAST_KERNEL
 
 namespace {
+struct Fast64Args { const FastParams& f; const RichParams& r; const PolParams& q; dim3 g; uint32_t lds; hipStream_t s; };
+template <bool POL>
 struct LaunchFast64 {
-  const FastParams& f; const RichParams& r; const PolParams& q; dim3 g; uint32_t lds; hipStream_t s;
+  Fast64Args a;
   template <bool FL, bool O, bool C, bool X, bool R>
   void operator()(std::integer_sequence<bool, FL, O, C, X, R>) const {
-    hipLaunchKernelGGL((step_fast64_kernel<FL, O, C, X, R>), g, dim3(256), lds, s, f, r, q);
+    hipLaunchKernelGGL((step_fast64_kernel<FL, O, C, X, R, POL>), a.g, dim3(256), a.lds, a.s, a.f, a.r, a.q);
+  }
+};
+// The slot loop's instantiations (FLAT, RICH, POL; no EXTRA switches): dispatched by recorded-mobility block (RP) and memory
+// block (MEM), then chosen by step mode and information-age block - (CH, IA) has three legal values, not four - and out dtype
+struct LaunchFast64Slots {
+  Fast64Args a; bool ch, ia, out64;
+  template <bool CH, bool IA, bool RP, bool MEM>
+  void as() const {
+    if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, CH, false, true, true, IA, RP, MEM>), a.g, dim3(256), a.lds, a.s, a.f, a.r, a.q);
+    else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, CH, false, true, true, IA, RP, MEM>), a.g, dim3(256), a.lds, a.s, a.f, a.r, a.q);
+  }
+  template <bool RP, bool MEM>
+  void operator()(std::integer_sequence<bool, RP, MEM>) const {
+    if (ia) as<true, true, RP, MEM>();
+    else if (ch) as<true, false, RP, MEM>();
+    else as<false, false, RP, MEM>();
   }
 };
 }  // namespace
 
 hipError_t launch_fast64(const FastParams& f, const RichParams& r, const KernelSel& k, int B, hipStream_t s) {
   static const PolParams no_policy{};
-  const LaunchFast64 l{f, r, no_policy, dim3(B), fast_lds_layout(f.K, f.A, k.rich, k.out64, k.flat, k.ch || k.extra).total, s};
+  const LaunchFast64<false> l{{f, r, no_policy, dim3(B), fast_lds_layout(f.K, f.A, k.rich, k.out64, k.flat, k.ch || k.extra).total, s}};
 #ifdef DIRAL_FAST_BENCH_ONLY
   // tuning builds (profiles/build_variant.sh): only the instantiations the C2 / C4 bench lines run - seconds to compile
   if (!k.flat || k.out64 || k.ch || k.extra) return hipErrorInvalidValue;
@@ -37,40 +55,19 @@ hipError_t launch_fast64(const FastParams& f, const RichParams& r, const KernelS
 
 // the one-slot POL instantiations (policy epilogue): the flat highway, my_step, no EXTRA switches, RICH
 hipError_t launch_fast64_policy(const FastParams& f, const RichParams& r, const PolParams& q, bool out64, int B, hipStream_t s) {
-  const uint32_t lds = fast_lds_layout(f.K, f.A, true, out64, true, false).total;
-  if (out64) hipLaunchKernelGGL((step_fast64_kernel<true, true, false, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
-  else hipLaunchKernelGGL((step_fast64_kernel<true, false, false, false, true, true>), dim3(B), dim3(256), lds, s, f, r, q);
+  const LaunchFast64<true> l{{f, r, q, dim3(B), fast_lds_layout(f.K, f.A, true, out64, true, false).total, s}};
+  if (out64) l(std::integer_sequence<bool, true, true, false, false, true>{});
+  else l(std::integer_sequence<bool, true, false, false, false, true>{});
   return hipGetLastError();
 }
-
-namespace {
-// one of the slot loop's instantiations (FLAT, RICH, POL; no EXTRA switches), in the launch's out dtype
-template <bool CH, bool IA, bool RP, bool MEM>
-void launch_slots_as(const FastParams& f, const RichParams& r, const PolParams& q, bool out64, int B, uint32_t lds, hipStream_t s) {
-  if (out64) hipLaunchKernelGGL((step_fast64_slots_kernel<true, true, CH, false, true, true, IA, RP, MEM>), dim3(B), dim3(256), lds, s, f, r, q);
-  else hipLaunchKernelGGL((step_fast64_slots_kernel<true, false, CH, false, true, true, IA, RP, MEM>), dim3(B), dim3(256), lds, s, f, r, q);
-}
-template <bool RP, bool MEM>
-void launch_slots_blocks(const FastParams& f, const RichParams& r, const PolParams& q, bool ch, bool ia, bool out64, int B, uint32_t lds,
-                         hipStream_t s) {
-  if (ia) launch_slots_as<true, true, RP, MEM>(f, r, q, out64, B, lds, s);
-  else if (ch) launch_slots_as<true, false, RP, MEM>(f, r, q, out64, B, lds, s);
-  else launch_slots_as<false, false, RP, MEM>(f, r, q, out64, B, lds, s);
-}
-}  // namespace
 
 // ... K slots per launch (PolParams::K > 1): step_fast64_slots_kernel, the same body with the env kept on the chip; `ch`:
 // my_step_ch slots (the reception ratios of P1 in LDS next to the policy's arrays)
 hipError_t launch_fast64_slots(const FastParams& f, const RichParams& r, const PolParams& q, bool ch, bool out64, int B, hipStream_t s) {
   const bool ia = ch && q.ia_on != 0;       // the information-age block: the IA instantiations (arrival stamps, histogram pass, term)
-  const uint32_t lds = fast_lds_layout(f.K, f.A, true, out64, true, ch, true, ia).total;
-  // the recorded-mobility block: the RP instantiations (positions from the caller's sequence, the position log); the memory
-  // block: the MEM instantiations (the slots write rows of the caller's replay rings)
-  const bool rp = q.rp_on != 0, mem = q.mem_on != 0;
-  if (rp && mem) launch_slots_blocks<true, true>(f, r, q, ch, ia, out64, B, lds, s);
-  else if (rp) launch_slots_blocks<true, false>(f, r, q, ch, ia, out64, B, lds, s);
-  else if (mem) launch_slots_blocks<false, true>(f, r, q, ch, ia, out64, B, lds, s);
-  else launch_slots_blocks<false, false>(f, r, q, ch, ia, out64, B, lds, s);
+  const LaunchFast64Slots l{{f, r, q, dim3(B), fast_lds_layout(f.K, f.A, true, out64, true, ch, true, ia).total, s}, ch, ia, out64};
+  // the RP instantiations: positions from the caller's sequence, the position log; MEM: the slots write rows of the caller's replay rings
+  bool_dispatch(l, std::integer_sequence<bool>{}, q.rp_on != 0, q.mem_on != 0);
   return hipGetLastError();
 }
 }  // namespace diral

@@ -6,15 +6,16 @@
 
 namespace diral {
 namespace {
-template <int G, bool OUT64>
-hipError_t launch_sub_slots(const StepParams& p, const PolParams& q, hipStream_t s) {
-  constexpr int kEnvsPerBlock = kSubwaveThreads / G;
-  const unsigned int grid = (unsigned int)((p.B + kEnvsPerBlock - 1) / kEnvsPerBlock);
-  // (the memory block, PolParams::mem_on: the MEM instantiations - the slots write rows of the caller's replay rings)
-  if (q.mem_on) hipLaunchKernelGGL((step_subwave_slots_kernel<G, OUT64, true>), dim3(grid), dim3(kSubwaveThreads), 0, s, p, q);
-  else hipLaunchKernelGGL((step_subwave_slots_kernel<G, OUT64, false>), dim3(grid), dim3(kSubwaveThreads), 0, s, p, q);
-  return hipGetLastError();
-}
+// G lanes per env; by out dtype and memory block (PolParams::mem_on: the MEM instantiations - the slots write rows of the caller's replay rings)
+template <int G>
+struct LaunchSubSlots {
+  const StepParams& p; const PolParams& q; hipStream_t s;
+  template <bool OUT64, bool MEM>
+  void operator()(std::integer_sequence<bool, OUT64, MEM>) const {
+    const unsigned int grid = (unsigned int)((p.B + kSubwaveThreads / G - 1) / (kSubwaveThreads / G));   // kSubwaveThreads / G envs per block
+    hipLaunchKernelGGL((step_subwave_slots_kernel<G, OUT64, MEM>), dim3(grid), dim3(kSubwaveThreads), 0, s, p, q);
+  }
+};
 }  // namespace
 
 hipError_t launch_subwave_slots(const StepParams& p, const PolParams& q, hipStream_t s) {
@@ -22,7 +23,8 @@ hipError_t launch_subwave_slots(const StepParams& p, const PolParams& q, hipStre
       p.B < 1 || q.K < 1)
     return hipErrorInvalidValue;                  // (diral_env_subwave_ok refuses these before a handle is pinned)
   if (q.prefill ? q.actions_out == nullptr : (q.rollout == 0 || q.actions_seq == nullptr)) return hipErrorInvalidValue;
-  if (p.N <= 4) return p.out_f64 ? launch_sub_slots<4, true>(p, q, s) : launch_sub_slots<4, false>(p, q, s);
-  return p.out_f64 ? launch_sub_slots<8, true>(p, q, s) : launch_sub_slots<8, false>(p, q, s);
+  if (p.N <= 4) bool_dispatch(LaunchSubSlots<4>{p, q, s}, std::integer_sequence<bool>{}, p.out_f64 != 0, q.mem_on != 0);
+  else bool_dispatch(LaunchSubSlots<8>{p, q, s}, std::integer_sequence<bool>{}, p.out_f64 != 0, q.mem_on != 0);
+  return hipGetLastError();
 }
 }  // namespace diral
