@@ -2,7 +2,6 @@
 reference-shaped TestEnv shim, sharding and the metric reduction over gloo."""
 import ctypes
 import os
-import re
 
 import numpy as np
 import pytest
@@ -14,34 +13,13 @@ from diral_amd.shard import env_shard
 from tests.golden_util import Golden, golden_names
 from tests.oracle_backend import OracleBackend
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
 # ---- C-ABI ----------------------------------------------------------------------
-
-def header_functions():
-    src = open(os.path.join(ROOT, "include", "diral_env.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(diral_[a-z_0-9]+)\s*\(", src)))
-
-
-def test_library_exports_every_declared_symbol():
-    lib = _lib.load()
-    names = header_functions()
-    assert len(names) >= 19
-    assert sorted(_lib.SYMBOLS) == names, "diral_amd/_lib.py and include/diral_env.h disagree"
-    for n in names:
-        assert hasattr(lib, n), n
-    from diral_amd.config import ABI_VERSION
-    src = open(os.path.join(ROOT, "include", "diral_env.h")).read()
-    assert lib.diral_env_abi_version() == ABI_VERSION == int(re.search(r"#define DIRAL_ABI_VERSION (\d+)", src).group(1)) == 8
-
 
 def test_cfg_struct_layout_matches_header():
     lib = _lib.load()
     c = DiralCfg()
     lib.diral_cfg_defaults(ctypes.byref(c))
-    assert c.struct_bytes == ctypes.sizeof(DiralCfg) == 88
+    assert c.struct_bytes == ctypes.sizeof(DiralCfg)
     # the reference's kwargs.setdefault defaults (test_env.py:12-24)
     assert (c.num_users, c.num_channels, c.reward_design) == (3, 3, 1)
     assert (c.highway_length, c.communication_range, c.bin_range) == (200.0, 1.0, 500.0)
@@ -49,22 +27,9 @@ def test_cfg_struct_layout_matches_header():
 
 
 def test_slot_policy_struct_layout_and_argument_checks():
-    """`DiralSlotPolicy` (diral_env_step_policy): the ctypes image has the header's size (a gcc-compiled probe of the
-    header), and the entry point rejects null handles / wrong struct sizes without touching a device."""
-    import subprocess
-    import tempfile
+    """`DiralSlotPolicy` (diral_env_step_policy): the entry point rejects null handles without touching a device (the
+    struct's layout against the header: tests/test_abi_mirror.py)."""
     from diral_amd.config import DiralSlotPolicy
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "p.c")
-        with open(c, "w") as fh:
-            fh.write('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(void) { printf("%%zu %%zu %%zu %%zu\\n", '
-                     'sizeof(DiralSlotPolicy), offsetof(DiralSlotPolicy, shaped_out), offsetof(DiralSlotPolicy, rssi_threshold), '
-                     'offsetof(DiralSlotPolicy, actions_out)); return 0; }\n' % os.path.join(ROOT, "include", "diral_env.h"))
-        exe = os.path.join(d, "p")
-        subprocess.check_call(["gcc", c, "-o", exe])
-        size, o1, o2, o3 = (int(x) for x in subprocess.check_output([exe]).split())
-    assert size == ctypes.sizeof(DiralSlotPolicy)
-    assert (o1, o2, o3) == (DiralSlotPolicy.shaped_out.offset, DiralSlotPolicy.rssi_threshold.offset, DiralSlotPolicy.actions_out.offset)
     lib = _lib.load()
     q = DiralSlotPolicy()
     q.struct_bytes = ctypes.sizeof(DiralSlotPolicy)

@@ -3,32 +3,13 @@ themselves) are part of the library and of include/diral_env.h, within ABI 8.  N
 first.  (The checks that need a handle - its B, N and state size against the block's - run in
 tests/test_gpu_rollout_memory.py, each on an otherwise valid call.)"""
 import ctypes
-import os
-import re
 
 import pytest
 
 from diral_amd import _lib
-from diral_amd.config import (ABI_VERSION, DT_F32, DT_F64, ERR_BAD_ARG, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, DiralMemory,
+from diral_amd.config import (DT_F32, DT_F64, ERR_BAD_ARG, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, DiralMemory,
                               DiralRollout)
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-P, I, I64, U64, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_double
-
-
-def header():
-    return open(os.path.join(ROOT, "include", "diral_env.h")).read()
-
-
-def prototype(name):
-    """The parameter types of `name` as the header declares them, pointers folded to one word."""
-    m = re.search(r"^int %s\((.*?)\);" % name, header(), re.M | re.S)
-    assert m, name
-    kinds = []
-    for par in m.group(1).split(","):
-        par = " ".join(par.split())
-        kinds.append("ptr" if "*" in par else par.rsplit(" ", 1)[0])
-    return kinds
+from tests import abi_header
 
 
 def a_block(**kw):
@@ -44,31 +25,12 @@ def a_block(**kw):
 
 
 def test_the_two_entry_points_are_exported_and_declared_as_their_base_plus_the_block():
-    lib = _lib.load()
-    for name in ("diral_env_rollout_memory", "diral_env_prefill_memory"):
-        assert name in _lib.SYMBOLS and hasattr(lib, name)
+    protos = abi_header.prototypes()
     # diral_env_rollout_replay / diral_env_prefill_mode with `const DiralMemory* memory` in front of the stream
     for name, base in (("diral_env_rollout_memory", "diral_env_rollout_replay"), ("diral_env_prefill_memory", "diral_env_prefill_mode")):
-        got, want = prototype(name), prototype(base)
-        assert got == want[:-1] + ["ptr", "ptr"], (name, got, want)
-        assert re.search(r"^int %s\([^;]*const DiralMemory\* memory,\s*void\* stream\);" % name, header(), re.M | re.S)
-    ctype = {"ptr": P, "int": I, "int32_t": ctypes.c_int32, "int64_t": I64, "uint64_t": U64, "double": D}
-    for name in ("diral_env_rollout_memory", "diral_env_prefill_memory"):
-        fn = getattr(lib, name)
-        assert fn.restype is I
-        assert [ctypes.sizeof(t) for t in fn.argtypes] == [ctypes.sizeof(ctype[k]) for k in prototype(name)], name
-    assert lib.diral_env_abi_version() == ABI_VERSION == 8
-
-
-def test_the_descriptor_is_the_replay_memory_s():
-    src = header()
-    body = re.search(r"typedef struct DiralMemory \{(.*?)\} DiralMemory;", src, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    names = [n.strip(" *") for decl in body.split(";") if decl.strip() for n in
-             [decl.split(",")[0].split()[-1]] + decl.split(",")[1:]]
-    assert names == [f[0] for f in DiralMemory._fields_]
-    # uint32 + 5 int32 | 3 pointers | int64 | pointer
-    assert ctypes.sizeof(DiralMemory) == 24 + 24 + 8 + 8
+        got, want = protos[name], protos[base]
+        assert (got.ret, got.params) == (want.ret, want.params[:-1] + [abi_header.PTR, abi_header.PTR]), (name, got, want)
+        assert got.text.endswith("const DiralMemory* memory, void* stream);")
 
 
 @pytest.mark.parametrize("mode", [STEP_MY_STEP, STEP_MY_STEP_CH])
