@@ -6,6 +6,7 @@ infrastructure and is never imported from here.)
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -73,45 +74,64 @@ SIGNATURES = {
     "diral_sps_init": (I, [I, I, P, P, U64, P]),
     "diral_env_last_hip_error": (ctypes.c_char_p, [P]),
 }
-SYMBOLS = list(SIGNATURES)      # what load() binds, read at call time (tuning scripts bind a library that lacks some)
+SYMBOLS = list(SIGNATURES)
 
-_lib = None
+_lib = None                     # what load() returns: bind(LIB_PATH) once made, or the library of a use() block
 
 
 class DiralLibraryError(RuntimeError):
     pass
 
 
-def load() -> ctypes.CDLL:
-    global _lib
-    if _lib is not None:
-        return _lib
+def bind(path, lacking=()) -> ctypes.CDLL:
+    """A libdiral_env.so at `path` with every prototype of SIGNATURES set, but for the names in `lacking` (a library built from
+    an earlier commit predates them).  Touches no module state: a second library next to load()'s is a supported thing."""
     # PyTorch-ROCm bundles its own libamdhip64; it must be in the process BEFORE
     # libdiral_env.so is dlopen'ed so both bind to the SAME HIP runtime (same
     # SONAME -> the loader reuses it).  Loading ours first would pull in
     # /opt/rocm's copy and torch's device pointers would belong to another runtime.
     import torch  # noqa: F401
-    if not os.path.exists(LIB_PATH):
+    if not os.path.exists(path):
         raise DiralLibraryError(
             "%s is missing - build it with `python -m diral_amd.build` (hipcc, gfx950). "
-            "There is no CPU fallback." % LIB_PATH)
+            "There is no CPU fallback." % path)
     try:
-        lib = ctypes.CDLL(LIB_PATH)
+        lib = ctypes.CDLL(path)
     except OSError as exc:  # e.g. libamdhip64 not present
-        raise DiralLibraryError("cannot load %s: %s" % (LIB_PATH, exc)) from exc
-    for name in SYMBOLS:
+        raise DiralLibraryError("cannot load %s: %s" % (path, exc)) from exc
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if name in lacking:
+            continue
         try:
             fn = getattr(lib, name)
         except AttributeError as exc:
             raise DiralLibraryError("libdiral_env.so lacks symbol %s" % name) from exc
-        fn.restype, fn.argtypes = SIGNATURES[name]
+        fn.restype, fn.argtypes = restype, argtypes
     from .config import ABI_VERSION
     got = int(lib.diral_env_abi_version())
     if got != ABI_VERSION:
         raise DiralLibraryError("%s speaks ABI %d, this package binds ABI %d (include/diral_env.h): rebuild it with "
-                                "`python -m diral_amd.build`" % (LIB_PATH, got, ABI_VERSION))
-    _lib = lib
+                                "`python -m diral_amd.build`" % (path, got, ABI_VERSION))
     return lib
+
+
+def load() -> ctypes.CDLL:
+    global _lib
+    if _lib is None:
+        _lib = bind(LIB_PATH)
+    return _lib
+
+
+@contextlib.contextmanager
+def use(lib):
+    """Inside the block load() returns `lib`: what is built there (VecV2VEnv, SpsPolicy, QPolicy, ReplayMemory) binds to it and
+    keeps it (`self.lib`).  On exit, exception included, the previous library is back.  Single-threaded by contract."""
+    global _lib
+    keep, _lib = _lib, lib
+    try:
+        yield lib
+    finally:
+        _lib = keep
 
 
 def strerror(status: int) -> str:

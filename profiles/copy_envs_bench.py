@@ -13,14 +13,10 @@ is in ring form, as it is inside a search, whenever a copy or an export meets it
   python profiles/copy_envs_bench.py [--rounds 9] [--warm 2] [--only c2,c5,fork] > profiles/copy_envs/copy_bench.txt
 """
 import argparse
-import json
-import os
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
+import ab  # noqa: E402  (puts the repository's root on sys.path)
 from diral_amd.config import bench_config, c2_config  # noqa: E402
 from diral_amd.search import candidate_index  # noqa: E402
 from diral_amd.vec_env import VecV2VEnv  # noqa: E402
@@ -40,29 +36,14 @@ def state_bytes_per_env(env):
     return 3 * N * 8 + planes + NR * 8 * 8 + packed + 6 * 8, planes
 
 
-def timed_rounds(forms, between, rounds, warm):
-    for r in range(warm + rounds):
-        for f in forms:                                             # interleaved: one call per form and round
-            between()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            f["body"]()
-            e1.record()
-            torch.cuda.synchronize()
-            if r >= warm:
-                f["ms"].append(e0.elapsed_time(e1))
-
-
-def report(config, B, forms, rounds, extra):
-    us = {f["form"]: round(sorted(f["ms"])[len(f["ms"]) // 2] * 1e3, 1) for f in forms}
-    out = dict(config=config, B=B, rounds=rounds, us=us, us_rounds={f["form"]: [round(m * 1e3, 1) for m in f["ms"]] for f in forms})
+def show(emit, config, B, forms, rounds, extra):
+    us, rnd = ab.summary(forms, digits=1)
+    out = dict(config=config, B=B, rounds=rounds, us=us, us_rounds=rnd)
     out.update(extra)
-    print("%s B=%d: %s" % (config, B, "  ".join("%s %.1f" % kv for kv in us.items())), flush=True)
-    print(json.dumps(out), flush=True)
+    emit("%s B=%d: %s" % (config, B, "  ".join("%s %.1f" % kv for kv in us.items())), out)
 
 
-def run_copy(name, rounds, warm):
+def run_copy(emit, name, rounds, warm):
     make, B = SHAPES[name]
     cfg = make()
     dev = torch.device("cuda:0")
@@ -88,14 +69,12 @@ def run_copy(name, rounds, warm):
              dict(form="flat copy_", body=lambda: flat_a.copy_(flat_b))]
     if name == "c2":
         forms.insert(2, dict(form="broadcast", body=lambda: dst.copy_envs_from(src, src_index=one)))
-    for f in forms:
-        f["ms"] = []
     clock = [10]
 
-    def between():
+    def between(_):
         src.step(acts, clock[0])
         clock[0] += 1
-    timed_rounds(forms, between, rounds, warm)
+    ab.timed_rounds(forms, ab.own_body, rounds, warm, between=between)
     # the copy did what the old route does, and more: tables and positions agree, metrics only on the copied handle
     dst.copy_envs_from(src)
     export_import()
@@ -104,8 +83,8 @@ def run_copy(name, rounds, warm):
     for e in (src, dst, dst2):
         e.check()
     moved = 2 * per_env * B
-    us = {f["form"]: sorted(f["ms"])[len(f["ms"]) // 2] * 1e3 for f in forms}
-    report("%s copy" % name, B, forms, rounds,
+    us = {f["form"]: ab.per_unit(ab.median(f["ms"]), 1) for f in forms}
+    show(emit, "%s copy" % name, B, forms, rounds,
            dict(N=cfg.num_users, A=cfg.num_channels, bytes_per_env=per_env, plane_bytes_per_env=planes, equal=equal,
                 tb_per_s={k: round(moved / (v * 1e-6) / 1e12, 2) for k, v in us.items() if k != "export+import"},
                 copy_vs_flat=round(us["copy"] / us["flat copy_"], 3), export_import_vs_copy=round(us["export+import"] / us["copy"], 2)))
@@ -113,7 +92,7 @@ def run_copy(name, rounds, warm):
     torch.cuda.empty_cache()
 
 
-def run_fork(rounds, warm):
+def run_fork(emit, rounds, warm):
     cfg = c2_config()
     dev = torch.device("cuda:0")
     B, C = 512, 8
@@ -126,18 +105,18 @@ def run_fork(rounds, warm):
     gather = candidate_index(B, C, dev)
     alone.copy_envs_from(env, src_index=gather)
     seq = torch.stack([work.sample(4000 + k) for k in range(K)])
-    forms = [dict(form="rollout", ms=[], body=lambda: alone.rollout(seq, 0, states=None)),
-             dict(form="fork+rollout", ms=[], body=lambda: (work.copy_envs_from(env, src_index=gather), work.rollout(seq, 0, states=None)))]
+    forms = [dict(form="rollout", body=lambda: alone.rollout(seq, 0, states=None)),
+             dict(form="fork+rollout", body=lambda: (work.copy_envs_from(env, src_index=gather), work.rollout(seq, 0, states=None)))]
     clock = [10]
 
-    def between():
+    def between(_):
         env.step(acts, clock[0])
         clock[0] += 1
-    timed_rounds(forms, between, rounds, warm)
+    ab.timed_rounds(forms, ab.own_body, rounds, warm, between=between)
     for e in (env, alone, work):
         e.check()
-    us = {f["form"]: sorted(f["ms"])[len(f["ms"]) // 2] * 1e3 for f in forms}
-    report("c2 fork %d x %d + %d slots" % (B, C, K), B * C, forms, rounds,
+    us = {f["form"]: ab.per_unit(ab.median(f["ms"]), 1) for f in forms}
+    show(emit, "c2 fork %d x %d + %d slots" % (B, C, K), B * C, forms, rounds,
            dict(us_per_slot={k: round(v / K, 2) for k, v in us.items()}, fork_share=round(us["fork+rollout"] / us["rollout"] - 1.0, 4)))
 
 
@@ -149,11 +128,12 @@ def main():
     args = ap.parse_args()
     only = args.only.split(",")
     print("device: %s" % torch.cuda.get_device_name(0), flush=True)
-    for name in ("c2", "c5"):
-        if name in only:
-            run_copy(name, args.rounds, args.warm)
-    if "fork" in only:
-        run_fork(args.rounds, args.warm)
+    with ab.report() as emit:
+        for name in ("c2", "c5"):
+            if name in only:
+                run_copy(emit, name, args.rounds, args.warm)
+        if "fork" in only:
+            run_fork(emit, args.rounds, args.warm)
 
 
 if __name__ == "__main__":

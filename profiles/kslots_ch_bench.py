@@ -11,14 +11,10 @@ the two forms of (a) and of (b) leave equal tables, positions, metrics (and poli
   python profiles/kslots_ch_bench.py [--batches 64,1024,4096] [--rounds 7] [--warm 2]
 """
 import argparse
-import json
-import os
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
+import ab  # noqa: E402  (puts the repository's root on sys.path)
 from diral_amd.config import KERNEL_CH, KERNEL_POLICY, STEP_MY_STEP_CH, c2_config  # noqa: E402
 from diral_amd.driver import DriverLoop  # noqa: E402
 from diral_amd.sps import SpsPolicy  # noqa: E402
@@ -77,34 +73,17 @@ def run(B, rounds, warm):
             assert env.last_kernel() & KERNEL_POLICY and env.last_kernel() & KERNEL_CH
             f["seed"] += K
 
-    for r in range(warm + rounds):
-        for f in forms:                                         # interleaved: one round of 25 slots per form
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            slots25(f)
-            e1.record()
-            torch.cuda.synchronize()
-            if r >= warm:
-                f["ms"].append(e0.elapsed_time(e1))
-
-    def same_env(x, y):
-        sa, sb = x["env"].export_state(), y["env"].export_state()
-        return all(torch.equal(sa[k], sb[k]) for k in sa) and torch.equal(x["env"].metrics(), y["env"].metrics())
+    ab.timed_rounds(forms, slots25, rounds, warm)
+    us, rnd = ab.summary(forms, K)
     a0, a1, p0, p1 = forms
-    equal = {"K=25": bool(same_env(a0, a1) and torch.equal(a0["pol"].prev_action, a1["pol"].prev_action) and
+    equal = {"K=25": bool(ab.same_env(a0["env"], a1["env"]) and torch.equal(a0["pol"].prev_action, a1["pol"].prev_action) and
                           torch.equal(a0["pol"].counter, a1["pol"].counter) and torch.equal(a0["sh"], a1["sh"]) and
                           torch.equal(a0["sr"], a1["sr"]) and torch.equal(a0["co"], a1["co"])),
-             "prefill launch": bool(same_env(p0, p1) and torch.equal(p0["states"], p1["states"]))}
+             "prefill launch": bool(ab.same_env(p0["env"], p1["env"]) and torch.equal(p0["states"], p1["states"]))}
     out = {"config": "c2 my_step_ch reward_design 2", "N": N, "A": A, "B": B, "slots_per_round": K, "rounds": rounds,
-           "us_per_slot": {}, "us_per_slot_rounds": {}, "equal_to_baseline": equal}
-    for f in forms:
-        ms = sorted(f["ms"])
-        out["us_per_slot"][f["form"]] = round(ms[len(ms) // 2] * 1e3 / K, 2)
-        out["us_per_slot_rounds"][f["form"]] = [round(m * 1e3 / K, 2) for m in f["ms"]]
-    u = out["us_per_slot"]
-    out["saving"] = {"K=25 vs three-launch": round(1.0 - u["K=25"] / u["three-launch"], 4),
-                     "prefill launch vs loop": round(1.0 - u["prefill launch"] / u["prefill loop"], 4)}
+           "us_per_slot": us, "us_per_slot_rounds": rnd, "equal_to_baseline": equal}
+    out["saving"] = {"K=25 vs three-launch": round(1.0 - us["K=25"] / us["three-launch"], 4),
+                     "prefill launch vs loop": round(1.0 - us["prefill launch"] / us["prefill loop"], 4)}
     for f in forms:
         f["env"].check()
     del forms
@@ -118,11 +97,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--warm", type=int, default=2)
     args = ap.parse_args()
-    for b in args.batches.split(","):
-        r = run(int(b), args.rounds, args.warm)
-        print("B=%s: %s  equal: %s" % (b, "  ".join("%s %.1f us/slot" % kv for kv in r["us_per_slot"].items()),
-                                       r["equal_to_baseline"]))
-        print(json.dumps(r))
+    with ab.report() as emit:
+        for b in args.batches.split(","):
+            r = run(int(b), args.rounds, args.warm)
+            emit("B=%s: %s  equal: %s" % (b, "  ".join("%s %.1f us/slot" % kv for kv in r["us_per_slot"].items()), r["equal_to_baseline"]), r)
 
 
 if __name__ == "__main__":

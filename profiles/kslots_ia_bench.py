@@ -18,77 +18,17 @@ the parent's library and on this one, interleaved in the same way (`slower_than_
   python profiles/kslots_ia_bench.py --parent-lib /path/to/parent/libdiral_env.so [--rounds 7] [--warm 2] [--only c2,guard]
 """
 import argparse
-import ctypes
-import importlib.util
-import json
 import os
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-from diral_amd import _lib, vec_env  # noqa: E402
+import ab  # noqa: E402  (puts the repository's root on sys.path)
+from diral_amd import _lib  # noqa: E402
 from diral_amd.config import KERNEL_POLICY, STEP_MY_STEP_CH, c2_config  # noqa: E402
 from diral_amd.sps import SpsPolicy  # noqa: E402
 from diral_amd.vec_env import VecV2VEnv, driver_shape  # noqa: E402
 
 K = 25
-NEW_SYMBOLS = ("diral_env_rollout_ia", "diral_env_step_policy_ia")
-
-
-def load_parent(path):
-    """A second copy of the loader bound to the parent's library (it lacks the two _ia entry points)."""
-    spec = importlib.util.spec_from_file_location("diral_amd._lib_parent", _lib.__file__)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.LIB_PATH = path
-    mod.SYMBOLS = [s for s in mod.SYMBOLS if s not in NEW_SYMBOLS]
-    return mod.load()
-
-
-class on_library:
-    """VecV2VEnv (and what it builds) on `lib` inside the block."""
-
-    def __init__(self, lib):
-        self.lib = lib
-
-    def __enter__(self):
-        self.keep = vec_env._lib.load
-        if self.lib is not None:
-            vec_env._lib.load = lambda: self.lib
-
-    def __exit__(self, *exc):
-        vec_env._lib.load = self.keep
-
-
-def timed_rounds(forms, body, rounds, warm):
-    for r in range(warm + rounds):
-        for f in forms:                                             # interleaved: one round of K slots per form
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            body(f)
-            e1.record()
-            torch.cuda.synchronize()
-            if r >= warm:
-                f["ms"].append(e0.elapsed_time(e1))
-
-
-def medians(forms):
-    us, rnd = {}, {}
-    for f in forms:
-        ms = sorted(f["ms"])
-        us[f["form"]] = round(ms[len(ms) // 2] * 1e3 / K, 2)
-        rnd[f["form"]] = [round(m * 1e3 / K, 2) for m in f["ms"]]
-    return us, rnd
-
-
-def same_env(x, y):
-    sa, sb = x["env"].export_state(), y["env"].export_state()
-    return bool(all(torch.equal(sa[k], sb[k]) for k in sa) and torch.equal(x["env"].metrics(), y["env"].metrics()))
-
-
 FORMS = (("loop+ia (parent)", True, "loop_ia"), ("launch hist+term", False, "term"), ("loop (parent)", True, "loop"),
          ("launch stamps", False, "stamps"), ("launch hist", False, "hist"))
 
@@ -99,7 +39,7 @@ def run_feature(B, parent, rounds, warm):
     dev = torch.device("cuda:0")
     forms = []
     for form, on_parent, kind in FORMS:
-        with on_library(parent if on_parent else None):
+        with _lib.use(parent if on_parent else _lib.load()):
             env = VecV2VEnv(cfg, batch=B, device=dev, out_dtype=torch.float32)
         env.reset_topology(seed=1234)
         f = dict(form=form, kind=kind, env=env, t=0, ms=[], prev=torch.zeros((B,), dtype=torch.int64, device=dev))
@@ -131,14 +71,14 @@ def run_feature(B, parent, rounds, warm):
                 driver_shape(env, rew, seq[k], shaped=f["sh"][k], sum_r=f["sr"][k], collision=f["co"][k], global_reward_avg=True)
             f["t"] += 1
 
-    timed_rounds(forms, body, rounds, warm)
-    us, rnd = medians(forms)
+    ab.timed_rounds(forms, body, rounds, warm)
+    us, rnd = ab.summary(forms, K)
     by = {f["kind"]: f for f in forms}
     equal = {}
     for kind, ref, keys in (("term", "loop_ia", ("sh", "sr", "co", "ia", "ia_sum", "pen", "prev")), ("stamps", "loop", ("sh", "sr", "co")),
                             ("hist", "loop", ("sr", "co"))):
         x, p = by[kind], by[ref]
-        equal[x["form"]] = bool(same_env(p, x) and all(torch.equal(p[k], x[k]) for k in keys))
+        equal[x["form"]] = bool(ab.same_env(p["env"], x["env"]) and all(torch.equal(p[k], x[k]) for k in keys))
     equal["launch hist (histograms)"] = bool(torch.equal(by["hist"]["ia"], by["loop_ia"]["ia"]))
     saving = {"launch hist+term vs loop+ia (parent)": round(1.0 - us["launch hist+term"] / us["loop+ia (parent)"], 4),
               "launch stamps vs loop (parent)": round(1.0 - us["launch stamps"] / us["loop (parent)"], 4)}
@@ -160,8 +100,8 @@ def run_guard(B, parent, rounds, warm):
     dev = torch.device("cuda:0")
     forms = []
     for what in ("step_policy K=25", "rollout K=25"):
-        for tag, lib in ((" (parent)", parent), ("", None)):
-            with on_library(lib):
+        for tag, lib in ((" (parent)", parent), ("", _lib.load())):
+            with _lib.use(lib):
                 env = VecV2VEnv(cfg, batch=B, device=dev, out_dtype=torch.float32)
             env.reset_topology(seed=1234)
             f = dict(form=what + tag, what=what, env=env, t=0, i=0, ms=[])
@@ -186,11 +126,11 @@ def run_guard(B, parent, rounds, warm):
         f["t"] += K
         assert env.last_kernel() & KERNEL_POLICY
 
-    timed_rounds(forms, body, rounds, warm)
-    us, rnd = medians(forms)
+    ab.timed_rounds(forms, body, rounds, warm)
+    us, rnd = ab.summary(forms, K)
     s0, s1, r0, r1 = forms
-    equal = {"step_policy K=25": bool(same_env(s0, s1) and torch.equal(s0["sh"], s1["sh"]) and torch.equal(s0["pol"].counter, s1["pol"].counter)),
-             "rollout K=25": bool(same_env(r0, r1) and torch.equal(r0["sh"], r1["sh"]))}
+    equal = {"step_policy K=25": bool(ab.same_env(s0["env"], s1["env"]) and torch.equal(s0["sh"], s1["sh"]) and torch.equal(s0["pol"].counter, s1["pol"].counter)),
+             "rollout K=25": bool(ab.same_env(r0["env"], r1["env"]) and torch.equal(r0["sh"], r1["sh"]))}
     slower = {w: round(us[w] / us[w + " (parent)"] - 1.0, 4) for w in ("step_policy K=25", "rollout K=25")}
     out = {"config": "guard: c2 my_step_ch, no arrival stamps", "B": B, "slots_per_round": K, "rounds": rounds, "us_per_slot": us,
            "us_per_slot_rounds": rnd, "equal_to_parent": equal, "slower_than_parent": slower}
@@ -208,18 +148,11 @@ def main():
     ap.add_argument("--only", default="c2,guard")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "kslots_ia", "kslots_ia_bench.txt"))
     args = ap.parse_args()
-    parent = load_parent(os.path.abspath(args.parent_lib))
-    assert ctypes.cast(parent.diral_env_step, ctypes.c_void_p).value != ctypes.cast(_lib.load().diral_env_step, ctypes.c_void_p).value, \
-        "the parent's library must be a second library"
+    parent, _ = ab.two_libraries(args.parent_lib, lacking=("diral_env_rollout_ia", "diral_env_step_policy_ia"))
     only = args.only.split(",")
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as fh:
+    with ab.report(args.out) as emit:
         def show(r, key):
-            for line in ("%s B=%d: %s  %s" % (r["config"], r["B"], "  ".join("%s %.1f" % kv for kv in r["us_per_slot"].items()), r[key]),
-                         json.dumps(r)):
-                print(line, flush=True)
-                fh.write(line + "\n")
-                fh.flush()
+            emit("%s B=%d: %s  %s" % (r["config"], r["B"], "  ".join("%s %.1f" % kv for kv in r["us_per_slot"].items()), r[key]), r)
         if "c2" in only:
             for b in args.batches.split(","):
                 show(run_feature(int(b), parent, args.rounds, args.warm), "saving")

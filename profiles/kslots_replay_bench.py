@@ -18,29 +18,18 @@ all WITHOUT the block, at C2, B = 4096, on the parent's library and on this one,
   python profiles/kslots_replay_bench.py --parent-lib /path/to/parent/libdiral_env.so [--rounds 7] [--warm 2] [--only c2,guard]
 """
 import argparse
-import ctypes
-import importlib.util
-import json
 import os
-import sys
 
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-
+import ab  # noqa: E402  (puts the repository's root on sys.path)
 from diral_amd import _lib  # noqa: E402
 from diral_amd.config import KERNEL_POLICY, STEP_MY_STEP, STEP_MY_STEP_CH, c2_config  # noqa: E402
 from diral_amd.sps import SpsPolicy  # noqa: E402
 from diral_amd.vec_env import VecV2VEnv, driver_shape  # noqa: E402
 
-_spec = importlib.util.spec_from_file_location("kslots_ia_bench", os.path.join(HERE, "kslots_ia_bench.py"))
-ia_bench = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(ia_bench)
-ia_bench.NEW_SYMBOLS = ("diral_env_rollout_replay", "diral_env_step_policy_replay")   # what the parent's library lacks
-on_library, timed_rounds, medians, same_env = ia_bench.on_library, ia_bench.timed_rounds, ia_bench.medians, ia_bench.same_env
-
-K = ia_bench.K
+HERE = os.path.dirname(os.path.abspath(__file__))
+K = 25
 MODES = {"my_step": STEP_MY_STEP, "my_step_ch": STEP_MY_STEP_CH}
 # (name of the pair, mode, states, closed loop, information age, position log)
 PAIRS = (("rollout my_step", "my_step", None, False, False, False),
@@ -54,7 +43,7 @@ PAIRS = (("rollout my_step", "my_step", None, False, False, False),
 
 
 def make_form(name, cfg, B, lib, dev, **kw):
-    with on_library(lib):
+    with _lib.use(lib):
         env = VecV2VEnv(cfg, batch=B, device=dev, out_dtype=torch.float32)
     env.reset_topology(seed=1234)
     N = cfg.num_users
@@ -132,17 +121,17 @@ def run_feature(B, parent, rounds, warm):
             lp = make_form(name + ": loop (parent)", cfgs[ia_on], B, parent, dev, launch=False, **kw)
             lp["env"].load_saved_positions(tr)
             forms.append(lp)
-        forms.append(make_form(name + ": launch", cfgs[ia_on], B, None, dev, launch=True, **kw))
+        forms.append(make_form(name + ": launch", cfgs[ia_on], B, _lib.load(), dev, launch=True, **kw))
     seq = torch.stack([forms[0]["env"].sample(4000 + k) for k in range(K)])
-    timed_rounds(forms, lambda f: body(f, seq, tr), rounds, warm)
-    us, rnd = medians(forms)
+    ab.timed_rounds(forms, lambda f: body(f, seq, tr), rounds, warm)
+    us, rnd = ab.summary(forms, K)
     by = {f["form"]: f for f in forms}
     equal, saving = {}, {}
     for name, mode, states, closed, ia_on, log in PAIRS:
         ref = by[(name[:-5] if log else name) + ": loop (parent)"]
         x = by[name + ": launch"]
         keys = ("sh", "sr", "co") + (("prev",) if ia_on else ())
-        ok = same_env(ref, x) and all(torch.equal(ref[k], x[k]) for k in keys)
+        ok = ab.same_env(ref["env"], x["env"]) and all(torch.equal(ref[k], x[k]) for k in keys)
         if closed:
             ok = ok and torch.equal(ref["pol"].counter, x["pol"].counter) and torch.equal(ref["pol"].prev_action, x["pol"].prev_action)
         if log:
@@ -170,17 +159,17 @@ def run_guard(B, parent, rounds, warm):
     forms = []
     for name, mode, closed, ia_on in calls:
         cfg = c2_config(reward_design=2, track_arrival=ia_on)
-        for tag, lib in ((" (parent)", parent), ("", None)):
+        for tag, lib in ((" (parent)", parent), ("", _lib.load())):
             forms.append(make_form(name + tag, cfg, B, lib, dev, launch=True, block=False, mode=mode, states=None, closed=closed,
                                    ia_on=ia_on, log=False))
     seq = torch.stack([forms[0]["env"].sample(4000 + k) for k in range(K)])
-    timed_rounds(forms, lambda f: body(f, seq, None), rounds, warm)
-    us, rnd = medians(forms)
+    ab.timed_rounds(forms, lambda f: body(f, seq, None), rounds, warm)
+    us, rnd = ab.summary(forms, K)
     by = {f["form"]: f for f in forms}
     equal, slower = {}, {}
     for name, mode, closed, ia_on in calls:
         p, x = by[name + " (parent)"], by[name]
-        ok = same_env(p, x) and torch.equal(p["sh"], x["sh"]) and torch.equal(p["prev"], x["prev"])
+        ok = ab.same_env(p["env"], x["env"]) and torch.equal(p["sh"], x["sh"]) and torch.equal(p["prev"], x["prev"])
         if closed:
             ok = ok and torch.equal(p["pol"].counter, x["pol"].counter)
         equal[name] = bool(ok)
@@ -201,17 +190,11 @@ def main():
     ap.add_argument("--only", default="c2,guard")
     ap.add_argument("--out", default=os.path.join(HERE, "kslots_replay", "kslots_replay_bench.txt"))
     args = ap.parse_args()
-    parent = ia_bench.load_parent(os.path.abspath(args.parent_lib))
-    assert ctypes.cast(parent.diral_env_step, ctypes.c_void_p).value != ctypes.cast(_lib.load().diral_env_step, ctypes.c_void_p).value, \
-        "the parent's library must be a second library"
+    parent, _ = ab.two_libraries(args.parent_lib, lacking=("diral_env_rollout_replay", "diral_env_step_policy_replay"))
     only = args.only.split(",")
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as fh:
+    with ab.report(args.out) as emit:
         def show(r, key):
-            for line in ("%s B=%d: %s" % (r["config"], r["B"], r[key]), json.dumps(r)):
-                print(line, flush=True)
-                fh.write(line + "\n")
-                fh.flush()
+            emit("%s B=%d: %s" % (r["config"], r["B"], r[key]), r)
         if "c2" in only:
             for b in args.batches.split(","):
                 show(run_feature(int(b), parent, args.rounds, args.warm), "saving")

@@ -11,29 +11,15 @@ for each library given (tuning variants next to the tree's own): --libs name=pat
 import argparse
 import json
 import os
-import sys
 
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
-
-import kslots_replay_bench as rb  # noqa: E402
+import ab  # noqa: E402  (puts the repository's root on sys.path)
 from diral_amd import _lib  # noqa: E402
 from diral_amd.config import c2_config  # noqa: E402
 from diral_amd.vec_env import VecV2VEnv  # noqa: E402
 
 K = 25
-
-
-def load_lib(path):
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("diral_amd._lib_x" + str(abs(hash(path))), _lib.__file__)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.LIB_PATH = path
-    return mod.load()
 
 
 def main():
@@ -46,23 +32,25 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     cfg = c2_config(reward_design=2)
-    libs = [(n, None if p == "this" else load_lib(os.path.abspath(p))) for n, p in (x.split("=") for x in args.libs.split(","))]
+    libs = [(n, _lib.load() if p == "this" else _lib.bind(os.path.abspath(p))) for n, p in (x.split("=") for x in args.libs.split(","))]
     total = K * (args.rounds + args.warm)
     for B in (int(b) for b in args.batches.split(",")):
         # the velocity model's own positions over the whole run
         rec = VecV2VEnv(cfg, batch=B, device=dev, out_dtype=torch.float32)
         rec.reset_topology(seed=1234)
         seq = torch.stack([rec.sample(4000 + k) for k in range(K)])
+        s0 = rec.export_state(tables=False)                           # [B, K, N]: where the velocity model takes the envs in K slots
+        k = torch.arange(1, K + 1, dtype=torch.float64, device=dev).view(1, K, 1)
+        wrap = torch.remainder(s0["pos_x"].unsqueeze(1) + s0["vel"].unsqueeze(1) * k, float(cfg.highway_length)).contiguous()
         logs = []
         for r in range(args.rounds + args.warm):
             logs.append(rec.rollout(seq, r * K, mode=args.mode, states=None, global_reward_avg=True, log_positions=True)["xpos"])
         exact = torch.cat(logs).transpose(0, 1).contiguous()          # [B, total, N]
         del logs
-        wrap = rb.sequence(cfg, B, dev)
         forms = []
         for name, lib in libs:
             for kind in ("none", "log", "exact", "wrap"):
-                with rb.on_library(lib):
+                with _lib.use(lib):
                     env = VecV2VEnv(cfg, batch=B, device=dev, out_dtype=torch.float32)
                 env.reset_topology(seed=1234)
                 forms.append(dict(form=name + ":" + kind, kind=kind, env=env, t=0, ms=[]))
@@ -71,12 +59,12 @@ def main():
             kw = {"none": {}, "log": dict(log_positions=True), "exact": dict(positions=exact), "wrap": dict(positions=wrap)}[f["kind"]]
             f["out"] = f["env"].rollout(seq, f["t"], mode=args.mode, states=None, global_reward_avg=True, **kw)
             f["t"] += K
-        rb.timed_rounds(forms, body, args.rounds, args.warm)
-        us, rnd = rb.medians(forms)
+        ab.timed_rounds(forms, body, args.rounds, args.warm)
+        us, _ = ab.summary(forms, K)
         same = {f["form"]: bool(torch.equal(f["env"].export_state()["pos_x"], rec.export_state()["pos_x"])) for f in forms}
         print(json.dumps({"B": B, "us_per_slot": us, "ends_where_the_velocity_model_ends": same}), flush=True)
         assert total == exact.shape[1]
-        del forms, exact, wrap, rec
+        del forms, exact, wrap, rec, s0
         torch.cuda.empty_cache()
 
 

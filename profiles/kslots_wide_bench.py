@@ -8,14 +8,10 @@ Prints us per slot per form and checks that the forms leave equal tables, positi
   python profiles/kslots_wide_bench.py [--configs c5,c3] [--rounds 6] [--warm 2]
 """
 import argparse
-import json
-import os
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
+import ab  # noqa: E402  (puts the repository's root on sys.path)
 from diral_amd.config import KERNEL_POLICY, bench_config  # noqa: E402
 from diral_amd.sps import SpsPolicy  # noqa: E402
 from diral_amd.vec_env import VecV2VEnv  # noqa: E402
@@ -60,35 +56,19 @@ def run(name, rounds, warm):
             f["i"] ^= 1
             f["t"] += K
 
-    for r in range(warm + rounds):
-        for f in forms:                                         # interleaved: one round of 25 slots per form
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            slots25(f)
-            e1.record()
-            torch.cuda.synchronize()
-            if r >= warm:
-                f["ms"].append(e0.elapsed_time(e1))
+    ab.timed_rounds(forms, slots25, rounds, warm)
+    us, rnd = ab.summary(forms, K)
     ref = forms[0]
-    sa = ref["env"].export_state()
     equal = {}
     for f in forms[1:]:
-        sb = f["env"].export_state()
-        ok = all(torch.equal(sa[k], sb[k]) for k in sa)
-        ok = ok and torch.equal(ref["env"].metrics(), f["env"].metrics())
+        ok = ab.same_env(ref["env"], f["env"])
         ok = ok and torch.equal(ref["pol"].prev_action, f["pol"].prev_action) and torch.equal(ref["pol"].counter, f["pol"].counter)
         ok = ok and torch.equal(ref["acts"][ref["i"]], f["acts"][f["i"]])
         ok = ok and torch.equal(ref["sh"], f["sh"]) and torch.equal(ref["sr"], f["sr"]) and torch.equal(ref["co"], f["co"])
         equal[f["form"]] = bool(ok)
     out = {"config": name, "N": N, "A": A, "B": B, "mobility_vary": vary, "slots_per_round": K, "rounds": rounds,
-           "us_per_slot": {}, "us_per_slot_rounds": {}, "equal_to_three_launch": equal}
-    for f in forms:
-        ms = sorted(f["ms"])
-        out["us_per_slot"][f["form"]] = round(ms[len(ms) // 2] * 1e3 / K, 2)
-        out["us_per_slot_rounds"][f["form"]] = [round(m * 1e3 / K, 2) for m in f["ms"]]
-    base = out["us_per_slot"]["three-launch"]
-    out["saving_vs_three_launch"] = {k: round(1.0 - v / base, 4) for k, v in out["us_per_slot"].items() if k != "three-launch"}
+           "us_per_slot": us, "us_per_slot_rounds": rnd, "equal_to_three_launch": equal}
+    out["saving_vs_three_launch"] = {k: round(1.0 - v / us["three-launch"], 4) for k, v in us.items() if k != "three-launch"}
     for f in forms:
         f["env"].check()
     del forms
@@ -102,11 +82,10 @@ def main():
     ap.add_argument("--rounds", type=int, default=6)
     ap.add_argument("--warm", type=int, default=2)
     args = ap.parse_args()
-    for name in args.configs.split(","):
-        r = run(name, args.rounds, args.warm)
-        print("%s: %s  equal: %s" % (name, "  ".join("%s %.1f us/slot" % kv for kv in r["us_per_slot"].items()),
-                                     r["equal_to_three_launch"]))
-        print(json.dumps(r))
+    with ab.report() as emit:
+        for name in args.configs.split(","):
+            r = run(name, args.rounds, args.warm)
+            emit("%s: %s  equal: %s" % (name, "  ".join("%s %.1f us/slot" % kv for kv in r["us_per_slot"].items()), r["equal_to_three_launch"]), r)
 
 
 if __name__ == "__main__":

@@ -16,37 +16,16 @@ Shapes: C2 (B = 4096, N = 64, S = 52; float32 -> float32 and -> bfloat16, step 6
   python profiles/replay_memory_bench.py [--rounds 7] [--warm 2] [--reps 20] > profiles/replay_memory/memory_bench.txt
 """
 import argparse
-import json
-import os
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
+import ab  # noqa: E402  (puts the repository's root on sys.path)
 from diral_amd.config import bench_config, c2_config  # noqa: E402
 from diral_amd.memory import ReplayMemory  # noqa: E402
 from diral_amd.vec_env import VecV2VEnv  # noqa: E402
 
 FLAT_COPY_TB_S = 6.29
 CAPACITY, K, STEP = 60, 25, 6
-
-
-def timed(forms, rounds, warm, reps):
-    for f in forms:
-        f["us"] = []
-    for r in range(warm + rounds):
-        for f in forms:                                             # interleaved: every form in every round
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(reps):
-                f["body"]()
-            e1.record()
-            torch.cuda.synchronize()
-            if r >= warm:
-                f["us"].append(e0.elapsed_time(e1) * 1e3 / reps)
-    return {f["form"]: round(sorted(f["us"])[len(f["us"]) // 2], 2) for f in forms}
 
 
 def torch_sample(mem, idx, env, step, out_dtype):
@@ -61,7 +40,7 @@ def torch_sample(mem, idx, env, step, out_dtype):
     return s, a, r, n
 
 
-def run(name, cfg, B, Ms, out_dtypes, rounds, warm, reps):
+def run(emit, name, cfg, B, Ms, out_dtypes, rounds, warm, reps):
     dev = torch.device("cuda:0")
     env = VecV2VEnv(cfg, batch=B, device=dev, out_dtype=torch.float32)
     if env.N <= 8:
@@ -90,14 +69,14 @@ def run(name, cfg, B, Ms, out_dtypes, rounds, warm, reps):
 
     forms = [dict(form="add_many", body=add), dict(form="torch index_copy", body=torch_add),
              dict(form="rollout", body=lambda: env.rollout(seq, states="all"))]
-    us = timed(forms, rounds, warm, max(2, reps // 4))
+    ab.timed_rounds(forms, ab.own_body, rounds, warm, reps=max(2, reps // 4))
+    us, _ = ab.summary(forms, max(2, reps // 4))
     add_bytes = 2 * (K * B * N * S * 4 + 2 * K * B * N * 4)
     rec = dict(shape=name, B=B, N=N, S=S, K=K, capacity=CAPACITY, us_per_call=us, add_bytes=add_bytes,
                add_tb_per_s=round(add_bytes / (us["add_many"] * 1e-6) / 1e12, 3),
                add_share_of_rollout=round(us["add_many"] / us["rollout"], 3), state_row_mb=round(B * N * S * 4 / 1e6, 1))
-    print("%s add: B=%d N=%d S=%d K=%d, us per call: %s; add_many = %.1f %% of the %d-slot rollout" % (
-        name, B, N, S, K, "  ".join("%s %.1f" % kv for kv in us.items()), 100.0 * rec["add_share_of_rollout"], K), flush=True)
-    print(json.dumps(rec), flush=True)
+    emit("%s add: B=%d N=%d S=%d K=%d, us per call: %s; add_many = %.1f %% of the %d-slot rollout" % (
+        name, B, N, S, K, "  ".join("%s %.1f" % kv for kv in us.items()), 100.0 * rec["add_share_of_rollout"], K), rec)
     mem.count = count0 + K
     del twin_s, twin_a, twin_r, out, st
     for M in Ms:
@@ -114,15 +93,15 @@ def run(name, cfg, B, Ms, out_dtypes, rounds, warm, reps):
             forms = [dict(form="sample", body=lambda: mem.sample(M, STEP, out_dtype=od, last_only=True, out=outs)),
                      dict(form="sample idx", body=lambda: mem.sample(M, STEP, out_dtype=od, last_only=True, idx=idx, env=e, out=outs)),
                      dict(form="torch", body=lambda: torch_sample(mem, idx, e, STEP, od))]
-            us = timed(forms, rounds, warm, reps)
+            ab.timed_rounds(forms, ab.own_body, rounds, warm, reps=reps)
+            us, rnd = ab.summary(forms, reps)
             nbytes = M * (STEP + 1) * N * S * 4 + 2 * M * STEP * N * S * outs["states"].element_size()
             rec = dict(shape=name, B=B, N=N, S=S, M=M, step=STEP, out_dtype=str(od), us_per_call=us, equals_torch=agree,
                        sample_bytes=nbytes,
                        sample_tb_per_s={k: round(nbytes / (v * 1e-6) / 1e12, 3) for k, v in us.items() if k != "torch"},
-                       flat_copy_tb_per_s=FLAT_COPY_TB_S, us_rounds={f["form"]: [round(v, 2) for v in f["us"]] for f in forms})
-            print("%s sample: M=%d -> %s, us per call: %s (equals torch: %s)"
-                  % (name, M, od, "  ".join("%s %.1f" % kv for kv in us.items()), agree), flush=True)
-            print(json.dumps(rec), flush=True)
+                       flat_copy_tb_per_s=FLAT_COPY_TB_S, us_rounds=rnd)
+            emit("%s sample: M=%d -> %s, us per call: %s (equals torch: %s)"
+                 % (name, M, od, "  ".join("%s %.1f" % kv for kv in us.items()), agree), rec)
 
 
 def main():
@@ -132,9 +111,10 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     args = ap.parse_args()
     print("device: %s" % torch.cuda.get_device_name(0), flush=True)
-    run("c2", c2_config(), 4096, (512, 4096), (torch.float32, torch.bfloat16), args.rounds, args.warm, args.reps)
     toy = bench_config(4, 3, 100.0, communication_range=250.0, State=dict(num_bins=20))
-    run("toy", toy, 65536, (512, 4096), (torch.float32,), args.rounds, args.warm, args.reps)
+    with ab.report() as emit:
+        run(emit, "c2", c2_config(), 4096, (512, 4096), (torch.float32, torch.bfloat16), args.rounds, args.warm, args.reps)
+        run(emit, "toy", toy, 65536, (512, 4096), (torch.float32,), args.rounds, args.warm, args.reps)
 
 
 if __name__ == "__main__":

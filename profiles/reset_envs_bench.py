@@ -16,16 +16,12 @@ once (untimed): it is in ring form with live tables, as it is in a training loop
 """
 import argparse
 import ctypes
-import json
-import os
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
+import ab  # noqa: E402  (puts the repository's root on sys.path)
 from diral_amd import _lib  # noqa: E402
-from diral_amd.config import DiralCfg, bench_config, c2_config  # noqa: E402
+from diral_amd.config import bench_config, c2_config  # noqa: E402
 from diral_amd.vec_env import VecV2VEnv  # noqa: E402
 
 COPY_PEAK_TB_S = 6.29       # what copy_envs_kernel reaches (profiles/copy_envs/copy_bench.txt)
@@ -54,19 +50,13 @@ class RawLib:
     """`diral_env_reset` of a build of the library - this one or another - on a handle of its own, through raw ctypes: the
     same calling path for both, none of the Python wrapper's host time inside the timed bracket."""
 
-    def __init__(self, path, cfg, B):
-        P = ctypes.c_void_p
-        self.lib = ctypes.CDLL(os.path.abspath(path))
-        self.lib.diral_env_create.restype = ctypes.c_int
-        self.lib.diral_env_create.argtypes = [ctypes.POINTER(DiralCfg), ctypes.c_int, ctypes.c_int, ctypes.POINTER(P)]
-        self.lib.diral_env_reset.restype = ctypes.c_int
-        self.lib.diral_env_reset.argtypes = [P, P, P, P, ctypes.c_uint64, P]
-        self.lib.diral_env_destroy.argtypes = [P]
+    def __init__(self, lib, cfg, B):
+        self.lib = lib                                              # (from _lib.load() or _lib.bind(): the prototypes are set)
         self.ccfg = cfg.to_c()
-        self.h = P()
+        self.h = ctypes.c_void_p()
         st = self.lib.diral_env_create(ctypes.byref(self.ccfg), B, 0, ctypes.byref(self.h))
         if st != 0:
-            raise RuntimeError("%s: diral_env_create returned %d" % (path, st))
+            raise RuntimeError("diral_env_create returned %d" % st)
 
     def reset(self):
         s = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -78,25 +68,7 @@ class RawLib:
         self.lib.diral_env_destroy(self.h)
 
 
-def timed_rounds(forms, between, rounds, warm):
-    for r in range(warm + rounds):
-        for f in forms:                                             # interleaved: one call per form and round
-            between()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            f["body"]()
-            e1.record()
-            torch.cuda.synchronize()
-            if r >= warm:
-                f["ms"].append(e0.elapsed_time(e1))
-
-
-def median_us(f):
-    return sorted(f["ms"])[len(f["ms"]) // 2] * 1e3
-
-
-def run(name, rounds, warm, parent_path):
+def run(emit, name, rounds, warm, parent_lib):
     make, B = SHAPES[name]
     cfg = make()
     dev = torch.device("cuda:0")
@@ -119,22 +91,20 @@ def run(name, rounds, warm, parent_path):
             written["%s %d" % (kind, n)] = n * per_env
     forms.append(dict(form="reset", body=lambda: E.reset_topology(seed=SEED)))
     written["reset"] = B * per_env
-    own_raw = RawLib(_lib.LIB_PATH, cfg, B)
+    own_raw = RawLib(_lib.load(), cfg, B)
     forms.append(dict(form="reset raw", body=own_raw.reset))
     written["reset raw"] = B * per_env
     parent = None
-    if parent_path:
-        parent = RawLib(parent_path, cfg, B)
+    if parent_lib:
+        parent = RawLib(parent_lib, cfg, B)
         forms.append(dict(form="reset parent", body=parent.reset))
         written["reset parent"] = B * per_env
-    for f in forms:
-        f["ms"] = []
     clock = [10]
 
-    def between():
+    def between(_):
         E.step(acts, clock[0])
         clock[0] += 1
-    timed_rounds(forms, between, rounds, warm)
+    ab.timed_rounds(forms, ab.own_body, rounds, warm, between=between)
     # the subset call over every env leaves what the whole reset leaves
     E.reset_envs(count=B, seed=SEED)
     a = E.export_state()
@@ -145,11 +115,11 @@ def run(name, rounds, warm, parent_path):
     equal = bool(all(torch.equal(a[k], b[k]) for k in a))
     for e in (E, T):
         e.check()
-    us = {f["form"]: round(median_us(f), 1) for f in forms}
+    us, rnd = ab.summary(forms, digits=1)
     tb = {k: round(written[k] / (us[k] * 1e-6) / 1e12, 3) for k in us if us[k] > 0}
     out = dict(config=name, B=B, N=cfg.num_users, A=cfg.num_channels, rounds=rounds, bytes_per_env=per_env, equal=equal, us=us,
                tb_written_per_s=tb, copy_kernel_tb_per_s=COPY_PEAK_TB_S,
-               us_rounds={f["form"]: [round(m * 1e3, 1) for m in f["ms"]] for f in forms},
+               us_rounds=rnd,
                full_index_vs_reset=round(us["index %d" % B] / us["reset"], 3),
                full_mask_vs_reset=round(us["mask %d" % B] / us["reset"], 3))
     if parent:
@@ -157,8 +127,7 @@ def run(name, rounds, warm, parent_path):
         out["full_index_vs_parent"] = round(us["index %d" % B] / us["reset parent"], 3)
         parent.close()
     own_raw.close()
-    print("%s B=%d (%d bytes per env), us: %s" % (name, B, per_env, "  ".join("%s %.1f" % kv for kv in us.items())), flush=True)
-    print(json.dumps(out), flush=True)
+    emit("%s B=%d (%d bytes per env), us: %s" % (name, B, per_env, "  ".join("%s %.1f" % kv for kv in us.items())), out)
     del forms, E, T
     torch.cuda.empty_cache()
 
@@ -173,9 +142,11 @@ def main():
     print("device: %s" % torch.cuda.get_device_name(0), flush=True)
     if not args.parent_lib:
         print("no --parent-lib: the `reset parent` column is left out", flush=True)
-    for name in ("c2", "toy"):
-        if name in args.only.split(","):
-            run(name, args.rounds, args.warm, args.parent_lib)
+    parent = ab.two_libraries(args.parent_lib, lacking=("diral_env_reset_envs",))[0] if args.parent_lib else None
+    with ab.report() as emit:
+        for name in ("c2", "toy"):
+            if name in args.only.split(","):
+                run(emit, name, args.rounds, args.warm, parent)
 
 
 if __name__ == "__main__":

@@ -15,17 +15,11 @@ C2, B = 4096, on the parent's library and on this one, interleaved in the same w
   python profiles/rollout_bench.py --parent-lib /path/to/parent/libdiral_env.so [--rounds 7] [--warm 2] [--only c2,wide,guard]
 """
 import argparse
-import ctypes
-import importlib.util
-import json
-import os
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
-from diral_amd import _lib, vec_env  # noqa: E402
+import ab  # noqa: E402  (puts the repository's root on sys.path)
+from diral_amd import _lib  # noqa: E402
 from diral_amd.config import KERNEL_POLICY, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config, c2_config  # noqa: E402
 from diral_amd.driver import DriverLoop  # noqa: E402
 from diral_amd.sps import SpsPolicy  # noqa: E402
@@ -35,58 +29,6 @@ K = 25
 VEL_SEED = 77
 WIDE = {"c5": (128, 64, 4000.0, 16384, True), "c3": (256, 64, 4000.0, 8192, False)}
 MODES = {"my_step": STEP_MY_STEP, "my_step_ch": STEP_MY_STEP_CH}
-
-
-def load_parent(path):
-    """A second copy of the loader bound to the parent's library (it lacks diral_env_rollout)."""
-    spec = importlib.util.spec_from_file_location("diral_amd._lib_parent", _lib.__file__)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.LIB_PATH = path
-    mod.SYMBOLS = [s for s in mod.SYMBOLS if s != "diral_env_rollout"]
-    return mod.load()
-
-
-class on_library:
-    """VecV2VEnv (and what it builds) on `lib` inside the block."""
-
-    def __init__(self, lib):
-        self.lib = lib
-
-    def __enter__(self):
-        self.keep = vec_env._lib.load
-        if self.lib is not None:
-            vec_env._lib.load = lambda: self.lib
-
-    def __exit__(self, *exc):
-        vec_env._lib.load = self.keep
-
-
-def timed_rounds(forms, body, rounds, warm):
-    for r in range(warm + rounds):
-        for f in forms:                                             # interleaved: one round of K slots per form
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            body(f)
-            e1.record()
-            torch.cuda.synchronize()
-            if r >= warm:
-                f["ms"].append(e0.elapsed_time(e1))
-
-
-def medians(forms):
-    us, rnd = {}, {}
-    for f in forms:
-        ms = sorted(f["ms"])
-        us[f["form"]] = round(ms[len(ms) // 2] * 1e3 / K, 2)
-        rnd[f["form"]] = [round(m * 1e3 / K, 2) for m in f["ms"]]
-    return us, rnd
-
-
-def same_env(x, y):
-    sa, sb = x["env"].export_state(), y["env"].export_state()
-    return bool(all(torch.equal(sa[k], sb[k]) for k in sa) and torch.equal(x["env"].metrics(), y["env"].metrics()))
 
 
 def shape(env, rew, a, sh, sr, co):
@@ -100,10 +42,10 @@ def run_rollout(name, cfg, B, mode, kinds, parent, rounds, warm):
     dev = torch.device("cuda:0")
     vary = cfg.mobility_vary
     EI = cfg.episode_interval
-    forms = []
+    forms, branch = [], _lib.load()
     for kind in kinds:
-        for form, lib in (("loop (parent) " + kind, parent), ("loop " + kind, None), ("rollout " + kind, None)):
-            with on_library(lib):
+        for form, lib in (("loop (parent) " + kind, parent), ("loop " + kind, branch), ("rollout " + kind, branch)):
+            with _lib.use(lib):
                 env = VecV2VEnv(cfg, batch=B, device=dev, out_dtype=torch.float32)
             env.reset_topology(seed=1234)
             f = dict(form=form, kind=kind, env=env, t=0, ms=[], launch=form.startswith("rollout"))
@@ -135,13 +77,13 @@ def run_rollout(name, cfg, B, mode, kinds, parent, rounds, warm):
         if not every:
             f["states"] = obs
 
-    timed_rounds(forms, body, rounds, warm)
-    us, rnd = medians(forms)
+    ab.timed_rounds(forms, body, rounds, warm)
+    us, rnd = ab.summary(forms, K)
     equal, saving = {}, {}
     for i in range(0, len(forms), 3):
         p, l, r = forms[i:i + 3]
         for x in (l, r):
-            equal[x["form"]] = bool(same_env(p, x) and all(torch.equal(p[k], x[k]) for k in ("sh", "sr", "co", "states")))
+            equal[x["form"]] = bool(ab.same_env(p["env"], x["env"]) and all(torch.equal(p[k], x[k]) for k in ("sh", "sr", "co", "states")))
         saving["rollout %s vs loop (parent)" % p["kind"]] = round(1.0 - us[r["form"]] / us[p["form"]], 4)
         saving["loop %s vs loop (parent)" % p["kind"]] = round(1.0 - us[l["form"]] / us[p["form"]], 4)
     for f in forms:
@@ -160,8 +102,8 @@ def run_guard(B, parent, rounds, warm):
     dev = torch.device("cuda:0")
     forms = []
     for what in ("step_policy K=25", "prefill K=25"):
-        for tag, lib in ((" (parent)", parent), ("", None)):
-            with on_library(lib):
+        for tag, lib in ((" (parent)", parent), ("", _lib.load())):
+            with _lib.use(lib):
                 env = VecV2VEnv(cfg, batch=B, device=dev, out_dtype=torch.float32)
                 env.reset_topology(seed=1234)
                 f = dict(form=what + tag, what=what, env=env, t=0, i=0, ms=[])
@@ -189,11 +131,11 @@ def run_guard(B, parent, rounds, warm):
             f["seed"] += K
         assert env.last_kernel() & KERNEL_POLICY
 
-    timed_rounds(forms, body, rounds, warm)
-    us, rnd = medians(forms)
+    ab.timed_rounds(forms, body, rounds, warm)
+    us, rnd = ab.summary(forms, K)
     s0, s1, p0, p1 = forms
-    equal = {"step_policy K=25": bool(same_env(s0, s1) and torch.equal(s0["sh"], s1["sh"]) and torch.equal(s0["pol"].counter, s1["pol"].counter)),
-             "prefill K=25": bool(same_env(p0, p1) and torch.equal(p0["states"], p1["states"]))}
+    equal = {"step_policy K=25": bool(ab.same_env(s0["env"], s1["env"]) and torch.equal(s0["sh"], s1["sh"]) and torch.equal(s0["pol"].counter, s1["pol"].counter)),
+             "prefill K=25": bool(ab.same_env(p0["env"], p1["env"]) and torch.equal(p0["states"], p1["states"]))}
     slower = {w: round(us[w] / us[w + " (parent)"] - 1.0, 4) for w in ("step_policy K=25", "prefill K=25")}
     out = {"config": "guard: c2 my_step", "B": B, "slots_per_round": K, "rounds": rounds, "us_per_slot": us,
            "us_per_slot_rounds": rnd, "equal_to_parent": equal, "slower_than_parent": slower}
@@ -210,23 +152,20 @@ def main():
     ap.add_argument("--warm", type=int, default=2)
     ap.add_argument("--only", default="c2,wide,guard")
     args = ap.parse_args()
-    parent = load_parent(os.path.abspath(args.parent_lib))
-    assert ctypes.cast(parent.diral_env_step, ctypes.c_void_p).value != ctypes.cast(_lib.load().diral_env_step, ctypes.c_void_p).value, \
-        "the parent's library must be a second library"
+    parent, _ = ab.two_libraries(args.parent_lib, lacking=("diral_env_rollout",))
     only = args.only.split(",")
-
-    def show(r, key="saving"):
-        print("%s B=%d: %s  %s" % (r["config"], r["B"], "  ".join("%s %.1f" % kv for kv in r["us_per_slot"].items()), r[key]), flush=True)
-        print(json.dumps(r), flush=True)
-    if "c2" in only:
-        for b in args.batches.split(","):
-            for mode in ("my_step", "my_step_ch"):
-                show(run_rollout("c2", c2_config(reward_design=2), int(b), mode, ("last", "all"), parent, args.rounds, args.warm))
-    if "wide" in only:
-        for name, (N, A, L, B, vary) in WIDE.items():
-            show(run_rollout(name, bench_config(N, A, L, mobility_vary=vary), B, "my_step", ("last",), parent, args.rounds, args.warm))
-    if "guard" in only:
-        show(run_guard(4096, parent, args.rounds, args.warm), "slower_than_parent")
+    with ab.report() as emit:
+        def show(r, key="saving"):
+            emit("%s B=%d: %s  %s" % (r["config"], r["B"], "  ".join("%s %.1f" % kv for kv in r["us_per_slot"].items()), r[key]), r)
+        if "c2" in only:
+            for b in args.batches.split(","):
+                for mode in ("my_step", "my_step_ch"):
+                    show(run_rollout("c2", c2_config(reward_design=2), int(b), mode, ("last", "all"), parent, args.rounds, args.warm))
+        if "wide" in only:
+            for name, (N, A, L, B, vary) in WIDE.items():
+                show(run_rollout(name, bench_config(N, A, L, mobility_vary=vary), B, "my_step", ("last",), parent, args.rounds, args.warm))
+        if "guard" in only:
+            show(run_guard(4096, parent, args.rounds, args.warm), "slower_than_parent")
 
 
 if __name__ == "__main__":

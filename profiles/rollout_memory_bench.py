@@ -18,62 +18,29 @@ my_step_ch, the toy config (N = 4) at B = 4096 / 65536; K = 25 slots, capacity 6
   python profiles/rollout_memory_bench.py --parent-lib PATH [--rounds 7] [--warm 2] [--reps 5] > profiles/rollout_memory/rollout_memory_bench.txt
 """
 import argparse
-import json
-import os
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
+import ab  # noqa: E402  (puts the repository's root on sys.path)
 from diral_amd import _lib  # noqa: E402
 from diral_amd.config import bench_config, c2_config  # noqa: E402
 from diral_amd.memory import ReplayMemory  # noqa: E402
 from diral_amd.vec_env import VecV2VEnv  # noqa: E402
 
 CAPACITY, K = 60, 25
-NEW_SYMBOLS = ("diral_env_rollout_memory", "diral_env_prefill_memory")
-
-
-def library(path, drop=()):
-    """A libdiral_env.so with its prototypes, as `_lib.load()` returns it; handles made while it is current bind to it."""
-    saved = list(_lib.SYMBOLS)
-    _lib._lib, _lib.LIB_PATH = None, path
-    _lib.SYMBOLS[:] = [s for s in saved if s not in drop]
-    try:
-        return _lib.load()
-    finally:
-        _lib.SYMBOLS[:] = saved
-
-
-def timed(forms, rounds, warm, reps):
-    for f in forms:
-        f["us"] = []
-    for r in range(warm + rounds):
-        for f in forms:                                             # interleaved: every form in every round
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(reps):
-                f["body"]()
-            e1.record()
-            torch.cuda.synchronize()
-            if r >= warm:
-                f["us"].append(e0.elapsed_time(e1) * 1e3 / reps)
-    return {f["form"]: round(sorted(f["us"])[len(f["us"]) // 2], 2) for f in forms}
 
 
 def handle(lib, cfg, B):
-    _lib._lib = lib
-    env = VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=torch.float32)
+    with _lib.use(lib):
+        env = VecV2VEnv(cfg, batch=B, device="cuda:0", out_dtype=torch.float32)
+        mem = ReplayMemory(CAPACITY, B, env.N, env.S, seed=1, device="cuda:0")
     if env.N <= 8:
         env.use_subwave_path(slots=True)
     env.reset_topology(seed=1)
-    mem = ReplayMemory(CAPACITY, B, env.N, env.S, seed=1, device="cuda:0")
     return env, mem
 
 
-def run(name, cfg, B, mode, libs, rounds, warm, reps):
+def run(emit, name, cfg, B, mode, libs, rounds, warm, reps):
     parent, new = libs
     # a handle (and a memory) per form, all from one topology: every form makes the same calls in the same order, so the
     # five envs move in lockstep and every form times the same slots
@@ -121,16 +88,15 @@ def run(name, cfg, B, mode, libs, rounds, warm, reps):
                            "a new": fill_alone("a new")})
     for what in ("rollout", "prefill"):
         timing = [dict(form=form, body=bodies[what][form]) for form, _ in forms]
-        us = timed(timing, rounds, warm, reps)
+        ab.timed_rounds(timing, ab.own_body, rounds, warm, reps=reps)
+        us, _ = ab.summary(timing, reps)
         spread = abs(us["a"] - us["a'"]) / min(us["a"], us["a'"])
         rec = dict(shape=name, what=what, mode=mode, B=B, N=N, S=S, K=K, capacity=CAPACITY, us_per_call=us,
                    c_over_b=round(us["c"] / us["b"], 3), c_over_a=round(us["c"] / min(us["a"], us["a'"]), 3),
                    a_new_over_a=round(us["a new"] / min(us["a"], us["a'"]), 3), a_spread=round(spread, 4),
-                   us_rounds={f["form"]: [round(v, 1) for v in f["us"]] for f in timing})
-        print("%s %s %s B=%d: us per call  a %.1f  a' %.1f  a new %.1f  b %.1f  c %.1f;  c / b = %.3f,  c / a = %.3f  (a against a': %.2f %%)"
-              % (name, what, mode, B, us["a"], us["a'"], us["a new"], us["b"], us["c"], rec["c_over_b"], rec["c_over_a"], 100.0 * spread),
-              flush=True)
-        print(json.dumps(rec), flush=True)
+                   us_rounds=ab.summary(timing, reps, digits=1)[1])
+        emit("%s %s %s B=%d: us per call  a %.1f  a' %.1f  a new %.1f  b %.1f  c %.1f;  c / b = %.3f,  c / a = %.3f  (a against a': %.2f %%)"
+             % (name, what, mode, B, us["a"], us["a'"], us["a new"], us["b"], us["c"], rec["c_over_b"], rec["c_over_a"], 100.0 * spread), rec)
     for form, _ in forms:
         env[form].check()
         env[form].close()
@@ -143,15 +109,15 @@ def main():
     ap.add_argument("--warm", type=int, default=2)
     ap.add_argument("--reps", type=int, default=5)
     args = ap.parse_args()
-    here = _lib.LIB_PATH
-    libs = (library(os.path.abspath(args.parent_lib), drop=NEW_SYMBOLS), library(here))
+    libs = ab.two_libraries(args.parent_lib, lacking=("diral_env_rollout_memory", "diral_env_prefill_memory"))
     print("device: %s" % torch.cuda.get_device_name(0), flush=True)
-    for mode in ("my_step", "my_step_ch"):
-        for B in (64, 1024, 4096):
-            run("c2", c2_config(reward_design=2), B, mode, libs, args.rounds, args.warm, args.reps)
     toy = bench_config(4, 3, 100.0, communication_range=250.0, State=dict(num_bins=20))
-    for B in (4096, 65536):
-        run("toy", toy, B, "my_step", libs, args.rounds, args.warm, args.reps)
+    with ab.report() as emit:
+        for mode in ("my_step", "my_step_ch"):
+            for B in (64, 1024, 4096):
+                run(emit, "c2", c2_config(reward_design=2), B, mode, libs, args.rounds, args.warm, args.reps)
+        for B in (4096, 65536):
+            run(emit, "toy", toy, B, "my_step", libs, args.rounds, args.warm, args.reps)
 
 
 if __name__ == "__main__":

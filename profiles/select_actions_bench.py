@@ -16,21 +16,17 @@ profiles/copy_envs/copy_bench.txt.
   python profiles/select_actions_bench.py [--rounds 7] [--warm 2] [--reps 50] > profiles/select_actions/select_bench.txt
 """
 import argparse
-import json
-import os
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
+import ab  # noqa: E402  (puts the repository's root on sys.path)
 from diral_amd.qpolicy import QPolicy  # noqa: E402
 
 SHAPES = [("c2 f32", 4096, 64, 32, torch.float32), ("c2 bf16", 4096, 64, 32, torch.bfloat16), ("toy f32", 65536, 4, 3, torch.float32)]
 FLAT_COPY_TB_S = 6.29
 
 
-def run(name, B, N, A, dtype, rounds, warm, reps):
+def run(emit, name, B, N, A, dtype, rounds, warm, reps):
     dev = torch.device("cuda:0")
     q = torch.randn((B, N, A), dtype=torch.float32, device=dev).to(dtype)
     out = torch.empty((B, N), dtype=torch.int32, device=dev)
@@ -51,19 +47,7 @@ def run(name, B, N, A, dtype, rounds, warm, reps):
     forms = [dict(form=k, body=(lambda p=p: p.act_clocked(q, clk, out=out))) for k, p in pols.items()]
     forms += [dict(form="torch argmax", body=lambda: q.argmax(-1).to(torch.int32)),
               dict(form="torch eps_greedy", body=torch_eps), dict(form="torch softmax", body=torch_softmax)]
-    for f in forms:
-        f["us"] = []
-    for r in range(warm + rounds):
-        for f in forms:                                             # interleaved: every form in every round
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for _ in range(reps):
-                f["body"]()
-            e1.record()
-            torch.cuda.synchronize()
-            if r >= warm:
-                f["us"].append(e0.elapsed_time(e1) * 1e3 / reps)
+    ab.timed_rounds(forms, ab.own_body, rounds, warm, reps=reps)
     # the device's share of a call: the same `reps` calls captured into one graph, its replay timed (multinomial is left
     # out: it is not capturable on every torch build)
     side = torch.cuda.Stream()
@@ -77,34 +61,22 @@ def run(name, B, N, A, dtype, rounds, warm, reps):
             for _ in range(reps):
                 f["body"]()
         torch.cuda.current_stream().wait_stream(side)
-        graphs.append((f, g))
-        f["graph_us"] = []
-    for r in range(warm + rounds):
-        for f, g in graphs:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            g.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            if r >= warm:
-                f["graph_us"].append(e0.elapsed_time(e1) * 1e3 / reps)
-    gus = {f["form"]: round(sorted(f["graph_us"])[len(f["graph_us"]) // 2], 2) for f, _ in graphs}
+        graphs.append(dict(form=f["form"], body=g.replay))
+    ab.timed_rounds(graphs, ab.own_body, rounds, warm)
+    gus, grnd = ab.summary(graphs, reps)
     # what was timed is what the tests compare: the launch agrees with torch's argmax wherever the row has one maximum
     g = pols["greedy"].act(q).long()
     top2 = q.double().topk(min(2, A), -1).values
     unique = (top2[..., 0] > top2[..., -1]) if A > 1 else torch.ones((B, N), dtype=torch.bool, device=dev)
     agree = bool(torch.equal(g[unique], q.argmax(-1)[unique]))
-    us = {f["form"]: round(sorted(f["us"])[len(f["us"]) // 2], 2) for f in forms}
+    us, rnd = ab.summary(forms, reps)
     q_bytes = B * N * A * q.element_size()
     rec = dict(shape=name, B=B, N=N, A=A, q_dtype=str(dtype), rounds=rounds, reps=reps, us_per_call=us, us_per_call_in_graph=gus,
                greedy_agrees_with_torch=agree, q_bytes=q_bytes,
                q_tb_per_s_in_graph={k: round(q_bytes / (v * 1e-6) / 1e12, 3) for k, v in gus.items()}, flat_copy_tb_per_s=FLAT_COPY_TB_S,
-               us_rounds={f["form"]: [round(v, 2) for v in f["us"]] for f in forms},
-               graph_us_rounds={f["form"]: [round(v, 2) for v in f["graph_us"]] for f, _ in graphs})
-    print("%s B=%d N=%d A=%d, us per call: %s" % (name, B, N, A, "  ".join("%s %.1f" % kv for kv in us.items())), flush=True)
-    print("%s ... inside a graph:      %s" % (name, "  ".join("%s %.1f" % kv for kv in gus.items())), flush=True)
-    print(json.dumps(rec), flush=True)
+               us_rounds=rnd, graph_us_rounds=grnd)
+    emit("%s B=%d N=%d A=%d, us per call: %s\n%s ... inside a graph:      %s" % (
+        name, B, N, A, "  ".join("%s %.1f" % kv for kv in us.items()), name, "  ".join("%s %.1f" % kv for kv in gus.items())), rec)
 
 
 def main():
@@ -114,8 +86,9 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     args = ap.parse_args()
     print("device: %s" % torch.cuda.get_device_name(0), flush=True)
-    for shape in SHAPES:
-        run(*shape, rounds=args.rounds, warm=args.warm, reps=args.reps)
+    with ab.report() as emit:
+        for shape in SHAPES:
+            run(emit, *shape, rounds=args.rounds, warm=args.warm, reps=args.reps)
 
 
 if __name__ == "__main__":

@@ -11,14 +11,10 @@ add_action + the type-2 piggybacked histogram), float32 outputs.  my_step with a
   python profiles/subwave_bench.py [--rounds 7] [--warm 2] [--slots 50] [--batches 4096,65536,262144] [--out FILE]
 """
 import argparse
-import json
-import os
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-
+import ab  # noqa: E402  (puts the repository's root on sys.path)
 from diral_amd.config import (KERNEL_FAST64, KERNEL_GENERAL, KERNEL_SUBWAVE, STEP_MY_STEP, STEP_MY_STEP_CH,  # noqa: E402
                               bench_config)
 from diral_amd.vec_env import VecV2VEnv  # noqa: E402
@@ -44,28 +40,19 @@ def run(B, mode, slots, rounds, warm):
         env.reset_topology(seed=1234)
         forms.append(dict(form=form, env=env, t=0, ms=[]))
     acts = [forms[0]["env"].sample(4000 + k).clone() for k in range(slots)]
-    for r in range(warm + rounds):
-        for f in forms:                                             # interleaved: one round of `slots` slots per form
-            env = f["env"]
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for k in range(slots):
-                obs, rew, _ = env._step(MODES[mode], acts[k], f["t"])
-                f["t"] += 1
-            e1.record()
-            torch.cuda.synchronize()
-            assert (env.last_kernel() & 15) == FAMILY[f["form"]], (f["form"], env.last_kernel())
-            f["obs"], f["rew"] = obs.clone(), rew.clone()
-            if r >= warm:
-                f["ms"].append(e0.elapsed_time(e1))
+
+    def body(f):
+        for k in range(slots):
+            f["obs"], f["rew"], _ = f["env"]._step(MODES[mode], acts[k], f["t"])
+            f["t"] += 1
+    ab.timed_rounds(forms, body, rounds, warm)
+    for f in forms:
+        assert (f["env"].last_kernel() & 15) == FAMILY[f["form"]], (f["form"], f["env"].last_kernel())
+    us, rnd = ab.summary(forms, slots)
     base = forms[0]
     sa = base["env"].export_state()
-    us, rnd, steps, equal = {}, {}, {}, {}
+    steps, equal = {}, {}
     for f in forms:
-        ms = sorted(f["ms"])
-        us[f["form"]] = round(ms[len(ms) // 2] * 1e3 / slots, 2)
-        rnd[f["form"]] = [round(m * 1e3 / slots, 2) for m in f["ms"]]
         steps[f["form"]] = round(B * cfg.num_users / (us[f["form"]] * 1e-6))
         sb = f["env"].export_state()
         equal[f["form"]] = bool(all(torch.equal(sa[k], sb[k]) for k in sa) and torch.equal(base["obs"], f["obs"]) and
@@ -88,21 +75,14 @@ def main():
     ap.add_argument("--slots", type=int, default=50)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    lines = []
-
-    def show(r):
-        lines.append("%s B=%d: %s us/slot  |  %s agent-steps/s  |  SUBWAVE / AUTO = %.3f  equal %s" % (
-            r["config"], r["B"], "  ".join("%s %.2f" % kv for kv in r["us_per_slot"].items()),
-            "  ".join("%s %.3e" % kv for kv in r["agent_steps_per_s"].items()), r["subwave_vs_auto"], all(r["equal_to_auto"].values())))
-        lines.append(json.dumps(r))
-        print("\n".join(lines[-2:]), flush=True)
-    for b in args.batches.split(","):
-        show(run(int(b), "my_step", args.slots, args.rounds, args.warm))
-    show(run(args.ch_batch, "my_step_ch", args.slots, args.rounds, args.warm))
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    with ab.report(args.out) as emit:
+        def show(r):
+            emit("%s B=%d: %s us/slot  |  %s agent-steps/s  |  SUBWAVE / AUTO = %.3f  equal %s" % (
+                r["config"], r["B"], "  ".join("%s %.2f" % kv for kv in r["us_per_slot"].items()),
+                "  ".join("%s %.3e" % kv for kv in r["agent_steps_per_s"].items()), r["subwave_vs_auto"], all(r["equal_to_auto"].values())), r)
+        for b in args.batches.split(","):
+            show(run(int(b), "my_step", args.slots, args.rounds, args.warm))
+        show(run(args.ch_batch, "my_step_ch", args.slots, args.rounds, args.warm))
 
 
 if __name__ == "__main__":

@@ -19,23 +19,14 @@ K-slot launch itself - `rollout` of K = 25 `my_step` slots with states last, and
   python profiles/subwave_slots_bench.py --parent-lib /path/to/parent/libdiral_env.so [--rounds 7] [--warm 2] [--out FILE]
 """
 import argparse
-import ctypes
-import json
-import os
-import sys
 
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.dirname(HERE))
-sys.path.insert(0, HERE)
-
-import kslots_ia_bench as ia_bench  # noqa: E402
+import ab  # noqa: E402  (puts the repository's root on sys.path)
 from diral_amd import _lib  # noqa: E402
 from diral_amd.config import KERNEL_POLICY, KERNEL_SUBWAVE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config  # noqa: E402
 from diral_amd.vec_env import VecV2VEnv, driver_shape  # noqa: E402
 
-ia_bench.NEW_SYMBOLS = ()                                            # (the option adds no symbol: the parent has them all)
 MODES = {"my_step": STEP_MY_STEP, "my_step_ch": STEP_MY_STEP_CH}
 K = 25
 
@@ -45,7 +36,7 @@ def toy_config():
 
 
 def make_env(B, lib, slots):
-    with ia_bench.on_library(lib):
+    with _lib.use(lib or _lib.load()):
         env = VecV2VEnv(toy_config(), batch=B, device=torch.device("cuda:0"), out_dtype=torch.float32)
     if slots:
         env.use_subwave_path(slots=True)
@@ -55,31 +46,8 @@ def make_env(B, lib, slots):
     return env
 
 
-def timed(forms, rounds, warm):
-    for r in range(warm + rounds):
-        for f in forms:                                             # interleaved: one round of K slots per form
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            f["body"](f)
-            e1.record()
-            torch.cuda.synchronize()
-            if r >= warm:
-                f["ms"].append(e0.elapsed_time(e1))
-
-
-def medians(forms, slots=K):
-    us, rnd = {}, {}
-    for f in forms:
-        ms = sorted(f["ms"])
-        us[f["form"]] = round(ms[len(ms) // 2] * 1e3 / slots, 2)
-        rnd[f["form"]] = [round(m * 1e3 / slots, 2) for m in f["ms"]]
-    return us, rnd
-
-
-def same_env(a, b):
-    sa, sb = a.export_state(), b.export_state()
-    return bool(all(torch.equal(sa[k], sb[k]) for k in sa) and torch.equal(a.metrics(), b.metrics()))
+def own_body(f):
+    f["body"](f)
 
 
 def run_rollout(B, mode, states, parent, rounds, warm):
@@ -106,12 +74,12 @@ def run_rollout(B, mode, states, parent, rounds, warm):
     forms = [dict(form="loop (parent)", env=loop, t=0, ms=[], body=loop_body, sh=torch.empty((K, B, 4), **o), sr=torch.empty((K, B), **o),
                   co=torch.empty((K, B), **o), st=torch.empty((K, B, 4, loop.S), **o) if states == "all" else None),
              dict(form="launch", env=one, t=0, ms=[], body=launch_body)]
-    timed(forms, rounds, warm)
+    ab.timed_rounds(forms, own_body, rounds, warm)
     assert (loop.last_kernel() & 15) == KERNEL_SUBWAVE and not (loop.last_kernel() & KERNEL_POLICY)
     assert one.last_kernel() == (KERNEL_SUBWAVE | KERNEL_POLICY), one.last_kernel()
-    us, rnd = medians(forms)
+    us, rnd = ab.summary(forms, K)
     p, x = forms
-    equal = same_env(loop, one) and all(torch.equal(p[k], x[k]) for k in ("sh", "sr", "co"))
+    equal = ab.same_env(loop, one) and all(torch.equal(p[k], x[k]) for k in ("sh", "sr", "co"))
     if states == "all":
         equal = equal and torch.equal(p["st"], x["last"])
     elif states == "last":
@@ -148,10 +116,10 @@ def run_prefill(B, parent, rounds, warm):
 
     forms = [dict(form="loop (parent)", env=loop, seed=77001, ms=[], body=loop_body, st=torch.empty((K, B, 4, loop.S), **o)),
              dict(form="launch", env=one, seed=77001, ms=[], body=launch_body)]
-    timed(forms, rounds, warm)
+    ab.timed_rounds(forms, own_body, rounds, warm)
     assert one.last_kernel() == (KERNEL_SUBWAVE | KERNEL_POLICY), one.last_kernel()
-    us, rnd = medians(forms)
-    equal = same_env(loop, one) and torch.equal(forms[0]["st"], forms[1]["st"])
+    us, rnd = ab.summary(forms, K)
+    equal = ab.same_env(loop, one) and torch.equal(forms[0]["st"], forms[1]["st"])
     loop.check(); one.check()
     out = {"config": "4ue_3r_toy prefill my_step_design", "B": B, "slots_per_round": K, "rounds": rounds, "us_per_slot": us,
            "us_per_slot_rounds": rnd, "equal_to_parent_loop": bool(equal), "launch_vs_loop": round(us["launch"] / us["loop (parent)"], 4)}
@@ -171,10 +139,10 @@ def run_guard(B, parent, rounds, warm, slots=50):
             f["t"] += 1
 
     forms = [dict(form=name, env=env, t=0, ms=[], body=body) for name, env in envs]
-    timed(forms, rounds, warm)
-    us, rnd = medians(forms, slots)
+    ab.timed_rounds(forms, own_body, rounds, warm)
+    us, rnd = ab.summary(forms, slots)
     p, x = forms
-    equal = same_env(p["env"], x["env"]) and torch.equal(p["obs"], x["obs"]) and torch.equal(p["rew"], x["rew"])
+    equal = ab.same_env(p["env"], x["env"]) and torch.equal(p["obs"], x["obs"]) and torch.equal(p["rew"], x["rew"])
     out = {"config": "4ue_3r_toy my_step one slot per call (guard)", "B": B, "slots_per_round": slots, "rounds": rounds, "us_per_slot": us,
            "us_per_slot_rounds": rnd, "equal_to_parent": bool(equal),
            "slower_than_parent": round(us["one-slot step"] / us["one-slot step (parent)"] - 1.0, 4)}
@@ -205,13 +173,13 @@ def run_guard_slots(B, parent, rounds, warm, what):
             f["t"] += K
 
     forms = [dict(form=name, env=env, t=0 if what == "rollout" else 77001, ms=[], body=body) for name, env in envs]
-    timed(forms, rounds, warm)
+    ab.timed_rounds(forms, own_body, rounds, warm)
     for f in forms:
         assert f["env"].last_kernel() == (KERNEL_SUBWAVE | KERNEL_POLICY), f["env"].last_kernel()
         f["env"].check()
-    us, rnd = medians(forms)
+    us, rnd = ab.summary(forms, K)
     p, x = forms
-    equal = same_env(p["env"], x["env"]) and all(torch.equal(a, b) for a, b in zip(p["out"], x["out"]))
+    equal = ab.same_env(p["env"], x["env"]) and all(torch.equal(a, b) for a, b in zip(p["out"], x["out"]))
     name = "my_step states=last rollout" if what == "rollout" else "prefill my_step_design"
     out = {"config": "4ue_3r_toy %s, K slots per launch (guard)" % name, "B": B, "slots_per_round": K, "rounds": rounds,
            "us_per_slot": us, "us_per_slot_rounds": rnd, "equal_to_parent": bool(equal),
@@ -229,28 +197,19 @@ def main():
     ap.add_argument("--warm", type=int, default=2)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    parent = ia_bench.load_parent(os.path.abspath(args.parent_lib))
-    assert ctypes.cast(parent.diral_env_step, ctypes.c_void_p).value != ctypes.cast(_lib.load().diral_env_step, ctypes.c_void_p).value, \
-        "the parent's library must be a second library"
-    lines = []
-
-    def show(r, key):
-        lines.append("%s B=%d: %s us/slot  |  %s = %s  equal %s" % (
-            r["config"], r["B"], "  ".join("%s %.2f" % kv for kv in r["us_per_slot"].items()), key, r[key],
-            r.get("equal_to_parent_loop", r.get("equal_to_parent"))))
-        lines.append(json.dumps(r))
-        print("\n".join(lines[-2:]), flush=True)
-    for b in args.batches.split(","):
-        for mode, states in (("my_step", "last"), ("my_step", "all"), ("my_step", None), ("my_step_ch", "last")):
-            show(run_rollout(int(b), mode, states, parent, args.rounds, args.warm), "launch_vs_loop")
-        show(run_prefill(int(b), parent, args.rounds, args.warm), "launch_vs_loop")
-    show(run_guard(65536, parent, args.rounds, args.warm), "slower_than_parent")
-    for what in ("rollout", "prefill"):
-        show(run_guard_slots(65536, parent, args.rounds, args.warm, what), "slower_than_parent")
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as fh:
-            fh.write("\n".join(lines) + "\n")
+    parent, _ = ab.two_libraries(args.parent_lib)                       # (the option adds no symbol: the parent has them all)
+    with ab.report(args.out) as emit:
+        def show(r, key):
+            emit("%s B=%d: %s us/slot  |  %s = %s  equal %s" % (
+                r["config"], r["B"], "  ".join("%s %.2f" % kv for kv in r["us_per_slot"].items()), key, r[key],
+                r.get("equal_to_parent_loop", r.get("equal_to_parent"))), r)
+        for b in args.batches.split(","):
+            for mode, states in (("my_step", "last"), ("my_step", "all"), ("my_step", None), ("my_step_ch", "last")):
+                show(run_rollout(int(b), mode, states, parent, args.rounds, args.warm), "launch_vs_loop")
+            show(run_prefill(int(b), parent, args.rounds, args.warm), "launch_vs_loop")
+        show(run_guard(65536, parent, args.rounds, args.warm), "slower_than_parent")
+        for what in ("rollout", "prefill"):
+            show(run_guard_slots(65536, parent, args.rounds, args.warm, what), "slower_than_parent")
 
 
 if __name__ == "__main__":
