@@ -8,7 +8,7 @@ interface.  See DESIGN.md.
 from .config import (ConfigError, EnvConfig, StateConfig, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH,
                      bench_config, c2_config)
 
-__all__ = ["EnvConfig", "StateConfig", "ConfigError", "VecV2VEnv", "StreamedVecEnv", "TestEnv", "QPolicy", "ReplayMemory",
+__all__ = ["EnvConfig", "StateConfig", "ConfigError", "VecV2VEnv", "StreamedVecEnv", "TestEnv", "QPolicy", "ReplayMemory", "QLoss",
            "bench_config", "c2_config", "STEP_MY_STEP", "STEP_MY_STEP_CH", "STEP_DESIGN"]
 
 
@@ -27,6 +27,9 @@ def __getattr__(name):
     if name == "ReplayMemory":
         from .memory import ReplayMemory
         return ReplayMemory
+    if name == "QLoss":
+        from .qloss import QLoss
+        return QLoss
     if name == "TestEnv":
         from .compat import TestEnv
         return TestEnv

@@ -23,6 +23,7 @@
 #include "reset_envs_kernel.hpp"
 #include "select_kernel.hpp"
 #include "step_params.hpp"
+#include "td_kernel.hpp"
 
 using namespace diral;
 
@@ -1844,6 +1845,70 @@ int diral_memory_sample(const DiralMemory* m, const DiralMemorySample* s, void* 
   };
   if (f64) return hip_status(od == DIRAL_F64 ? launch(double{}, double{}) : launch(double{}, float{}));
   return hip_status(od == DIRAL_F32 ? launch(float{}, float{}) : od == DIRAL_F16 ? launch(float{}, _Float16{}) : launch(float{}, bf16_bits{}));
+}
+
+int diral_memory_history(const DiralMemory* m, int32_t step, int32_t out_dtype, void* out, int32_t* bad, void* stream) {
+  if (!memory_ok(m) || step < 1 || !out) return DIRAL_ERR_BAD_ARG;
+  if (!m->count_dev && (long long)step > std::min<long long>(m->count, m->capacity) + 1) return DIRAL_ERR_BAD_ARG;
+  const bool f64 = m->dtype == DIRAL_F64;
+  const int od = out_dtype;
+  if (f64 ? (od != DIRAL_F64 && od != DIRAL_F32) : (od != DIRAL_F32 && od != DIRAL_F16 && od != DIRAL_BF16)) return DIRAL_ERR_UNSUPPORTED;
+  const long long NS = (long long)m->num_users * m->state_space;
+  if (NS > 0x7fffffffLL || ((long long)m->batch + 8) * step > 0x7fffffffLL) return DIRAL_ERR_UNSUPPORTED;
+  DEVICE_ENTER(m->states);
+  MemHistoryParams p{};
+  p.states = m->states; p.C = m->capacity; p.B = m->batch; p.N = m->num_users; p.S = m->state_space;
+  p.count = (long long)m->count; p.count_dev = (const long long*)m->count_dev;
+  p.step = step; p.out = out; p.bad = bad;
+  const size_t er = f64 ? 8 : 4, eo = od == DIRAL_F64 ? 8 : od == DIRAL_F32 ? 4 : 2;
+  const int vec = mem_vec(NS, er, {m->states});
+  p.vst = vec > 1 && mem_vec(m->state_space, eo, {out}) >= vec;
+  p.ushift = NS / vec <= 256 ? 6 : 8;
+  // per XCD: the items of ceil(B / 8) envs, kMemBlock >> ushift of them to a workgroup (memory_kernel.hpp)
+  const size_t per_xcd = ((size_t)m->batch + 7) / 8 * (size_t)step, ipb = (size_t)(kMemBlock >> p.ushift);
+  const dim3 grid((uint32_t)(8 * ((per_xcd + ipb - 1) / ipb)));
+  const hipStream_t st = (hipStream_t)stream;
+  auto launch = [&](auto ring, auto o) {
+    return by_vec(vec, [&](auto v) {
+      return launch_k<memory_history_kernel<decltype(ring), decltype(o), decltype(v)::value>>(grid, dim3(kMemBlock), 0, st, p);
+    });
+  };
+  if (f64) return hip_status(od == DIRAL_F64 ? launch(double{}, double{}) : launch(double{}, float{}));
+  return hip_status(od == DIRAL_F32 ? launch(float{}, float{}) : od == DIRAL_F16 ? launch(float{}, _Float16{}) : launch(float{}, bf16_bits{}));
+}
+
+int diral_td_head(int32_t rows, int32_t num_actions, const void* q, const void* q_next_target, const void* q_next_eval,
+                  int32_t q_dtype, const int32_t* actions, const void* rewards, int32_t rewards_dtype, double gamma,
+                  int32_t hysteretic, float* targets_out, float* td_out, int32_t* next_action_out, void* grad_q_out,
+                  float* loss_out, int32_t* bad_rows, void* stream) {
+  if (!q_next_target || !actions || !rewards || rows < 1 || num_actions < 1) return DIRAL_ERR_BAD_ARG;
+  if (q_dtype < DIRAL_F32 || q_dtype > DIRAL_BF16 || (rewards_dtype != DIRAL_F32 && rewards_dtype != DIRAL_F64)) return DIRAL_ERR_BAD_ARG;
+  if (!std::isfinite(gamma)) return DIRAL_ERR_BAD_ARG;
+  if (!q && (td_out || grad_q_out || loss_out)) return DIRAL_ERR_BAD_ARG;
+  if (loss_out && !td_out) return DIRAL_ERR_BAD_ARG;
+  if (num_actions > kTdMaxA || rows > kTdMaxRows || q_dtype == DIRAL_F64) return DIRAL_ERR_UNSUPPORTED;
+  DEVICE_ENTER(q_next_target);
+  const int A = num_actions;
+  TdParams p{};
+  p.q = q; p.qn_target = q_next_target; p.qn_eval = q_next_eval; p.actions = actions; p.rewards = rewards;
+  p.rows = rows; p.A = A;
+  while ((1 << p.gshift) < A || p.gshift < 2) ++p.gshift;          // lanes per row (A <= 64), as diral_policy_select's
+  p.gamma = (float)gamma; p.rows_f = (float)rows; p.hysteretic = hysteretic != 0;
+  p.targets_out = targets_out; p.td_out = td_out; p.next_action_out = next_action_out; p.grad_q_out = grad_q_out;
+  p.bad_rows = bad_rows;
+  const hipStream_t st = (hipStream_t)stream;
+  auto launch = [&](auto qt, auto rt) {
+    using QT = decltype(qt);
+    using RT = decltype(rt);
+    if (A > 64) return launch_k<td_head_wide_kernel<QT, RT>>(dim3((uint32_t)rows), dim3(64), 0, st, p);
+    const size_t waves = ((size_t)rows + (64u >> p.gshift) - 1) >> (6 - p.gshift);
+    return launch_k<td_head_kernel<QT, RT>>(dim3(blocks(waves * 64, kTdBlock)), dim3(kTdBlock), 0, st, p);
+  };
+  const hipError_t head = by_dtype(rewards_dtype, [&](auto rt) {
+    return q_dtype == DIRAL_F32 ? launch(float{}, rt) : q_dtype == DIRAL_F16 ? launch(_Float16{}, rt) : launch(bf16_bits{}, rt);
+  });
+  if (head != hipSuccess || !loss_out) return hip_status(head);
+  return hip_status(launch_k<td_loss_kernel>(dim3(1), dim3(kTdBlock), 0, st, (const float*)td_out, (int)rows, loss_out));
 }
 
 int diral_env_check(DiralEnv* e, void* stream) {

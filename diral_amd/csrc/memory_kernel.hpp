@@ -1,6 +1,7 @@
-// memory_kernel.hpp - diral_memory_add / diral_memory_sample: the DRQN agent's replay memory (utils/memory.py:162-194,
-// a deque of (state, action, reward, next_state)) for B envs at once, and the regrouping of a sampled batch
-// (DRQN.get_states_user and the three like it, algorithms/drl_drqn.py:294-377) as ONE gather launch.
+// memory_kernel.hpp - diral_memory_add / diral_memory_sample / diral_memory_history: the DRQN agent's replay memory
+// (utils/memory.py:162-194, a deque of (state, action, reward, next_state)) for B envs at once, the regrouping of a sampled
+// batch (DRQN.get_states_user and the three like it, algorithms/drl_drqn.py:294-377) as ONE gather launch, and the acting
+// window of the newest states (memory_history_kernel below) as another.
 //
 // Storage: three rings of C + 1 rows owned by the caller - states [C + 1][B][N][S], actions and rewards [C + 1][B][N].
 // The driver always has state = next_state, so logical state j is stored once, in row j mod (C + 1); transition j keeps
@@ -173,6 +174,76 @@ __global__ __launch_bounds__(kMemBlock) void memory_sample_kernel(MemSampleParam
       if (p.rewards_out) static_cast<RT*>(p.rewards_out)[d] = ok ? r_src[n] : (RT)0;
     }
   }
+}
+
+// The sample kernel's state-block loop as a function (the sample kernel keeps its own text: the register counts of its
+// instantiations are on record).  The N * S values at `src` (one ring row of one env) -> N segments of S values, `ustride`
+// apart, in `so` and / or `no`, by the item's U threads (`t` this one's place among them).  !ok: zeros, and nothing is read.
+template <typename RT, typename OT, int VEC>
+__device__ __forceinline__ void mem_scatter_block(const RT* src, bool ok, OT* so, OT* no, size_t ustride, int N, int S, int t,
+                                                  int U, int vst) {
+  const uint32_t nv = (uint32_t)(N * S) / VEC;
+  for (uint32_t q = t; q < nv; q += U) {
+    MemVec<RT, VEC> in;
+    if (ok) in = *reinterpret_cast<const MemVec<RT, VEC>*>(src + (size_t)q * VEC);
+    MemVec<OT, VEC> o;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o.v[k] = ok ? mem_cvt<OT, RT>(in.v[k]) : mem_zero<OT>();
+    const uint32_t e = q * VEC;
+    if (VEC == 1 || vst) {
+      const uint32_t n = e / (uint32_t)S, c = e - n * (uint32_t)S;
+      const size_t d = (size_t)n * ustride + c;
+      if (so) *reinterpret_cast<MemVec<OT, VEC>*>(so + d) = o;
+      if (no) *reinterpret_cast<MemVec<OT, VEC>*>(no + d) = o;
+    } else {
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) {
+        const uint32_t n = (e + k) / (uint32_t)S, c = (e + k) - n * (uint32_t)S;
+        const size_t d = (size_t)n * ustride + c;
+        if (so) so[d] = o.v[k];
+        if (no) no[d] = o.v[k];
+      }
+    }
+  }
+}
+
+struct MemHistoryParams {
+  const void* states;            // the state ring
+  int C, B, N, S;
+  long long count;
+  const long long* count_dev;
+  int step;
+  void* out;                     // [B * N][step][S] of OT
+  int32_t* bad;                  // counter of the calls answered with zeros, or null
+  int ushift, vst;               // as MemSampleParams'
+};
+
+// diral_memory_history: the acting window - np.array(deque(maxlen=step)) of the newest states, every agent's rows
+// (state_vector[:, user], main_test.py:86, 125; drl_drqn.py:171-172).  The sample kernel's item with another destination:
+// an item is (env b, window row s), its source the block of logical state count - step + 1 + s, its destination N segments
+// of S values, step * S apart, from out[b * N][s] on - row b * N + n is env-major.  The step items of an env write into the
+// same N rows and go to one XCD like a window's (above), env b to XCD b mod 8.  step > len + 1 reaches behind the live
+// states [count - len, count]: the whole output is zeros then and the first item counts one in *bad.
+template <typename RT, typename OT, int VEC>
+__global__ __launch_bounds__(kMemBlock) void memory_history_kernel(MemHistoryParams p) {
+  const int U = 1 << p.ushift;
+  const int t = threadIdx.x & (U - 1);
+  const int N = p.N, S = p.S, step = p.step;
+  const long long slot = (long long)(blockIdx.x >> 3) * (kMemBlock >> p.ushift) + (threadIdx.x >> p.ushift);
+  const long long bq = slot / step;
+  const int sp = (int)(slot - bq * step);
+  const long long b = bq * 8 + (blockIdx.x & 7);
+  if (b >= (long long)p.B) return;                                  // (whole waves: an item is a wave or the workgroup)
+
+  long long count = p.count_dev ? *p.count_dev : p.count;
+  if (count < 0) count = 0;
+  const long long len = count < (long long)p.C ? count : (long long)p.C;
+  const bool ok = (long long)step <= len + 1;
+  if (!ok && b == 0 && sp == 0 && t == 0 && p.bad) atomicAdd(p.bad, 1);
+  const long long r = ok ? mem_mod(count - step + 1 + sp, (long long)p.C + 1) : 0;   // (nothing is read from the ring then)
+  const RT* src = static_cast<const RT*>(p.states) + ((size_t)r * p.B + (size_t)b) * N * S;
+  OT* dst = static_cast<OT*>(p.out) + ((size_t)b * N * step + sp) * S;
+  mem_scatter_block<RT, OT, VEC>(src, ok, dst, nullptr, (size_t)step * S, N, S, t, U, p.vst);
 }
 
 struct MemAddParams {

@@ -237,6 +237,31 @@ class ReplayMemory:
         check_tensor("clock", ct, torch.int64, (1,), self.device, MSG_OUT)
         return self._sample(batch_size, step_size, out_dtype, None, None, last_only, out, policy_seed(self.seed, 0), ct, offset)
 
+    def history(self, step_size: int, out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None
+                ) -> torch.Tensor:
+        """The acting window: ``np.array(history_input)`` of ``deque(maxlen=step_size)`` and ``state_vector[:, user]``
+        of every agent (main_test.py:86, 125; drl_drqn.py:171-172) as ONE launch of ``diral_memory_history`` - the last
+        `step_size` states, ENDING at the newest one, ``[B * N, step_size, S]`` with row ``b * N + n``: a network's
+        output on it viewed as ``[B, N, A]`` is what ``QPolicy.act`` takes.  ``step_size <= len + 1`` (right after
+        `begin`: 1, the begin state); with the count on the device a longer window is zeros and counts in `bad_samples`.
+        `out_dtype` as `sample`'s; `out`: a caller-owned output."""
+        step = int(step_size)
+        out_dtype = self.dtype if out_dtype is None else out_dtype
+        if out_dtype not in OUT_DTYPES:
+            raise ValueError("out_dtype must be a torch float dtype")
+        if step < 1:
+            raise ValueError("step_size must be >= 1")
+        shape = (self.B * self.N, step, self.S)
+        if out is None:
+            out = torch.empty(shape, dtype=out_dtype, device=self.device)
+        check_tensor("out", out, out_dtype, shape, self.device, MSG_OUT)
+        if self._state0 is not None:                      # a pending begin state: the window reads state row 0 (`commit`)
+            self.states[0].copy_(self._state0)
+        m = self._desc()
+        check_status(self.lib.diral_memory_history(ctypes.byref(m), step, OUT_DTYPES[out_dtype], _ptr(out),
+                                                   _ptr(self.bad_samples), self._stream()), "diral_memory_history")
+        return out
+
     # ---- Memory.save / Memory.load ----
     def state_dict(self) -> Dict[str, object]:
         count = self.count if self.count_dev is None else int(self.count_dev.item())

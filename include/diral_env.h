@@ -132,7 +132,7 @@ typedef enum DiralStepMode {
 
 /* element type of the floating-point OUTPUT buffers (state, reward, chobs).
  * The arithmetic is always float64, like the reference; F32 is a final cast. */
-typedef enum DiralDType { DIRAL_F32 = 0, DIRAL_F64 = 1, DIRAL_F16 = 2, DIRAL_BF16 = 3 } DiralDType;   /* the 16-bit kinds: DiralSelect::q_dtype only */
+typedef enum DiralDType { DIRAL_F32 = 0, DIRAL_F64 = 1, DIRAL_F16 = 2, DIRAL_BF16 = 3 } DiralDType;   /* the 16-bit kinds: Q-values (DiralSelect::q_dtype, diral_td_head) and the memory's state outputs only */
 
 /* limits of this build (the reference has none: TestEnv takes any N, A and State.num_bins, test_env.py:12-13, 40).
  * The specialised kernels (csrc/step_fast64.hpp, step_wide.hpp: every number bench.py reports) serve num_users <= 256
@@ -867,6 +867,51 @@ typedef struct DiralMemorySample {
   int32_t* bad_samples;
 } DiralMemorySample;
 int diral_memory_sample(const DiralMemory* m, const DiralMemorySample* s, void* stream);
+
+/* diral_memory_history (additive within ABI 8): the acting window, ONE launch - history_input = deque(maxlen=step_size),
+ * np.array(history_input) and state_vector[:, user] (main_test.py:86, 114, 125, 219; drl_drqn.py:171-172) of every agent:
+ *   out [batch * num_users][step][state_space]  out_dtype, row b * num_users + n - ENV-major, so that a network's output
+ *   on it viewed as [batch][num_users][A] is what diral_policy_select takes.
+ * Step s holds logical state count - step + 1 + s (ring row mod capacity + 1): the window ENDS at the newest state, which
+ * no window of diral_memory_sample contains.  The live states are [count - len, count], so step <= len + 1; with a host
+ * count anything else is DIRAL_ERR_BAD_ARG, with count_dev the kernel writes zeros to all of `out` and adds one to *bad
+ * (may be NULL).  State row `count` must be valid: after a begin the caller has written state0 there.  The dtype pairs are
+ * diral_memory_sample's (any other: DIRAL_ERR_UNSUPPORTED).  Enqueue-only.
+ * DIRAL_ERR_BAD_ARG, before any device is touched: what DiralMemory is refused for (above), step < 1, a NULL out. */
+int diral_memory_history(const DiralMemory* m, int32_t step, int32_t out_dtype, void* out, int32_t* bad, void* stream);
+
+/* diral_td_head (additive within ABI 8): the TD targets of DRQN._calc_target (drl_drqn.py:267-292), the loss head
+ * (:76-80) and its gradient dL/dQ for rows = num_users * batch rows of num_actions Q-values.  Handle-free, flat arguments,
+ * ONE launch and a second, single-workgroup one for the loss (skipped when loss_out is NULL).
+ *   q             [rows][num_actions]  the eval net on `states`; NULL: targets only (_calc_target by itself; actions must
+ *                                      still be given and is not read)
+ *   q_next_target [rows][num_actions]  the target net on `next_states`
+ *   q_next_eval   [rows][num_actions]  the eval net on `next_states`, or NULL for use_double = False
+ *   q_dtype       of all three: DIRAL_F32 / F16 / BF16, converted exactly to float32
+ *   actions [rows] int32, rewards [rows] DIRAL_F32 / F64 (rewards_dtype): diral_memory_sample's last_only outputs
+ * Per row, float32 arithmetic unless said otherwise:
+ *   1. j = np.argmax(q_next_eval row, or q_next_target row when that is NULL): the first index between equals (-0.0 ==
+ *      +0.0) and between NaNs, a NaN above any number
+ *   2. nv = q_next_target[row][j] - np.max in the plain case (a NaN row gives NaN; the sign of a zero maximum is the first
+ *      zero's, numerically equal to np.max)
+ *   3. target = (float)((double)r + (double)((float)gamma * nv)), never fused
+ *   4. Q = q[row][a], h = Q - target.  a outside [0, num_actions): Q = 0, a zero gradient row (tf.one_hot's), one more in
+ *      *bad_rows, nothing read out of bounds.  Q is gathered where the reference has reduce_sum(q * one_hot): a non-finite
+ *      value in a column that was not chosen does not poison the row, and a chosen -0.0 stays -0.0
+ *   5. hl = (hysteretic != 0 && h < 0) ? h / 10.0f : h
+ *   6. g = (2.0f * hl) / (float)rows, and g / 10.0f on the rows of the hysteretic branch
+ * Outputs, each may be NULL: targets_out [rows] float32; td_out [rows] float32 (hl); next_action_out [rows] int32 (j);
+ * grad_q_out [rows][num_actions] q_dtype - g rounded to nearest even once in column a, zeros elsewhere, all of it written
+ * by the launch; loss_out, one float32: mean(hl^2) = (float)(sum / rows), the sum in double over td_out - thread t of 256
+ * adds (double)hl * (double)hl of the rows t, t + 256, ... in turn, the 256 partial sums are added in index order -, so the
+ * same input gives the same bits; bad_rows, an int32 counter that is added to.  grad_q_out does not depend on the loss.
+ * DIRAL_ERR_BAD_ARG, before any device is touched: a NULL q_next_target, actions or rewards, rows < 1, num_actions < 1,
+ *   an unknown dtype, a non-finite gamma, q == NULL with td_out, grad_q_out or loss_out, loss_out without td_out;
+ * DIRAL_ERR_UNSUPPORTED: num_actions > 4096, rows > 2^24 ((float)rows must be exact), q_dtype == DIRAL_F64. */
+int diral_td_head(int32_t rows, int32_t num_actions, const void* q, const void* q_next_target, const void* q_next_eval,
+                  int32_t q_dtype, const int32_t* actions, const void* rewards, int32_t rewards_dtype, double gamma,
+                  int32_t hysteretic, float* targets_out, float* td_out, int32_t* next_action_out, void* grad_q_out,
+                  float* loss_out, int32_t* bad_rows, void* stream);
 
 /* The K-slot rollout and prefill write the ring rows themselves (additive within ABI 8; step_fast64_slots_kernel at
  * 8 <= N <= 64 and step_subwave_slots_kernel at N <= 8).  diral_env_rollout_memory is diral_env_rollout_replay with one

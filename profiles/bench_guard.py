@@ -3,7 +3,9 @@ in one session on one box, every measurement a fresh process (parent, branch, pa
 the criterion of profiles/slot_request/bench_guard.txt (ab.verdict).
 
   python profiles/bench_guard.py --parent-lib P [--branch-lib Q] [--rounds 6] [--lines c2,rollout_sps_fused,...]
-      [--workload-steps 200 --warmup 50] [--dump-outputs] [--out FILE]
+      [--workload-steps 200 --warmup 50] [--dump-outputs] [--lacking SYMBOL,...] [--out FILE]
+
+`--lacking`: the entry points the branch adds - the parent's library predates them and is bound without (`_lib.bind`).
 
 One child is alive at a time, under the time limit of its line; a child that fails or runs into its limit ends the run: what
 was collected is printed and the exit status is 1.  Nothing is tried twice.
@@ -31,10 +33,13 @@ LINES = {
 DUMP_LIMIT = 120
 
 
-def child(line, steps, warmup):
+def child(line, steps, warmup, lacking=()):
     """One measurement in this process, under the library DIRAL_LIB names: one JSON object on stdout."""
     import torch
 
+    if lacking:
+        with ab._lib.use(ab._lib.bind(ab._lib.LIB_PATH, lacking)):
+            return child(line, steps, warmup)
     import bench
     dev = torch.device("cuda:0")
     if line == "c2":
@@ -55,10 +60,10 @@ def child(line, steps, warmup):
     print(json.dumps(out), flush=True)
 
 
-def measure(lib, line, limit, args):
+def measure(lib, line, limit, args, lacking=None):
     """The child's JSON object, or None where it failed or ran into its limit."""
     cmd = [sys.executable, os.path.abspath(__file__), "--child", line, "--workload-steps", str(args.workload_steps),
-           "--warmup", str(args.warmup)]
+           "--warmup", str(args.warmup)] + (["--lacking", lacking] if lacking else [])
     try:
         done = subprocess.run(cmd, env=dict(os.environ, DIRAL_LIB=lib), stdout=subprocess.PIPE, timeout=limit)
     except subprocess.TimeoutExpired:
@@ -74,14 +79,14 @@ def collect(libs, lines, args, got):
     for r in range(args.rounds):
         for line in lines:
             for side, lib in libs:
-                res = measure(lib, line, LINES[line][0], args)
+                res = measure(lib, line, LINES[line][0], args, args.lacking if side == "parent" else None)
                 if res is None:
                     return False
                 for key, us in res.items():
                     got.setdefault((line, key), {"parent": [], "branch": []})[side].append(us)
     if args.dump_outputs:
         for side, lib in libs:
-            got[side] = measure(lib, "dump", DUMP_LIMIT, args)
+            got[side] = measure(lib, "dump", DUMP_LIMIT, args, args.lacking if side == "parent" else None)
             if got[side] is None:
                 return False
     return True
@@ -115,11 +120,12 @@ def main():
     ap.add_argument("--workload-steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--dump-outputs", action="store_true")
+    ap.add_argument("--lacking", default=None, help="comma-separated entry points the parent's library predates")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None, help="(what a child process of this script measures)")
     args = ap.parse_args()
     if args.child:
-        return child(args.child, args.workload_steps, args.warmup)
+        return child(args.child, args.workload_steps, args.warmup, tuple(args.lacking.split(",")) if args.lacking else ())
     if not args.parent_lib:
         ap.error("--parent-lib is required")
     libs = (("parent", os.path.abspath(args.parent_lib)), ("branch", os.path.abspath(args.branch_lib)))
