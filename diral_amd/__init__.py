@@ -8,7 +8,7 @@ interface.  See DESIGN.md.
 from .config import (ConfigError, EnvConfig, StateConfig, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH,
                      bench_config, c2_config)
 
-__all__ = ["EnvConfig", "StateConfig", "ConfigError", "VecV2VEnv", "StreamedVecEnv", "TestEnv", "QPolicy", "ReplayMemory", "QLoss",
+__all__ = ["EnvConfig", "StateConfig", "ConfigError", "VecV2VEnv", "StreamedVecEnv", "TestEnv", "QPolicy", "ReplayMemory", "QLoss", "QNet",
            "bench_config", "c2_config", "STEP_MY_STEP", "STEP_MY_STEP_CH", "STEP_DESIGN"]
 
 
@@ -30,6 +30,9 @@ def __getattr__(name):
     if name == "QLoss":
         from .qloss import QLoss
         return QLoss
+    if name == "QNet":
+        from .qnet import QNet
+        return QNet
     if name == "TestEnv":
         from .compat import TestEnv
         return TestEnv

@@ -71,6 +71,7 @@ SIGNATURES = {
     "diral_memory_sample": (I, [P, P, P]),
     "diral_memory_history": (I, [P, I, I, P, P, P]),
     "diral_td_head": (I, [I, I, P, P, P, I, P, P, I, D, I, P, P, P, P, P, P, P]),
+    "diral_qnet_forward": (I, [I, I, P, P, I, I64, P, I64, I, D, P, P]),
     "diral_env_rollout_memory": (I, [P, I, P, I, I64, P, I, P, P, I, P, P, P, P, P]),
     "diral_env_prefill_memory": (I, [P, I, P, I, U64, P, I, P, P, P, D, D, P, P]),
     "diral_sps_init": (I, [I, I, P, P, U64, P]),

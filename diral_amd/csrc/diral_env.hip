@@ -20,6 +20,7 @@
 #include "observe_kernel.hpp"
 #include "piggyback_kernel.hpp"
 #include "posdist_kernel.hpp"
+#include "qnet_params.hpp"
 #include "reset_envs_kernel.hpp"
 #include "select_kernel.hpp"
 #include "step_params.hpp"
@@ -1909,6 +1910,29 @@ int diral_td_head(int32_t rows, int32_t num_actions, const void* q, const void* 
   });
   if (head != hipSuccess || !loss_out) return hip_status(head);
   return hip_status(launch_k<td_loss_kernel>(dim3(1), dim3(kTdBlock), 0, st, (const float*)td_out, (int)rows, loss_out));
+}
+
+int diral_qnet_forward(int32_t rows, int32_t num_hidden, const int32_t* widths, const void* x, int32_t x_dtype,
+                       int64_t x_row_stride, const float* params, int64_t params_len, int32_t norm, double ln_eps,
+                       float* q_out, void* stream) {
+  if (!widths || !x || !params || !q_out || rows < 1 || num_hidden < 0) return DIRAL_ERR_BAD_ARG;
+  if (x_dtype < DIRAL_F32 || x_dtype > DIRAL_BF16 || !std::isfinite(ln_eps) || ln_eps < 0.0) return DIRAL_ERR_BAD_ARG;
+  if (num_hidden > kQnetMaxHidden || x_dtype == DIRAL_F64) return DIRAL_ERR_UNSUPPORTED;
+  for (int i = 0; i < num_hidden + 2; ++i)
+    if (widths[i] < 1) return DIRAL_ERR_BAD_ARG;
+  for (int i = 0; i < num_hidden + 2; ++i)
+    if (widths[i] > (i ? kQnetMaxWidth : kQnetMaxIn)) return DIRAL_ERR_UNSUPPORTED;
+  if (x_row_stride < widths[0] || params_len != qnet_params_len(widths, num_hidden)) return DIRAL_ERR_BAD_ARG;
+  DEVICE_ENTER(x);
+  QnetParams p{};
+  p.x = x; p.x_stride = x_row_stride; p.x_dtype = x_dtype; p.params = params; p.q = q_out;
+  p.rows = rows; p.L = num_hidden; p.norm = norm != 0; p.eps = (float)ln_eps;
+  int off = 0;
+  for (int l = 0; l <= num_hidden; ++l) {
+    p.width[l] = widths[l]; p.width[l + 1] = widths[l + 1]; p.off[l] = off;
+    off += widths[l] * widths[l + 1] + (l < num_hidden ? 3 : 1) * widths[l + 1];
+  }
+  return hip_status(launch_qnet(p, (hipStream_t)stream));
 }
 
 int diral_env_check(DiralEnv* e, void* stream) {

@@ -913,6 +913,41 @@ int diral_td_head(int32_t rows, int32_t num_actions, const void* q, const void* 
                   int32_t hysteretic, float* targets_out, float* td_out, int32_t* next_action_out, void* grad_q_out,
                   float* loss_out, int32_t* bad_rows, void* stream);
 
+/* diral_qnet_forward (additive within ABI 8): the dense chain of DRQN._create_network (drl_drqn.py:109-155) as ONE
+ * launch - [matmul + bias -> relu -> layer_norm] x num_hidden, then matmul + bias - for q [rows][A] from x [rows][D].  With
+ * use_lstm_input false it is the whole Q-network (the DQN branch, state_vector[-1:, user]), with it true everything behind
+ * lstm_out[:, -1, :].  Handle-free, flat arguments, no gradient.
+ *   widths   HOST array [D, h_1 .. h_num_hidden, A]: 0 <= num_hidden <= 3, 1 <= D <= 1024, 1 <= h_i <= 256, 1 <= A <= 256
+ *   x        rows of D elements of x_dtype (DIRAL_F32 / F16 / BF16, converted exactly to float32), unit stride along D,
+ *            x_row_stride >= D ELEMENTS from row to row, 64-bit addressing: window[:, -1] of a [rows][step][S] window
+ *            goes in as x = &window[0][step - 1][0], x_row_stride = step * S
+ *   params   ONE device blob of float32, params_len values: per hidden layer W [in][out] row-major (the reference's
+ *            orientation), b [out], gamma [out], beta [out] - gamma and beta are there with norm == 0 too -, then the
+ *            output layer's W [h_L][A], b [A].  Read at every launch (and at every replay of a captured one).
+ *   q_out    [rows][A] float32, contiguous
+ * Per row, float32 arithmetic, never fused:
+ *   1. z[j] = (sum over k = 0 .. in - 1, in that order, of x[k] * W[k][j]) + b[j]: the sum starts at zero and is the
+ *      f32-input MFMA's, acc = fmaf(x[k], W[k][j], acc) with one rounding per term; the bias is added to the finished sum
+ *   2. r[j] = z[j] > 0 ? z[j] : 0; a NaN stays a NaN
+ *   3. mean = (sum r) / h, var = (sum (r - mean)^2) / h over the h columns of the layer: two passes, biased, tf.nn.moments'.
+ *      Each sum is four partial sums - partial s adds the columns s, s + 4, s + 8, .. in turn - added as ((p0 + p1) + p2) + p3.
+ *      The mean is summed twice, m0 = (sum r) / h and mean = m0 + (sum (r - m0)) / h, which takes the first sum's rounding
+ *      out: a row of equal values c has mean == c, var == 0 and y == beta exactly (with ln_eps = 1e-12 an ulp in the mean
+ *      would come out as 0.06 in every column)
+ *   4. y[j] = (r[j] - mean) * (1.0f / sqrtf(var + (float)ln_eps)) * gamma[j] + beta[j], left to right
+ *   5. the output layer is step 1 alone
+ * norm == 0 leaves out 3 and 4 (relu only).  ln_eps is the caller's; tf.contrib.layers.layer_norm of TF 1.14 uses
+ * variance_epsilon = 1e-12 as far as its source is remembered - TensorFlow was not at hand to read it off.
+ * The order of every sum is fixed, and a row's Q-values depend on that row and the blob only: not on `rows`, not on the
+ * row's place in the call, not on what other rows hold.  Nothing past row `rows` is read or written.  Enqueue-only on
+ * `stream`, one kernel node, no allocation, no synchronisation.
+ * DIRAL_ERR_BAD_ARG, before any device is touched: a NULL widths, x, params or q_out, rows < 1, num_hidden < 0, a width
+ *   < 1, an unknown x_dtype, x_row_stride < D, params_len other than what widths implies, ln_eps negative or not finite;
+ * DIRAL_ERR_UNSUPPORTED, likewise: num_hidden > 3, D > 1024, h_i > 256, A > 256, x_dtype == DIRAL_F64. */
+int diral_qnet_forward(int32_t rows, int32_t num_hidden, const int32_t* widths, const void* x, int32_t x_dtype,
+                       int64_t x_row_stride, const float* params, int64_t params_len, int32_t norm, double ln_eps,
+                       float* q_out, void* stream);
+
 /* The K-slot rollout and prefill write the ring rows themselves (additive within ABI 8; step_fast64_slots_kernel at
  * 8 <= N <= 64 and step_subwave_slots_kernel at N <= 8).  diral_env_rollout_memory is diral_env_rollout_replay with one
  * more argument, the caller's DiralMemory; diral_env_prefill_memory is diral_env_prefill_mode with the same.  A ring row is
