@@ -8,7 +8,7 @@ interface.  See DESIGN.md.
 from .config import (ConfigError, EnvConfig, StateConfig, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH,
                      bench_config, c2_config)
 
-__all__ = ["EnvConfig", "StateConfig", "ConfigError", "VecV2VEnv", "StreamedVecEnv", "TestEnv", "QPolicy", "ReplayMemory", "QLoss", "QNet",
+__all__ = ["EnvConfig", "StateConfig", "ConfigError", "VecV2VEnv", "StreamedVecEnv", "TestEnv", "QPolicy", "ReplayMemory", "QLoss", "QNet", "LSTM", "DRQNet",
            "bench_config", "c2_config", "STEP_MY_STEP", "STEP_MY_STEP_CH", "STEP_DESIGN"]
 
 
@@ -33,6 +33,9 @@ def __getattr__(name):
     if name == "QNet":
         from .qnet import QNet
         return QNet
+    if name in ("LSTM", "DRQNet"):
+        from . import lstm
+        return getattr(lstm, name)
     if name == "TestEnv":
         from .compat import TestEnv
         return TestEnv

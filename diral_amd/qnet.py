@@ -12,7 +12,7 @@ arithmetic is pinned rule by rule) and has two ways through it:
   torch ops - the gradient path, ``net(states)``.  An optimiser step through it updates the blob in place, and the next
   `forward` launch reads the new weights: no copy in either direction.
 
-No LSTM cell, no backward kernel, no optimiser.
+No launch of the LSTM cell (its parameters and gradient path are diral_amd/lstm.py), no backward kernel, no optimiser.
 """
 from __future__ import annotations
 
