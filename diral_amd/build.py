@@ -13,8 +13,9 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdiral_env.so")
-# one translation unit per kernel family: hipcc compiles them in parallel
-SOURCES = ["diral_env.hip", "k_fast64.hip", "k_wide2.hip", "k_wide4.hip", "k_wide_slots.hip", "k_general.hip", "k_observe.hip",
+# the two host units (the env handle; the handle-free agent entry points), then one translation unit per kernel family:
+# hipcc compiles them in parallel
+SOURCES = ["diral_env.hip", "diral_agent.hip", "k_fast64.hip", "k_wide2.hip", "k_wide4.hip", "k_wide_slots.hip", "k_general.hip", "k_observe.hip",
            "k_large.hip", "k_subwave.hip", "k_subwave_slots.hip", "k_qnet.hip"]
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith((".hpp", ".inc")))
 

@@ -1,4 +1,5 @@
-// diral_env.hip - C-ABI implementation of include/diral_env.h for gfx950.
+// diral_env.hip - C-ABI implementation of include/diral_env.h for gfx950: the env handle and every diral_env_* call.
+// (The entry points that take no handle - diral_sps_*, diral_policy_select, diral_memory_*, ... - are diral_agent.hip's.)
 // Host side: config validation, HBM allocation, kernel launches.  No torch
 // types anywhere; every data pointer in the ABI is a device pointer.
 #include <hip/hip_runtime.h>
@@ -12,19 +13,17 @@
 #include <utility>
 #include <vector>
 
+#include "agent_host.hpp"
 #include "aux_kernels.hpp"
 #include "common.hpp"
 #include "copy_envs_kernel.hpp"
+#include "host_util.hpp"
 #include "launch.hpp"
-#include "memory_kernel.hpp"
 #include "observe_kernel.hpp"
 #include "piggyback_kernel.hpp"
 #include "posdist_kernel.hpp"
-#include "qnet_params.hpp"
 #include "reset_envs_kernel.hpp"
-#include "select_kernel.hpp"
 #include "step_params.hpp"
-#include "td_kernel.hpp"
 
 using namespace diral;
 
@@ -122,7 +121,6 @@ int note_hip(DiralEnv* e, hipError_t st, const char* what) {
   if (e) e->last_hip_error = std::string(what) + ": " + hipGetErrorString(st);
   return DIRAL_ERR_HIP;
 }
-int hip_status(hipError_t st) { return st == hipSuccess ? DIRAL_OK : DIRAL_ERR_HIP; }   // the handle-less entry points
 
 #define HIP_TRY(env, call)                                   \
   do {                                                       \
@@ -218,65 +216,6 @@ bool use_packed_table(const DiralEnv* e) {
   if (e->hooks.table_form != 0) return e->hooks.table_form > 0;
   const double neigh = e->N * 2.0 * e->cfg.communication_range / e->cfg.highway_length;
   return neigh >= (e->vpl == 2 ? kPackedMinNeighbours2 : kPackedMinNeighbours);
-}
-
-// The handle-less entry points (diral_sps_*, diral_driver_shape) take device pointers only: they run on the
-// device that owns `p` (their first mandatory buffer), whatever device is current in the calling thread.
-int device_of_ptr(const void* p) {
-  hipPointerAttribute_t a;
-  if (p && hipPointerGetAttributes(&a, p) == hipSuccess) return a.device;
-  (void)hipGetLastError();
-  return -1;
-}
-
-// Every entry point that touches the device runs with the handle's device current - or the device that owns a buffer -
-// and restores the caller's (torch's) current device afterwards.
-struct DeviceGuard {
-  int prev = -1, dev;
-  bool ok = true;
-  explicit DeviceGuard(int d) : dev(d) {
-    if (dev < 0) return;                                        // not a device allocation HIP knows: current device
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
-  }
-  explicit DeviceGuard(const void* p) : DeviceGuard(device_of_ptr(p)) {}
-  ~DeviceGuard() { if (dev >= 0 && prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
-#define DEVICE_ENTER(owner) \
-  DeviceGuard guard(owner); \
-  if (!guard.ok) return DIRAL_ERR_NO_DEVICE
-
-int blocks(size_t total, int threads) { return (int)((total + threads - 1) / threads); }
-
-// a launch and its status; launch_1d: one thread per item, in blocks of 256
-template <auto Kernel, typename... Args>
-hipError_t launch_k(dim3 grid, dim3 block, uint32_t lds, hipStream_t s, Args... args) {
-  hipLaunchKernelGGL(Kernel, grid, block, lds, s, args...);
-  return hipGetLastError();
-}
-template <auto Kernel, typename... Args>
-hipError_t launch_1d(size_t total, hipStream_t s, Args... args) {
-  return launch_k<Kernel>(dim3(blocks(total, 256)), dim3(256), 0, s, args...);
-}
-// run-time DIRAL_F32 / DIRAL_F64 -> the element type, handed to `f` as a value of it
-template <typename F>
-hipError_t by_dtype(int dtype, F&& f) { return dtype == DIRAL_F64 ? f(double{}) : f(float{}); }
-// VEC of the memory kernels: the widest of 4 / 2 / 1 elements per lane that `values` per block and the addresses allow
-int mem_vec(long long values, size_t elem, std::initializer_list<const void*> ptrs) {
-  for (int v = 4; v > 1; v >>= 1) {
-    bool ok = values % v == 0;
-    for (const void* q : ptrs) ok = ok && (q == nullptr || (uintptr_t)q % (elem * v) == 0);
-    if (ok) return v;
-  }
-  return 1;
-}
-template <typename F>
-hipError_t by_vec(int vec, F&& f) {
-  return vec == 4 ? f(std::integral_constant<int, 4>{}) : vec == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 1>{});
-}
-bool memory_ok(const DiralMemory* m) {
-  return m && m->struct_bytes == sizeof(DiralMemory) && m->states && m->actions && m->rewards && m->capacity >= 1 && m->batch >= 1 &&
-         m->num_users >= 1 && m->state_space >= 1 && (m->dtype == DIRAL_F32 || m->dtype == DIRAL_F64) && (m->count_dev || m->count >= 0);
 }
 
 // State flags that only add OUTPUT columns to the state vector (test_env.py:527-583): served
@@ -784,16 +723,6 @@ int refresh_flat_y(DiralEnv* e, hipStream_t s) {
   return DIRAL_OK;
 }
 
-// sps_step_wave_kernel, one wave lane per 1 / 2 / 4 resources (num_channels <= kSpsWaveMaxA).  `src` holds T: the float64
-// selection window, or (CHOBS) the env's channel observation in its own dtype; `rest`: the kernel's other arguments
-template <typename T, bool CHOBS, typename... Rest>
-hipError_t launch_sps_wave(int agents, int num_channels, const void* src, hipStream_t s, Rest... rest) {
-  const T* in = static_cast<const T*>(src);
-  if (num_channels <= 64) return launch_1d<sps_step_wave_kernel<1, T, CHOBS>>((size_t)agents, s, agents, num_channels, in, rest...);
-  if (num_channels <= 128) return launch_1d<sps_step_wave_kernel<2, T, CHOBS>>((size_t)agents, s, agents, num_channels, in, rest...);
-  return launch_1d<sps_step_wave_kernel<4, T, CHOBS>>((size_t)agents, s, agents, num_channels, in, rest...);
-}
-
 // The argument checks every step entry point shares: the step mode (`not_taken`: the one DIRAL_STEP_* the entry does not
 // take, -1: it takes all three), the out dtype, my_step_ch's reward_design - rewards only for 2, 3, 4 (test_env.py:413-429)
 int call_check(const DiralEnv* e, int mode, int not_taken, int out_dtype) {
@@ -1165,12 +1094,6 @@ int diral_env_step(DiralEnv* e, int mode, const int32_t* actions, int64_t t, voi
   return DIRAL_OK;
 }
 
-static int sps_step_chobs_impl(int agents, int num_channels, const void* chobs, int chobs_dtype, const int32_t* actions,
-                               int32_t* prev_action, int32_t* counter, double rssi_threshold, double inc_db,
-                               double keep_prob, const int32_t* draw_counter, const double* draw_keep,
-                               const int32_t* draw_choice, uint64_t seed, const long long* clock, int32_t* actions_out,
-                               void* stream);
-
 // The information-age block of a K-slot my_step_ch call (DiralSlotInfoAge): its own argument checks ...
 static int ia_block_check(const DiralSlotInfoAge* ia, const void* shaped_out) {
   if (ia->struct_bytes != sizeof(DiralSlotInfoAge) || (ia->flags & ~1) != 0) return DIRAL_ERR_BAD_ARG;
@@ -1247,9 +1170,9 @@ static int step_policy_impl(DiralEnv* e, int mode, const int32_t* actions, int64
                                       pol->shaped_out, pol->sum_r_out, pol->collision_out, nullptr, nullptr, stream);
     if (st != DIRAL_OK) return st;
   }
-  return sps_step_chobs_impl(e->B * e->N, e->A, chobs_out, out_dtype, actions, pol->sps_prev_action, pol->sps_counter,
-                             pol->rssi_threshold, pol->inc_db, pol->keep_prob, pol->draw_counter, pol->draw_keep,
-                             pol->draw_choice, pol->seed, (const long long*)pol->seed_clock, pol->actions_out, stream);
+  return sps_step_chobs_with_clock(e->B * e->N, e->A, chobs_out, out_dtype, actions, pol->sps_prev_action, pol->sps_counter,
+                                   pol->rssi_threshold, pol->inc_db, pol->keep_prob, pol->draw_counter, pol->draw_keep,
+                                   pol->draw_choice, pol->seed, (const long long*)pol->seed_clock, pol->actions_out, stream);
 }
 
 int diral_env_step_policy(DiralEnv* e, int mode, const int32_t* actions, int64_t t, void* state_out, void* rew_out,
@@ -1609,100 +1532,6 @@ int diral_env_debug_timing(DiralEnv* e, unsigned long long* host_out, int waves)
 }
 #endif
 
-int diral_sps_step(int agents, int num_channels, const double* selection_window, int32_t* prev_action,
-                   int32_t* counter, double rssi_threshold, double inc_db, double keep_prob,
-                   const int32_t* draw_counter, const double* draw_keep, const int32_t* draw_choice, uint64_t seed,
-                   int32_t* actions_out, void* stream) {
-  if (agents < 1 || num_channels < 1 || !selection_window || !prev_action || !counter || !actions_out)
-    return DIRAL_ERR_BAD_ARG;
-  DEVICE_ENTER(prev_action);
-  const hipStream_t s = (hipStream_t)stream;
-  if (num_channels <= kSpsWaveMaxA)
-    return hip_status(launch_sps_wave<double, false>(agents, num_channels, selection_window, s, (const int32_t*)nullptr, prev_action,
-                                                     counter, rssi_threshold, inc_db, keep_prob, draw_counter, draw_keep,
-                                                     draw_choice, seed, (const long long*)nullptr, actions_out));
-  // one thread per agent
-  return hip_status(launch_k<sps_step_kernel>(dim3(blocks((size_t)agents, 128)), dim3(128), 0, s, agents, num_channels,
-                                              selection_window, prev_action, counter, rssi_threshold, inc_db, keep_prob,
-                                              draw_counter, draw_keep, draw_choice, seed, actions_out));
-}
-
-int diral_driver_shape(int envs, int num_users, int num_channels, const void* reward_in, int dtype,
-                       const int32_t* actions, const int32_t* ia, int64_t* sum_ia_prev, int32_t* pen_counter,
-                       int32_t* prev_actions, int flags, int ia_penalty_threshold, double ia_penalty_value,
-                       void* reward_out, void* sum_r_out, void* collision_out, int64_t* ia_sum_out,
-                       int32_t* ia_penalty_out, void* stream) {
-  if (envs < 1 || num_users < 1 || !reward_in || !reward_out) return DIRAL_ERR_BAD_ARG;
-  if (dtype != DIRAL_F32 && dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
-  if ((flags & 4) && (!actions || !pen_counter || !prev_actions)) return DIRAL_ERR_BAD_ARG;
-  if ((flags & 2) && (!ia || !sum_ia_prev)) return DIRAL_ERR_BAD_ARG;
-  DEVICE_ENTER(reward_in);
-  return hip_status(by_dtype(dtype, [&](auto tag) {
-    using T = decltype(tag);
-    const T* in = static_cast<const T*>(reward_in);
-    T *out = static_cast<T*>(reward_out), *sum = static_cast<T*>(sum_r_out), *coll = static_cast<T*>(collision_out);
-    if (!ia && !(flags & 2) && num_users >= 8 && num_users <= 64)   // no information-age terms, one wave per env (aux_kernels.hpp)
-      return launch_k<driver_shape_wave_kernel<T>>(dim3(blocks((size_t)envs, kShapeWaveBlock / 64)), dim3(kShapeWaveBlock), 0,
-                                                   (hipStream_t)stream, envs, num_users, num_channels, in, actions, pen_counter,
-                                                   prev_actions, flags, ia_penalty_threshold, ia_penalty_value, out, sum, coll);
-    return launch_k<driver_shape_kernel<T>>(dim3(blocks((size_t)envs, kShapeEnvsPerBlock)), dim3(256), 0, (hipStream_t)stream, envs,
-                                            num_users, num_channels, in, actions, ia, (long long*)sum_ia_prev, pen_counter,
-                                            prev_actions, flags, ia_penalty_threshold, ia_penalty_value, out, sum, coll,
-                                            (long long*)ia_sum_out, ia_penalty_out);
-  }));
-}
-
-int diral_sps_window_from_chobs(int agents, int num_channels, const void* chobs, int chobs_dtype,
-                                const int32_t* actions, double* window_out, void* stream) {
-  if (agents < 1 || num_channels < 1 || !chobs || !actions || !window_out) return DIRAL_ERR_BAD_ARG;
-  if (chobs_dtype != DIRAL_F32 && chobs_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
-  DEVICE_ENTER(chobs);
-  const size_t total = (size_t)agents * num_channels;
-  return hip_status(by_dtype(chobs_dtype, [&](auto tag) {
-    using T = decltype(tag);
-    return launch_1d<sps_window_kernel<T>>(total, (hipStream_t)stream, total, num_channels, static_cast<const T*>(chobs), actions, window_out);
-  }));
-}
-
-static int sps_step_chobs_impl(int agents, int num_channels, const void* chobs, int chobs_dtype, const int32_t* actions,
-                               int32_t* prev_action, int32_t* counter, double rssi_threshold, double inc_db,
-                               double keep_prob, const int32_t* draw_counter, const double* draw_keep,
-                               const int32_t* draw_choice, uint64_t seed, const long long* clock, int32_t* actions_out,
-                               void* stream) {
-  if (agents < 1 || num_channels < 1 || !chobs || !actions || !prev_action || !counter || !actions_out)
-    return DIRAL_ERR_BAD_ARG;
-  if (chobs_dtype != DIRAL_F32 && chobs_dtype != DIRAL_F64) return DIRAL_ERR_BAD_ARG;
-  if (num_channels > kSpsWaveMaxA) return DIRAL_ERR_UNSUPPORTED;   // use window_from_chobs + sps_step
-  DEVICE_ENTER(prev_action);
-  return hip_status(by_dtype(chobs_dtype, [&](auto tag) {
-    return launch_sps_wave<decltype(tag), true>(agents, num_channels, chobs, (hipStream_t)stream, actions, prev_action, counter,
-                                                rssi_threshold, inc_db, keep_prob, draw_counter, draw_keep, draw_choice, seed,
-                                                clock, actions_out);
-  }));
-}
-
-int diral_sps_step_chobs(int agents, int num_channels, const void* chobs, int chobs_dtype, const int32_t* actions,
-                         int32_t* prev_action, int32_t* counter, double rssi_threshold, double inc_db,
-                         double keep_prob, const int32_t* draw_counter, const double* draw_keep,
-                         const int32_t* draw_choice, uint64_t seed, int32_t* actions_out, void* stream) {
-  return sps_step_chobs_impl(agents, num_channels, chobs, chobs_dtype, actions, prev_action, counter, rssi_threshold, inc_db,
-                             keep_prob, draw_counter, draw_keep, draw_choice, seed, nullptr, actions_out, stream);
-}
-
-int diral_sps_step_chobs_clocked(int agents, int num_channels, const void* chobs, int chobs_dtype, const int32_t* actions,
-                                 int32_t* prev_action, int32_t* counter, double rssi_threshold, double inc_db,
-                                 double keep_prob, uint64_t seed, const int64_t* clock, int32_t* actions_out, void* stream) {
-  if (!clock) return DIRAL_ERR_BAD_ARG;
-  return sps_step_chobs_impl(agents, num_channels, chobs, chobs_dtype, actions, prev_action, counter, rssi_threshold, inc_db,
-                             keep_prob, nullptr, nullptr, nullptr, seed, (const long long*)clock, actions_out, stream);
-}
-
-int diral_clock_add(int64_t* clock, int64_t inc, void* stream) {
-  if (!clock) return DIRAL_ERR_BAD_ARG;
-  DEVICE_ENTER(clock);
-  return hip_status(launch_k<clock_add_kernel>(dim3(1), dim3(1), 0, (hipStream_t)stream, (long long*)clock, (long long)inc));
-}
-
 int diral_env_set_clock(DiralEnv* e, const int64_t* t_dev) {
   if (!e) return DIRAL_ERR_BAD_ARG;
   e->base.t_dev = (const long long*)t_dev;
@@ -1727,212 +1556,6 @@ int diral_env_align_phase(DiralEnv* e, int phase, void* stream) {
   if (hipMemsetAsync(e->slow, 0, buf_of(e, e->slow).bytes, s) != hipSuccess) return DIRAL_ERR_HIP;
   while ((int)(e->slow_launches % 3) != phase) ++e->slow_launches;
   return DIRAL_OK;
-}
-
-int diral_sps_init(int agents, int selection_window, int32_t* prev_action, int32_t* counter, uint64_t seed,
-                   void* stream) {
-  if (agents < 1 || selection_window < 0 || !prev_action || !counter) return DIRAL_ERR_BAD_ARG;
-  DEVICE_ENTER(prev_action);
-  return hip_status(launch_1d<sps_init_kernel>((size_t)agents, (hipStream_t)stream, agents, selection_window, seed, prev_action, counter));
-}
-
-int diral_policy_select(const DiralSelect* s, void* stream) {
-  if (!s || s->struct_bytes != sizeof(DiralSelect) || !s->q || !s->actions_out) return DIRAL_ERR_BAD_ARG;
-  if (s->agents < 1 || s->num_channels < 1 || s->num_users < 1 || s->agents % s->num_users != 0) return DIRAL_ERR_BAD_ARG;
-  if (s->kind < DIRAL_SELECT_GREEDY || s->kind > DIRAL_SELECT_BOLTZMANN) return DIRAL_ERR_BAD_ARG;
-  if (s->q_dtype < DIRAL_F32 || s->q_dtype > DIRAL_BF16) return DIRAL_ERR_BAD_ARG;
-  if (s->kind == DIRAL_SELECT_SOFTMAX && !s->param_dev && !(s->tmp > 0.0 && std::isfinite(s->tmp))) return DIRAL_ERR_BAD_ARG;
-  if (s->param_per_env && !s->param_dev) return DIRAL_ERR_BAD_ARG;
-  if (s->num_channels > kSelMaxA) return DIRAL_ERR_UNSUPPORTED;
-  DEVICE_ENTER(s->q);
-  const int A = s->num_channels;
-  SelParams p{};
-  p.q = s->q; p.agents = s->agents; p.N = s->num_users; p.A = A;
-  while ((1 << p.gshift) < A || p.gshift < 2) ++p.gshift;          // lanes per row (A <= 64): the power of two >= A, at least 4
-  p.param = s->kind == DIRAL_SELECT_EPS_GREEDY ? s->eps : s->kind == DIRAL_SELECT_SOFTMAX ? s->tmp : s->explore_p;
-  p.beta = s->beta; p.alpha = s->alpha;
-  p.param_dev = s->kind == DIRAL_SELECT_GREEDY ? nullptr : s->param_dev; p.param_per_env = s->param_per_env;
-  p.draw_u = s->draw_u; p.draw_a = s->draw_a; p.seed = s->seed; p.idx0 = s->idx0;
-  p.clock = (const long long*)s->clock; p.clock_offset = (long long)s->clock_offset;
-  p.actions_out = s->actions_out; p.explored_out = s->explored_out; p.bad_rows = s->bad_rows;
-  const hipStream_t st = (hipStream_t)stream;
-  auto launch = [&](auto tag, auto kind) {
-    using QT = decltype(tag);
-    constexpr int KIND = decltype(kind)::value;
-    if (A > 64) {
-      const uint32_t lds = (KIND == kSelSoftmax || KIND == kSelBoltzmann) ? (uint32_t)A * 8u : 0u;
-      return launch_k<select_actions_wide_kernel<QT, KIND>>(dim3((uint32_t)p.agents), dim3(64), lds, st, p);
-    }
-    const size_t waves = ((size_t)p.agents + (64u >> p.gshift) - 1) >> (6 - p.gshift);
-    return launch_k<select_actions_kernel<QT, KIND>>(dim3(blocks(waves * 64, kSelBlock)), dim3(kSelBlock), 0, st, p);
-  };
-  auto by_q = [&](auto kind) {
-    switch (s->q_dtype) {
-      case DIRAL_F64: return launch(double{}, kind);
-      case DIRAL_F32: return launch(float{}, kind);
-      case DIRAL_F16: return launch(_Float16{}, kind);
-      default: return launch(bf16_bits{}, kind);
-    }
-  };
-  switch (s->kind) {
-    case DIRAL_SELECT_GREEDY: return hip_status(by_q(std::integral_constant<int, kSelGreedy>{}));
-    case DIRAL_SELECT_EPS_GREEDY: return hip_status(by_q(std::integral_constant<int, kSelEpsGreedy>{}));
-    case DIRAL_SELECT_SOFTMAX: return hip_status(by_q(std::integral_constant<int, kSelSoftmax>{}));
-    default: return hip_status(by_q(std::integral_constant<int, kSelBoltzmann>{}));
-  }
-}
-
-int diral_memory_add(const DiralMemory* m, const DiralMemoryAdd* a, void* stream) {
-  if (!memory_ok(m) || !a || a->struct_bytes != sizeof(DiralMemoryAdd)) return DIRAL_ERR_BAD_ARG;
-  if (a->slots < 1 || a->slots > m->capacity || !a->next_states || !a->actions || !a->rewards) return DIRAL_ERR_BAD_ARG;
-  if ((a->src_dtype != DIRAL_F32 && a->src_dtype != DIRAL_F64) || (a->rewards_dtype != DIRAL_F32 && a->rewards_dtype != DIRAL_F64))
-    return DIRAL_ERR_BAD_ARG;
-  DEVICE_ENTER(m->states);
-  MemAddParams p{};
-  p.states = m->states; p.actions = m->actions; p.rewards = m->rewards;
-  p.C = m->capacity; p.K = a->slots;
-  p.BN = (long long)m->batch * m->num_users; p.BNS = p.BN * m->state_space;
-  p.count = (long long)m->count; p.count_dev = (const long long*)m->count_dev;
-  p.next_states = a->next_states; p.state0 = a->state0; p.a_in = a->actions; p.r_in = a->rewards;
-  p.r_f64 = a->rewards_dtype == DIRAL_F64; p.r_bcast = a->rewards_broadcast != 0;
-  const size_t es = a->src_dtype == DIRAL_F64 ? 8 : 4, er = m->dtype == DIRAL_F64 ? 8 : 4;
-  const int vec = std::min(mem_vec(p.BNS, es, {a->next_states, a->state0}), mem_vec(p.BNS, er, {m->states}));
-  const int ny = p.K + (p.state0 ? 1 : 0);
-  const dim3 grid((uint32_t)std::min<size_t>(blocks((size_t)p.BNS / vec, kMemBlock), 4096), (uint32_t)std::min(ny, 65535));
-  const hipStream_t st = (hipStream_t)stream;
-  return hip_status(by_dtype(a->src_dtype, [&](auto src) {
-    return by_dtype(m->dtype, [&](auto ring) {
-      return by_vec(vec, [&](auto v) {
-        return launch_k<memory_add_kernel<decltype(src), decltype(ring), decltype(v)::value>>(grid, dim3(kMemBlock), 0, st, p);
-      });
-    });
-  }));
-}
-
-int diral_memory_sample(const DiralMemory* m, const DiralMemorySample* s, void* stream) {
-  if (!memory_ok(m) || !s || s->struct_bytes != sizeof(DiralMemorySample)) return DIRAL_ERR_BAD_ARG;
-  if (s->step < 1 || s->windows < 1 || (s->idx == nullptr) != (s->env == nullptr)) return DIRAL_ERR_BAD_ARG;
-  if (!m->count_dev) {
-    const long long len = std::min<long long>(m->count, m->capacity);
-    if (len <= s->step) return DIRAL_ERR_BAD_ARG;
-    if (!s->idx && (long long)s->windows > (len - s->step) * m->batch) return DIRAL_ERR_BAD_ARG;
-  }
-  const bool f64 = m->dtype == DIRAL_F64;
-  const int od = s->out_dtype;
-  if (f64 ? (od != DIRAL_F64 && od != DIRAL_F32) : (od != DIRAL_F32 && od != DIRAL_F16 && od != DIRAL_BF16)) return DIRAL_ERR_UNSUPPORTED;
-  const long long NS = (long long)m->num_users * m->state_space;
-  if (NS > 0x7fffffffLL || ((long long)s->windows + 8) * (s->step + 1LL) > 0x7fffffffLL) return DIRAL_ERR_UNSUPPORTED;
-  DEVICE_ENTER(m->states);
-  MemSampleParams p{};
-  p.states = m->states; p.actions = m->actions; p.rewards = m->rewards;
-  p.C = m->capacity; p.B = m->batch; p.N = m->num_users; p.S = m->state_space;
-  p.count = (long long)m->count; p.count_dev = (const long long*)m->count_dev;
-  p.M = s->windows; p.step = s->step; p.last_only = s->last_only != 0;
-  p.idx = s->idx; p.env = s->env; p.seed = s->seed; p.clock = (const long long*)s->clock; p.clock_offset = (long long)s->clock_offset;
-  p.states_out = s->states_out; p.next_out = s->next_states_out; p.actions_out = s->actions_out; p.rewards_out = s->rewards_out;
-  p.idx_out = s->idx_out; p.env_out = s->env_out; p.bad = s->bad_samples;
-  const size_t er = f64 ? 8 : 4, eo = od == DIRAL_F64 ? 8 : od == DIRAL_F32 ? 4 : 2;
-  const int vec = mem_vec(NS, er, {m->states});
-  p.vst = vec > 1 && mem_vec(m->state_space, eo, {s->states_out, s->next_states_out}) >= vec;
-  p.ushift = NS / vec <= 256 ? 6 : 8;                               // a wave per item up to four loads per lane
-  // per XCD: the items of ceil(M / 8) windows, kMemBlock >> ushift of them to a workgroup (memory_kernel.hpp)
-  const size_t per_xcd = ((size_t)s->windows + 7) / 8 * ((size_t)s->step + 1), ipb = (size_t)(kMemBlock >> p.ushift);
-  const dim3 grid((uint32_t)(8 * ((per_xcd + ipb - 1) / ipb)));
-  const hipStream_t st = (hipStream_t)stream;
-  auto launch = [&](auto ring, auto out) {
-    return by_vec(vec, [&](auto v) {
-      return launch_k<memory_sample_kernel<decltype(ring), decltype(out), decltype(v)::value>>(grid, dim3(kMemBlock), 0, st, p);
-    });
-  };
-  if (f64) return hip_status(od == DIRAL_F64 ? launch(double{}, double{}) : launch(double{}, float{}));
-  return hip_status(od == DIRAL_F32 ? launch(float{}, float{}) : od == DIRAL_F16 ? launch(float{}, _Float16{}) : launch(float{}, bf16_bits{}));
-}
-
-int diral_memory_history(const DiralMemory* m, int32_t step, int32_t out_dtype, void* out, int32_t* bad, void* stream) {
-  if (!memory_ok(m) || step < 1 || !out) return DIRAL_ERR_BAD_ARG;
-  if (!m->count_dev && (long long)step > std::min<long long>(m->count, m->capacity) + 1) return DIRAL_ERR_BAD_ARG;
-  const bool f64 = m->dtype == DIRAL_F64;
-  const int od = out_dtype;
-  if (f64 ? (od != DIRAL_F64 && od != DIRAL_F32) : (od != DIRAL_F32 && od != DIRAL_F16 && od != DIRAL_BF16)) return DIRAL_ERR_UNSUPPORTED;
-  const long long NS = (long long)m->num_users * m->state_space;
-  if (NS > 0x7fffffffLL || ((long long)m->batch + 8) * step > 0x7fffffffLL) return DIRAL_ERR_UNSUPPORTED;
-  DEVICE_ENTER(m->states);
-  MemHistoryParams p{};
-  p.states = m->states; p.C = m->capacity; p.B = m->batch; p.N = m->num_users; p.S = m->state_space;
-  p.count = (long long)m->count; p.count_dev = (const long long*)m->count_dev;
-  p.step = step; p.out = out; p.bad = bad;
-  const size_t er = f64 ? 8 : 4, eo = od == DIRAL_F64 ? 8 : od == DIRAL_F32 ? 4 : 2;
-  const int vec = mem_vec(NS, er, {m->states});
-  p.vst = vec > 1 && mem_vec(m->state_space, eo, {out}) >= vec;
-  p.ushift = NS / vec <= 256 ? 6 : 8;
-  // per XCD: the items of ceil(B / 8) envs, kMemBlock >> ushift of them to a workgroup (memory_kernel.hpp)
-  const size_t per_xcd = ((size_t)m->batch + 7) / 8 * (size_t)step, ipb = (size_t)(kMemBlock >> p.ushift);
-  const dim3 grid((uint32_t)(8 * ((per_xcd + ipb - 1) / ipb)));
-  const hipStream_t st = (hipStream_t)stream;
-  auto launch = [&](auto ring, auto o) {
-    return by_vec(vec, [&](auto v) {
-      return launch_k<memory_history_kernel<decltype(ring), decltype(o), decltype(v)::value>>(grid, dim3(kMemBlock), 0, st, p);
-    });
-  };
-  if (f64) return hip_status(od == DIRAL_F64 ? launch(double{}, double{}) : launch(double{}, float{}));
-  return hip_status(od == DIRAL_F32 ? launch(float{}, float{}) : od == DIRAL_F16 ? launch(float{}, _Float16{}) : launch(float{}, bf16_bits{}));
-}
-
-int diral_td_head(int32_t rows, int32_t num_actions, const void* q, const void* q_next_target, const void* q_next_eval,
-                  int32_t q_dtype, const int32_t* actions, const void* rewards, int32_t rewards_dtype, double gamma,
-                  int32_t hysteretic, float* targets_out, float* td_out, int32_t* next_action_out, void* grad_q_out,
-                  float* loss_out, int32_t* bad_rows, void* stream) {
-  if (!q_next_target || !actions || !rewards || rows < 1 || num_actions < 1) return DIRAL_ERR_BAD_ARG;
-  if (q_dtype < DIRAL_F32 || q_dtype > DIRAL_BF16 || (rewards_dtype != DIRAL_F32 && rewards_dtype != DIRAL_F64)) return DIRAL_ERR_BAD_ARG;
-  if (!std::isfinite(gamma)) return DIRAL_ERR_BAD_ARG;
-  if (!q && (td_out || grad_q_out || loss_out)) return DIRAL_ERR_BAD_ARG;
-  if (loss_out && !td_out) return DIRAL_ERR_BAD_ARG;
-  if (num_actions > kTdMaxA || rows > kTdMaxRows || q_dtype == DIRAL_F64) return DIRAL_ERR_UNSUPPORTED;
-  DEVICE_ENTER(q_next_target);
-  const int A = num_actions;
-  TdParams p{};
-  p.q = q; p.qn_target = q_next_target; p.qn_eval = q_next_eval; p.actions = actions; p.rewards = rewards;
-  p.rows = rows; p.A = A;
-  while ((1 << p.gshift) < A || p.gshift < 2) ++p.gshift;          // lanes per row (A <= 64), as diral_policy_select's
-  p.gamma = (float)gamma; p.rows_f = (float)rows; p.hysteretic = hysteretic != 0;
-  p.targets_out = targets_out; p.td_out = td_out; p.next_action_out = next_action_out; p.grad_q_out = grad_q_out;
-  p.bad_rows = bad_rows;
-  const hipStream_t st = (hipStream_t)stream;
-  auto launch = [&](auto qt, auto rt) {
-    using QT = decltype(qt);
-    using RT = decltype(rt);
-    if (A > 64) return launch_k<td_head_wide_kernel<QT, RT>>(dim3((uint32_t)rows), dim3(64), 0, st, p);
-    const size_t waves = ((size_t)rows + (64u >> p.gshift) - 1) >> (6 - p.gshift);
-    return launch_k<td_head_kernel<QT, RT>>(dim3(blocks(waves * 64, kTdBlock)), dim3(kTdBlock), 0, st, p);
-  };
-  const hipError_t head = by_dtype(rewards_dtype, [&](auto rt) {
-    return q_dtype == DIRAL_F32 ? launch(float{}, rt) : q_dtype == DIRAL_F16 ? launch(_Float16{}, rt) : launch(bf16_bits{}, rt);
-  });
-  if (head != hipSuccess || !loss_out) return hip_status(head);
-  return hip_status(launch_k<td_loss_kernel>(dim3(1), dim3(kTdBlock), 0, st, (const float*)td_out, (int)rows, loss_out));
-}
-
-int diral_qnet_forward(int32_t rows, int32_t num_hidden, const int32_t* widths, const void* x, int32_t x_dtype,
-                       int64_t x_row_stride, const float* params, int64_t params_len, int32_t norm, double ln_eps,
-                       float* q_out, void* stream) {
-  if (!widths || !x || !params || !q_out || rows < 1 || num_hidden < 0) return DIRAL_ERR_BAD_ARG;
-  if (x_dtype < DIRAL_F32 || x_dtype > DIRAL_BF16 || !std::isfinite(ln_eps) || ln_eps < 0.0) return DIRAL_ERR_BAD_ARG;
-  if (num_hidden > kQnetMaxHidden || x_dtype == DIRAL_F64) return DIRAL_ERR_UNSUPPORTED;
-  for (int i = 0; i < num_hidden + 2; ++i)
-    if (widths[i] < 1) return DIRAL_ERR_BAD_ARG;
-  for (int i = 0; i < num_hidden + 2; ++i)
-    if (widths[i] > (i ? kQnetMaxWidth : kQnetMaxIn)) return DIRAL_ERR_UNSUPPORTED;
-  if (x_row_stride < widths[0] || params_len != qnet_params_len(widths, num_hidden)) return DIRAL_ERR_BAD_ARG;
-  DEVICE_ENTER(x);
-  QnetParams p{};
-  p.x = x; p.x_stride = x_row_stride; p.x_dtype = x_dtype; p.params = params; p.q = q_out;
-  p.rows = rows; p.L = num_hidden; p.norm = norm != 0; p.eps = (float)ln_eps;
-  int off = 0;
-  for (int l = 0; l <= num_hidden; ++l) {
-    p.width[l] = widths[l]; p.width[l + 1] = widths[l + 1]; p.off[l] = off;
-    off += widths[l] * widths[l + 1] + (l < num_hidden ? 3 : 1) * widths[l + 1];
-  }
-  return hip_status(launch_qnet(p, (hipStream_t)stream));
 }
 
 int diral_env_check(DiralEnv* e, void* stream) {

@@ -1,4 +1,4 @@
-// policy_device.hpp - device functions shared by the stand-alone policy / shaping kernels (aux_kernels.hpp) and the
+// policy_device.hpp - device functions shared by the stand-alone policy / shaping kernels (agent_kernels.hpp) and the
 // policy epilogue of the fused step (step_fast64.hpp, POL instantiations): the counter-based generator, the SPS agent
 // (algorithms/v2x_sps.py:8-104), np.sum's summation order walked by one wave.  ONE statement of each, so that the fused
 // slot and the three-launch slot decide and round identically.

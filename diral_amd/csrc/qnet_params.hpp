@@ -1,4 +1,4 @@
-// qnet_params.hpp - what diral_qnet_forward (diral_env.hip) hands to the launcher of qnet_forward_kernel (k_qnet.hip,
+// qnet_params.hpp - what diral_qnet_forward (diral_agent.hip) hands to the launcher of qnet_forward_kernel (k_qnet.hip,
 // qnet_kernel.hpp): the limits of the dense chain, the parameter struct and the launcher's declaration.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -23,10 +23,14 @@ struct QnetParams {
   int off[kQnetMaxHidden + 1];         // layer l's W in the blob; b, gamma and beta follow it
 };
 
-// the number of floats in the blob of a chain: per hidden layer W, b, gamma, beta; then W, b
-inline long long qnet_params_len(const int* width, int L) {
+// one walk over the blob of a chain - per hidden layer W, b, gamma, beta; then W, b -: where each layer's W starts
+// (QnetParams::off), and the number of floats in all
+inline long long qnet_params_walk(const int* width, int L, int* off) {
   long long n = 0;
-  for (int l = 0; l <= L; ++l) n += (long long)width[l] * width[l + 1] + (l < L ? 3 : 1) * (long long)width[l + 1];
+  for (int l = 0; l <= L; ++l) {
+    off[l] = (int)n;
+    n += (long long)width[l] * width[l + 1] + (l < L ? 3 : 1) * (long long)width[l + 1];
+  }
   return n;
 }
 

@@ -966,7 +966,7 @@ def main_sps():
     run_sps_case("s3_sps_small_window", n_agents=24, A=3, T=200, threshold=-110.0, seed=83,
                  level_lo=-120, level_hi=-100, tie_step=0.5)
     # wide windows: exactly one wavefront of subframes, then 2 and 4 subframes per lane of the
-    # wave-cooperative kernel (csrc/aux_kernels.hpp), then beyond it (one thread per agent)
+    # wave-cooperative kernel (csrc/agent_kernels.hpp), then beyond it (one thread per agent)
     run_sps_case("s4_sps_window64", n_agents=70, A=64, T=40, threshold=-110.0, seed=84,
                  level_lo=-125, level_hi=-95, tie_step=1.0, keep_lo=0.7)
     run_sps_case("s5_sps_window100", n_agents=30, A=100, T=60, threshold=-110.3, seed=85,
