@@ -1,6 +1,7 @@
 """Host statement of `diral_qnet_forward` (include/diral_env.h) in NumPy float64, shared by tests/test_qnet_cases.py (no
 device: the statement against torch's CPU graph, wrong restatements told apart) and tests/test_gpu_qnet.py (the kernel
-against the statement), with the case generators both use.
+against the statement), with the case generators both use.  tests/qnet_ordered.py is the same chain in float32 in the
+kernel's documented order, which tests/test_gpu_qnet_ordered.py holds the kernel to bit for bit.
 
 The chain is the reference's ``DRQN._create_network`` (algorithms/drl_drqn.py:109-155):
 ``[matmul + bias -> relu -> layer_norm] x L``, then ``matmul + bias``; the blob holds per hidden layer ``W [in, out]``,
@@ -25,6 +26,9 @@ MIN_VAR = 1e-2          # real_case: the smallest variance a row may have in fro
 MEASURED_SERIAL = 3.183133e-05
 MEASURED_TORCH = 3.691303e-05
 TOL_REL = 4 * max(MEASURED_SERIAL, MEASURED_TORCH)
+# The same figure for tests/qnet_ordered.py's qnet_ordered_f32, the header's rules in the header's order (at the same shape;
+# tests/test_qnet_ordered.py recomputes it).  No tolerance comes from it: the kernel is held to that statement in bits.
+MEASURED_ORDERED = 1.517816e-05
 
 
 def shape_id(shape):
