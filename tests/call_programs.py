@@ -24,7 +24,8 @@ from diral_amd.config import (KERNEL_FAST64, KERNEL_GENERAL, KERNEL_LARGE, KERNE
                               STEP_MY_STEP_CH, bench_config)
 from tests import host_closed_loop as H
 # the suite's own bars (importable without a GPU)
-from tests.host_closed_loop import EXP_ATOL, _exp_bounds, uses_exp  # noqa: F401  (re-exported)
+from tests.host_closed_loop import _exp_bounds, uses_exp  # noqa: F401  (re-exported)
+from tests.oracle_compare import stored_age
 
 RICH_STATE = dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=True, add_position=True)
 MODE_NAME = {STEP_MY_STEP: "my_step", STEP_MY_STEP_CH: "my_step_ch", STEP_DESIGN: "my_step_design"}
@@ -347,7 +348,7 @@ class HostModel:
     # -- pieces ----------------------------------------------------------------------------------------------------
     def tables(self):
         e = self.orc.export()
-        return dict(seq=e["seq"].copy(), age=np.minimum(e["age"], 255), x=e["x"].copy())
+        return dict(seq=e["seq"].copy(), age=stored_age(e["age"]), x=e["x"].copy())
 
     def flat(self):
         return not self.orc.export()["pos_y"].any()
@@ -479,7 +480,7 @@ class HostModel:
 
     def op_export_entries_import(self, op):
         e = self.orc.export()                                        # MA_NeighborTableEntry keeps pos_x as float32
-        self.orc.import_state(x=e["x"].astype(np.float32).astype(np.float64), age=np.minimum(e["age"], 255))
+        self.orc.import_state(x=e["x"].astype(np.float32).astype(np.float64), age=stored_age(e["age"]))
         self.sync_table_y()
         return {}
 
@@ -520,7 +521,7 @@ class HostModel:
 
     def export(self):
         e = self.orc.export()
-        out = dict(pos_x=e["pos_x"], pos_y=e["pos_y"], vel=e["vel"], seq=e["seq"], age=np.minimum(e["age"], 255), x=e["x"])
+        out = dict(pos_x=e["pos_x"], pos_y=e["pos_y"], vel=e["vel"], seq=e["seq"], age=stored_age(e["age"]), x=e["x"])
         if self.cfg.track_arrival:
             out["la"] = e["la"]
         return out

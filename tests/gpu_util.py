@@ -1,6 +1,9 @@
-"""Helpers the GPU test modules share: making a handle and stepping it against the oracle and the reference fixtures
-(what tests/test_gpu_parity.py started with), the twin-handle helpers of the copy tests, the oracle-side helpers of the
-sequence-number horizon tests, and small comparators.  Test modules import from here, never from each other."""
+"""Helpers the GPU test modules share: making a handle and stepping it against the oracle (`against_oracle`,
+`three_handles`, `random_rollout`; the rules themselves are tests/oracle_compare.py's) and the reference fixtures, the
+twin-handle helpers of the copy tests and the oracle-side helpers of the sequence-number horizon tests.  Test modules
+import from here, never from each other."""
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -9,7 +12,8 @@ from diral_amd.config import (ERR_SEQ_OVERFLOW, KERNEL_FAST64, KERNEL_GENERAL, K
                               STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config)
 from diral_amd.vec_env import DiralError
 from tests import call_programs as P
-from tests.golden_util import EXP_ATOL, Golden, out_sha, ulp_diff
+from tests.golden_util import Golden, out_sha, ulp_diff
+from tests.oracle_compare import exp_close, metrics_equal, same, slot_equal, tables_equal, uses_exp  # noqa: F401  (`same`: re-exported)
 
 DIST_ULP = 1       # sqrt(x*x+y*y) vs sqrt(pow(x,2)+pow(y,2))
 
@@ -28,17 +32,130 @@ def gpu_step(env, mode, acts, t, ep=0.0, eps=1.0):
         done.cpu().numpy().copy()
 
 
-def uses_exp(cfg, mode):
-    return cfg.reward_design in (3, 4)
+def host(t):
+    return t.cpu().numpy().copy()
 
 
-def exp_close(a, b):
-    return bool(np.all(np.abs(np.asarray(a) - np.asarray(b)) <= EXP_ATOL))
+def exported(env):
+    return {k: v.cpu().numpy() for k, v in env.export_state().items()}
+
+
+def env_of(d, b):
+    """Env `b` of a dict of batched arrays."""
+    return {k: v[b] for k, v in d.items()}
+
+
+def default_family(N):
+    """What `plan_step` (csrc/diral_env.hip) serves a one-lane highway with at most 64 resources on."""
+    return KERNEL_FAST64 if N <= 64 else KERNEL_WIDE
+
+
+@contextlib.contextmanager
+def general_kernel(env):
+    """This env's steps run on the general step_kernel (DIRAL_OPT_KERNEL_PATH, include/diral_env.h)."""
+    env.force_general_kernel(True)
+    try:
+        yield
+    finally:
+        env.force_general_kernel(False)
+
+
+def xpos_of(seq, B, N):
+    """Imported tables: an entry is the subject's stamp at that sequence number, so entries about one subject with
+    equal seq carry equal xpos in every reachable state (DIRAL_ERR_TABLE_CONFLICT otherwise).  `seq` is [B, N, N] with
+    the subject last."""
+    kk, bb = np.arange(N)[None, None, :], np.arange(B)[:, None, None]
+    return ((kk * 7919 + seq * 104729 + bb * 31) % 200000) / 100.0
+
+
+def oracle_slot(orc, mode, acts, t, state=True):
+    """The oracle's slot `t` as `slot_equal` wants it: (state, reward, chobs)."""
+    rew, chobs = orc.step(mode, acts, t)
+    return orc.obtain_state(acts, chobs, rew) if state else None, rew, chobs
+
+
+def draw_velocities(rng, B, N, *handles):
+    draws = rng.integers(1, 4, size=(B, N)).astype(np.uint8)
+    for h in handles:
+        h.update_velocity(draws)
+
+
+def against_oracle(env, orc, cfg, mode, T, rng, *, compare_at=None, actions=None, vel_every=None, dtype=np.float64,
+                   want_chobs=True, each_slot=None):
+    """One handle and the oracle through the slots `T` (a count, or the slot numbers themselves): draw actions (or take
+    `actions(t)`), step both, `slot_equal` at the slots `compare_at(t)` names (default: all), then `each_slot(t, acts)`,
+    then `update_velocity` on both every `vel_every`.  `want_chobs`: the channel observation is asked for and compared
+    (a RICH instantiation); without it the plain `step` runs.  Returns the last compared slot's (state, reward, chobs)."""
+    B, N, A = env.B, cfg.num_users, cfg.num_channels
+    out = None
+    for t in (range(T) if isinstance(T, int) else T):
+        acts = rng.integers(0, A, size=(B, N)).astype(np.int32) if actions is None else actions(t)
+        obs, rew, _ = env._step(mode, env._actions(acts), t, want_chobs=want_chobs)
+        compare = compare_at is None or compare_at(t)
+        want = oracle_slot(orc, mode, acts, t, state=compare)
+        if compare:
+            out = host(obs), host(rew), host(env._chobs) if want_chobs else None
+            slot_equal(cfg, mode, out, want, t, dtype)
+        if each_slot is not None:
+            each_slot(t, acts)
+        if vel_every and t % vel_every == vel_every - 1:
+            draw_velocities(rng, B, N, env, orc)
+    return out
+
+
+def three_handles(cfg, B, T, *, mode, seed, family, y0=None, actions=None, each_slot=None, f32=True):
+    """A float32 handle (with `f32`), a float64 handle, a float64 handle forced to the general kernel and the oracle on
+    one random topology (`y0(rng)`: lanes, drawn between positions and speeds) and `T` slots of random actions (or
+    `actions(rng, t, previous)`).  Every slot: the float64 handle equals the general one bit for bit and passes
+    `slot_equal` against the oracle, the float32 handle equals the cast, the specialised handles ran on `family` and the
+    forced one on KERNEL_GENERAL; then `each_slot(t, handles, orc)`.  At the end every exported plane is equal between
+    the handles and to the oracle's, the metrics agree and `check()` passes.  Returns ((f32 or None, f64, gen), orc)."""
+    from oracle.oracle import Oracle, SQ_IEEE
+    N, A, L = cfg.num_users, cfg.num_channels, cfg.highway_length
+    name = {STEP_MY_STEP: "my_step", STEP_MY_STEP_CH: "my_step_ch", STEP_DESIGN: "my_step_design"}[mode]
+    rng = np.random.default_rng(seed)
+    x0 = rng.integers(0, int(L), size=(B, N)).astype(np.float64)
+    lanes = None if y0 is None else y0(rng)
+    v0 = rng.uniform(1.1, 2.7, size=(B, N))
+    e32 = make_env(cfg, B, mode=name, dtype=torch.float32) if f32 else None
+    e64, gen = make_env(cfg, B, mode=name, dtype=torch.float64), make_env(cfg, B, mode=name, dtype=torch.float64)
+    special = [e for e in (e32, e64) if e is not None]
+    orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=8)
+    for e in special + [gen]:
+        e.reset_topology(x0, lanes, v0)
+    orc.reset(x0, np.zeros((B, N)) if lanes is None else lanes, v0)
+    a = None
+    for t in range(T):
+        a = rng.integers(0, A, size=(B, N)).astype(np.int32) if actions is None else actions(rng, t, a)
+        got = [[host(x) for x in e.step(a, t)] for e in special]
+        with general_kernel(gen):
+            want = [host(x) for x in gen.step(a, t)]
+        oracle = oracle_slot(orc, mode, a, t)
+        for e, (obs, rew, done), dt in zip(special, got, (np.float32, np.float64)[2 - len(special):]):
+            ran_on(e, family)
+            slot_equal(cfg, mode, (obs, rew, None), oracle, (t, dt.__name__), dt)
+            same(done, want[2], (t, "done"))
+        for g, w, what in zip(got[-1], want, ("state", "reward")):
+            same(g, w, (t, what, "against the general kernel"))
+        ran_on(gen, KERNEL_GENERAL)
+        if each_slot is not None:
+            each_slot(t, (e32, e64, gen), orc)
+    sg, mg = exported(gen), host(gen.metrics())
+    for e in special:
+        st = exported(e)
+        assert set(st) == set(sg)
+        for k in sg:
+            same(st[k], sg[k], (k, "against the general kernel"))
+        metrics_equal(host(e.metrics()), mg, "against the general kernel", prr=mode == STEP_MY_STEP_CH or cfg.track_prr)
+    tables_equal(exported(e64), orc.export(), "end")
+    for e in special + [gen]:
+        e.check()
+    return (e32, e64, gen), orc
 
 
 def assert_slot_matches_reference(g, i, mode, rew, chobs, obs):
     """One env's outputs of slot i against what the reference recorded (tests/golden/*.npz): rewards exact (exp()
-    designs within EXP_ATOL), distances within DIST_ULP, the type-2 histogram bins exact.  A thinned fixture
+    designs within the exp() bar), distances within DIST_ULP, the type-2 histogram bins exact.  A thinned fixture
     (gen_golden.py `record_every`) holds the arrays at some slots and a hash at every slot: the hash is compared
     wherever this bar is "exact", so a slot without arrays still pins its rewards."""
     cfg, name = g.cfg, g.name
@@ -87,17 +204,7 @@ def golden_replay_on_gpu(name):
         o_rew, o_chobs = orc.step(mode, acts, t)
         o_state = orc.obtain_state(acts, o_chobs, o_rew, ep, eps)
         for b in range(B):
-            # --- vs the oracle (IEEE squares): bit-exact except exp() rewards
-            if uses_exp(cfg, mode):
-                assert exp_close(rew[b], o_rew[0]), (name, i)
-            else:
-                assert np.array_equal(rew[b], o_rew[0]), (name, i, rew[b], o_rew[0])
-            assert np.array_equal(chobs[b], o_chobs[0]), (name, i)
-            if cfg.State.add_reward and uses_exp(cfg, mode):
-                assert exp_close(obs[b], o_state[0])
-            else:
-                assert np.array_equal(obs[b], o_state[0]), (name, i, np.argwhere(obs[b] != o_state[0])[:5])
-            # --- vs the reference fixture
+            slot_equal(cfg, mode, (obs[b], rew[b], chobs[b]), (o_state[0], o_rew[0], o_chobs[0]), (name, i))
             assert_slot_matches_reference(g, i, mode, rew[b], chobs[b], obs[b])
             assert done[b] == ((t % cfg.episode_interval) == cfg.episode_interval - 1)
         if i in g.vel_updates:
@@ -107,15 +214,10 @@ def golden_replay_on_gpu(name):
             env.load_saved_positions(g.trace)
             orc.set_trace(g.trace)
         ia = env.info_age(t).cpu().numpy()
-        st = {k: v.cpu().numpy() for k, v in env.export_state().items()}
-        oe = orc.export()
+        st, oe = exported(env), env_of(orc.export(), 0)
         for b in range(B):
             assert_moves_match_reference(g, i, st["pos_x"][b], st["vel"][b], ia[b])
-            assert np.array_equal(st["seq"][b], oe["seq"][0]), (name, i)
-            assert np.array_equal(st["age"][b], np.minimum(oe["age"][0], 255)), (name, i)
-            assert np.array_equal(st["x"][b], oe["x"][0]), (name, i)
-            assert np.array_equal(st["y"][b], oe["y"][0]), (name, i)
-            assert np.array_equal(st["la"][b].astype(np.int64), oe["la"][0]), (name, i)
+            tables_equal(env_of(st, b), oe, (name, i))
             if i in ck:
                 j = ck[i]
                 assert np.array_equal(st["seq"][b], g["tab_seq"][j])
@@ -144,7 +246,7 @@ def random_rollout(cfg, B, T, seed, mode=STEP_MY_STEP, sticky=0.0, vel_every=Non
                    expect_kernel=None, force_general=False, path=None, y0=None):
     """GPU vs oracle (IEEE squares) on B different random envs, T slots; returns
     the number of compared slots.  Everything must match bit for bit (exp()
-    rewards within EXP_ATOL).  The specialised kernels serve every configuration they can
+    rewards within the exp() bar).  The specialised kernels serve every configuration they can
     (`expect_kernel`: assert which family ran); `force_general` pins the run to the general
     kernel (DIRAL_OPT_KERNEL_PATH), `path="large"` to the three launches of csrc/step_large.hpp (the only path beyond
     256 vehicles / 256 resources / 64 bins); track_prr: PRR metrics also in my_step (a build extension); `y0`: a
@@ -163,61 +265,34 @@ def random_rollout(cfg, B, T, seed, mode=STEP_MY_STEP, sticky=0.0, vel_every=Non
     env.reset_topology(x0, y0, v0)
     orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=threads)
     orc.reset(x0, y0, v0)
-    acts = rng.integers(0, A, size=(B, N))
-    for t in range(T):
+    observe = KERNEL_LARGE if (path == "large" or expect_kernel == KERNEL_LARGE) else (KERNEL_GENERAL if force_general else KERNEL_OBSERVE)
+    held = [rng.integers(0, A, size=(B, N))]
+
+    def actions(t):
         new = rng.integers(0, A, size=(B, N))
-        acts = np.where(rng.random((B, N)) < sticky, acts, new).astype(np.int32)
-        obs, rew, chobs, _ = gpu_step(env, mode, acts, t)
+        held[0] = np.where(rng.random((B, N)) < sticky, held[0], new).astype(np.int32)
+        return held[0]
+
+    def each_slot(t, acts):
         if expect_kernel is not None:
-            assert (env.last_kernel() & 15) == expect_kernel, env.last_kernel()
-        o_rew, o_chobs = orc.step(mode, acts, t)
-        o_state = orc.obtain_state(acts, o_chobs, o_rew)
-        if uses_exp(cfg, mode):
-            assert exp_close(rew, o_rew)
-        else:
-            assert np.array_equal(rew, o_rew), t
-        assert np.array_equal(chobs, o_chobs), t
-        if uses_exp(cfg, mode) and cfg.State.add_reward:       # the state carries the exp() reward
-            assert exp_close(obs, o_state), t
-        else:
-            assert np.array_equal(obs, o_state), (t, np.argwhere(obs != o_state)[:5])
+            ran_on(env, expect_kernel)
         if t % 6 == 4 and env.S > 0:
             # a stand-alone obtain_state with FOREIGN arguments (test_env.py:527-583 on the current tables):
             # diral_env_observe -> observe_kernel.hpp (the general kernel's observe mode when forced)
-            from diral_amd.config import KERNEL_GENERAL, KERNEL_LARGE, KERNEL_OBSERVE
             fa = rng.integers(0, A, size=(B, N)).astype(np.int32)
             fc = rng.uniform(0.0, 300.0, size=(B, N, cfg.chobs_width))
             fr = rng.uniform(-3.0, 1.0, size=(B, N))
             s1 = env.obtain_state(fc, fa, fr, 3.0, 0.25).cpu().numpy()
-            assert (env.last_kernel() & 15) == (KERNEL_LARGE if (path == "large" or expect_kernel == KERNEL_LARGE) else (KERNEL_GENERAL if force_general else KERNEL_OBSERVE))
-            s2 = orc.obtain_state(fa, fc, fr, 3.0, 0.25)
-            assert np.array_equal(s1, s2), (t, np.argwhere(s1 != s2)[:5])
-        if vel_every and t % vel_every == vel_every - 1:
-            draws = rng.integers(1, 4, size=(B, N)).astype(np.uint8)
-            env.update_velocity(draws)
-            orc.update_velocity(draws)
-    st = {k: v.cpu().numpy() for k, v in env.export_state().items()}
+            ran_on(env, observe)
+            same(s1, orc.obtain_state(fa, fc, fr, 3.0, 0.25), (t, "foreign arguments"))
+
+    against_oracle(env, orc, cfg, mode, T, rng, actions=actions, each_slot=each_slot, vel_every=vel_every)
     oe = orc.export()
-    assert np.array_equal(st["pos_x"], oe["pos_x"])
-    assert np.array_equal(st["vel"], oe["vel"])
-    assert np.array_equal(st["seq"], oe["seq"])
-    assert np.array_equal(st["age"], np.minimum(oe["age"], 255))
-    assert np.array_equal(st["x"], oe["x"])
-    assert np.array_equal(st["y"], oe["y"])
-    assert np.array_equal(st["la"].astype(np.int64), oe["la"])
-    assert np.array_equal(env.info_age(T - 1).cpu().numpy(), orc.info_age(T - 1))
+    tables_equal(exported(env), oe, "end")
+    same(host(env.info_age(T - 1)), orc.info_age(T - 1), "information age")
     if cfg.proportional_fair and mode == STEP_MY_STEP and sticky >= 0.9 and T >= 40:
         assert oe["pf"].max() > 10                    # the threshold was crossed: the penalty branch ran
-    m, om = env.metrics().cpu().numpy(), orc.metrics()
-    assert np.array_equal(m[:, [0, 2, 3]], om[:, [0, 2, 3]])                # counts: exact
-    assert np.allclose(m[:, 1], om[:, 1], rtol=1e-12, atol=1e-9)            # float sums: order differs
-    if track_prr or mode == STEP_MY_STEP_CH:
-        assert np.array_equal(m[:, 5], om[:, 5])
-        assert np.allclose(m[:, 4], om[:, 4], rtol=1e-12, atol=1e-9)
-        # PRR parity (north_star: within 1e-6)
-        prr = m[:, 4] / np.maximum(m[:, 5], 1)
-        oprr = om[:, 4] / np.maximum(om[:, 5], 1)
-        assert np.max(np.abs(prr - oprr)) < 1e-6
+    metrics_equal(host(env.metrics()), orc.metrics(), "end", prr=track_prr or mode == STEP_MY_STEP_CH)
     env.check()
     return T
 
@@ -273,18 +348,12 @@ def everything(env, t):
     return out
 
 
-# ---- which family ran; arrays bit for bit ----------------------------------------------------------------------------------
+# ---- which family ran --------------------------------------------------------------------------------------------------------
 FAMILY = {KERNEL_FAST64: "FAST64", KERNEL_WIDE: "WIDE", KERNEL_GENERAL: "GENERAL", KERNEL_LARGE: "LARGE", KERNEL_OBSERVE: "OBSERVE"}
 
 
 def ran_on(env, family):
-    assert (env.last_kernel() & 15) == family, (FAMILY.get(env.last_kernel() & 15), FAMILY[family], env.last_kernel())
-
-
-def same(got, want, what, equal_nan=False):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    ok = (got == want) | (np.isnan(got) & np.isnan(want)) if equal_nan else got == want
-    assert np.array_equal(got, want, equal_nan=equal_nan), (what, int((~ok).sum()), np.argwhere(~ok)[:5], got[~ok][:5], want[~ok][:5])
+    assert (env.last_kernel() & 15) == family, (FAMILY.get(env.last_kernel() & 15), FAMILY.get(family, family), env.last_kernel())
 
 
 # ---- handles and oracles on given tables (tests/test_gpu_seq_horizon.py, tests/test_gpu_subwave.py) ------------------------
@@ -300,34 +369,6 @@ def make_oracle(cfg, tab, threads=8):
 def load(env, tab):
     env.reset_topology(tab["pos_x"], 0.0, tab["vel"])
     env.import_state(tab["pos_x"], np.zeros(tab["pos_x"].shape), tab["vel"], seq=tab["seq"], age=tab["age"], x=tab["x"])
-
-
-def exported(env):
-    return {k: v.cpu().numpy() for k, v in env.export_state().items()}
-
-
-def assert_tables(st, oe, what):
-    for k in ("seq", "x", "y", "pos_x", "vel"):
-        assert np.array_equal(st[k], oe[k]), (k, what, np.argwhere(st[k] != oe[k])[:4])
-    assert np.array_equal(st["age"], np.minimum(oe["age"], 255)), what
-    if "la" in st:
-        assert np.array_equal(st["la"].astype(np.int64), oe["la"]), what
-
-
-def assert_slot(cfg, mode, got, orc, acts, t, what):
-    """rewards, channel observation and state of one slot against the oracle (exp() rewards within EXP_ATOL)."""
-    obs, rew, chobs = got
-    o_rew, o_chobs = orc.step(mode, acts, t)
-    o_state = orc.obtain_state(acts, o_chobs, o_rew)
-    if uses_exp(cfg, mode):
-        assert exp_close(rew, o_rew), what
-    else:
-        assert np.array_equal(rew, o_rew), what
-    assert np.array_equal(chobs, o_chobs), what
-    if uses_exp(cfg, mode) and cfg.State.add_reward:
-        assert exp_close(obs, o_state), what
-    else:
-        assert np.array_equal(obs, o_state), (what, np.argwhere(obs != o_state)[:4])
 
 
 def _expect_overflow(env):

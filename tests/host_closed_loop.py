@@ -17,7 +17,7 @@ import torch
 from diral_amd.config import STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH
 from diral_amd.driver import np_sum_lastdim
 from oracle.oracle import SQ_IEEE
-from tests.golden_util import EXP_ATOL
+from tests.oracle_compare import exp_bounds as _exp_bounds, stored_age  # noqa: F401  (`_exp_bounds`: re-exported)
 from tests.oracle_backend import OracleBackend
 
 U64 = (1 << 64) - 1
@@ -320,7 +320,7 @@ class HostClosedLoop:
     # ---- what the tests read ---------------------------------------------------------------------------------
     def export_state(self):
         e = self.ob.export_state()
-        e["age"] = np.minimum(e["age"], 255)            # the device saturates ages at 255, as the suite compares them
+        e["age"] = stored_age(e["age"])                 # as the suite compares them
         return e
 
     def metrics(self):
@@ -340,15 +340,6 @@ RICH = dict(add_channel_obs=True, add_reward=True, add_index=True, add_velocity=
 
 
 MODE_NAME = {STEP_MY_STEP: "my_step", STEP_MY_STEP_CH: "my_step_ch"}
-
-
-def _exp_bounds(N):
-    """Rewards built on exp() differ by at most EXP_ATOL each (|reward| <= e).  A sum of N of them in one fixed order
-    then differs by at most N * EXP_ATOL plus the rounding of N - 1 additions of partial sums below N * e on either
-    side, 2 * N * 2**-53 * N * e; a shaped reward (reward + sum / N) by its own EXP_ATOL, that over N, and the rounding
-    of one division and one addition below 8 on either side (4 * 2**-52 * 4)."""
-    sum_atol = N * EXP_ATOL + 2.0 * N * N * math.e * 2.0 ** -53
-    return sum_atol, EXP_ATOL + sum_atol / N + 16 * 2.0 ** -52
 
 
 def uses_exp(cfg, mode):

@@ -7,7 +7,7 @@ as a wrong number.  `export_state`, `export_entries`, `observe` and `check` chan
 only where the program draws them; one full export + metrics + information age + check closes every program.
 
 Bars (the suite's own, imported): state, reward, channel observation, actions, tables, positions, arrival stamps,
-information age and metric counts bit for bit; exp() rewards within EXP_ATOL and sums built from them within
+information age and metric counts bit for bit; exp() rewards within the exp() bar of tests/oracle_compare.py and sums built from them within
 `_exp_bounds`; metric float sums at rtol 1e-12, atol 1e-9; float32 outputs are the float32 cast of the float64 values.
 
 A failure names the family, the seed, the op index and the ops so far: `draw_program(family, seed)` replays it."""
@@ -17,7 +17,8 @@ import torch
 
 from diral_amd.config import ERR_UNSUPPORTED, KERNEL_POLICY, STEP_MY_STEP_CH
 from tests import call_programs as P
-from tests.call_programs import EXP_ATOL, _exp_bounds, uses_exp
+from tests.call_programs import _exp_bounds, uses_exp
+from tests.oracle_compare import exp_atol, metrics_equal
 from tests.gpu_util import make_env
 
 pytestmark = pytest.mark.gpu
@@ -45,8 +46,8 @@ class Run:
         self.t, self.i, self.log = 0, -1, []
         self.exp = uses_exp(self.cfg, f["mode"])
         self.sum_atol, self.shaped_atol = _exp_bounds(self.N) if self.exp else (None, None)
-        self.rew_atol = EXP_ATOL if self.exp else None
-        self.state_atol = EXP_ATOL if (self.exp and self.cfg.State.add_reward) else None
+        self.rew_atol = exp_atol(self.exp)
+        self.state_atol = exp_atol(self.exp and self.cfg.State.add_reward)
 
     # -- comparison ------------------------------------------------------------------------------------------------
     def where(self, what):
@@ -219,8 +220,7 @@ class Run:
 
     def compare_metrics(self, m, want):
         m = m.cpu().numpy()
-        self.eq("metric counts", m[:, [0, 2, 3, 5]], want[:, [0, 2, 3, 5]])
-        assert np.allclose(m[:, [1, 4]], want[:, [1, 4]], rtol=1e-12, atol=1e-9), self.where("metric sums %r, expected %r" % (m[:, [1, 4]], want[:, [1, 4]]))
+        metrics_equal(m, want, self.where("metrics"), prr=True)
 
     def op_metrics(self, op, e):
         self.compare_metrics(self.env.metrics(clear=op["clear"]), e["metrics"])

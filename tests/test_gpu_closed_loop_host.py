@@ -4,8 +4,8 @@ from the same start.  The other closed-loop tests compare one device path with a
 functions; here the second side shares no code with the device.
 
 Bars (the suite's own, tests/test_gpu_parity.py): everything bit for bit against the oracle in its IEEE-square mode; the
-metric float sums at rtol 1e-12, atol 1e-9; exp()-based rewards (reward_design 3, and 4 in my_step_ch) within EXP_ATOL,
-and what is summed from them within the bound `_exp_bounds` derives from EXP_ATOL and the float64 format.
+metric float sums at rtol 1e-12, atol 1e-9; exp()-based rewards (reward_design 3, and 4 in my_step_ch) within the exp() bar,
+and what is summed from them within the bound `_exp_bounds` derives from that bar and the float64 format (tests/oracle_compare.py).
 
 What is indexed how: the topology, `sample` and velocity draws are indexed by the GLOBAL vehicle index
 (DIRAL_OPT_ENV_OFFSET * N + b * N + lane: shards draw what the whole batch draws); the SPS draws (initial state, new
@@ -21,7 +21,8 @@ import torch
 from diral_amd.config import (KERNEL_CH, KERNEL_FAST64, KERNEL_PACKED, KERNEL_POLICY, KERNEL_WIDE, STEP_MY_STEP_CH,
                               bench_config, c2_config)
 from tests import host_closed_loop as H
-from tests.host_closed_loop import EXP_ATOL, RICH, Case, _eq, _exp_bounds, host_run, uses_exp
+from tests.oracle_compare import exp_atol, metrics_equal
+from tests.host_closed_loop import RICH, Case, _eq, _exp_bounds, host_run, uses_exp
 
 pytestmark = pytest.mark.gpu
 
@@ -104,10 +105,10 @@ def device_run(c, monkeypatch=None):
         _eq(tag + "shaped", sh.reshape((K, B, N)), o["shaped"], keep, 1, shaped_atol)
         _eq(tag + "sum_r", sr.reshape((K, B)), o["sum_r"], keep, 1, sum_atol)
         _eq(tag + "collisions", co.reshape((K, B)), o["coll"], keep, 1, sum_atol)
-        _eq(tag + "reward", env._rew, o["rew"], keep, 0, EXP_ATOL if exp else None)
+        _eq(tag + "reward", env._rew, o["rew"], keep, 0, exp_atol(exp))
         _eq(tag + "done", env._done, o["done"], keep)
         if c.want_obs:
-            _eq(tag + "state", env._obs, o["state"], keep, 0, EXP_ATOL if (exp and cfg.State.add_reward) else None)
+            _eq(tag + "state", env._obs, o["state"], keep, 0, exp_atol(exp and cfg.State.add_reward))
         if c.want_chobs:
             _eq(tag + "channel observation", env._chobs, o["chobs"], keep)
         _eq(tag + "actions_out", nxt, o["actions"], keep)
@@ -123,11 +124,8 @@ def device_run(c, monkeypatch=None):
     for k in ("pos_x", "vel", "seq", "age", "x"):
         _eq("export_state " + k, st[k], he[k], keep)
     m, hm = env.metrics().cpu().numpy()[keep], host.metrics()[keep]
-    assert np.array_equal(m[:, [0, 2, 3]], hm[:, [0, 2, 3]])
-    assert np.allclose(m[:, 1], hm[:, 1], rtol=1e-12, atol=1e-9)
-    if c.mode == STEP_MY_STEP_CH:
-        assert np.array_equal(m[:, 5], hm[:, 5]) and float(m[:, 5].min()) > 0
-        assert np.allclose(m[:, 4], hm[:, 4], rtol=1e-12, atol=1e-9)
+    metrics_equal(m, hm, "metrics", prr=c.mode == STEP_MY_STEP_CH)
+    assert c.mode != STEP_MY_STEP_CH or float(m[:, 5].min()) > 0
     env.check()
     return env, host
 
@@ -214,7 +212,7 @@ FAST = {
     # subframes: only here does the order the general path gives differ from the shortcut's
     "far_30km": dict(cfg=bench_config(64, 32, 30000.0, reward_design=4, communication_range=20000.0), dt=torch.float32,
                      plan=[1] * 2 + [5, 25], keep=0.0, expect=("far",)),
-    # exp() rewards: the EXP_ATOL rule
+    # exp() rewards: the exp() bar
     "rd3_exp": dict(cfg=c2_config(reward_design=3), dt=torch.float64, plan=[1] * 2 + [5, 25], counter_mod=3),
 }
 
@@ -316,7 +314,5 @@ def test_prefill_launch_against_the_host_loop(mode, rd, dt):
     for k in ("pos_x", "vel", "seq", "age", "x"):
         assert np.array_equal(st[k].cpu().numpy(), he[k]), k
     m, hm = env.metrics().cpu().numpy(), host.metrics()
-    assert np.array_equal(m[:, [0, 2, 3]], hm[:, [0, 2, 3]]) and np.allclose(m[:, 1], hm[:, 1], rtol=1e-12, atol=1e-9)
-    if mode == "my_step_ch":
-        assert np.array_equal(m[:, 5], hm[:, 5]) and np.allclose(m[:, 4], hm[:, 4], rtol=1e-12, atol=1e-9)
+    metrics_equal(m, hm, "metrics", prr=mode == "my_step_ch")
     env.check()

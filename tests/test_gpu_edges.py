@@ -15,7 +15,8 @@ import torch
 
 from diral_amd.config import KERNEL_FAST64, KERNEL_GENERAL, KERNEL_RING, KERNEL_WIDE, STEP_MY_STEP, bench_config
 from tests.hist_edge_cases import numpy_hist
-from tests.gpu_util import make_env
+from tests.gpu_util import host, make_env, oracle_slot
+from tests.oracle_compare import slot_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -198,11 +199,10 @@ def test_c4_shard_sized_run_properties_and_sampled_oracle():
         a = env.sample(seed=9000 + t)
         obs, rew, done = env.step(a, t)
         an = a.cpu().numpy()[pick]
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, an, t)
-        o_state = orc.obtain_state(an, o_chobs, o_rew)
+        want = oracle_slot(orc, STEP_MY_STEP, an, t)
         if t % 7 == 0 or t == T - 1:
-            assert np.array_equal(obs[torch.as_tensor(pick, device=obs.device)].cpu().numpy(), o_state.astype(np.float32)), t
-            assert np.array_equal(rew[torch.as_tensor(pick, device=obs.device)].cpu().numpy(), o_rew.astype(np.float32)), t
+            at = torch.as_tensor(pick, device=obs.device)
+            slot_equal(cfg, STEP_MY_STEP, (host(obs[at]), host(rew[at]), None), want, t, np.float32)
     assert env.last_kernel() == KERNEL_FAST64 | KERNEL_RING | 256           # (256: KERNEL_PACKED, the packed table form)
     # properties on all 32768 envs of the last slot
     onehot = obs[:, :, :A]

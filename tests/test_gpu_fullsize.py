@@ -11,6 +11,8 @@ import torch
 
 from diral_amd.config import (KERNEL_FAST64, KERNEL_PACKED, KERNEL_RICH, KERNEL_RING, KERNEL_WIDE, STEP_MY_STEP,
                               bench_config)
+from tests.gpu_util import oracle_slot
+from tests.oracle_compare import slot_equal, tables_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -72,11 +74,8 @@ def _run(N, A, L, B, vary, n_sample, T, fam, vel_slot=None, dtype=torch.float32,
         assert torch.all(done == (1 if t % cfg.episode_interval == cfg.episode_interval - 1 else 0))
         # (5) sampled envs bit for bit vs the oracle
         acts_s = a_t[sample_t].cpu().numpy()
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, acts_s, t)
-        o_state = orc.obtain_state(acts_s, o_chobs, o_rew)
-        assert np.array_equal(obs[sample_t].cpu().numpy(), o_state.astype(npdt)), t
-        assert np.array_equal(rew[sample_t].cpu().numpy(), o_rew.astype(npdt)), t
-        assert np.array_equal(chobs[sample_t].cpu().numpy(), o_chobs.astype(npdt)), t
+        slot_equal(cfg, STEP_MY_STEP, [x[sample_t].cpu().numpy() for x in (obs, rew, chobs)],
+                   oracle_slot(orc, STEP_MY_STEP, acts_s, t), t, npdt)
         if vel_slot is not None and t == vel_slot:
             draws = torch.randint(1, 4, (B, N), device="cuda:0", dtype=torch.uint8, generator=g)
             env.update_velocity(draws)
@@ -86,10 +85,7 @@ def _run(N, A, L, B, vary, n_sample, T, fam, vel_slot=None, dtype=torch.float32,
     assert st["pos_x"].min() >= 0 and st["pos_x"].max() < L
     diag = torch.diagonal(st["seq"], dim1=1, dim2=2)
     assert torch.all(diag == T) and torch.all(st["seq"] <= T)
-    oe = orc.export()
-    for k in ("pos_x", "vel", "seq", "x"):
-        assert np.array_equal(st[k][sample_t].cpu().numpy(), oe[k]), k
-    assert np.array_equal(st["age"][sample_t].cpu().numpy(), np.minimum(oe["age"], 255))
+    tables_equal({k: v[sample_t].cpu().numpy() for k, v in st.items()}, orc.export(), "sampled envs")
     if min_slow:
         # which envs ended the run on the slow list: an entry that was heard and lags its subject by 7 stamps or more flags
         # its quad for the keyed path of the next slot (step_fast64.hpp `keep` / `hand`).  Enough of them were compared above.

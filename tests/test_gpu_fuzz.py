@@ -8,19 +8,19 @@ import pytest
 
 from diral_amd.config import (ConfigError, EnvConfig, KERNEL_FAST64, KERNEL_GENERAL, KERNEL_WIDE, STEP_DESIGN,
                               STEP_MY_STEP, STEP_MY_STEP_CH, bench_config)
-from tests.gpu_util import draw_case, random_rollout
+from tests.gpu_util import draw_case, exported, random_rollout
+from tests.oracle_compare import exp_close, tables_equal
 
 pytestmark = pytest.mark.gpu
 
 
 def exp_reward_close(got, want, f64):
-    """Values that pass through exp(): a float64 handle's within EXP_ATOL of the oracle's; a float32 handle's the float32
+    """Values that pass through exp(): a float64 handle's within the exp() bar of the oracle's; a float32 handle's the float32
     cast of the oracle's value or the float32 next to it (two float64 values 2e-15 apart cast to the same or to adjacent
     float32) - and never further from the cast than the 1e-6 this replaces."""
-    from tests.gpu_util import EXP_ATOL
     want = np.asarray(want, dtype=np.float64)
     if f64:
-        return bool(np.all(np.abs(got - want) <= EXP_ATOL))
+        return exp_close(got, want)
     w = want.astype(np.float32)
     near = (got == w) | (got == np.nextafter(w, np.float32(np.inf))) | (got == np.nextafter(w, np.float32(-np.inf)))
     return got.dtype == np.float32 and bool(np.all(near & (np.abs(got.astype(np.float64) - w.astype(np.float64)) <= 1e-6)))
@@ -72,7 +72,7 @@ def test_random_default_flag_configuration_on_the_specialised_kernels(i):
     so the specialised kernels run) against the oracle, bit for bit."""
     import torch
     from oracle.oracle import Oracle, SQ_IEEE
-    from tests.gpu_util import EXP_ATOL, make_env
+    from tests.gpu_util import make_env
     cfg, mode, sticky, f64 = draw_fast_case(i)
     cfg.validate()
     N, A, L = cfg.num_users, cfg.num_channels, cfg.highway_length
@@ -103,11 +103,7 @@ def test_random_default_flag_configuration_on_the_specialised_kernels(i):
             d = rng.integers(1, 4, size=(B, N)).astype(np.uint8)
             env.update_velocity(d)
             orc.update_velocity(d)
-    st, oe = env.export_state(), orc.export()
-    assert np.array_equal(st["seq"].cpu().numpy(), oe["seq"])
-    assert np.array_equal(st["x"].cpu().numpy(), oe["x"])
-    assert np.array_equal(st["age"].cpu().numpy(), np.minimum(oe["age"], 255))
-    assert np.array_equal(st["pos_x"].cpu().numpy(), oe["pos_x"])
+    tables_equal(exported(env), orc.export(), "end")
     env.check()
 
 
@@ -144,7 +140,7 @@ def test_random_rich_configuration_on_the_specialised_kernels(i):
     bit (exp() rewards within the documented tolerance)."""
     import torch
     from oracle.oracle import Oracle, SQ_IEEE
-    from tests.gpu_util import EXP_ATOL, make_env
+    from tests.gpu_util import make_env
     cfg, mode, sticky, f64, offlane = draw_rich_case(i)
     cfg.validate()
     N, A, L = cfg.num_users, cfg.num_channels, cfg.highway_length
@@ -192,11 +188,6 @@ def test_random_rich_configuration_on_the_specialised_kernels(i):
             d = rng.integers(1, 4, size=(B, N)).astype(np.uint8)
             for e in (fused, two, orc):
                 e.update_velocity(d)
-    st, oe = fused.export_state(), orc.export()
-    assert np.array_equal(st["seq"].cpu().numpy(), oe["seq"])
-    assert np.array_equal(st["x"].cpu().numpy(), oe["x"])
-    assert np.array_equal(st["pos_x"].cpu().numpy(), oe["pos_x"])
-    if cfg.track_arrival:
-        assert np.array_equal(st["la"].cpu().numpy().astype(np.int64), oe["la"])
+    tables_equal(exported(fused), orc.export(), "end")
     fused.check()
     two.check()

@@ -11,6 +11,7 @@ import pytest
 import tests.gpu_util as gu
 from diral_amd.config import KERNEL_FAST64, KERNEL_LARGE, KERNEL_WIDE
 from tests.golden_util import Golden, golden_names
+from tests.oracle_compare import ALL, slot_equal, tables_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -54,16 +55,7 @@ def test_reference_fixture_as_one_env_of_a_mixed_batch(name):
         obs, rew, chobs, _ = gu.gpu_step(env, mode, acts, t, ep, eps)
         assert (env.last_kernel() & 15) == fam, env.last_kernel()
         o_rew, o_chobs = orc.step(mode, acts, t)
-        o_state = orc.obtain_state(acts, o_chobs, o_rew, ep, eps)
-        if gu.uses_exp(cfg, mode):
-            assert gu.exp_close(rew, o_rew), (name, i)
-        else:
-            assert np.array_equal(rew, o_rew), (name, i, np.argwhere(rew != o_rew)[:5])
-        assert np.array_equal(chobs, o_chobs), (name, i)
-        if cfg.State.add_reward and gu.uses_exp(cfg, mode):
-            assert gu.exp_close(obs, o_state), (name, i)
-        else:
-            assert np.array_equal(obs, o_state), (name, i, np.argwhere(obs != o_state)[:5])
+        slot_equal(cfg, mode, (obs, rew, chobs), (orc.obtain_state(acts, o_chobs, o_rew, ep, eps), o_rew, o_chobs), (name, i))
         gu.assert_slot_matches_reference(g, i, mode, rew[REF], chobs[REF], obs[REF])
         if i in g.vel_updates:
             draws = rng.integers(1, 4, size=(B, N)).astype(np.uint8)
@@ -78,13 +70,8 @@ def test_reference_fixture_as_one_env_of_a_mixed_batch(name):
         tables = i in ck or i == g.T - 1
         st = {k: v.cpu().numpy() for k, v in env.export_state(tables=tables).items()}
         oe = orc.export()
-        assert np.array_equal(st["pos_x"], oe["pos_x"]) and np.array_equal(st["vel"], oe["vel"]), (name, i)
+        tables_equal(st, oe, (name, i), planes=ALL if tables else ("pos_x", "vel"))
         gu.assert_moves_match_reference(g, i, st["pos_x"][REF], st["vel"][REF], ia[REF])
-        if tables:
-            assert np.array_equal(st["seq"], oe["seq"]), (name, i)
-            assert np.array_equal(st["age"], np.minimum(oe["age"], 255)), (name, i)
-            assert np.array_equal(st["x"], oe["x"]) and np.array_equal(st["y"], oe["y"]), (name, i)
-            assert np.array_equal(st["la"].astype(np.int64), oe["la"]), (name, i)
         if i in ck:
             j = ck[i]
             assert np.array_equal(st["seq"][REF], g["tab_seq"][j])

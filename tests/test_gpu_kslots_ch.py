@@ -9,6 +9,7 @@ import torch
 from diral_amd.config import (ERR_BAD_CONFIG, ERR_UNSUPPORTED, KERNEL_CH, KERNEL_FAST64, KERNEL_POLICY, STEP_MY_STEP_CH,
                               bench_config, c2_config)
 from tests.kslots_harness import RICH, assert_same_envs, closed_loop_twins, compare_closed_loop
+from tests.oracle_compare import metrics_equal, tables_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -152,14 +153,8 @@ def test_ch_k_slots_against_the_cpu_oracle():
     assert np.array_equal(env._chobs.cpu().numpy(), o_chobs)
     st = {k: v.cpu().numpy() for k, v in env.export_state().items()}
     oe = ob.export_state()
-    assert np.array_equal(st["pos_x"], oe["pos_x"])
-    assert np.array_equal(st["seq"], oe["seq"])
-    assert np.array_equal(st["age"], np.minimum(oe["age"], 255))
-    assert np.array_equal(st["x"], oe["x"])
-    m, om = env.metrics().cpu().numpy(), ob.o.metrics()
-    assert np.array_equal(m[:, [0, 2, 3]], om[:, [0, 2, 3]])
-    assert np.array_equal(m[:, 5], om[:, 5])
-    assert np.allclose(m[:, 4], om[:, 4], rtol=1e-12, atol=1e-9)
+    tables_equal(st, oe, "end")
+    metrics_equal(env.metrics().cpu().numpy(), ob.o.metrics(), "end", prr=True)
     env.check()
 
 

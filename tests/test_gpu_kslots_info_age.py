@@ -21,7 +21,8 @@ from diral_amd.vec_env import DiralError, VecV2VEnv
 from oracle.oracle import SQ_IEEE, Oracle
 from tests import host_closed_loop as H
 from tests.golden_util import GOLDEN_DIR, ulp_diff
-from tests.host_closed_loop import EXP_ATOL, _exp_bounds
+from tests.host_closed_loop import _exp_bounds
+from tests.oracle_compare import exp_atol, same
 from tests.kslots_harness import (DEV, PEN_VAL, VEL_SEED, as_rollout, assert_same, assert_same_envs, chain_cfg, go_on_alike,
                                    slot_loop, start, stuck_penalty_state, twins)
 
@@ -219,7 +220,7 @@ def test_closed_loop_with_information_age_against_the_cpu_oracle(N, A, rd, dtype
     sum_atol, shaped_atol = _exp_bounds(N) if exp else (0.0, 0.0)
     assert np.abs(sh.cpu().numpy() - np.stack([h["shaped"][0] for h in h_out])).max() <= shaped_atol
     assert np.abs(sr.cpu().numpy() - np.stack([h["sum_r"][0] for h in h_out])).max() <= sum_atol
-    assert np.abs(rew.cpu().numpy() - h_out[-1]["rew"]).max() <= (EXP_ATOL if exp else 0.0)
+    same(rew.cpu().numpy(), h_out[-1]["rew"], "reward", atol=exp_atol(exp))
     assert np.array_equal(nxt.cpu().numpy(), h_out[-1]["actions"])
     want_sum = np.stack([[sum((i + 1) * int(v) for i, v in enumerate(row) if v > 0) for row in ia] for ia in h_ia])
     assert np.array_equal(iad["ia_sum"].cpu().numpy(), want_sum)

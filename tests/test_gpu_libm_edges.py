@@ -6,7 +6,7 @@ tests/test_libm_cases.py shows without a GPU that the inputs hold what they are 
   RICH, its K-slot form (an open-loop rollout of two slots and `step_policy(slots=2)`), step_wide in both table forms at
   128 and 256 vehicles, the general kernel and the large path, both output types.  Every float64 reward against the
   chain R = k / n, a = 1.0 - R, E = RN(exp(a)), 1.0 - E or -E within `libm_cases.exp_ulp_bound` (the oracle's measured
-  error of 1 ulp of E plus one, half an ulp more where 1 - E rounds again, never beyond EXP_ATOL); every float32 reward
+  error of 1 ulp of E plus one, half an ulp more where 1 - E rounds again, never beyond the exp() bar); every float32 reward
   is the float32 cast of the same path's float64 one; the PRR count exact, the PRR sum within the bound of a sum in any
   order; and ONE device value per (design, argument) over every path, size, table form and slot;
 * log10(): `window_from_chobs` on rows built by hand against -40.0 - 30.0 * RN(log10(max(d, 1))) within
@@ -34,6 +34,7 @@ from diral_amd.config import (KERNEL_CH, KERNEL_FAST64, KERNEL_GENERAL, KERNEL_L
                               KERNEL_WIDE, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config)
 from tests import libm_cases as C
 from tests.gpu_util import make_env
+from tests.oracle_compare import exp_close
 
 ORACLE_EXP_ULPS, HOST_LOG10_ULPS = C.ORACLE_EXP_ULPS, C.HOST_LOG10_ULPS
 
@@ -176,7 +177,7 @@ def ch_case(path, N, form):
             if design == 2:
                 assert C.same_bits(rew, orc["rew"]), tag
             else:
-                assert np.all(np.abs(rew - orc["rew"]) <= C.EXP_ATOL), tag
+                assert exp_close(rew, orc["rew"]), tag
             f32_is_the_cast(rew32, rew, tag)
             for m in (met, met32):
                 assert np.array_equal(m[:, 5], np.full(len(m), float(slots * N))), tag          # DIRAL_M_PRR_CNT
@@ -211,7 +212,7 @@ def count_case(path, N, form):
         for (tag, rew, _, _), (_, rew32, _, _) in zip(r64, r32):
             tag = (path_id((path, N, form)), design, mode, tag)
             if design == 3 and mode == STEP_MY_STEP:
-                assert np.all(np.abs(rew - orc) <= C.EXP_ATOL), tag
+                assert exp_close(rew, orc), tag
                 bad = C.reward_failures(3, rew, ref3, bound3)
                 assert len(bad) == 0, (tag, bad[:4], [(rew[tuple(i)], ref3[tuple(i)]) for i in bad[:4]])
                 note(("my_step", 3), c, rew)

@@ -22,8 +22,9 @@ import pytest
 import torch
 
 from diral_amd.config import KERNEL_FAST64, KERNEL_POLICY, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config
-from tests.gpu_util import make_env
+from tests.gpu_util import exported, host, make_env, ran_on
 from tests.kslots_harness import check_rollout, closed_loop_twins, compare_closed_loop
+from tests.oracle_compare import metrics_equal, same, slot_equal, tables_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -100,33 +101,14 @@ def _run(N, A, kind, dtype, chobs):
     env = make_env(cfg, B, mode=mode, dtype=dtype)
     env.reset_topology(ref["x0"], np.zeros((B, N)), ref["v0"])
     for t, (acts, o_rew, o_chobs, o_state) in enumerate(ref["slots"]):
-        a = env._actions(acts)
-        obs, rew, _ = env._step(mode, a, t, 0.0, 1.0, want_chobs=chobs)
-        torch.cuda.synchronize()
-        assert (env.last_kernel() & 15) == KERNEL_FAST64, env.last_kernel()
-        where = (N, A, kind, t)
-        assert np.array_equal(rew.cpu().numpy(), o_rew.astype(npdt)), where
-        obs = obs.cpu().numpy()
-        want = o_state.astype(npdt)
-        assert np.array_equal(obs, want), (where, np.argwhere(obs != want)[:5])
-        if chobs:
-            got = env._chobs.cpu().numpy()
-            want = o_chobs.astype(npdt)
-            assert np.array_equal(got, want), (where, np.argwhere(got != want)[:5])
-    st = {k: v.cpu().numpy() for k, v in env.export_state().items()}
-    oe = ref["export"]
-    for k in ("pos_x", "vel", "seq", "x", "y"):
-        assert np.array_equal(st[k], oe[k]), (N, A, kind, k)
-    assert np.array_equal(st["age"], np.minimum(oe["age"], 255)), (N, A, kind)
+        obs, rew, _ = env._step(mode, env._actions(acts), t, 0.0, 1.0, want_chobs=chobs)
+        ran_on(env, KERNEL_FAST64)
+        got = (host(obs), host(rew), host(env._chobs) if chobs else None)
+        slot_equal(cfg, mode, got, (o_state, o_rew, o_chobs), (N, A, kind, t), npdt)
+    tables_equal(exported(env), ref["export"], (N, A, kind))
     if cfg.track_arrival:
-        assert np.array_equal(st["la"].astype(np.int64), oe["la"]), (N, A, kind)
-        assert np.array_equal(env.info_age(T - 1).cpu().numpy(), ref["info_age"]), (N, A, kind)
-    m, om = env.metrics().cpu().numpy(), ref["metrics"]
-    assert np.array_equal(m[:, [0, 2, 3]], om[:, [0, 2, 3]]), (N, A, kind)
-    assert np.allclose(m[:, 1], om[:, 1], rtol=1e-12, atol=1e-9), (N, A, kind)   # a float sum: the order differs
-    if mode == STEP_MY_STEP_CH:
-        assert np.array_equal(m[:, 5], om[:, 5]), (N, A, kind)
-        assert np.allclose(m[:, 4], om[:, 4], rtol=1e-12, atol=1e-9), (N, A, kind)
+        same(host(env.info_age(T - 1)), ref["info_age"], (N, A, kind, "information age"))
+    metrics_equal(host(env.metrics()), ref["metrics"], (N, A, kind), prr=mode == STEP_MY_STEP_CH)
     env.check()
 
 

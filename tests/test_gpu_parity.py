@@ -15,10 +15,12 @@ import torch
 
 from diral_amd.config import (EnvConfig, STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config,
                               c2_config)
-from tests.golden_util import EXP_ATOL, Golden, golden_names, out_sha, ulp_diff
-from tests.gpu_util import (DIST_ULP, assert_moves_match_reference, exp_close, golden_replay_on_gpu,
-                            gpu_step, make_env, random_rollout, uses_exp)
+from tests.golden_util import Golden, golden_names, out_sha, ulp_diff
+from tests.gpu_util import (DIST_ULP, against_oracle, assert_moves_match_reference, default_family as _fam, exported,
+                            golden_replay_on_gpu, gpu_step, host, make_env, oracle_slot, random_rollout, ran_on,
+                            three_handles, xpos_of)
 from tests.kslots_harness import closed_loop_twins, compare_closed_loop
+from tests.oracle_compare import exp_close, metrics_equal, same, slot_equal, tables_equal, uses_exp
 
 pytestmark = pytest.mark.gpu
 
@@ -29,11 +31,6 @@ UNBUILT = set()
 def test_golden_replay_on_gpu(name):
     """Every reference fixture replayed through libdiral_env.so (B=3 replicas)."""
     golden_replay_on_gpu(name)
-
-
-def _fam(N):
-    from diral_amd.config import KERNEL_FAST64, KERNEL_WIDE
-    return KERNEL_FAST64 if N <= 64 else KERNEL_WIDE
 
 
 def test_c2_random_vs_oracle():
@@ -224,10 +221,8 @@ def test_full_size_c2_properties_and_sampled_oracle():
         assert torch.all(rew[c > 2] == -c[c > 2].double())
         assert torch.all((rew[c == 2] == 0) | (rew[c == 2] == -2))
         # (4) sampled envs bit-exact vs the oracle
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, acts[sample], t)
-        o_state = orc.obtain_state(acts[sample], o_chobs, o_rew)
-        assert np.array_equal(obs[sample].cpu().numpy(), o_state), t
-        assert np.array_equal(rew[sample].cpu().numpy(), o_rew), t
+        slot_equal(cfg, STEP_MY_STEP, (host(obs[sample]), host(rew[sample]), None),
+                   oracle_slot(orc, STEP_MY_STEP, acts[sample], t), t)
     # (5) positions stay in [0, L) and sequence numbers equal the slot count on the diagonal
     st = env.export_state()
     assert st["pos_x"].min() >= 0 and st["pos_x"].max() < 2000
@@ -267,55 +262,13 @@ def test_fast64_kernel_matches_general_kernel_and_oracle(N, A, K, rd, toy):
     default State flags) against the general kernel (f64 outputs, forced with
     DIRAL_OPT_KERNEL_PATH) and the oracle: f64 states identical, f32 states equal to
     their cast, rewards, positions and every table plane identical."""
-    from oracle.oracle import Oracle, SQ_IEEE
-
     L = 100.0 if toy else 30.0 * N + 100
     cfg = bench_config(N, A, L, reward_design=rd, congestion_test=toy, State=dict(num_bins=K),
                        communication_range=250.0 if N > 8 else 40.0)
-    rng = np.random.default_rng(1000 + N + A + K + rd)
     B = 40
-    x0 = rng.integers(0, int(L), size=(B, N)).astype(np.float64)
-    y0 = rng.integers(0, 2, size=(B, N)).astype(np.float64) if toy else np.zeros((B, N))
-    v0 = rng.uniform(1.1, 2.7, size=(B, N))
-    fast, fast64, gen = (make_env(cfg, B, dtype=torch.float32), make_env(cfg, B, dtype=torch.float64),
-                         make_env(cfg, B, dtype=torch.float64))
-    orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=8)
-    for e in (fast, fast64, gen):
-        e.reset_topology(x0, y0, v0)
-    orc.reset(x0, y0, v0)
-    for t in range(45):
-        a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        of, rf, df = fast.step(a, t)
-        o6, r6, d6 = fast64.step(a, t)
-        with _general_kernel(gen):
-            og, rg, dg = gen.step(a, t)
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, a, t)
-        o_state = orc.obtain_state(a, o_chobs, o_rew)
-        torch.cuda.synchronize()
-        assert torch.equal(o6, og) and torch.equal(r6, rg) and torch.equal(d6, dg), t
-        assert np.array_equal(o6.cpu().numpy(), o_state), t
-        assert torch.equal(of, og.to(torch.float32)), t
-        assert torch.equal(df, dg)
-        assert np.array_equal(of.cpu().numpy(), o_state.astype(np.float32)), t
-        if rd in (3, 4):
-            assert torch.allclose(rf.double(), rg, rtol=0, atol=1e-6)
-            assert np.all(np.abs(r6.cpu().numpy() - o_rew) <= EXP_ATOL), t
-        else:
-            assert torch.equal(rf, rg.to(torch.float32)), t
-            assert np.array_equal(rf.cpu().numpy(), o_rew.astype(np.float32)), t
-            assert np.array_equal(r6.cpu().numpy(), o_rew), t
-    sf, s6, sg, oe = fast.export_state(), fast64.export_state(), gen.export_state(), orc.export()
-    for k in ("pos_x", "vel", "seq", "age", "x", "y"):
-        assert torch.equal(sf[k], sg[k]), k
-        assert torch.equal(s6[k], sg[k]), k
-    assert np.array_equal(sf["seq"].cpu().numpy(), oe["seq"])
-    assert np.array_equal(sf["x"].cpu().numpy(), oe["x"])
-    assert np.array_equal(sf["pos_x"].cpu().numpy(), oe["pos_x"])
-    mf, mg = fast.metrics().cpu().numpy(), gen.metrics().cpu().numpy()
-    assert np.array_equal(mf[:, [0, 2, 3]], mg[:, [0, 2, 3]])
-    assert np.allclose(mf[:, 1], mg[:, 1], rtol=1e-12, atol=1e-9)
-    fast.check()
-    gen.check()
+    lanes = (lambda rng: rng.integers(0, 2, size=(B, N)).astype(np.float64)) if toy else (lambda rng: np.zeros((B, N)))
+    three_handles(cfg, B, 45, mode=STEP_MY_STEP, seed=1000 + N + A + K + rd, family=_fam(N), y0=lanes)
+
 
 
 @pytest.mark.parametrize("margin", ["0", "2500", "16384"])
@@ -346,18 +299,11 @@ def test_fast64_float32_screening_of_the_bin_is_exact(N, A, K, grid, margin, mon
     orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=8)
     env.reset_topology(x0, y0, v0)
     orc.reset(x0, y0, v0)
-    for t in range(30):
-        a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        o, r, d = env.step(a, t)
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, a, t)
-        o_state = orc.obtain_state(a, o_chobs, o_rew)
-        assert np.array_equal(o.cpu().numpy(), o_state), t
-        assert np.array_equal(r.cpu().numpy(), o_rew), t
-    assert (env.last_kernel() & 15) == _fam(N)
-    se, oe = env.export_state(), orc.export()
-    for k in ("seq", "x", "pos_x"):
-        assert np.array_equal(se[k].cpu().numpy(), oe[k]), k
+    against_oracle(env, orc, cfg, STEP_MY_STEP, 30, rng, want_chobs=False)
+    ran_on(env, _fam(N))
+    tables_equal(exported(env), orc.export(), "end")
     env.check()
+
 
 
 @pytest.mark.parametrize("name", ["g1_step_rd2", "g1_ch_rd2", "g1_design", "g1_flags_all"])
@@ -398,29 +344,17 @@ def test_fast64_packed_merge_and_its_fallback_on_stale_tables(stale_frac):
     seq = np.where(stale, rng.integers(0, T0 - 1023, size=(B, N, N)), seq)  # lag >= 1023, some seq == 0
     seq[:, np.arange(N), np.arange(N)] = T0
     age = rng.integers(0, 40, size=(B, N, N))
-    # a table entry is the subject's stamp at that sequence number, so entries about the same
-    # subject with equal seq carry equal xpos in every reachable state; keep that invariant
-    kk = np.arange(N)[None, None, :]
-    bb = np.arange(B)[:, None, None]
-    x = ((kk * 7919 + seq * 104729 + bb * 31) % 200000) / 100.0
+    x = xpos_of(seq, B, N)
     fast = make_env(cfg, B, dtype=torch.float32)
     orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=8)
     fast.reset_topology(x0, None, v0)
     fast.import_state(seq=seq, age=age, x=x)
     orc.reset(x0, np.zeros((B, N)), v0)
     orc.import_state(seq=seq, age=age, x=x, y=np.zeros((B, N, N)))
-    for t in range(30):
-        a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        obs, rew, _ = fast.step(a, t)
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, a, t)
-        o_state = orc.obtain_state(a, o_chobs, o_rew)
-        torch.cuda.synchronize()
-        assert np.array_equal(obs.cpu().numpy(), o_state.astype(np.float32)), t
-    st, oe = fast.export_state(), orc.export()
-    assert np.array_equal(st["seq"].cpu().numpy(), oe["seq"])
-    assert np.array_equal(st["age"].cpu().numpy(), np.minimum(oe["age"], 255))
-    assert np.array_equal(st["x"].cpu().numpy(), oe["x"])
+    against_oracle(fast, orc, cfg, STEP_MY_STEP, 30, rng, want_chobs=False, dtype=np.float32)
+    tables_equal(exported(fast), orc.export(), "end")
     fast.check()
+
 
 
 @pytest.mark.parametrize("N,A,full,ptype", [(64, 32, True, 2), (64, 32, False, 1), (64, 32, True, 1),
@@ -592,20 +526,13 @@ def test_long_run_past_the_packed_rank_horizon():
     orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE)
     fast.reset_topology(x0, None, v0)
     orc.reset(x0, np.zeros((B, N)), v0)
-    for t in range(1300):
-        a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        obs, rew, _ = fast.step(a, t)
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, a, t)
-        if t % 50 == 49 or t > 1270:
-            o_state = orc.obtain_state(a, o_chobs, o_rew)
-            torch.cuda.synchronize()
-            assert np.array_equal(obs.cpu().numpy(), o_state.astype(np.float32)), t
-    st, oe = fast.export_state(), orc.export()
+    against_oracle(fast, orc, cfg, STEP_MY_STEP, 1300, rng, compare_at=lambda t: t % 50 == 49 or t > 1270,
+                   want_chobs=False, dtype=np.float32)
+    oe = orc.export()
     assert (oe["seq"] == 0).any() and (oe["age"] > 255).any()
-    assert np.array_equal(st["seq"].cpu().numpy(), oe["seq"])
-    assert np.array_equal(st["age"].cpu().numpy(), np.minimum(oe["age"], 255))
-    assert np.array_equal(st["x"].cpu().numpy(), oe["x"])
+    tables_equal(exported(fast), oe, "end")
     fast.check()
+
 
 
 def test_step_is_capturable_in_a_hip_graph():
@@ -713,21 +640,6 @@ def test_example_rollout_script_runs():
         assert "collision fraction" in out.stdout
 
 
-def _general_kernel(env):
-    """Context manager: this env's steps run on the general step_kernel
-    (DIRAL_OPT_KERNEL_PATH, include/diral_env.h)."""
-    import contextlib
-
-    @contextlib.contextmanager
-    def cm():
-        env.force_general_kernel(True)
-        try:
-            yield
-        finally:
-            env.force_general_kernel(False)
-    return cm()
-
-
 @pytest.mark.parametrize("N,A,K,rd,toy", [(256, 64, 20, 2, False), (128, 64, 20, 2, False), (130, 33, 10, 1, False),
                                            (65, 3, 8, 2, False), (200, 64, 40, 5, False), (256, 64, 20, 3, False),
                                            (100, 7, 20, 4, False), (129, 64, 21, 2, False), (255, 1, 20, 2, False),
@@ -737,49 +649,8 @@ def test_wide_kernel_matches_general_kernel_and_oracle(N, A, K, rd, toy):
     merge, rank-indexed xpos hand-over) against the general kernel and the oracle:
     f64 states identical, f32 states equal to their cast, rewards, positions, metrics
     and every table plane identical."""
-    from oracle.oracle import Oracle, SQ_IEEE
-    L = 15.0 * N + 100
-    cfg = bench_config(N, A, L, reward_design=rd, congestion_test=toy, State=dict(num_bins=K))
-    rng = np.random.default_rng(2000 + N + A + K + rd)
-    B = 6
-    x0 = rng.integers(0, int(L), size=(B, N)).astype(np.float64)
-    v0 = rng.uniform(1.1, 2.7, size=(B, N))
-    w32, w64, gen = (make_env(cfg, B, dtype=torch.float32), make_env(cfg, B, dtype=torch.float64),
-                     make_env(cfg, B, dtype=torch.float64))
-    orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=8)
-    for e in (w32, w64, gen):
-        e.reset_topology(x0, None, v0)
-    orc.reset(x0, np.zeros((B, N)), v0)
-    for t in range(30):
-        a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        o3, r3, d3 = w32.step(a, t)
-        o6, r6, d6 = w64.step(a, t)
-        with _general_kernel(gen):
-            og, rg, dg = gen.step(a, t)
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, a, t)
-        o_state = orc.obtain_state(a, o_chobs, o_rew)
-        torch.cuda.synchronize()
-        assert torch.equal(o6, og) and torch.equal(d6, dg) and torch.equal(d3, dg), t
-        assert np.array_equal(o6.cpu().numpy(), o_state), t
-        assert torch.equal(o3, og.to(torch.float32)), t
-        if rd in (3, 4):
-            assert np.all(np.abs(r6.cpu().numpy() - o_rew) <= EXP_ATOL), t
-            assert torch.allclose(r3.double(), rg, rtol=0, atol=1e-6)
-        else:
-            assert torch.equal(r6, rg) and torch.equal(r3, rg.to(torch.float32)), t
-            assert np.array_equal(r6.cpu().numpy(), o_rew), t
-    s3, s6, sg, oe = w32.export_state(), w64.export_state(), gen.export_state(), orc.export()
-    for k in ("pos_x", "vel", "seq", "age", "x", "y"):
-        assert torch.equal(s3[k], sg[k]), k
-        assert torch.equal(s6[k], sg[k]), k
-    assert np.array_equal(s6["seq"].cpu().numpy(), oe["seq"])
-    assert np.array_equal(s6["x"].cpu().numpy(), oe["x"])
-    assert np.array_equal(s6["age"].cpu().numpy(), np.minimum(oe["age"], 255))
-    m6, mg = w64.metrics().cpu().numpy(), gen.metrics().cpu().numpy()
-    assert np.array_equal(m6[:, [0, 2, 3]], mg[:, [0, 2, 3]])
-    assert np.allclose(m6[:, 1], mg[:, 1], rtol=1e-12, atol=1e-9)
-    for e in (w32, w64, gen):
-        e.check()
+    cfg = bench_config(N, A, 15.0 * N + 100, reward_design=rd, congestion_test=toy, State=dict(num_bins=K))
+    three_handles(cfg, 6, 30, mode=STEP_MY_STEP, seed=2000 + N + A + K + rd, family=_fam(N))
 
 
 @pytest.mark.parametrize("N,stale_frac,lag_hi", [(256, 0.0, 40), (256, 0.01, 40), (128, 0.3, 40), (150, 0.05, 40),
@@ -817,26 +688,15 @@ def test_wide_rank_merge_and_its_fallback_on_stale_tables(N, stale_frac, lag_hi)
     seq = np.where(rng.random((B, N, N)) < 0.05, 0, seq)                    # never-heard entries
     seq[:, np.arange(N), np.arange(N)] = T0
     age = rng.integers(0, 40, size=(B, N, N))
-    kk = np.arange(N)[None, None, :]
-    bb = np.arange(B)[:, None, None]
-    x = ((kk * 7919 + seq * 104729 + bb * 31) % 200000) / 100.0   # xpos is a function of (subject, seq)
+    x = xpos_of(seq, B, N)
     env = make_env(cfg, B, dtype=torch.float64)
     orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=8)
     env.reset_topology(x0, None, v0)
     env.import_state(seq=seq, age=age, x=x)
     orc.reset(x0, np.zeros((B, N)), v0)
     orc.import_state(seq=seq, age=age, x=x, y=np.zeros((B, N, N)))
-    for t in range(12):
-        a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        obs, rew, _ = env.step(a, t)
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, a, t)
-        o_state = orc.obtain_state(a, o_chobs, o_rew)
-        torch.cuda.synchronize()
-        assert np.array_equal(obs.cpu().numpy(), o_state), t
-    st, oe = env.export_state(), orc.export()
-    assert np.array_equal(st["seq"].cpu().numpy(), oe["seq"])
-    assert np.array_equal(st["age"].cpu().numpy(), np.minimum(oe["age"], 255))
-    assert np.array_equal(st["x"].cpu().numpy(), oe["x"])
+    against_oracle(env, orc, cfg, STEP_MY_STEP, 12, rng, want_chobs=False)
+    tables_equal(exported(env), orc.export(), "end")
     env.check()
 
 
@@ -850,53 +710,22 @@ def test_fast_paths_run_my_step_ch_like_the_general_kernel_and_the_oracle(N, A, 
     oracle: integer reception counts bit-exact, so R and the rd 2 rewards are
     identical; rd 3/4 go through exp (absolute tolerance); states, tables and the
     PRR metric columns identical."""
-    from oracle.oracle import Oracle, SQ_IEEE
     L = (30.0 if N <= 64 else 15.0) * N + 100
     cfg = bench_config(N, A, L, reward_design=rd, State=dict(num_bins=K),
                        communication_range=250.0 if N > 8 else 40.0)
-    rng = np.random.default_rng(3000 + N + A + K + rd)
     B = 8
-    x0 = rng.integers(0, int(L), size=(B, N)).astype(np.float64)
-    v0 = rng.uniform(1.1, 2.7, size=(B, N))
-    f32, f64, gen = (make_env(cfg, B, mode="my_step_ch", dtype=torch.float32),
-                     make_env(cfg, B, mode="my_step_ch", dtype=torch.float64),
-                     make_env(cfg, B, mode="my_step_ch", dtype=torch.float64))
-    orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=8)
-    for e in (f32, f64, gen):
-        e.reset_topology(x0, None, v0)
-    orc.reset(x0, np.zeros((B, N)), v0)
-    for t in range(30):
+
+    def actions(rng, t, prev):
         a = rng.integers(0, A, size=(B, N)).astype(np.int32)
         if t % 3 == 2:                                       # some sticky slots: fewer collisions, R spread
             a[:, ::2] = prev[:, ::2]
-        prev = a
-        o3, r3, _ = f32.step(a, t)
-        o6, r6, d6 = f64.step(a, t)
-        with _general_kernel(gen):
-            og, rg, dg = gen.step(a, t)
-        o_rew, o_chobs = orc.step(STEP_MY_STEP_CH, a, t)
-        o_state = orc.obtain_state(a, o_chobs, o_rew)
-        torch.cuda.synchronize()
-        assert torch.equal(o6, og) and torch.equal(d6, dg), t
-        assert np.array_equal(o6.cpu().numpy(), o_state), t
-        assert torch.equal(o3, og.to(torch.float32)), t
-        if rd == 2:
-            assert torch.equal(r6, rg) and torch.equal(r3, rg.to(torch.float32)), t
-            assert np.array_equal(r6.cpu().numpy(), o_rew), t
-        else:
-            assert torch.equal(r6, rg), t                    # same device exp() on the same R
-            assert np.all(np.abs(r6.cpu().numpy() - o_rew) <= EXP_ATOL), t
-            assert torch.allclose(r3.double(), rg, rtol=0, atol=1e-6)
-    s6, sg, oe = f64.export_state(), gen.export_state(), orc.export()
-    for k in ("pos_x", "seq", "age", "x"):
-        assert torch.equal(s6[k], sg[k]), k
-    assert np.array_equal(s6["seq"].cpu().numpy(), oe["seq"])
-    m6, mg, mo = f64.metrics().cpu().numpy(), gen.metrics().cpu().numpy(), orc.metrics()
-    assert np.array_equal(m6[:, [0, 2, 3, 5]], mg[:, [0, 2, 3, 5]])
-    assert np.array_equal(m6[:, 4], mg[:, 4])                # PRR sums: same values, same summation order
-    assert np.allclose(m6[:, 4] / m6[:, 5], mo[:, 4] / mo[:, 5], rtol=0, atol=1e-12)
-    for e in (f32, f64, gen):
-        e.check()
+        return a
+
+    (_, f64, gen), orc = three_handles(cfg, B, 30, mode=STEP_MY_STEP_CH, seed=3000 + N + A + K + rd, family=_fam(N),
+                                       actions=actions)
+    m6, mg, mo = host(f64.metrics()), host(gen.metrics()), orc.metrics()
+    same(m6[:, 4], mg[:, 4], "PRR sums: same values, same summation order")
+    same(m6[:, 4] / m6[:, 5], mo[:, 4] / mo[:, 5], "PRR", atol=1e-12)
 
 
 def test_wide_long_run_in_and_out_of_the_rank_window():
@@ -914,25 +743,16 @@ def test_wide_long_run_in_and_out_of_the_rank_window():
     orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=4)
     env.reset_topology(x0, None, v0)
     orc.reset(x0, np.zeros((B, N)), v0)
-    for t in range(700):
-        a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        obs, rew, _ = env.step(a, t)
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, a, t)
-        if t % 25 == 24 or t > 680:
-            o_state = orc.obtain_state(a, o_chobs, o_rew)
-            torch.cuda.synchronize()
-            assert np.array_equal(obs.cpu().numpy(), o_state), t
-            assert np.array_equal(rew.cpu().numpy(), o_rew), t
-    st, oe = env.export_state(), orc.export()
+    against_oracle(env, orc, cfg, STEP_MY_STEP, 700, rng, compare_at=lambda t: t % 25 == 24 or t > 680, want_chobs=False)
+    oe = orc.export()
     seq = oe["seq"]
     own = seq[:, np.arange(N), np.arange(N)]                  # [B, k]: the subject's own sequence number
     lag = own[:, None, :] - seq                               # seq is [B, viewer, subject]
     assert ((lag >= 255) & (seq > 0)).any(), "the run never left the rank window"
     assert ((lag < 255) & (seq > 0)).any()
-    assert np.array_equal(st["seq"].cpu().numpy(), seq)
-    assert np.array_equal(st["age"].cpu().numpy(), np.minimum(oe["age"], 255))
-    assert np.array_equal(st["x"].cpu().numpy(), oe["x"])
+    tables_equal(exported(env), oe, "end")
     env.check()
+
 
 
 @pytest.mark.parametrize("N,A,L,form", [(128, 64, 4000.0, None), (128, 16, 4000.0, "packed"), (200, 32, 5000.0, "packed")])
@@ -957,31 +777,21 @@ def test_packed_form_long_run_on_highways_that_break_apart(N, A, L, form, monkey
     orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=8)
     env.reset_topology(x0, None, v0)
     orc.reset(x0, np.zeros((B, N)), v0)
-    for t in range(T):
-        a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        obs, rew, _ = env.step(a, t)
+    def packed(t, acts):
         assert env.last_kernel() & (15 | KERNEL_PACKED) == KERNEL_WIDE | KERNEL_PACKED, env.last_kernel()
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, a, t)
-        if t % 50 == 49 or t >= T - 30:
-            o_state = orc.obtain_state(a, o_chobs, o_rew)
-            torch.cuda.synchronize()
-            assert np.array_equal(obs.cpu().numpy(), o_state), t
-            assert np.array_equal(rew.cpu().numpy(), o_rew), t
-        if t % 25 == 24:
-            draws = rng.integers(1, 4, size=(B, N)).astype(np.uint8)
-            env.update_velocity(draws)
-            orc.update_velocity(draws)
-    st, oe = env.export_state(), orc.export()
+
+    against_oracle(env, orc, cfg, STEP_MY_STEP, T, rng, compare_at=lambda t: t % 50 == 49 or t >= T - 30, vel_every=25,
+                   want_chobs=False, each_slot=packed)
+    oe = orc.export()
     seq = oe["seq"]
     own = seq[:, np.arange(N), np.arange(N)]
     lag = own[:, None, :] - seq
     if N <= 128:
         assert ((lag >= 254) & (seq > 0)).any(), "no entry ever fell 254 stamps behind"
     assert ((lag >= 8) & (lag < 254) & (seq > 0)).any() and ((lag < 8) & (seq > 0)).any()
-    assert np.array_equal(st["seq"].cpu().numpy(), seq)
-    assert np.array_equal(st["age"].cpu().numpy(), np.minimum(oe["age"], 255))
-    assert np.array_equal(st["x"].cpu().numpy(), oe["x"])
+    tables_equal(exported(env), oe, "end")
     env.check()
+
 
 
 @pytest.mark.parametrize("N,A,K", [(64, 32, 20), (64, 5, 10), (6, 3, 20), (40, 48, 20), (256, 64, 20), (128, 16, 10),
@@ -991,40 +801,11 @@ def test_specialised_kernels_run_my_step_design_like_the_general_kernel_and_the_
     number of same-resource transmitters within 2 Rc) on step_fast64 / step_wide - a
     runtime switch of the my_step instantiation - against the general kernel and the
     oracle, bit for bit."""
-    from oracle.oracle import Oracle, SQ_IEEE
     L = (20.0 if N <= 64 else 10.0) * N + 100
     cfg = bench_config(N, A, L, State=dict(num_bins=K), communication_range=100.0 if N > 8 else 20.0)
-    rng = np.random.default_rng(4000 + N + A + K)
-    B = 6
-    x0 = rng.integers(0, int(L), size=(B, N)).astype(np.float64)
-    v0 = rng.uniform(1.1, 2.7, size=(B, N))
-    f32, f64, gen = (make_env(cfg, B, mode="my_step_design", dtype=torch.float32),
-                     make_env(cfg, B, mode="my_step_design", dtype=torch.float64),
-                     make_env(cfg, B, mode="my_step_design", dtype=torch.float64))
-    orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=8)
-    for e in (f32, f64, gen):
-        e.reset_topology(x0, None, v0)
-    orc.reset(x0, np.zeros((B, N)), v0)
-    for t in range(24):
-        a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        o3, r3, _ = f32.step(a, t)
-        o6, r6, d6 = f64.step(a, t)
-        with _general_kernel(gen):
-            og, rg, dg = gen.step(a, t)
-        o_rew, o_chobs = orc.step(STEP_DESIGN, a, t)
-        o_state = orc.obtain_state(a, o_chobs, o_rew)
-        torch.cuda.synchronize()
-        assert torch.equal(o6, og) and torch.equal(r6, rg) and torch.equal(d6, dg), t
-        assert np.array_equal(o6.cpu().numpy(), o_state) and np.array_equal(r6.cpu().numpy(), o_rew), t
-        assert torch.equal(o3, og.to(torch.float32)) and torch.equal(r3, rg.to(torch.float32)), t
-    s6, sg, oe = f64.export_state(), gen.export_state(), orc.export()
-    for k in ("pos_x", "seq", "age", "x"):
-        assert torch.equal(s6[k], sg[k]), k
-    assert np.array_equal(s6["seq"].cpu().numpy(), oe["seq"])
-    m6, mg = f64.metrics().cpu().numpy(), gen.metrics().cpu().numpy()
-    assert np.array_equal(m6[:, [0, 1, 2, 3]], mg[:, [0, 1, 2, 3]])      # integer-valued rewards: sums exact
-    for e in (f32, f64, gen):
-        e.check()
+    (_, f64, gen), _ = three_handles(cfg, 6, 24, mode=STEP_DESIGN, seed=4000 + N + A + K, family=_fam(N))
+    metrics_equal(host(f64.metrics()), host(gen.metrics()), "integer-valued rewards", sums_exact=True)
+
 
 
 @pytest.mark.parametrize("N,A,mode", [(64, 32, STEP_MY_STEP_CH), (64, 32, STEP_MY_STEP), (40, 6, STEP_DESIGN),
@@ -1033,35 +814,19 @@ def test_arrival_stamps_and_information_age_on_the_specialised_kernels(N, A, mod
     """track_arrival on step_fast64 / step_wide: last_arrival_time (test_env.py:436 stamps,
     network.py:394 '-1' side effect) and get_information_age (network.py:560-574) equal the
     oracle's after every slot - the whole main_test.py slot sequence on the fast path."""
-    from oracle.oracle import Oracle, SQ_IEEE
     L = (20.0 if N <= 64 else 10.0) * N + 100
-    rd = 2
-    cfg = bench_config(N, A, L, reward_design=rd, communication_range=120.0).replace(track_arrival=True)
-    rng = np.random.default_rng(5000 + N + A + mode)
-    B = 4
-    x0 = rng.integers(0, int(L), size=(B, N)).astype(np.float64)
-    v0 = rng.uniform(1.1, 2.7, size=(B, N))
-    names = {STEP_MY_STEP: "my_step", STEP_MY_STEP_CH: "my_step_ch", STEP_DESIGN: "my_step_design"}
-    env, gen = make_env(cfg, B, mode=names[mode]), make_env(cfg, B, mode=names[mode])
-    orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=8)
-    for e in (env, gen):
-        e.reset_topology(x0, None, v0)
-    orc.reset(x0, np.zeros((B, N)), v0)
-    for t in range(20):
-        a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        obs, rew, _ = env.step(a, t)
-        with _general_kernel(gen):
-            og, rg, _ = gen.step(a, t)
-        o_rew, o_chobs = orc.step(mode, a, t)
-        ia, iag, oia = env.info_age(t), gen.info_age(t), orc.info_age(t)
-        torch.cuda.synchronize()
-        assert torch.equal(obs, og) and torch.equal(rew, rg), t
-        assert torch.equal(ia, iag) and np.array_equal(ia.cpu().numpy(), oia), t
-    st, sg, oe = env.export_state(), gen.export_state(), orc.export()
-    assert torch.equal(st["la"], sg["la"])
-    assert np.array_equal(st["la"].cpu().numpy().astype(np.int64), oe["la"])
-    env.check()
-    gen.check()
+    cfg = bench_config(N, A, L, reward_design=2, communication_range=120.0).replace(track_arrival=True)
+
+    def information_age(t, handles, orc):
+        _, env, gen = handles
+        ia = host(env.info_age(t))
+        same(ia, host(gen.info_age(t)), (t, "information age against the general kernel"))
+        same(ia, orc.info_age(t), (t, "information age"))
+
+    (_, env, _), _ = three_handles(cfg, 4, 20, mode=mode, seed=5000 + N + A + mode, family=_fam(N), f32=False,
+                                   each_slot=information_age)
+    assert "la" in exported(env)                               # the stamps were among the planes compared
+
 
 
 def _default_flag_goldens():
@@ -1315,43 +1080,29 @@ def test_packed_tables_and_xpos_ring_agree_with_the_oracle_through_every_consume
     orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=8)
     orc.reset(x0, np.zeros((B, N)), v0)
 
-    def same_tables(t):
-        st = {k: v.cpu().numpy() for k, v in env.export_state().items()}
-        oe = orc.export()
-        for k in ("seq", "x", "pos_x", "vel"):
-            assert np.array_equal(st[k], oe[k]), (k, t)
-        assert np.array_equal(st["age"], np.minimum(oe["age"], 255)), t
-
+    general = lambda t: t in (13, 14, 37) or 55 <= t < 58            # the general kernel takes over for some slots
     max_lag = 0
-    for t in range(75):
-        acts = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        general = t in (13, 14, 37) or 55 <= t < 58                  # the general kernel takes over for some slots
-        env.force_general_kernel(general)
-        obs, rew, chobs, _ = gpu_step(env, STEP_MY_STEP, acts, t)
-        assert (env.last_kernel() & (15 | KERNEL_RING)) == (KERNEL_GENERAL if general else _fam(N) | KERNEL_RING)
-        assert general or bool(env.last_kernel() & KERNEL_PACKED) == want_packed, env.last_kernel()
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, acts, t)
-        o_state = orc.obtain_state(acts, o_chobs, o_rew)
-        assert np.array_equal(obs, o_state), (t, np.argwhere(obs != o_state)[:5])
-        assert np.array_equal(rew, o_rew) and np.array_equal(chobs, o_chobs), t
+
+    def consumers(t, acts):
+        nonlocal max_lag
+        assert (env.last_kernel() & (15 | KERNEL_RING)) == (KERNEL_GENERAL if general(t) else _fam(N) | KERNEL_RING)
+        assert general(t) or bool(env.last_kernel() & KERNEL_PACKED) == want_packed, env.last_kernel()
         if t % 7 == 3:
-            same_tables(t)                                           # export: the plane completed from the ring
+            tables_equal(exported(env), orc.export(), t)             # export: the plane completed from the ring
         if t % 9 == 5:                                               # foreign arguments: a diral_env_observe launch
             other = rng.integers(0, A, size=(B, N)).astype(np.int32)
             fake = np.full((B, N), 0.25)
             s1 = env.obtain_state(None, other, fake).cpu().numpy()
-            s2 = orc.obtain_state(other, np.zeros((B, N, A)), fake)
-            assert np.array_equal(s1, s2), t
+            same(s1, orc.obtain_state(other, np.zeros((B, N, A)), fake), (t, "foreign arguments"))
         if t in (26, 60):                                            # checkpoint round trip through import_state
             st = env.export_state()
             lag = torch.diagonal(st["seq"], dim1=1, dim2=2).unsqueeze(1) - st["seq"]
             max_lag = max(max_lag, int(lag[st["seq"] > 0].max().item()))
             env.import_state(st["pos_x"], st["pos_y"], st["vel"], seq=st["seq"], age=st["age"], x=st["x"])
-        if t % 25 == 24:
-            draws = rng.integers(1, 4, size=(B, N)).astype(np.uint8)
-            env.update_velocity(draws)
-            orc.update_velocity(draws)
-    same_tables(75)
+        env.force_general_kernel(general(t + 1))
+
+    against_oracle(env, orc, cfg, STEP_MY_STEP, 75, rng, each_slot=consumers, vel_every=25)
+    tables_equal(exported(env), orc.export(), 75)
     if Rc < 200:
         assert max_lag > 7, max_lag                                  # the sparse topologies do leave the ring
     env.check()
@@ -1482,7 +1233,7 @@ def test_streamed_sub_batches_equal_one_handle(N, A, G, B):
         a, b = one.export_state(), many.export_state()
         for k in a:
             assert torch.equal(a[k], b[k]), k
-        assert torch.equal(one.metrics(clear=True)[:, [0, 2, 3]], many.metrics()[:, [0, 2, 3]])
+        metrics_equal(host(one.metrics(clear=True)), host(many.metrics()), "one handle against sub-batches")
         many.check()
         many.close()
     one.check()
@@ -1520,7 +1271,7 @@ def test_graph_rollout_equals_eager(N, A, B, ch, K):
         assert torch.equal(x, y)
     assert torch.equal(e1._done, e2._done) and torch.equal(e1._chobs, e2._chobs)
     m1, m2 = e1.metrics(), e2.metrics()
-    assert torch.equal(m1[:, [0, 2, 3]], m2[:, [0, 2, 3]]) and torch.allclose(m1, m2, rtol=1e-12, atol=1e-9)
+    metrics_equal(host(m1), host(m2), "graph against eager", prr=True)
     assert float(m1[:, 0].min()) == 21.0 * K
     if ch:
         assert torch.equal(e1.info_age(21 * K - 1), e2.info_age(21 * K - 1))
@@ -1689,17 +1440,12 @@ def test_closest_transmitter_on_ties_and_at_the_range_boundary(N, A):
     orc = Oracle(cfg, batch=B, sq_mode=SQ_IEEE, threads=8)
     orc.reset(x0, y0, v0)
     seen_boundary = seen_tie = False
-    for t in range(12):
-        acts = rng.integers(0, A, size=(B, N)).astype(np.int32)
-        obs, rew, chobs, _ = gpu_step(env, STEP_MY_STEP, acts, t)
-        assert (env.last_kernel() & 15) == _fam(N)
-        o_rew, o_chobs = orc.step(STEP_MY_STEP, acts, t)
-        o_state = orc.obtain_state(acts, o_chobs, o_rew)
-        assert np.array_equal(rew, o_rew), t
-        assert np.array_equal(chobs, o_chobs), (t, np.argwhere(chobs != o_chobs)[:5])
-        assert np.array_equal(obs, o_state), (t, np.argwhere(obs != o_state)[:5])
+
+    def cases(t, acts):
         # the slot really held the cases: a (viewer, transmitter) pair exactly Rc apart, and a viewer with two
         # equidistant nearest transmitters on one resource
+        nonlocal seen_boundary, seen_tie
+        ran_on(env, _fam(N))
         for b in range(2):
             for i in range(A):
                 tx = np.flatnonzero(acts[b] == i)
@@ -1710,13 +1456,12 @@ def test_closest_transmitter_on_ties_and_at_the_range_boundary(N, A):
                 if len(tx) > 1:
                     ds = np.sort(d, axis=1)
                     seen_tie |= bool(np.any((ds[:, 0] == ds[:, 1]) & (ds[:, 0] < 250.0)))
+
+    against_oracle(env, orc, cfg, STEP_MY_STEP, 12, rng, each_slot=cases)
     assert seen_boundary and seen_tie
-    st = {k: v.cpu().numpy() for k, v in env.export_state().items()}
-    oe = orc.export()
-    for k in ("pos_x", "seq", "x"):
-        assert np.array_equal(st[k], oe[k]), k
-    assert np.array_equal(st["age"], np.minimum(oe["age"], 255))
+    tables_equal(exported(env), orc.export(), "end")
     env.check()
+
 
 
 def test_graph_replays_with_rotating_slow_sets_survive_eager_steps_in_between():
@@ -1755,7 +1500,7 @@ def test_graph_replays_with_rotating_slow_sets_survive_eager_steps_in_between():
     assert torch.equal(p1.prev_action, p2.prev_action) and torch.equal(p1.counter, p2.counter)
     assert torch.equal(e1._obs, e2._obs) and torch.equal(e1._rew, e2._rew) and torch.equal(e1._chobs, e2._chobs)
     m1, m2 = e1.metrics(), e2.metrics()
-    assert torch.equal(m1[:, [0, 2, 3]], m2[:, [0, 2, 3]])
+    metrics_equal(host(m1), host(m2), "graph against eager")
     assert float(m1[:, 0].min()) == float(m1[:, 0].max()) == 26.0 * K + 4          # (the eager pass of the capture, 25 runs, 4 steps)
     for e, _, r in runs:
         e.check()
@@ -1816,7 +1561,7 @@ def test_graph_replays_on_a_frozen_slow_set_survive_eager_steps_in_between(K, N,
     assert torch.equal(p1.prev_action, p2.prev_action) and torch.equal(p1.counter, p2.counter)
     assert torch.equal(e1._obs, e2._obs) and torch.equal(e1._rew, e2._rew) and torch.equal(e1._chobs, e2._chobs)
     m1, m2 = e1.metrics(), e2.metrics()
-    assert torch.equal(m1[:, [0, 2, 3]], m2[:, [0, 2, 3]])
+    metrics_equal(host(m1), host(m2), "graph against eager")
     for e, _, r in runs:
         e.check()
         r.close()
@@ -1929,21 +1674,12 @@ def test_flagged_passes_whose_far_entries_stay_put_run_coded_and_propagation_fal
     orc.reset(x0, np.zeros((B, N)), v0)
 
     def run(t0, t1):
-        for t in range(t0, t1):
-            a = rng.integers(0, A, size=(B, N)).astype(np.int32)
-            obs, rew, chobs, _ = gpu_step(env, STEP_MY_STEP, a, t)
-            o_rew, o_chobs = orc.step(STEP_MY_STEP, a, t)
-            o_state = orc.obtain_state(a, o_chobs, o_rew)
-            assert np.array_equal(rew, o_rew) and np.array_equal(chobs, o_chobs), t
-            assert np.array_equal(obs, o_state), (t, np.argwhere(obs != o_state)[:4])
+        against_oracle(env, orc, cfg, STEP_MY_STEP, range(t0, t1), rng)
         assert (env.last_kernel() & 15) == KERNEL_WIDE and (env.last_kernel() & KERNEL_PACKED)
 
-    def tables_equal(tag):
-        st = {k: v.cpu().numpy() for k, v in env.export_state().items()}
+    def same_tables(tag):
         oe = orc.export()
-        for k in ("pos_x", "seq", "x"):
-            assert np.array_equal(st[k], oe[k]), (tag, k)
-        assert np.array_equal(st["age"], np.minimum(oe["age"], 255)), tag
+        tables_equal(exported(env), oe, tag)
         return oe
 
     def move(fn):
@@ -1957,7 +1693,7 @@ def test_flagged_passes_whose_far_entries_stay_put_run_coded_and_propagation_fal
     half = N // 2
     move(lambda px: px.__setitem__((slice(None), slice(half, None)), px[:, half:] + 2000.0))
     run(12, 60)                                                    # two clusters: the entries across age beyond the codes and stay put
-    oe = tables_equal("split")
+    oe = same_tables("split")
     own = np.einsum("bkk->bk", oe["seq"])
     assert ((own[:, None, :] - oe["seq"]) >= 8).mean() > 0.3       # ... nearly half of all entries by now
     # relays: a few vehicles of the first cluster in the gap, 240 m apart - stale stamps about the far cluster start to travel
@@ -1966,10 +1702,10 @@ def test_flagged_passes_whose_far_entries_stay_put_run_coded_and_propagation_fal
             px[:, i] = 1500.0 + 230.0 * i
     move(relays)
     run(60, 90)
-    tables_equal("relays")
+    same_tables("relays")
     move(lambda px: px.__setitem__((slice(None), slice(half, None)), px[:, half:] - 2000.0))
     run(90, 120)                                                   # one cluster again: everything comes back within the codes
-    oe = tables_equal("merged")
+    same_tables("merged")
     env.check()
 
 

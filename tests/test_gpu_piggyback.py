@@ -16,6 +16,7 @@ from diral_amd.config import (ERR_BAD_CONFIG, ERR_PIGGY_NO_TX, ERR_UNSUPPORTED, 
                               STEP_DESIGN, STEP_MY_STEP, STEP_MY_STEP_CH, bench_config)
 from tests.golden_util import Golden
 from tests.gpu_util import gpu_step, make_env, random_rollout
+from tests.oracle_compare import slot_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -144,7 +145,7 @@ def test_piggybacking_receiver_out_of_range_raises_like_the_reference():
                 raised += 1
                 break
             env.check()
-            assert np.array_equal(chobs, o_chobs) and np.array_equal(rew, o_rew)
+            slot_equal(cfg, STEP_MY_STEP, (None, rew, chobs), (None, o_rew, o_chobs), (trial, t))
     assert raised >= 3
 
 

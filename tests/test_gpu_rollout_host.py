@@ -5,7 +5,7 @@ tests/test_gpu_rollout.py compares the launch with the device's own one-slot loo
 with the device.
 
 Bars: those of tests/test_gpu_closed_loop_host.py - everything bit for bit, but exp()-based rewards (reward_design 3, and
-4 in my_step_ch) within EXP_ATOL and what is summed from them within `_exp_bounds`; the metric float sums at rtol 1e-12,
+4 in my_step_ch) within the exp() bar of tests/oracle_compare.py and what is summed from them within `_exp_bounds`; the metric float sums at rtol 1e-12,
 atol 1e-9."""
 import numpy as np
 import pytest
@@ -14,7 +14,8 @@ import torch
 from diral_amd.config import (KERNEL_CH, KERNEL_FAST64, KERNEL_PACKED, KERNEL_POLICY, KERNEL_WIDE, STEP_MY_STEP,
                               STEP_MY_STEP_CH, bench_config, c2_config)
 from tests import host_closed_loop as H
-from tests.host_closed_loop import EXP_ATOL, MODE_NAME, RICH, Case, _eq, _exp_bounds, host_run, uses_exp
+from tests.oracle_compare import exp_atol, metrics_equal
+from tests.host_closed_loop import MODE_NAME, RICH, Case, _eq, _exp_bounds, host_run, uses_exp
 
 pytestmark = pytest.mark.gpu
 
@@ -70,7 +71,7 @@ def run_case(c, states, monkeypatch, constant=0):
         pn = (2, -10.0, torch.zeros((B, N), dtype=torch.int32, device="cuda:0"), torch.full((B, N), -1, dtype=torch.int32, device="cuda:0"))
     exp = uses_exp(cfg, c.mode)
     sum_atol, shaped_atol = _exp_bounds(N) if exp else (None, None)
-    state_atol = EXP_ATOL if (exp and cfg.State.add_reward) else None
+    state_atol = exp_atol(exp and cfg.State.add_reward)
     keep = np.ones(B, bool)
     dseq = torch.as_tensor(seq, device="cuda:0")
     t = 0
@@ -92,7 +93,7 @@ def run_case(c, states, monkeypatch, constant=0):
             if states == "all":
                 _eq(tag + "state %d" % k, got["states"][k], o["state"], keep, 0, state_atol)
         last = outs[t + K - 1]
-        _eq(tag + "reward", got["reward"], last["rew"], keep, 0, EXP_ATOL if exp else None)
+        _eq(tag + "reward", got["reward"], last["rew"], keep, 0, exp_atol(exp))
         _eq(tag + "done", got["done"], last["done"], keep)
         if states == "last":
             _eq(tag + "state", got["states"], last["state"], keep, 0, state_atol)
@@ -104,11 +105,8 @@ def run_case(c, states, monkeypatch, constant=0):
     for k in ("pos_x", "vel", "seq", "age", "x"):
         _eq("export_state " + k, st[k], he[k], keep)
     m, hm = env.metrics().cpu().numpy(), host.metrics()
-    assert np.array_equal(m[:, [0, 2, 3]], hm[:, [0, 2, 3]]) and float(m[:, 0].min()) == T
-    assert np.allclose(m[:, 1], hm[:, 1], rtol=1e-12, atol=1e-9)
-    if c.mode == STEP_MY_STEP_CH:
-        assert np.array_equal(m[:, 5], hm[:, 5]) and float(m[:, 5].min()) > 0
-        assert np.allclose(m[:, 4], hm[:, 4], rtol=1e-12, atol=1e-9)
+    metrics_equal(m, hm, "metrics", prr=c.mode == STEP_MY_STEP_CH)
+    assert float(m[:, 0].min()) == T and (c.mode != STEP_MY_STEP_CH or float(m[:, 5].min()) > 0)
     env.check()
     return env, host
 

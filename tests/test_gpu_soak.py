@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from diral_amd.config import bench_config, STEP_MY_STEP, STEP_MY_STEP_CH
+from tests.oracle_compare import metrics_equal, slot_equal, tables_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -43,17 +44,10 @@ def soak(N, A, L, B, T, mode, vary, rc=250.0, every=250, rich=False):
             d = rng.integers(1, 4, size=(B, N)).astype(np.uint8)
             env.update_velocity(d); orc.update_velocity(d)
         if t % every == every - 1 or t == T - 1:
-            st = orc.obtain_state(a, o_ch, o_rew)
-            torch.cuda.synchronize()
-            assert np.array_equal(obs.cpu().numpy(), st), (N, t)
-            assert np.array_equal(rew.cpu().numpy(), o_rew), (N, t)
-            if rich:
-                assert np.array_equal(chobs.cpu().numpy(), o_ch), (N, t)
-    s, oe = env.export_state(), orc.export()
-    assert np.array_equal(s["seq"].cpu().numpy(), oe["seq"]) and np.array_equal(s["x"].cpu().numpy(), oe["x"])
-    assert np.array_equal(s["pos_x"].cpu().numpy(), oe["pos_x"]) and np.array_equal(s["age"].cpu().numpy(), np.minimum(oe["age"], 255))
-    m, mo = env.metrics().cpu().numpy(), orc.metrics()
-    assert np.array_equal(m[:, [0, 2, 3]], mo[:, [0, 2, 3]])
+            got = (obs.cpu().numpy(), rew.cpu().numpy(), chobs.cpu().numpy() if rich else None)
+            slot_equal(cfg, mode, got, (orc.obtain_state(a, o_ch, o_rew), o_rew, o_ch), (N, t))
+    tables_equal({k: v.cpu().numpy() for k, v in env.export_state().items()}, orc.export(), N)
+    metrics_equal(env.metrics().cpu().numpy(), orc.metrics(), N)
     env.check()
     print("soak ok N=%d A=%d L=%g B=%d T=%d mode=%d vary=%s rc=%g rich=%s  %.1fs" % (N, A, L, B, T, mode, vary, rc, rich, time.time() - t0), flush=True)
 

@@ -29,7 +29,8 @@ import pytest
 import torch
 
 from diral_amd.config import KERNEL_FAST64, KERNEL_POLICY, STEP_DESIGN, STEP_MY_STEP, bench_config
-from tests.gpu_util import make_env
+from tests.gpu_util import host, make_env
+from tests.oracle_compare import slot_equal
 
 gpu = pytest.mark.gpu
 
@@ -105,11 +106,8 @@ def _run(N, A, K, dtype, chobs, pol):
         torch.cuda.synchronize()
         lk = env.last_kernel()
         assert (lk & 15) == KERNEL_FAST64 and bool(lk & KERNEL_POLICY) == pol, lk
-        where = (N, A, K, t)
-        _same(rew, o_rew.astype(npdt), where)
-        _same(obs, o_state.astype(npdt), where)
-        if chobs:
-            _same(env._chobs, o_chobs.astype(npdt), where)
+        got = (host(obs), host(rew), host(env._chobs) if chobs else None)
+        slot_equal(cfg, STEP_MY_STEP, got, (o_state, o_rew, o_chobs), (N, A, K, t), npdt)
     env.check()
 
 
